@@ -2,7 +2,18 @@
 """bench.py -- the AWR hot path on MI355X: depth-images/sec of the full train step.
 
     python bench.py [--gpus N] [--steps K] [--warmup W] [--batch B] [--net resnet_18|hourglass_1] [--graph] [--dp-selftest]
+                    [--dump-outputs DIR] [--full]
     python -m torch.distributed.run --nnodes=1 --nproc-per-node N --master-addr 127.0.0.1 --master-port P bench.py --gpus N ...
+
+A plain run sets up, warms up, times the K steps and prints the headline line; nothing else.  `--full` adds everything else the
+benchmark measures or checks: the live roofline blocks, the joint error against the oracle, the CPU baseline, the batch-256 shape,
+the inference / Hourglass / data-path / Winograd / parity-mode / split-operand sub-records and, for N > 1, the replica check, the
+bucket timeline and the transport A/B (each still switched off by its own --no-* option).  `--dump-outputs DIR` writes what the
+timed path computes as DIR/<name>.npy: after the timed steps, the train step is run once more from the seeded starting state
+(weights, optimiser state and batch are the same in every run), so two runs, or two builds, can be compared output for output.  The
+last of the timed steps would not serve: split-K weight gradients are summed with atomics in the default mode, and Adam, stepping on
+one batch again and again, amplifies their last-bit differences about tenfold per step.  With --deterministic the dumps are bitwise
+identical.
 
 `--gpus N` with N > 1 works both ways: under torchrun (RANK / LOCAL_RANK / WORLD_SIZE in the environment) this process is one rank;
 started plainly (`python bench.py --gpus 8`) it spawns the N rank processes itself, one per GPU, and relays rank 0's JSON line.
@@ -12,9 +23,9 @@ reference iteration per step (GT map + forward + head + dense/joint Huber + back
 on synthetic crops with reference-initialised weights.  N > 1 = one process per GPU, each
 stepping its own batch-64 shard (weak scaling) with an RCCL all-reduce of the flat gradient arena.
 
-Prints ONE JSON line (rank 0).  `roofline` is measured live with HIP events around every launch of the
-implicit-GEMM conv kernels inside the timed steps; `cpu_baseline` times the oracle (the CPU restatement
-of the reference step, proven bit-identical to the reference in tools/gen_golden.py) on the host cores.
+Prints ONE JSON line (rank 0).  With --full, `roofline` is measured live with HIP events around every launch of the
+implicit-GEMM conv kernels in serialised passes of the plan after the timed steps; `cpu_baseline` times the oracle (the CPU
+restatement of the reference step, proven bit-identical to the reference in tools/gen_golden.py) on the host cores.
 """
 import argparse
 import json
@@ -257,9 +268,11 @@ def _pool_info(L):
     return k.value
 
 
-def measure_inference(awr_amd, O, net_name, batch, dev, rank, steps, warmup, graph, peak_tf, flop_mult, per_layer="", net=None, parity=False, winograd=None):
+def measure_inference(awr_amd, O, net_name, batch, dev, rank, steps, warmup, graph, peak_tf, flop_mult, per_layer="", net=None, parity=False, winograd=None,
+                      dump=""):
     """test.py:67-86 path: eval-mode BatchNorm folded into the GEMM epilogues, img -> dense map -> joints.  Returns images/s, ms per
-    batch and the fraction of the MFMA roofline (algorithmic conv FLOPs of the forward / time / peak)."""
+    batch and the fraction of the MFMA roofline (algorithmic conv FLOPs of the forward / time / peak).  dump: directory that receives
+    the joints of the last timed call."""
     from awr_amd.trainer import InferEngine
     ks = 1.0 if net_name.startswith("resnet") else 0.4
     if net is None:
@@ -273,9 +286,11 @@ def measure_inference(awr_amd, O, net_name, batch, dev, rank, steps, warmup, gra
     torch.cuda.synchronize()
     t0 = time.perf_counter()
     for _ in range(steps):
-        inf(imgs)
+        jt = inf(imgs)
     torch.cuda.synchronize()
     el = time.perf_counter() - t0
+    if dump:
+        _dump_outputs(dump, {"jt_uvd_pred": jt})
     macs = sum(v for k, v in inf.plan.macs.items())
     if per_layer:
         per = {}
@@ -437,138 +452,65 @@ def _rccl_version():
         return None
 
 
-def main():
-    ap = argparse.ArgumentParser()
-    ap.add_argument("--gpus", type=int, default=1)
-    ap.add_argument("--steps", type=int, default=20)
-    ap.add_argument("--warmup", type=int, default=5)
-    ap.add_argument("--batch", type=int, default=64, help="images per GPU per step (BASELINE configs[1]: 64)")
-    ap.add_argument("--net", default="resnet_18")
-    ap.add_argument("--graph", action="store_true",
-                    help="replay the step as ONE hipGraph (weight-gradient side streams forked / joined inside the capture) instead of issuing every launch "
-                         "eagerly.  Measured slower on this stack (15.80 vs 14.93 ms / step, profiles/r02_summary.md): the eager two-stream issue stays the default")
-    ap.add_argument("--no-extras", action="store_true", help="skip the inference / config-3 measurements reported under 'forward' and 'config3'")
-    ap.add_argument("--no-cpu-baseline", action="store_true")
-    ap.add_argument("--no-parity", action="store_true", help="skip the small HIP-vs-oracle joint check (keeps profiler traces to the timed workload)")
-    ap.add_argument("--coord-weight", type=float, default=0.0, help="reference default config.py:41")
-    ap.add_argument("--mode", default="train", choices=["train", "infer"], help="infer = test.py:67-86 path (eval BN, img -> joints); not the headline metric")
-    ap.add_argument("--wgrad-streams", type=int, default=2, help="extra HIP streams for the weight-gradient GEMMs (0 = fully serial step)")
-    ap.add_argument("--gemm-products", type=int, default=1, choices=[1, 6],
-                    help="1 = FP32 MFMA (default, the headline); 6 = split-operand mode (fp32 operands as 3 exact bf16 pieces, 6 bf16 MFMA products)")
-    ap.add_argument("--no-split-mode", action="store_true", help="skip the extra split-operand measurement reported under 'split_mode'")
-    ap.add_argument("--per-layer", default="", help="write a per-GEMM-launch table (TFLOP/s per layer) to this file")
-    ap.add_argument("--dp-selftest", action="store_true", help="data parallel: fail unless all replicas hold bitwise-identical parameters after the timed steps; "
-                                                               "the per-bucket all-reduce timeline is reported either way when N > 1")
-    ap.add_argument("--no-hourglass-train", action="store_true", help="skip the Hourglass training sub-records 'hg1_train_b64' and 'config5'")
-    ap.add_argument("--no-b256", action="store_true", help="skip the config-4 per-GPU shape (batch 256) sub-record")
-    ap.add_argument("--no-data-path", action="store_true", help="skip the 'data_path' sub-record (host loader vs device loader, train step fed by the device path)")
-    ap.add_argument("--no-winograd", action="store_true", help="skip the 'winograd_mode' sub-record (Winograd F(2x2, 3x3) forward of the 3x3 convolutions)")
-    ap.add_argument("--no-accurate-mode", action="store_true", help="skip the blocked-accumulation (parity mode) sub-record 'accurate_mode'")
-    ap.add_argument("--no-native-rccl", action="store_true", help="N > 1: skip the 'native_rccl' sub-record (same steps, gradient buckets exchanged by the "
-                                                                  "library's own RCCL communicator instead of torch.distributed work objects)")
-    ap.add_argument("--deterministic", action="store_true", help="awr_amd.set_deterministic(True): bitwise-reproducible steps (no atomics on shared "
-                                                                  "accumulators, no autotuning); reports what that costs")
-    args = ap.parse_args()
+DUMP_LIMIT_BYTES = 64 << 20
+PARAM_SAMPLE = 1 << 20          # parameters dumped per run: a fixed, seeded sample (a ResNet18-deconv arena alone is ~60 MB)
 
-    if args.gpus > 1 and "WORLD_SIZE" not in os.environ:
-        raise SystemExit(_spawn_ranks(args.gpus))          # plain `python bench.py --gpus N`: be our own launcher
-    # stdout carries exactly ONE line, the JSON record: libraries that print banners on file descriptor 1 (RCCL's version block at
-    # communicator creation) are sent to stderr for the duration of the run
-    sys.stdout.flush()
-    real_stdout = os.dup(1)
-    os.dup2(2, 1)
 
-    def emit(line):
-        os.write(real_stdout, (line + "\n").encode())
-    world = int(os.environ.get("WORLD_SIZE", "1"))
-    rank = int(os.environ.get("RANK", "0"))
-    local = int(os.environ.get("AWR_FORCE_DEVICE", os.environ.get("LOCAL_RANK", "0")))     # AWR_FORCE_DEVICE: test hook (several ranks on one GPU)
-    if args.gpus != world and not (world == 1 and os.environ.get("AWR_FORCE_DP") == "1"):
-        raise SystemExit("--gpus %d but the launcher started %d rank(s)" % (args.gpus, world))
-    assert torch.cuda.is_available(), "bench.py needs an MI355X"
-    torch.cuda.set_device(local)
-    dev = torch.device("cuda", local)
-    affinity = None
-    if world > 1 and os.environ.get("AWR_NO_AFFINITY") != "1":
-        affinity = _pin_cpu_affinity(dev, int(os.environ.get("LOCAL_RANK", "0")), int(os.environ.get("LOCAL_WORLD_SIZE", str(world))))
-    pg, backend = None, None
-    if world > 1 or os.environ.get("AWR_FORCE_DP") == "1":      # AWR_FORCE_DP: exercise the data-parallel path on a 1-rank group (tests)
-        os.environ.setdefault("MASTER_ADDR", "127.0.0.1")
-        backend = os.environ.get("AWR_DIST_BACKEND", "nccl")        # "nccl" is RCCL on ROCm; tests run the same path over gloo on one GPU
-        torch.distributed.init_process_group(backend, rank=rank, world_size=world, **({"device_id": dev} if backend == "nccl" else {}))
-        pg = torch.distributed.group.WORLD
+def _sample_index(n, k, seed=0):
+    """Fixed, seeded choice of min(n, k) of n positions, ascending (the same positions in every run and every build)."""
+    if n <= k:
+        return torch.arange(n)
+    g = torch.Generator().manual_seed(seed)
+    return torch.randperm(n, generator=g)[:k].sort().values
 
-    import awr_amd
-    from awr_amd import _lib as L
-    from awr_amd.trainer import TrainEngine
-    sys.path.insert(0, os.path.join(REPO, "oracle"))
-    import awr_oracle as O          # synthetic-input generator + cpu_baseline only; never on the measured path
 
-    ks = 1.0 if args.net.startswith("resnet") else 0.4          # config.py:42
-    awr_amd.set_gemm_products(args.gemm_products)
-    awr_amd.set_deterministic(args.deterministic)
-    nprod = args.gemm_products
-    dtype = "f32" if nprod == 1 else "f32 (operands as 3 exact bf16 pieces, 6 bf16 MFMA products per f32 product, f32 accumulate)"
-    # MFMA roofline of the mode: FP32 MFMA peak, or the bf16 dense peak against 6 MFMA flops per algorithmic flop
-    peak_tf, flop_mult = (PEAK_FP32_MFMA_TFLOPS, 1) if nprod == 1 else (PEAK_BF16_MFMA_TFLOPS, 6)
-    torch.manual_seed(0)
-    net = _make_net(awr_amd, args.net).cuda()
-    if args.mode == "infer":
-        res = measure_inference(awr_amd, O, args.net, args.batch, dev, rank, args.steps, max(args.warmup, 3), args.graph, peak_tf, flop_mult,
-                                per_layer=args.per_layer, net=net)
-        emit(json.dumps({"metric": "depth-images/sec (inference, img -> joints)", "value": res["value"], "unit": "images/s",
-                          "n_gpus": 1, "steps": args.steps, "warmup": args.warmup, "ms_per_step": res["ms_per_step"],
-                          "dtype": dtype, "data": "synthetic", "config": {"workload": res["workload"], "hipgraph": bool(args.graph), "gemm_products": nprod},
-                          "mfma_frac": res["mfma_frac"]}))
-        return
-    def sync():
-        torch.cuda.synchronize()
-        if pg is not None:
-            torch.distributed.barrier()
+def _engine_state(eng, net):
+    """Copies of everything a train step reads and updates: parameters, gradients, BatchNorm running statistics and counters, the
+    optimiser's moments and its step count."""
+    return [t.clone() for t in _state_tensors(eng, net)], eng.step_count
 
-    def timed_steps(engine, im, jg, steps, warm):
-        """W untimed steps, then EXACTLY `steps` steps between barrier + synchronize on both sides; the MAX over ranks."""
-        for _ in range(warm):
-            engine.step(im, jg)
-        sync()
-        t0 = time.perf_counter()
-        for _ in range(steps):
-            engine.step(im, jg)
-        sync()
-        el = time.perf_counter() - t0
-        if pg is not None:
-            t = torch.tensor([el], device=dev, dtype=torch.float64)
-            torch.distributed.all_reduce(t, op=torch.distributed.ReduceOp.MAX)
-            el = float(t[0])
-        return el
 
-    eng = TrainEngine(net, args.batch, 128, ks, coord_weight=args.coord_weight, dense_weight=1.0, lr=1e-3, process_group=pg,
-                      use_graph=args.graph, wgrad_streams=args.wgrad_streams)
-    img, jt = O.synth_batch(args.batch, 128, 14, seed=1234 + rank)
-    img, jt = img.to(dev), jt.to(dev)           # inputs resident in HBM before the timed region
-    graph = bool(eng.use_graph)          # the engine falls back to eager issue in data-parallel mode (RCCL calls inside the backward)
-    eng.compile(img, jt)                 # set-up, not a step: kernel warm-up run (rolled back), GEMM tile autotune, hipGraph capture
-    warm = args.warmup
-    elapsed = timed_steps(eng, img, jt, args.steps, warm)
-    loss = float(eng.losses[2])
-    ranks_seen = _ranks_seen(pg, dev, {"cpu_affinity": affinity} if affinity is not None else None)
+def _state_tensors(eng, net):
+    return [t for t in (net.flat_params(), net.flat_grads(), net._barena, net._counters, eng.m, eng.v) if t is not None]
 
-    # data-parallel self-test (after the timed region): replicas must hold bitwise-identical parameters after all those steps (every rank
-    # stepped its own images; the all-reduced gradients and the optimiser are what keeps them together), and one traced step shows where
-    # each bucket's exchange sat relative to the backward
-    selftest = None
-    if pg is not None and (args.dp_selftest or world > 1):
-        same = _replicas_equal(net)
-        eng.trace_buckets = True
-        eng.step(img, jt)
-        tl = eng.bucket_timeline()
-        eng.trace_buckets = False
-        selftest = {"replicas_bitwise_equal_after_steps": same, "steps_checked": warm + args.steps, "n_params": int(net.n_active),
-                    "bucket_timeline_rank0": tl, "note": "timeline of one extra traced step: ms from the start of the step on the stream each bucket was handed to; "
-                                                         "tracing makes that stream wait for its collective"}
-        if args.dp_selftest and not same:
-            raise SystemExit("dp-selftest: parameters differ across ranks after %d steps" % (warm + args.steps))
 
+def _set_engine_state(eng, net, state):
+    """Put a state taken by _engine_state back, in place (plans and captured graphs keep their pointers)."""
+    saved, count = state
+    for dst, src in zip(_state_tensors(eng, net), saved):
+        dst.copy_(src)
+    eng.step_count = count
+    net.weights_changed()
+
+
+def _train_outputs(eng, net):
+    """What a caller of the train step holds after it: the losses [coord, dense, total] and the predicted joints the step returns,
+    and the parameters (seeded sample) and BatchNorm running statistics it updated in place."""
+    params = net.flat_params()[:net.n_active]
+    idx = _sample_index(params.numel(), PARAM_SAMPLE).to(params.device)
+    return {"losses": eng.losses, "jt_uvd_pred": eng.jt_pred, "params_sample": params[idx], "bn_running_stats": net._barena}
+
+
+def _dump_outputs(dirname, arrays):
+    """Write {name: tensor} as dirname/<name>.npy: float64 stays float64, everything else becomes float32.  Fails when the total
+    would exceed DUMP_LIMIT_BYTES."""
+    import numpy as np
+    host = {}
+    for name, t in arrays.items():
+        a = t.detach().cpu().numpy() if torch.is_tensor(t) else np.asarray(t)
+        host[name] = np.ascontiguousarray(a, dtype=np.float64 if a.dtype == np.float64 else np.float32)
+    total = sum(a.nbytes for a in host.values())
+    if total > DUMP_LIMIT_BYTES:
+        raise SystemExit("--dump-outputs: %d bytes exceed the %d-byte limit" % (total, DUMP_LIMIT_BYTES))
+    os.makedirs(dirname, exist_ok=True)
+    for name, a in host.items():
+        np.save(os.path.join(dirname, name + ".npy"), a)
+    return sorted(host)
+
+
+def _roofline_blocks(args, eng, net, elapsed, nprod, peak_tf, flop_mult, rank):
+    """--full / --per-layer: the per-kernel MFMA roofline of the conv launches and the HBM roofline of the head / loss / optimiser launches,
+    both from serialised event passes after the timed steps.  -> (roofline, roofline_hbm, conv FLOPs of the passes, passes)."""
     # per-kernel HIP events only make sense when kernels do not share the GPU: the timed region runs untouched (side streams /
     # graph replay) and the per-kernel roofline comes from serialised passes of the same plan right after it
     per = {}
@@ -648,6 +590,164 @@ def main():
            "adam_step": ("a8 Adam, 28 B / parameter", 28 * int(net.n_active))}
     roofline_hbm = {k: {"covers": alg[k][0], "bytes_algorithmic": alg[k][1], "avg_us": round(1e6 * v, 2), "gbps": round(alg[k][1] / v / 1e9, 1),
                         "frac_of_8TBps": round(alg[k][1] / v / 8e12, 4)} for k, v in hb.items() if k in alg}
+    return roofline, roofline_hbm, tot_fl, nsteps_timed
+
+
+def main():
+    ap = argparse.ArgumentParser()
+    ap.add_argument("--gpus", type=int, default=1)
+    ap.add_argument("--steps", type=int, default=20)
+    ap.add_argument("--warmup", type=int, default=5)
+    ap.add_argument("--batch", type=int, default=64, help="images per GPU per step (BASELINE configs[1]: 64)")
+    ap.add_argument("--net", default="resnet_18")
+    ap.add_argument("--graph", action="store_true",
+                    help="replay the step as ONE hipGraph (weight-gradient side streams forked / joined inside the capture) instead of issuing every launch "
+                         "eagerly.  Measured slower on this stack (15.80 vs 14.93 ms / step, profiles/r02_summary.md): the eager two-stream issue stays the default")
+    ap.add_argument("--no-extras", action="store_true", help="skip the inference / config-3 measurements reported under 'forward' and 'config3'")
+    ap.add_argument("--no-cpu-baseline", action="store_true")
+    ap.add_argument("--no-parity", action="store_true", help="skip the small HIP-vs-oracle joint check (keeps profiler traces to the timed workload)")
+    ap.add_argument("--coord-weight", type=float, default=0.0, help="reference default config.py:41")
+    ap.add_argument("--mode", default="train", choices=["train", "infer"], help="infer = test.py:67-86 path (eval BN, img -> joints); not the headline metric")
+    ap.add_argument("--wgrad-streams", type=int, default=2, help="extra HIP streams for the weight-gradient GEMMs (0 = fully serial step)")
+    ap.add_argument("--gemm-products", type=int, default=1, choices=[1, 6],
+                    help="1 = FP32 MFMA (default, the headline); 6 = split-operand mode (fp32 operands as 3 exact bf16 pieces, 6 bf16 MFMA products)")
+    ap.add_argument("--no-split-mode", action="store_true", help="skip the extra split-operand measurement reported under 'split_mode'")
+    ap.add_argument("--per-layer", default="", help="write a per-GEMM-launch table (TFLOP/s per layer) to this file")
+    ap.add_argument("--dp-selftest", action="store_true", help="data parallel: fail unless all replicas hold bitwise-identical parameters after the timed steps; "
+                                                               "the per-bucket all-reduce timeline is reported either way when N > 1")
+    ap.add_argument("--no-hourglass-train", action="store_true", help="skip the Hourglass training sub-records 'hg1_train_b64' and 'config5'")
+    ap.add_argument("--no-b256", action="store_true", help="skip the config-4 per-GPU shape (batch 256) sub-record")
+    ap.add_argument("--no-data-path", action="store_true", help="skip the 'data_path' sub-record (host loader vs device loader, train step fed by the device path)")
+    ap.add_argument("--no-winograd", action="store_true", help="skip the 'winograd_mode' sub-record (Winograd F(2x2, 3x3) forward of the 3x3 convolutions)")
+    ap.add_argument("--no-accurate-mode", action="store_true", help="skip the blocked-accumulation (parity mode) sub-record 'accurate_mode'")
+    ap.add_argument("--no-native-rccl", action="store_true", help="N > 1: skip the 'native_rccl' sub-record (same steps, gradient buckets exchanged by the "
+                                                                  "library's own RCCL communicator instead of torch.distributed work objects)")
+    ap.add_argument("--deterministic", action="store_true", help="awr_amd.set_deterministic(True): bitwise-reproducible steps (no atomics on shared "
+                                                                  "accumulators, no autotuning); reports what that costs")
+    ap.add_argument("--full", action="store_true", help="after the headline, run every other measurement and check of the benchmark (roofline blocks, "
+                                                        "oracle parity, CPU baseline, sub-records; N > 1: replica check, bucket timeline, transport A/B)")
+    ap.add_argument("--dump-outputs", default="", metavar="DIR", help="write what the timed path computes from the seeded starting state (train: "
+                                                                      "its step, run once more after the timing; infer: the last timed call) to "
+                                                                      "DIR/<name>.npy (float32 / float64, at most 64 MB in all)")
+    args = ap.parse_args()
+
+    if args.gpus > 1 and "WORLD_SIZE" not in os.environ:
+        raise SystemExit(_spawn_ranks(args.gpus))          # plain `python bench.py --gpus N`: be our own launcher
+    # stdout carries exactly ONE line, the JSON record: libraries that print banners on file descriptor 1 (RCCL's version block at
+    # communicator creation) are sent to stderr for the duration of the run
+    sys.stdout.flush()
+    real_stdout = os.dup(1)
+    os.dup2(2, 1)
+
+    def emit(line):
+        os.write(real_stdout, (line + "\n").encode())
+    world = int(os.environ.get("WORLD_SIZE", "1"))
+    rank = int(os.environ.get("RANK", "0"))
+    local = int(os.environ.get("AWR_FORCE_DEVICE", os.environ.get("LOCAL_RANK", "0")))     # AWR_FORCE_DEVICE: test hook (several ranks on one GPU)
+    if args.gpus != world and not (world == 1 and os.environ.get("AWR_FORCE_DP") == "1"):
+        raise SystemExit("--gpus %d but the launcher started %d rank(s)" % (args.gpus, world))
+    assert torch.cuda.is_available(), "bench.py needs an MI355X"
+    torch.cuda.set_device(local)
+    dev = torch.device("cuda", local)
+    affinity = None
+    if world > 1 and os.environ.get("AWR_NO_AFFINITY") != "1":
+        affinity = _pin_cpu_affinity(dev, int(os.environ.get("LOCAL_RANK", "0")), int(os.environ.get("LOCAL_WORLD_SIZE", str(world))))
+    pg, backend = None, None
+    if world > 1 or os.environ.get("AWR_FORCE_DP") == "1":      # AWR_FORCE_DP: exercise the data-parallel path on a 1-rank group (tests)
+        os.environ.setdefault("MASTER_ADDR", "127.0.0.1")
+        backend = os.environ.get("AWR_DIST_BACKEND", "nccl")        # "nccl" is RCCL on ROCm; tests run the same path over gloo on one GPU
+        torch.distributed.init_process_group(backend, rank=rank, world_size=world, **({"device_id": dev} if backend == "nccl" else {}))
+        pg = torch.distributed.group.WORLD
+
+    import awr_amd
+    from awr_amd import _lib as L
+    from awr_amd.trainer import TrainEngine
+    sys.path.insert(0, os.path.join(REPO, "oracle"))
+    import awr_oracle as O          # synthetic-input generator + cpu_baseline only; never on the measured path
+
+    ks = 1.0 if args.net.startswith("resnet") else 0.4          # config.py:42
+    awr_amd.set_gemm_products(args.gemm_products)
+    awr_amd.set_deterministic(args.deterministic)
+    nprod = args.gemm_products
+    dtype = "f32" if nprod == 1 else "f32 (operands as 3 exact bf16 pieces, 6 bf16 MFMA products per f32 product, f32 accumulate)"
+    # MFMA roofline of the mode: FP32 MFMA peak, or the bf16 dense peak against 6 MFMA flops per algorithmic flop
+    peak_tf, flop_mult = (PEAK_FP32_MFMA_TFLOPS, 1) if nprod == 1 else (PEAK_BF16_MFMA_TFLOPS, 6)
+    torch.manual_seed(0)
+    net = _make_net(awr_amd, args.net).cuda()
+    if args.mode == "infer":
+        res = measure_inference(awr_amd, O, args.net, args.batch, dev, rank, args.steps, max(args.warmup, 3), args.graph, peak_tf, flop_mult,
+                                per_layer=args.per_layer, net=net, dump=args.dump_outputs if rank == 0 else "")
+        emit(json.dumps({"metric": "depth-images/sec (inference, img -> joints)", "value": res["value"], "unit": "images/s",
+                          "n_gpus": 1, "steps": args.steps, "warmup": args.warmup, "ms_per_step": res["ms_per_step"],
+                          "dtype": dtype, "data": "synthetic", "config": {"workload": res["workload"], "hipgraph": bool(args.graph), "gemm_products": nprod},
+                          "mfma_frac": res["mfma_frac"]}))
+        return
+    def sync():
+        torch.cuda.synchronize()
+        if pg is not None:
+            torch.distributed.barrier()
+
+    def timed_steps(engine, im, jg, steps, warm):
+        """W untimed steps, then EXACTLY `steps` steps between barrier + synchronize on both sides; the MAX over ranks."""
+        for _ in range(warm):
+            engine.step(im, jg)
+        sync()
+        t0 = time.perf_counter()
+        for _ in range(steps):
+            engine.step(im, jg)
+        sync()
+        el = time.perf_counter() - t0
+        if pg is not None:
+            t = torch.tensor([el], device=dev, dtype=torch.float64)
+            torch.distributed.all_reduce(t, op=torch.distributed.ReduceOp.MAX)
+            el = float(t[0])
+        return el
+
+    eng = TrainEngine(net, args.batch, 128, ks, coord_weight=args.coord_weight, dense_weight=1.0, lr=1e-3, process_group=pg,
+                      use_graph=args.graph, wgrad_streams=args.wgrad_streams)
+    img, jt = O.synth_batch(args.batch, 128, 14, seed=1234 + rank)
+    img, jt = img.to(dev), jt.to(dev)           # inputs resident in HBM before the timed region
+    graph = bool(eng.use_graph)          # the engine falls back to eager issue in data-parallel mode (RCCL calls inside the backward)
+    eng.compile(img, jt)                 # set-up, not a step: kernel warm-up run (rolled back), GEMM tile autotune, hipGraph capture
+    start = _engine_state(eng, net) if args.dump_outputs else None
+    warm = args.warmup
+    elapsed = timed_steps(eng, img, jt, args.steps, warm)
+    loss = float(eng.losses[2])
+    if start is not None:
+        # The timed steps train on one batch over and over, and the default mode sums split-K weight gradients with atomics: their last-bit
+        # differences grow about tenfold per Adam step, and after 25 steps two runs disagree on the joints by ~5 %.  So the dump is the timed
+        # path's step taken from the seeded starting state (same engine, plan and inputs), run once more after the timing; every rank takes
+        # part (the all-reduce is part of the step), and the state after the timed steps is put back before anything else runs.
+        end = _engine_state(eng, net)
+        _set_engine_state(eng, net, start)
+        eng.step(img, jt)
+        if rank == 0:
+            _dump_outputs(args.dump_outputs, _train_outputs(eng, net))
+        _set_engine_state(eng, net, end)
+        del start, end
+    ranks_seen = _ranks_seen(pg, dev, {"cpu_affinity": affinity} if affinity is not None else None)
+    full = args.full
+
+    # data-parallel self-test (after the timed region): replicas must hold bitwise-identical parameters after all those steps (every rank
+    # stepped its own images; the all-reduced gradients and the optimiser are what keeps them together), and one traced step shows where
+    # each bucket's exchange sat relative to the backward
+    selftest = None
+    if pg is not None and (args.dp_selftest or (full and world > 1)):
+        same = _replicas_equal(net)
+        eng.trace_buckets = True
+        eng.step(img, jt)
+        tl = eng.bucket_timeline()
+        eng.trace_buckets = False
+        selftest = {"replicas_bitwise_equal_after_steps": same, "steps_checked": warm + args.steps, "n_params": int(net.n_active),
+                    "bucket_timeline_rank0": tl, "note": "timeline of one extra traced step: ms from the start of the step on the stream each bucket was handed to; "
+                                                         "tracing makes that stream wait for its collective"}
+        if args.dp_selftest and not same:
+            raise SystemExit("dp-selftest: parameters differ across ranks after %d steps" % (warm + args.steps))
+
+    roofline = roofline_hbm = None
+    tot_fl, nsteps_timed = 0.0, 1
+    if full or args.per_layer:
+        roofline, roofline_hbm, tot_fl, nsteps_timed = _roofline_blocks(args, eng, net, elapsed, nprod, peak_tf, flop_mult, rank)
 
     if rank == 0:
         n_cu, mhz = L.C.c_int(0), L.C.c_int(0)
@@ -664,11 +764,12 @@ def main():
                        "gemm_products": nprod, "deterministic": bool(args.deterministic), "device_cus": n_cu.value, "final_loss": loss,
                        "nhwc_head_loss": bool(eng.nhwc), "launcher": os.environ.get("AWR_LAUNCHER", "torch.distributed.run" if "TORCHELASTIC_RUN_ID" in os.environ else "direct")},
             "dist_backend": backend, "rccl_version": _rccl_version() if backend == "nccl" else None, "ranks_seen": ranks_seen,
-            "roofline": roofline, "roofline_hbm": roofline_hbm,
         }
+        if roofline is not None:
+            out["roofline"], out["roofline_hbm"] = roofline, roofline_hbm
         if selftest is not None:
             out["dp_selftest"] = selftest
-        if world == 1 and not args.no_parity:
+        if full and world == 1 and not args.no_parity:
             mean_mm, max_mm = parity_mm(args.net, ks, dev)
             out["joint_err_mm_vs_oracle"] = {"mean": round(mean_mm, 6), "max": round(max_mm, 6)}
             if not args.no_cpu_baseline:
@@ -676,7 +777,7 @@ def main():
     # config 4's per-GPU shape (batch 256 / GPU: north_star states its scaling target there) beside the batch-64 headline, same protocol,
     # every rank takes part (the all-reduce is part of the step)
     b256 = None
-    if args.batch != 256 and args.net == "resnet_18" and nprod == 1 and not args.no_b256 and not args.deterministic:
+    if full and args.batch != 256 and args.net == "resnet_18" and nprod == 1 and not args.no_b256 and not args.deterministic:
         del eng
         torch.cuda.empty_cache()
         eng2 = TrainEngine(net, 256, 128, ks, coord_weight=args.coord_weight, dense_weight=1.0, lr=1e-3, process_group=pg, use_graph=args.graph,
@@ -704,7 +805,7 @@ def main():
     # N > 1: the same K steps with the gradient buckets exchanged by the library's own RCCL communicator (awr_dp_*: ncclAllReduce issued from
     # inside the native backward replay, no Python callback per bucket) -- the A/B of the two transports in ONE run of the 8-GPU node
     native = None
-    if pg is not None and nprod == 1 and not args.no_native_rccl and not args.deterministic:
+    if full and pg is not None and nprod == 1 and not args.no_native_rccl and not args.deterministic:
         if backend != "nccl":
             native = {"skipped": "dist backend %r: the library's communicator is RCCL (one GPU per rank)" % backend}
         else:
@@ -745,7 +846,7 @@ def main():
             out["b256"] = b256
         if native is not None:
             out["native_rccl"] = native
-        if world == 1 and not args.no_extras:
+        if full and world == 1 and not args.no_extras:
             # north_star's forward target (>= 40 % MFMA utilisation on the ResNet18-deconv forward) and BASELINE config 3, each ~1 s,
             # outside the timed train region
             eng = None
@@ -765,14 +866,14 @@ def main():
                     import gc
                     gc.collect()
                     torch.cuda.empty_cache()
-        if world == 1 and nprod == 1 and not args.no_data_path and args.net == "resnet_18" and args.batch == 64 and not args.deterministic:
+        if full and world == 1 and nprod == 1 and not args.no_data_path and args.net == "resnet_18" and args.batch == 64 and not args.deterministic:
             eng = None
             torch.cuda.empty_cache()
             try:
                 out["data_path"] = measure_data_path(awr_amd, O, dev, out["ms_per_step"], max(args.steps, 20), 5)
             except Exception as e:          # (the headline has been measured: report, do not lose the line)
                 out["data_path"] = {"error": "%s: %s" % (type(e).__name__, str(e)[:300])}
-        if world == 1 and nprod == 1 and not args.no_winograd and not args.deterministic:
+        if full and world == 1 and nprod == 1 and not args.no_winograd and not args.deterministic:
             # Winograd F(2x2, 3x3) modes of the stride-1 3x3 convolutions (awr_amd.set_conv_winograd, opt-in): the headline's step, the Hourglass-1 step and
             # config 5, same protocol
             eng = None
@@ -812,7 +913,7 @@ def main():
             except Exception as e:          # (the headline has been measured: report, do not lose the line)
                 wm = {"error": "%s: %s" % (type(e).__name__, str(e)[:300])}
             out["winograd_mode"] = wm
-        if world == 1 and nprod == 1 and not args.no_accurate_mode and not args.deterministic:
+        if full and world == 1 and nprod == 1 and not args.no_accurate_mode and not args.deterministic:
             # the parity mode (blocked accumulation: awr_conv_args.accum = 1, what Trainer.test scores with and TrainEngine(accum="blocked") trains
             # with): the headline's step at the same batch, the scoring pass at batch 128, and the joint error against the oracle in that mode
             eng = None
@@ -826,7 +927,7 @@ def main():
                 mean_a, max_a = parity_mm(args.net, ks, dev, parity=True)
                 am["joint_err_mm_vs_oracle"] = {"mean": round(mean_a, 6), "max": round(max_a, 6)}
             out["accurate_mode"] = am
-        if world == 1 and nprod == 1 and not args.no_split_mode:
+        if full and world == 1 and nprod == 1 and not args.no_split_mode:
             # the same K steps in the opt-in split-operand mode (not the headline: `value` above is the FP32-MFMA path)
             awr_amd.set_gemm_products(6)
             torch.manual_seed(0)

@@ -256,3 +256,25 @@ def test_bench_rank_affinity_helpers(monkeypatch):
     # a failing query is reported, never raised (an unpinned rank is slower, not wrong)
     monkeypatch.setattr(torch.cuda, "get_device_properties", lambda dev: (_ for _ in ()).throw(RuntimeError("no device")))
     assert "error" in bench._pin_cpu_affinity(None, 0, 1)
+
+
+def test_bench_dump_outputs_helpers(tmp_path):
+    """bench.py --dump-outputs: float64 stays float64, every other dtype is written as float32, the parameter sample is the same
+    positions every time, and a dump over the 64 MB budget is refused before anything is written."""
+    import importlib.util
+    spec = importlib.util.spec_from_file_location("awr_bench", os.path.join(os.path.dirname(os.path.dirname(os.path.abspath(__file__))), "bench.py"))
+    bench = importlib.util.module_from_spec(spec)
+    spec.loader.exec_module(bench)
+    a = bench._sample_index(1000, 100)
+    assert torch.equal(a, bench._sample_index(1000, 100)) and a.numel() == 100 and torch.equal(a, a.sort().values) and len(set(a.tolist())) == 100
+    assert torch.equal(bench._sample_index(50, 100), torch.arange(50))
+    d = str(tmp_path / "out")
+    names = bench._dump_outputs(d, {"x": torch.arange(6, dtype=torch.float16).view(2, 3), "y": torch.ones(4, dtype=torch.float64), "n": np.arange(3)})
+    assert names == ["n", "x", "y"]
+    x, y, n = (np.load(os.path.join(d, k + ".npy")) for k in ("x", "y", "n"))
+    assert x.dtype == np.float32 and x.shape == (2, 3) and float(x[1, 2]) == 5.0
+    assert y.dtype == np.float64 and n.dtype == np.float32 and n.tolist() == [0.0, 1.0, 2.0]
+    big = str(tmp_path / "big")
+    with pytest.raises(SystemExit):
+        bench._dump_outputs(big, {"z": torch.zeros(bench.DUMP_LIMIT_BYTES // 4 + 1)})
+    assert not os.path.exists(big)

@@ -6,7 +6,7 @@ cd $GRAFT_REPO_ROOT
 STUDY=${1:?study name}; shift
 OUT=gpurun_out/$STUDY; mkdir -p $OUT
 export TMPDIR=/tmp
-QUIET="--no-cpu-baseline --no-parity --no-split-mode --no-extras --no-b256 --no-hourglass-train --no-accurate-mode"
+QUIET="--full --no-cpu-baseline --no-parity --no-split-mode --no-extras --no-b256 --no-hourglass-train --no-accurate-mode"
 
 line() {   # line <label> <bench args...> : one bench run, one summary line (images/s, ms, roofline.frac, step_mfma_frac)
   lab=$1; shift
