@@ -47,15 +47,33 @@ def set_conv_winograd(on):
     """Process-wide: plans built afterwards run the FORWARD (True / "forward") or the forward, the data gradient and the weight gradient ("full") of
     every eligible stride-1 3x3 convolution as Winograd F(2x2, 3x3) on the FP32 matrix pipe (include/awr_hip.h: awr_set_conv_winograd;
     csrc/awr_wino.hip) -- 2.25x fewer multiplies, 0.3-1.4x the direct kernels' rounding error, not bit-compatible with them.  Inference plans (InferEngine)
-    take the forward form in every non-zero mode."""
+    take the forward form in every non-zero mode.  "auto" is no library mode: it is resolved per engine (TrainEngine / InferEngine(winograd="auto"))."""
     from . import _lib as L
     L.call("awr_set_conv_winograd", _winograd_code(on))
 
 
+_WINOGRAD_NAMES = {"": 0, "direct": 0, "forward": 1, "full": 2, "forward+wgrad": 3, "force": 6}
+
+
 def _winograd_code(on):
-    """False / None -> 0, True / "forward" -> 1 (forward launches), "full" -> 2 (forward + data gradients + weight gradients), "forward+wgrad" -> 3 (the data gradients stay direct), "force" -> 6 (tests: "full" on every layer the
-    kernel can run, whatever the launch size)"""
-    return {"forward": 1, "full": 2, "forward+wgrad": 3, "force": 6}.get(on, 1 if on else 0) if not isinstance(on, int) or isinstance(on, bool) else int(on)
+    """False / None / "direct" -> 0, True / "forward" -> 1 (forward launches), "full" -> 2 (forward + data gradients + weight gradients), "forward+wgrad" -> 3 (the data gradients stay direct), "force" -> 6 (tests: "full" on every layer the
+    kernel can run, whatever the launch size); integers are library codes as they are.  Any other string is an error ("auto" included: the engines
+    resolve it, see winograd_auto.py)."""
+    if isinstance(on, str):
+        if on == "auto":
+            raise ValueError('winograd="auto" is chosen per engine by timing its plan: pass it to TrainEngine / InferEngine (or config.winograd), '
+                             "not to the process-wide library mode")
+        if on not in _WINOGRAD_NAMES:
+            raise ValueError("unknown Winograd mode %r: one of %s, \"auto\" (engines), a bool, None or an integer code" % (on, sorted(n for n in _WINOGRAD_NAMES if n)))
+        return _WINOGRAD_NAMES[on]
+    return int(on) if isinstance(on, int) and not isinstance(on, bool) else (1 if on else 0)
+
+
+def _engine_winograd(on):
+    """The engines' resolver: "auto" -> "auto" (timed per plan), everything else -> its library code (None stays None: the process-wide mode)."""
+    if on is None or (isinstance(on, str) and on == "auto"):
+        return on
+    return _winograd_code(on)
 
 
 def get_conv_winograd():

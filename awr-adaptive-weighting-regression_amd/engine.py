@@ -55,6 +55,25 @@ def plan_buckets(writes, n_active, n_buckets):
     return [tuple(b) for b in out]
 
 
+def tile_cache_key(base, products, staging, accum, winograd):
+    """AWR_TUNE_CACHE key of a plan's tile choices: tile choices differ between the modes (products, staging, the plan's accumulation order --
+    blocked doubles the accumulators -- and its Winograd code: a Winograd plan has other launches, and its direct ones run beside other neighbours)."""
+    return base + "/x%d/s%d/a%d/w%d" % (products, staging, accum, winograd)
+
+
+def cached_tiles(cache_file, key, names):
+    """The entry stored under `key` in the tuning cache if it covers every launch in `names`, else None."""
+    if not os.path.exists(cache_file):
+        return None
+    try:
+        ent = json.load(open(cache_file)).get(key)
+    except (OSError, ValueError):
+        return None
+    if ent and all(n in ent for n in names):
+        return ent
+    return None
+
+
 class NetHandle:
     """awr_net: the checkpoint layout of one backbone.  `layout` = [(key, shape, kind, offset, unused)] in state_dict order."""
 
@@ -333,23 +352,13 @@ class Plan:
             return
         cache_file = os.environ.get("AWR_TUNE_CACHE")
         if cache_key:
-            # tile choices differ between the modes (products, staging, and the plan's accumulation order: blocked doubles the accumulators)
-            cache_key += "/x%d/s%d/a%d" % (L.lib.awr_get_gemm_products(), L.lib.awr_get_gemm_staging(), int(getattr(self, "accum", 0)))
+            cache_key = tile_cache_key(cache_key, L.lib.awr_get_gemm_products(), L.lib.awr_get_gemm_staging(), int(getattr(self, "accum", 0)),
+                                       int(getattr(self, "winograd", 0)))
         names = [self._gemm(i)[0] for i in range(self.n_gemm)]
-        if cache_file and cache_key and os.path.exists(cache_file):
-            try:
-                ent = json.load(open(cache_file)).get(cache_key)
-            except (OSError, ValueError):
-                ent = None
-            if ent and all(n in ent for n in names):
-                for i, n in enumerate(names):
-                    (tm, tn, tb, *rest), t = ent[n]
-                    algo = rest[0] if rest else 0     # (files written before the algorithm was stored: the plan's own choice stays)
-                    if tm and tn:                     # (0, 0): a launch the tuner leaves alone (one-geometry kernels)
-                        L.call("awr_plan_set_gemm", self.h, i, tm, tn, tb, float(t))
-                        if algo:
-                            L.call("awr_plan_set_gemm_algo", self.h, i, algo)
-                    self.tuned[n] = ((tm, tn, tb, algo), t)
+        if cache_file and cache_key:
+            ent = cached_tiles(cache_file, cache_key, names)
+            if ent is not None:
+                self.apply_tuned(ent)
                 return
         L.call("awr_plan_autotune", self.h, int(reps), L.stream())
         for i in range(self.n_gemm):
@@ -365,6 +374,28 @@ class Plan:
                 json.dump(allc, open(cache_file, "w"))
             except OSError:
                 pass
+
+    def apply_tuned(self, tuned):
+        """Set the tile / split-K / algorithm choice of every GEMM launch from {launch name: ((tm, tn, tb[, algo]), us)} -- a cache entry, or the
+        `tuned` record of another instance of the same plan (winograd="auto" rebuilds the plan it chose: no second tuning)."""
+        for i in range(self.n_gemm):
+            n = self._gemm(i)[0]
+            (tm, tn, tb, *rest), t = tuned[n]
+            algo = rest[0] if rest else 0     # (files written before the algorithm was stored: the plan's own choice stays)
+            if tm and tn:                     # (0, 0): a launch the tuner leaves alone (one-geometry kernels)
+                L.call("awr_plan_set_gemm", self.h, i, tm, tn, tb, float(t))
+                if algo:
+                    L.call("awr_plan_set_gemm_algo", self.h, i, algo)
+            self.tuned[n] = ((tm, tn, tb, algo), t)
+
+    def release(self):
+        """Free the plan's native buffers now (not when the garbage collector gets to it: the bucket-hook trampoline holds a reference cycle).
+        The caller removes it from its network's plan table first (AwrBackbone.release_plan)."""
+        self._hook = self._cb = self._dp = None
+        if self.h and self.net._handle.h:
+            L.lib.awr_plan_destroy(self.h)
+        self.h = None
+        self.img = self.outputs = self.grad_outs = None
 
     def __del__(self):
         try:

@@ -154,15 +154,7 @@ class AwrBackbone(nn.Module):
         "auto" blocks the forward launches whose K extent reaches awr_get_gemm_accum_auto()'s threshold, include/awr_hip.h)."""
         if not self._arena.is_cuda:
             raise L.AwrError("the AWR backbone runs on the MI355X only: call .cuda() first (there is no CPU path)")
-        acc = int(L.lib.awr_get_gemm_accum()) if accum is None else {"ordered": 0, "blocked": 1, "auto": 2}[accum]
-        if acc == 2 and not training:
-            acc = 0          # auto never blocks an evaluation plan's launches (include/awr_hip.h): the same plan as "ordered"
-        if acc and (int(L.lib.awr_get_gemm_products()) != 1 or int(L.lib.awr_get_gemm_staging()) == 0):
-            # the blocked kernel exists for the FP32-MFMA mode with LDS-DMA staging only (include/awr_hip.h: awr_conv_args.accum): fail here, at
-            # build time and by name, rather than at the first launch -- "auto" never asks for what cannot run, so it degrades to ordered
-            if acc == 1:
-                raise L.AwrError("blocked accumulation (the parity mode) needs gemm_products = 1 and LDS-DMA staging; this process runs "
-                                 "products = %d, staging = %d" % (L.lib.awr_get_gemm_products(), L.lib.awr_get_gemm_staging()))
+        acc = self.plan_accum(accum, training)
         wino = int(L.lib.awr_get_conv_winograd()) if winograd is None else _winograd_code(winograd)      # captured when the plan is built, like accum
         key = (B, H, bool(training), supervised if isinstance(supervised, str) else tuple(supervised), bn_repeat, n_buckets, L.lib.awr_get_deterministic(), acc,
                _auto_rule() if acc == 2 else 0, wino)
@@ -180,8 +172,29 @@ class AwrBackbone(nn.Module):
             L.call("awr_plan_winograd", plan.h, L.C.byref(nw), L.C.byref(wm))
             plan.n_winograd, plan.winograd_macs = nw.value, wm.value       # launches that run as Winograd F(2x2, 3x3) (forward, data / weight gradients); their algorithmic MACs
             plan.accum = acc          # 0 = ordered, 1 = blocked, 2 = auto (blocked per launch by K extent): what the plan's GEMM launches captured
+            plan.winograd = wino      # the Winograd code the plan was built with (awr_set_conv_winograd)
             self._plans[key] = plan
         return plan
+
+    def release_plan(self, plan):
+        """Drop `plan` from this network's plan table and free its buffers now (winograd="auto" builds its candidate plans one at a time)."""
+        for k in [k for k, p in self._plans.items() if p is plan]:
+            del self._plans[k]
+        self._packed_sig.pop(id(plan), None)
+        plan.release()
+
+    def plan_accum(self, accum, training):
+        """The accumulation code (0 ordered, 1 blocked, 2 auto) a plan built with `accum` captures; raises where it cannot run."""
+        acc = int(L.lib.awr_get_gemm_accum()) if accum is None else {"ordered": 0, "blocked": 1, "auto": 2}[accum]
+        if acc == 2 and not training:
+            acc = 0          # auto never blocks an evaluation plan's launches (include/awr_hip.h): the same plan as "ordered"
+        if acc and (int(L.lib.awr_get_gemm_products()) != 1 or int(L.lib.awr_get_gemm_staging()) == 0):
+            # the blocked kernel exists for the FP32-MFMA mode with LDS-DMA staging only (include/awr_hip.h: awr_conv_args.accum): fail here, at
+            # build time and by name, rather than at the first launch -- "auto" never asks for what cannot run, so it degrades to ordered
+            if acc == 1:
+                raise L.AwrError("blocked accumulation (the parity mode) needs gemm_products = 1 and LDS-DMA staging; this process runs "
+                                 "products = %d, staging = %d" % (L.lib.awr_get_gemm_products(), L.lib.awr_get_gemm_staging()))
+        return acc
 
     def _sig(self):
         # Version counters of the Parameter / buffer OBJECTS, not of the arenas: `_rebind()` re-points `param.data` at arena

@@ -23,6 +23,8 @@ import numpy as np
 import torch
 
 from . import _lib as L
+from . import _engine_winograd, _winograd_code
+from . import winograd_auto as WA
 
 HUBER_DELTA = 0.01
 
@@ -60,7 +62,75 @@ class GradSync:
         return total / count if count else float("nan")
 
 
-class TrainEngine:
+class _WinogradAuto:
+    """winograd="auto" in both engines (winograd_auto.py): resolved at construction when deterministic mode or the decision cache settle it,
+    otherwise by timing the candidate plans one at a time in the engine's one-off set-up (`_wino_search`).  The engine provides `_attach(plan)`,
+    `_wino_plan(mode)`, `_tune_key()`, `_core()` and `_autotune`."""
+
+    def _wino_start(self, training, acc, process_group):
+        """-> the mode to build the engine's first plan with: the resolved one, or (search pending) the first candidate."""
+        self._wino_pg, self._wino_key = process_group, None
+        self._wino_candidates = WA.TRAIN_CANDIDATES if training else WA.INFER_CANDIDATES
+        if L.lib.awr_get_deterministic():
+            self.winograd_timings, self.winograd_source = {"skipped": WA.DETERMINISTIC_REASON}, "deterministic"
+            return "direct"
+        self._wino_key = WA.decision_key(training, type(self.net).__name__ + str(self.net.nstage), self.J, self.B, self.H,
+                                         int(L.lib.awr_get_gemm_products()), int(L.lib.awr_get_gemm_staging()), acc)
+        ent = WA.load_decision(self._wino_key, self._wino_candidates)
+        mode = WA.agree(ent["mode"] if ent else None, self._wino_candidates, process_group, self.net.device)
+        if mode is not None:
+            self.winograd_timings, self.winograd_source = dict(ent["timings"]), "cache"
+            return mode
+        self._wino_pending = True
+        return self._wino_candidates[0]
+
+    def _wino_search(self, restore=None):
+        """Build, warm up, tile-tune and time every distinct candidate -- one plan alive at a time: a candidate this engine built is freed
+        before the next one is built -- and leave the chosen plan attached, with the tile choices it was timed with.  The input batch is
+        carried over to every candidate; restore() (training: the BatchNorm running statistics) runs after each one.  The caller has detached
+        the collectives."""
+        img, tiles = self.plan.img.clone(), {}
+
+        def build(mode):
+            code = _winograd_code(mode)
+            if self.plan.winograd != code:
+                old, self.plan = self.plan, None
+                if id(old) in self._wino_own:
+                    self._wino_own.discard(id(old))
+                    self.net.release_plan(old)
+                del old
+                n0 = len(self.net._plans)
+                plan = self._wino_plan(mode)
+                if len(self.net._plans) > n0:
+                    self._wino_own.add(id(plan))
+                plan.img.copy_(img)
+                self._attach(plan)
+            if not self.plan.training:
+                self.net.sync_weights(self.plan)          # (training passes repack the weights themselves)
+            return self.plan.n_winograd
+
+        def time_ms(mode):
+            self._core()                                  # warm-up: kernels loaded, buffers hold real data
+            if self._autotune and not self.plan.tuned and not self.plan.det:
+                self.plan.autotune(cache_key=self._tune_key())
+            tiles[mode] = dict(self.plan.tuned)
+            ms = WA.time_steps(self._core)
+            if restore is not None:
+                restore()
+            return ms
+
+        mode, timings, n, collapsed = WA.search(self._wino_candidates, build, time_ms, WA.allreduce_max_fn(self._wino_pg, self.net.device))
+        rebuild = self.plan.winograd != _winograd_code(mode)
+        build(mode)
+        if rebuild and tiles.get(mode):
+            self.plan.apply_tuned(tiles[mode])
+        self._winograd, self.winograd_mode = mode, mode
+        self.winograd_timings, self.winograd_source, self._wino_pending = timings, "search", False
+        if self._wino_pg is None or torch.distributed.get_rank(self._wino_pg) == 0:
+            WA.store_decision(self._wino_key, mode, timings, n, collapsed)
+
+
+class TrainEngine(_WinogradAuto):
     def __init__(self, net, batch_size, img_size, kernel_size, coord_weight=0.0, dense_weight=1.0, lr=1e-3, weight_decay=0.0,
                  optimizer="adam", momentum=0.9, process_group=None, use_graph=False, n_buckets=4, autotune=True, wgrad_streams=2,
                  nhwc_boundary=None, trace_buckets=False, native_rccl=None, accum="auto", winograd=None, _share=None):
@@ -68,8 +138,10 @@ class TrainEngine:
         forward / data-gradient GEMMs of this engine's plan.  "blocked" is the parity mode (a conv's rounding error at torch-CPU's level, a few %
         slower); "auto" blocks only the launches with a long K extent (include/awr_hip.h: awr_set_gemm_accum), where an ordered chain's error
         is largest and blocking is cheapest; "ordered" is one chain per output element everywhere.
-        winograd: None (the process-wide mode, awr_amd.set_conv_winograd) | False | True ("forward") | "full" -- Winograd F(2x2, 3x3) forward, or forward +
-        data gradient + weight gradient, of the eligible stride-1 3x3 convolutions (include/awr_hip.h)."""
+        winograd: None (the process-wide mode, awr_amd.set_conv_winograd) | False | True ("forward") | "forward+wgrad" | "full" -- Winograd F(2x2, 3x3)
+        forward, or forward + weight gradient, or forward + data gradient + weight gradient, of the eligible stride-1 3x3 convolutions (include/awr_hip.h)
+        | "auto" -- the fastest of those for this plan, timed by compile() (winograd_auto.py); `winograd_mode` names what the plan runs,
+        `winograd_timings` holds the candidates' ms per step."""
         if not next(net.parameters()).is_cuda:
             raise L.AwrError("TrainEngine needs the network on the GPU")
         self.net, self.B, self.H = net, batch_size, img_size
@@ -85,20 +157,24 @@ class TrainEngine:
         self.dp = world > 1 or (process_group is not None and os.environ.get("AWR_FORCE_DP") == "1")   # test hook: 1-rank group
         # (single GPU: scattering the packed weight gradients bucket by bucket during the backward, like the data-parallel plans do, instead
         # of in one launch at the tail of the step was measured slower: 14.28-14.32 vs 14.00-14.05 ms, profiles/r03_summary.md)
-        self.plan = net.get_plan(batch_size, img_size, True, supervised=(self.stage,), bn_repeat=net.nstage,
-                                 n_buckets=n_buckets if self.dp else 1, accum=accum, winograd=winograd)
-        self._accum, self._winograd = accum, winograd
-        # weight-gradient GEMMs on extra HIP stream(s): co-resident DIFFERENT kernels fill each other's bubbles (0 = off); data
-        # parallel: one more stream that finished gradient buckets (scatter + all-reduce) are handed to
-        self.plan.set_streams(wgrad_streams, comm=(wgrad_streams > 0 and self.dp))
+        self._plan_kw = dict(supervised=(self.stage,), bn_repeat=net.nstage, n_buckets=n_buckets if self.dp else 1, accum=accum)
+        self._wgrad_streams = wgrad_streams
         # head + losses on the backbone's own NHWC layout (no transposes at the boundary, the dense map read once per step when
         # coord_weight == 0); AWR_NCHW_BOUNDARY=1 / nhwc_boundary=False keeps the reference-layout kernels (same-box A/B)
         import os as _os
-        want_nhwc = (_os.environ.get("AWR_NCHW_BOUNDARY") != "1") if nhwc_boundary is None else bool(nhwc_boundary)
-        self.nhwc = want_nhwc and self.plan.set_nhwc_boundary(True)
-        if self.nhwc:
-            self._pred, self._gpred, self._cp = self.plan.head_nhwc(self.stage)
-            self._scratch = torch.zeros(int(L.lib.awr_head_nhwc_scratch(batch_size, self.J, self.F)), device=dev)
+        self._want_nhwc = (_os.environ.get("AWR_NCHW_BOUNDARY") != "1") if nhwc_boundary is None else bool(nhwc_boundary)
+        self._scratch = None
+        self._accum = accum
+        self.winograd_timings, self.winograd_source = None, None
+        self._wino_pending = False
+        winograd = _engine_winograd(winograd)
+        if winograd == "auto":          # (ragged-batch children are handed the parent's resolved mode: _ragged)
+            winograd = self._wino_start(True, net.plan_accum(accum, True), process_group)
+        self._winograd = winograd
+        n0 = len(net._plans)
+        self._attach(net.get_plan(batch_size, img_size, True, winograd=winograd, **self._plan_kw))
+        self._wino_own = {id(self.plan)} if len(net._plans) > n0 else set()       # plans this engine built (a candidate search may free them)
+        self.winograd_mode = WA.mode_name(self.plan.winograd) if self.plan.n_winograd else "direct"
         self._autotune = bool(autotune)
         self._compiled = False
         self.jt_gt = torch.zeros(batch_size, self.J, 3, device=dev)
@@ -152,6 +228,24 @@ class TrainEngine:
                     self._trace.append((lo, hi, e0, e1))
             if self.dpcomm is None:
                 self.plan.bucket_hook = hook
+
+    def _attach(self, plan):
+        """Make `plan` the engine's plan: side streams, NHWC boundary, head pointers (collectives: __init__ / compile())."""
+        self.plan = plan
+        # weight-gradient GEMMs on extra HIP stream(s): co-resident DIFFERENT kernels fill each other's bubbles (0 = off); data
+        # parallel: one more stream that finished gradient buckets (scatter + all-reduce) are handed to
+        plan.set_streams(self._wgrad_streams, comm=(self._wgrad_streams > 0 and self.dp))
+        self.nhwc = self._want_nhwc and plan.set_nhwc_boundary(True)
+        if self.nhwc:
+            self._pred, self._gpred, self._cp = plan.head_nhwc(self.stage)
+            if self._scratch is None:
+                self._scratch = torch.zeros(int(L.lib.awr_head_nhwc_scratch(self.B, self.J, self.F)), device=self.net.device)
+
+    def _wino_plan(self, mode):
+        return self.net.get_plan(self.B, self.H, True, winograd=mode, **self._plan_kw)
+
+    def _tune_key(self):
+        return "train/%s/J%d/B%d/H%d" % (type(self.net).__name__ + str(self.net.nstage), self.J, self.B, self.H)
 
     # ---- the captured part: repack -> forward -> head + losses -> backward -------------------------------
     def _core(self):
@@ -269,6 +363,8 @@ class TrainEngine:
         (the reference's DataLoader keeps the ragged last batch, train.py:109 drop_last=False)."""
         eng = self._children.get(b)
         if eng is None:
+            if self._wino_pending:          # winograd="auto": the child runs the mode the parent chose (its own plan is not timed)
+                self.compile()
             eng = TrainEngine(self.net, b, self.H, self.ks, self.cw, self.dw, self.lr, self.wd, self.opt, self.momentum,
                               process_group=self.sync.pg, use_graph=False, n_buckets=self._n_buckets, autotune=False,
                               wgrad_streams=0, accum=self._accum, winograd=self._winograd, _share=self)
@@ -307,7 +403,7 @@ class TrainEngine:
             raise
         if self.trace_buckets:
             self._tev[1].record()
-        self.net._counters += plan.bn_repeat          # num_batches_tracked of every BatchNorm (host side)
+        self.net._counters += self.plan.bn_repeat          # num_batches_tracked of every BatchNorm (host side)
         if self.dp:
             for w in self._works:           # compute stream waits for the bucket all-reduces before the optimiser
                 w.wait()
@@ -322,7 +418,9 @@ class TrainEngine:
         input buffers (kernel warm-up; its only side effect -- the BatchNorm running statistics -- is rolled back), times the GEMM
         tile candidates of every launch in place (engine.Plan.autotune) and captures repack + forward + head + losses + backward,
         with the weight-gradient side streams forked and joined inside the capture, as ONE hipGraph.  `step()` calls it on its
-        first use; call it directly (optionally with a representative batch) to keep that cost out of the first step."""
+        first use; call it directly (optionally with a representative batch) to keep that cost out of the first step.
+        winograd="auto" (not settled by the decision cache): first builds and times every distinct candidate plan the same way, one at a
+        time, and keeps the chosen one (winograd_auto.py) -- parameters, BatchNorm statistics, optimiser state and inputs are left as they were."""
         if self._compiled:
             return
         if img is not None:
@@ -330,21 +428,25 @@ class TrainEngine:
             self.jt_gt.copy_(jt_uvd_gt, non_blocking=True)
         self._compiled = True
         tune = self._autotune and not self.plan.tuned and not self.plan.det
-        if not (self.use_graph or tune):
+        if not (self.use_graph or tune or self._wino_pending):
             return
         hook, self.plan.bucket_hook = self.plan.bucket_hook, None          # no collectives during set-up
         dpc = getattr(self, "dpcomm", None)
         if dpc is not None:
             self.plan.set_dp(None)
         keep = self.net._barena.clone()
-        self._core()
-        if tune:
-            self.plan.autotune(cache_key="train/%s/J%d/B%d/H%d" % (type(self.net).__name__ + str(self.net.nstage), self.J, self.B, self.H))
-        if self.use_graph:
-            torch.cuda.synchronize()
-            self.graph = torch.cuda.CUDAGraph()
-            with torch.cuda.graph(self.graph):
-                self._core()
+        if self._wino_pending:
+            self._wino_search(restore=lambda: self.net._barena.copy_(keep))
+            tune = self._autotune and not self.plan.tuned and not self.plan.det
+        if self.use_graph or tune:
+            self._core()
+            if tune:
+                self.plan.autotune(cache_key=self._tune_key())
+            if self.use_graph:
+                torch.cuda.synchronize()
+                self.graph = torch.cuda.CUDAGraph()
+                with torch.cuda.graph(self.graph):
+                    self._core()
         self.net._barena.copy_(keep)
         self.plan.bucket_hook = hook
         if dpc is not None:
@@ -402,14 +504,15 @@ def _load_opt_into(engine, sd):
 TrainEngine.load_optimizer_state_dict = lambda self, sd: _load_opt_into(self, sd)
 
 
-class InferEngine:
+class InferEngine(_WinogradAuto):
     """test.py:67-86 without the per-sample host loop: img -> dense map -> joints, eval-mode BN."""
 
     def __init__(self, net, batch_size, img_size, kernel_size, use_graph=False, autotune=True, parity=False, winograd=None):
         """parity=True: blocked accumulation in the GEMMs of this engine's plan (awr_amd.set_gemm_accum) -- scoring passes (test.py:67-86) care
         about the last digits of the joints, not about the last few per cent of throughput.
         winograd: None (the process-wide mode, awr_amd.set_conv_winograd) | False | True -- the eligible stride-1 3x3 convolutions of the eval plan as
-        Winograd F(2x2, 3x3) with the folded BatchNorm / residual add in its epilogue (Hourglass: instead of the fused conv2 + conv3 launch)."""
+        Winograd F(2x2, 3x3) with the folded BatchNorm / residual add in its epilogue (Hourglass: instead of the fused conv2 + conv3 launch) | "auto" --
+        "direct" or "forward", whichever the first call times faster (winograd_auto.py; `winograd_mode`, `winograd_timings`)."""
         self.net, self.B, self.H, self.ks = net, batch_size, img_size, float(kernel_size)
         self.parity = bool(parity)
         if self.parity and (int(L.lib.awr_get_gemm_products()) != 1 or int(L.lib.awr_get_gemm_staging()) == 0):
@@ -420,19 +523,40 @@ class InferEngine:
                           "scoring with ordered accumulation" % (L.lib.awr_get_gemm_products(), L.lib.awr_get_gemm_staging()))
             self.parity = False
         net.eval()
-        self.plan = net.get_plan(batch_size, img_size, False, accum="blocked" if self.parity else None, winograd=winograd)
-        if self.plan.n_side == 0:          # forward branches (ResNet downsample projections, Hourglass skip residuals) run beside the main chain
-            self.plan.set_streams(4)
-        self._autotune, self._compiled = bool(autotune), False
         self.J, self.F = net.J, img_size // getattr(net, "downsample", 2)
-        self.jt = torch.zeros(batch_size, self.J, 3, device=net.device)
         self.stage = net.nstage - 1
-        self.use_graph, self.graph = use_graph, None
         import os as _os
-        self.nhwc = _os.environ.get("AWR_NCHW_BOUNDARY") != "1" and self.plan.set_nhwc_boundary(True)
+        self._want_nhwc, self._scratch = _os.environ.get("AWR_NCHW_BOUNDARY") != "1", None
+        self._accum = "blocked" if self.parity else None
+        self.winograd_timings, self.winograd_source = None, None
+        self._wino_pending = False
+        winograd = _engine_winograd(winograd)
+        if winograd == "auto":
+            winograd = self._wino_start(False, net.plan_accum(self._accum, False), None)
+        self._winograd = winograd
+        n0 = len(net._plans)
+        self._attach(net.get_plan(batch_size, img_size, False, accum=self._accum, winograd=winograd))
+        self._wino_own = {id(self.plan)} if len(net._plans) > n0 else set()
+        self.winograd_mode = WA.mode_name(self.plan.winograd, training=False) if self.plan.n_winograd else "direct"
+        self._autotune, self._compiled = bool(autotune), False
+        self.jt = torch.zeros(batch_size, self.J, 3, device=net.device)
+        self.use_graph, self.graph = use_graph, None
+
+    def _attach(self, plan):
+        self.plan = plan
+        if plan.n_side == 0:          # forward branches (ResNet downsample projections, Hourglass skip residuals) run beside the main chain
+            plan.set_streams(4)
+        self.nhwc = self._want_nhwc and plan.set_nhwc_boundary(True)
         if self.nhwc:
-            self._pred, _, self._cp = self.plan.head_nhwc(self.stage)
-            self._scratch = torch.zeros(int(L.lib.awr_head_nhwc_scratch(batch_size, self.J, self.F)), device=net.device)
+            self._pred, _, self._cp = plan.head_nhwc(self.stage)
+            if self._scratch is None:
+                self._scratch = torch.zeros(int(L.lib.awr_head_nhwc_scratch(self.B, self.J, self.F)), device=self.net.device)
+
+    def _wino_plan(self, mode):
+        return self.net.get_plan(self.B, self.H, False, accum=self._accum, winograd=mode)
+
+    def _tune_key(self):
+        return "infer/%s/J%d/B%d/H%d" % (type(self.net).__name__ + str(self.net.nstage), self.J, self.B, self.H)
 
     def _core(self):
         plan = self.plan
@@ -449,13 +573,15 @@ class InferEngine:
     def __call__(self, img):
         self.net.sync_weights(self.plan)
         self.plan.img.copy_(img, non_blocking=True)
-        if not self._compiled:           # one-off: eager warm-up run, GEMM tile autotune, hipGraph capture
+        if not self._compiled:           # one-off: [winograd="auto": the candidate plans timed,] eager warm-up run, GEMM tile autotune, hipGraph capture
             self._compiled = True
+            if self._wino_pending:
+                self._wino_search()
             tune = self._autotune and not self.plan.tuned and not self.plan.det
             if self.use_graph or tune:
                 self._core()
                 if tune:
-                    self.plan.autotune(cache_key="infer/%s/J%d/B%d/H%d" % (type(self.net).__name__ + str(self.net.nstage), self.J, self.B, self.H))
+                    self.plan.autotune(cache_key=self._tune_key())
                 if self.use_graph:
                     torch.cuda.synchronize()
                     self.graph = torch.cuda.CUDAGraph()
@@ -589,6 +715,8 @@ class Trainer:
                                   config.lr, config.weight_decay, config.optimizer, process_group=process_group,
                                   use_graph=getattr(config, "use_hipgraph", False), accum=getattr(config, "accum", "auto"),
                                   winograd=getattr(config, "winograd", None))
+        # winograd="auto": the training step's choice is logged once; the scoring engine's is reused by every later test pass
+        self._wino_logged, self._infer_winograd = False, None
         if config.load_model and os.path.exists(config.load_model):
             self._msg("loading model from {}".format(config.load_model))
             pth = torch.load(config.load_model, map_location="cpu", weights_only=False)     # trusted project artefact (best_records may hold numpy scalars)
@@ -655,6 +783,10 @@ class Trainer:
                 return (t[:3] / t[3]).tolist()
             for ii, (img, jt_xyz_gt, jt_uvd_gt, center_xyz, M, cube) in enumerate(self._loader(self.trainData, True, epoch)):
                 losses, jt_pred = eng.step(self._images(img, "train"), jt_uvd_gt.cuda(non_blocking=True))
+                if not self._wino_logged and eng.winograd_source is not None:      # winograd="auto": what the first step chose
+                    self._wino_logged = True
+                    self._msg("winograd: auto -> {} ({}; {})".format(eng.winograd_mode, eng.winograd_source, ", ".join(
+                        "{} {:.3f} ms".format(k, v) if isinstance(v, float) else "{}: {}".format(k, v) for k, v in eng.winograd_timings.items())))
                 lsum += losses                                      # device-side meter: no loss.item() per iteration
                 lcnt += 1
                 pend.append((jt_pred.clone(), jt_xyz_gt, center_xyz, M, cube))
@@ -700,8 +832,11 @@ class Trainer:
         cfg = self.config
         world = torch.distributed.get_world_size(self.pg) if self.pg is not None else 1
         # config.parity_infer = True scores with blocked accumulation (eval-mode plans measure no gain from it: off by default since round 6)
+        wino = getattr(cfg, "winograd", None)
+        if isinstance(wino, str) and wino == "auto" and self._infer_winograd is not None:
+            wino = self._infer_winograd
         inf = self._last_infer = InferEngine(self.net, cfg.batch_size, cfg.img_size, cfg.kernel_size, use_graph=False,
-                                             parity=bool(getattr(cfg, "parity_infer", False)), winograd=getattr(cfg, "winograd", None))
+                                             parity=bool(getattr(cfg, "parity_infer", False)), winograd=wino)
         ev = self.EvalUtil(self.testData.img_size, self.testData.paras, self.testData.flip, self.testData.jt_num)
         n, bs = len(self.testData), cfg.batch_size
         mine = [b for b in range((n + bs - 1) // bs) if b % world == self.rank]
@@ -728,6 +863,8 @@ class Trainer:
                 self._vis.plot(img[0].numpy(), os.path.join(self.result_dir, "test_epoch_{}_iter_{}.png".format(epoch, ib)),
                                (jt[0] + 1) * half, (jt_uvd_gt[0].numpy() + 1) * half)
         self.net.train()
+        if inf.winograd_source is not None and not inf._wino_pending:
+            self._infer_winograd = inf.winograd_mode
         if world > 1:          # every rank ends up with the whole test set, in dataset order
             J = self.testData.jt_num
             err = np.concatenate(ev._err, 0) if ev._err else np.zeros((0, J), np.float32)
