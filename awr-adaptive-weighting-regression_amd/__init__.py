@@ -76,6 +76,27 @@ def _engine_winograd(on):
     return _winograd_code(on)
 
 
+def _split_k_flag(on):
+    """False / True are the only values of the training split-K option (TrainEngine(split_k=...), config.train_split_k, set_train_split_k);
+    anything else -- strings, integers, None -- is an error: an unknown value is never read as "on"."""
+    if not isinstance(on, bool):
+        raise ValueError("split_k / train_split_k is False or True, not %r" % (on,))
+    return on
+
+
+def set_train_split_k(on):
+    """Process-wide: TRAINING plans built afterwards split the K loop of their small forward / data-gradient launches and take the BatchNorm
+    statistics and the fused BatchNorm-backward reductions from the reduce kernel (include/awr_hip.h: awr_set_train_split_k).
+    Default off (or $AWR_TRAIN_SPLIT_K); TrainEngine(split_k=True) / config.train_split_k set it per engine."""
+    from . import _lib as L
+    L.call("awr_set_train_split_k", int(_split_k_flag(on)))
+
+
+def get_train_split_k():
+    from . import _lib as L
+    return bool(L.lib.awr_get_train_split_k())
+
+
 def get_conv_winograd():
     from . import _lib as L
     return int(L.lib.awr_get_conv_winograd())

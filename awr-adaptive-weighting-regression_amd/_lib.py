@@ -136,6 +136,9 @@ _SIGS = {
     "awr_set_gemm_accum_auto": ([_I, _I], C.c_int),
     "awr_get_gemm_accum_auto": ([C.POINTER(_I), C.POINTER(_I)], C.c_int),
     "awr_resolve_gemm_accum": ([_I, _I], C.c_int),
+    "awr_conv_split_depth": ([_P, C.POINTER(_I)], C.c_int),
+    "awr_set_train_split_k": ([_I], C.c_int),
+    "awr_get_train_split_k": ([], C.c_int),
     "awr_stem_im2col": ([_P, _I, _I, _I, _P, _P], C.c_int),
     "awr_stem_stats": ([_P, _P, _P, _I, _I, _I, _P, _I, _P], C.c_int),
     "awr_stem_conv": ([_P, _P, _P, _P, _P, _I, _I, _I, _I, _P, _P], C.c_int),

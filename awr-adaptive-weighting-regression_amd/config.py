@@ -30,6 +30,8 @@ _MI355X = dict(use_hipgraph=False,    # True: replay each step as one hipGraph (
                winograd=None,         # Winograd F(2x2, 3x3) forward of the stride-1 3x3 convolutions: None = the process-wide mode (awr_amd.set_conv_winograd,
                                       # $AWR_WINOGRAD), False / True (forward) / "full" (forward + data and weight gradients) = this run's own (the scoring pass takes the forward form),
                                       # "auto" = each engine times the modes on its own plan and keeps the fastest (logged at the first step)
+               train_split_k=False,   # True: the training plan's small forward / data-gradient launches split their K loop, BatchNorm statistics from the reduce
+                                      # kernel (TrainEngine(split_k=...)).  False = the process-wide mode (off unless $AWR_TRAIN_SPLIT_K).  Nothing else is accepted
                device_loader=True)    # NYU datasets built from this config keep their decoded frames in HBM and crop / augment / normalise on the
                                       # GPU (awr_amd.nyu_device: bit-identical to the host loader nyu_data.NYU, which False selects)
 
@@ -45,6 +47,8 @@ class Config(object):
             raise AttributeError("unknown config entries: %s" % sorted(unknown))
         for k, v in overrides.items():
             setattr(self, k, v)
+        if not isinstance(self.train_split_k, bool):
+            raise ValueError("train_split_k is False or True, not %r" % (self.train_split_k,))
         if self.dataset not in _DATASETS:
             raise ValueError("dataset must be one of %s" % sorted(_DATASETS))
         for k, v in zip(_DERIVED, _DATASETS[self.dataset]):

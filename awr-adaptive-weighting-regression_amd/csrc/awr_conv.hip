@@ -20,6 +20,7 @@ int g_staging = env_int("AWR_DMA", 2);
 int g_accum = env_int("AWR_ACCUM", 2);      // auto
 int g_accum_auto_k = 576;       // accum = 2 (auto): launches whose K extent reaches this many terms accumulate blocked ...
 int g_accum_auto_dgrad = 0;      // ... forward launches only (0) or data gradients too (1)
+int g_train_split_k = env_int("AWR_TRAIN_SPLIT_K", 0) != 0;      // training plans give their small forward / data-gradient launches split-K scratch (read per plan)
 // launch-path knobs, read ONCE (a getenv per launch is neither cheap nor safe against a concurrent setenv); tests and same-box A/Bs flip them
 // through awr_debug_set_knob
 int g_knob_deep = env_int("AWR_DEEP", 1), g_knob_deep_1x1 = env_int("AWR_DEEP_1X1", 0), g_knob_fast_stats = env_int("AWR_FAST_STATS", 1);
@@ -101,6 +102,14 @@ int awr_get_gemm_accum_auto(int* min_k, int* dgrad) {
     return AWR_OK;
 }
 
+int awr_set_train_split_k(int on) {
+    AWR_REQUIRE(on == 0 || on == 1, "train_split_k: 0 (off) or 1 (on)");
+    g_train_split_k = on;
+    return AWR_OK;
+}
+
+int awr_get_train_split_k(void) { return g_train_split_k; }
+
 int awr_resolve_gemm_accum(int k_extent, int kind) {
     if (g_accum != 2) return g_accum;
     if (kind != AWR_GEMM_FORWARD && !(kind == AWR_GEMM_DGRAD && g_accum_auto_dgrad)) return 0;
@@ -173,6 +182,65 @@ int awr_conv_gemm_part(const awr_conv_args* a, int nparts, int part, void* strea
 }
 #endif
 
+// The workgroup tile and the split-K depth one launch runs with -- shared by conv_gemm_one and awr_conv_split_depth (what a plan reports per launch).
+static int conv_tile_and_depth(const awr_conv_args* a, int& TM, int& TN, int& S) {
+    const int64_t M = (int64_t)a->B * a->Hq * a->Wq;
+    // Tile choice (measured, tools/microbench_gemm.py): 64-row tiles win on every ResNet18/Hourglass layer shape --
+    // 3-4 workgroups per CU de-synchronise prologue/epilogue bubbles that two lock-stepped 128x128 workgroups
+    // expose, and the extra L2 traffic is free at FP32-MFMA rates.  128 columns when N allows and the grid stays
+    // >= 2 workgroups per CU, else 64x64.
+    auto blocks = [&](int tm, int tn) { return ((M + 64 * tm - 1) / (64 * tm)) * ((a->N + 64 * tn - 1) / (64 * tn)) * a->nphase; };
+    TM = 1; TN = (a->N > 64 && blocks(1, 2) >= 512) ? 2 : 1;
+    if (a->Cin * a->ph[0].ntaps <= 64) TM = 2;     // one or two K-slices (the im2col'd stem): store-bound, amortise the epilogue
+    if (a->tile_m) {
+        AWR_REQUIRE((a->tile_m == 1 || a->tile_m == 2) && (a->tile_n == 1 || a->tile_n == 2), "conv_gemm: tile_m/tile_n must be 1 or 2");
+        TM = a->tile_m;
+        TN = a->tile_n;
+    }
+    if (g_force_tm) { TM = g_force_tm; TN = g_force_tn; }
+    // split-K: few workgroups with a long K loop (low-batch inference: a layer4 conv at batch 4 is 32 workgroups x 144 slices; the small launches
+    // of a training plan built under awr_set_train_split_k).  The launch's own epilogue -- BatchNorm statistics, the fused BatchNorm-backward
+    // reductions included -- runs in the reduce kernel.  Excluded: a second input tensor, the fused pair, an un-materialised BatchNorm-backward
+    // input, the split-operand product mode / a pre-cut input image, a launch that does not cover every output pixel (the reduce pass reads whole
+    // copies), and a blocked launch (accum = 1) whose nominal K range, ceil(slices / S), would be shorter than one 128-k block.
+    S = 1;
+    const bool train_epi = a->stats || a->bnr_y;
+    const bool covered = a->so == 1 || a->nphase == a->so * a->so;
+    int minsteps = a->ph[0].ntaps;
+    for (int p = 1; p < a->nphase; ++p) minsteps = a->ph[p].ntaps < minsteps ? a->ph[p].ntaps : minsteps;
+    minsteps *= a->Cin / BK;
+    if (a->split_k > 1) {       // an explicit depth the launch cannot honour is an error that names the reason; nothing is launched
+        AWR_REQUIRE(a->partial && a->split_max > 1, "conv_gemm: split_k=%d needs `partial` scratch (split_max copies of the output)", a->split_k);
+        AWR_REQUIRE(!a->in2, "conv_gemm: split_k excludes a second input tensor (in2)");
+        AWR_REQUIRE(!a->in_split, "conv_gemm: split_k excludes a pre-cut input image (in_split: the split-operand mode)");
+        AWR_REQUIRE(g_products == 1 || !train_epi, "conv_gemm: split_k with a statistics / BatchNorm-backward epilogue needs the FP32-MFMA mode "
+                    "(the split-operand product mode has no split-K form)");
+        AWR_REQUIRE(covered, "conv_gemm: split_k needs a launch that covers every output pixel (%d of %d phases)", a->nphase, a->so * a->so);
+    }
+    if (a->partial && a->split_max > 1 && g_products == 1 && !a->in2 && !a->in_bnb_y && !a->in_split && covered) {
+        if (a->split_k > 0) {
+            S = a->split_k;
+        } else {      // heuristic: fill ~2 workgroups per CU, keep >= 8 slices per range
+            const int64_t nb = blocks(TM, TN);
+            while (S * 2 <= a->split_max && nb * S * 2 <= 512 && minsteps / (S * 2) >= 8) S *= 2;
+        }
+        AWR_REQUIRE(S >= 1 && S <= a->split_max, "conv_gemm: split_k=%d exceeds split_max=%d", S, a->split_max);
+    }
+    if (S > 1 && a->accum == 1) {
+        // the accumulation rule (awr_hip.h): every K range is itself blocked and the ordered sum over the copies is the outer fold --
+        // admissible while the NOMINAL range, ceil(slices / S) slices, holds at least one whole 128-k block, so that the split adds no more outer
+        // terms than blocking has (the last range is what is left over and may be shorter: a shorter chain)
+        int maxsteps = a->ph[0].ntaps;
+        for (int p = 1; p < a->nphase; ++p) maxsteps = a->ph[p].ntaps > maxsteps ? a->ph[p].ntaps : maxsteps;
+        const int per = (minsteps + S - 1) / S;
+        AWR_REQUIRE(per * BK >= 128, "conv_gemm: blocked accumulation (accum = 1) admits split_k=%d only while the nominal K range holds a whole 128-k block "
+                    "(this launch: ceil(slices / split_k) = %d k per range of a K extent of %d)", S, per * BK, maxsteps * BK);
+    }
+    if (a->accum == 1 && S == 1)
+        AWR_REQUIRE(g_staging != 0, "conv_gemm: accum = 1 (blocked accumulation) needs LDS-DMA staging for an unsplit launch");
+    return AWR_OK;
+}
+
 static int conv_gemm_one(const awr_conv_args* a_in, void* stream) {
     // output-store policy (awr_conv_args.out_nt): 0 = automatic -> streaming (`buffer_store ... nt`, the epilogue's operand loads too) when the output tensor is
     // at least as large as the 256 MB Infinity Cache -- its consumer fetches it from HBM either way -- and the K extent is short (<= 512: the launches whose
@@ -205,8 +273,9 @@ static int conv_gemm_one(const awr_conv_args* a_in, void* stream) {
     AWR_REQUIRE(!a->in_bnb_y || !a->stats || a->bnr_y, "conv_gemm: an un-materialised BatchNorm-backward input (in_bnb_y) has no statistics-only epilogue");
     AWR_REQUIRE(!(a->in2 && !a->w2 && a->bnr_y), "conv_gemm: the two-tensor K extent (in2) has no fused BatchNorm-backward reduction epilogue");
     // blocked accumulation is a property of the LDS-DMA kernel: fail instead of returning ordered results under the parity flag
-    AWR_REQUIRE(a->accum == 0 || (g_products == 1 && g_staging != 0 && !a->w2 && !(a->partial && (a->split_k > 1 || a->split_max > 1))),
-                "conv_gemm: accum = 1 (blocked accumulation) needs the FP32-MFMA mode with LDS-DMA staging and no fused pair / split-K scratch");
+    // (a split launch honours accum = 1 in its own kernel form, whatever the staging mode: the rule is enforced where the depth is known, below)
+    AWR_REQUIRE(a->accum == 0 || (g_products == 1 && !a->w2 && (g_staging != 0 || (a->partial && a->split_max > 1))),
+                "conv_gemm: accum = 1 (blocked accumulation) needs the FP32-MFMA mode with LDS-DMA staging (or split-K scratch) and no fused pair");
     AWR_REQUIRE(!a->bnr2_y || (a->bnr_y && a->bnr2_coef && a->stats2), "conv_gemm: a second fused reduction (bnr2_y) needs bnr_y, bnr2_coef and stats2");
     AWR_REQUIRE((a->in_scale == nullptr) == (a->in_shift == nullptr), "conv_gemm: in_scale/in_shift must come together");
     AWR_REQUIRE((a->out_scale == nullptr) == (a->out_shift == nullptr), "conv_gemm: out_scale/out_shift must come together");
@@ -252,45 +321,30 @@ static int conv_gemm_one(const awr_conv_args* a_in, void* stream) {
     }
     AWR_REQUIRE((int64_t)a->B * a->Hin * a->Win * a->Cin * 4 < (1LL << 32) && (int64_t)a->B * a->Hout * a->Wout * a->N * 4 < (1LL << 32),
                 "conv_gemm: tensors must stay below 4 GB (32-bit buffer offsets)");
-    // Tile choice (measured, tools/microbench_gemm.py): 64-row tiles win on every ResNet18/Hourglass layer shape --
-    // 3-4 workgroups per CU de-synchronise prologue/epilogue bubbles that two lock-stepped 128x128 workgroups
-    // expose, and the extra L2 traffic is free at FP32-MFMA rates.  128 columns when N allows and the grid stays
-    // >= 2 workgroups per CU, else 64x64.
+    int TM, TN, S;
+    if (int e = conv_tile_and_depth(a, TM, TN, S)) return e;
     auto blocks = [&](int tm, int tn) { return ((M + 64 * tm - 1) / (64 * tm)) * ((a->N + 64 * tn - 1) / (64 * tn)) * a->nphase; };
-    int TM = 1, TN = (a->N > 64 && blocks(1, 2) >= 512) ? 2 : 1;
-    if (a->Cin * a->ph[0].ntaps <= 64) TM = 2;     // one or two K-slices (the im2col'd stem): store-bound, amortise the epilogue
-    if (a->tile_m) {
-        AWR_REQUIRE((a->tile_m == 1 || a->tile_m == 2) && (a->tile_n == 1 || a->tile_n == 2), "conv_gemm: tile_m/tile_n must be 1 or 2");
-        TM = a->tile_m;
-        TN = a->tile_n;
-    }
-    if (g_force_tm) { TM = g_force_tm; TN = g_force_tn; }
     hipStream_t st = as_stream(stream);
-    // split-K: few workgroups with a long K loop (low-batch inference: a layer4 conv at batch 4 is 32 workgroups x 144 slices)
-    int S = 1;
-    if (a->partial && a->split_max > 1 && g_products == 1 && !a->in2 && !a->stats && !a->bnr_y) {
-        int minsteps = a->ph[0].ntaps;
-        for (int p = 1; p < a->nphase; ++p) minsteps = a->ph[p].ntaps < minsteps ? a->ph[p].ntaps : minsteps;
-        minsteps *= a->Cin / BK;
-        if (a->split_k > 0) {
-            S = a->split_k;
-        } else {      // heuristic: fill ~2 workgroups per CU, keep >= 8 slices per range
-            const int64_t nb = blocks(TM, TN);
-            while (S * 2 <= a->split_max && nb * S * 2 <= 512 && minsteps / (S * 2) >= 8) S *= 2;
-        }
-        AWR_REQUIRE(S >= 1 && S <= a->split_max, "conv_gemm: split_k=%d exceeds split_max=%d", S, a->split_max);
-    } else {      // (the split-operand mode ignores a split-K request: a plan keeps its scratch and depth across mode switches)
-        AWR_REQUIRE(a->split_k <= 1 || (a->partial && a->split_max > 1 && !a->in2 && !a->stats && !a->bnr_y),
-                    "conv_gemm: split_k needs `partial` scratch and no stats / bnr_y / in2");
-    }
     if (S > 1) {
         const dim3 grid((unsigned)(blocks(TM, TN) / a->nphase), a->nphase, S);
-        if (TM == 2 && TN == 2) hipLaunchKernelGGL((conv_gemm_kernel<2, 2, 0, false, false, true>), grid, dim3(256), 0, st, *a);
+        if (a->accum == 1) {
+            if (TM == 2 && TN == 2) hipLaunchKernelGGL((conv_gemm_split_blocked_kernel<2, 2>), grid, dim3(256), 0, st, *a);
+            else if (TM == 2 && TN == 1) hipLaunchKernelGGL((conv_gemm_split_blocked_kernel<2, 1>), grid, dim3(256), 0, st, *a);
+            else if (TM == 1 && TN == 2) hipLaunchKernelGGL((conv_gemm_split_blocked_kernel<1, 2>), grid, dim3(256), 0, st, *a);
+            else hipLaunchKernelGGL((conv_gemm_split_blocked_kernel<1, 1>), grid, dim3(256), 0, st, *a);
+        } else if (TM == 2 && TN == 2) hipLaunchKernelGGL((conv_gemm_kernel<2, 2, 0, false, false, true>), grid, dim3(256), 0, st, *a);
         else if (TM == 2 && TN == 1) hipLaunchKernelGGL((conv_gemm_kernel<2, 1, 0, false, false, true>), grid, dim3(256), 0, st, *a);
         else if (TM == 1 && TN == 2) hipLaunchKernelGGL((conv_gemm_kernel<1, 2, 0, false, false, true>), grid, dim3(256), 0, st, *a);
         else hipLaunchKernelGGL((conv_gemm_kernel<1, 1, 0, false, false, true>), grid, dim3(256), 0, st, *a);
         if (int e = check_launch("conv_gemm_kernel<split>")) return e;
         const int64_t numel = (int64_t)a->B * a->Hout * a->Wout * a->N, n4 = numel / 4;
+        if (a->stats || a->bnr_y) {      // statistics / BatchNorm-backward reductions: the reduce kernel that carries the training epilogues
+            const int npix = (int)(numel / a->N);
+            const dim3 rgrid((unsigned)((npix + 63) / 64), (unsigned)((a->N + 63) / 64));
+            if (a->bnr_y) hipLaunchKernelGGL(splitk_reduce_epi_kernel<true>, rgrid, dim3(256), 0, st, *a, S, npix);
+            else hipLaunchKernelGGL(splitk_reduce_epi_kernel<false>, rgrid, dim3(256), 0, st, *a, S, npix);
+            return check_launch("splitk_reduce_epi_kernel");
+        }
         hipLaunchKernelGGL(splitk_reduce_kernel, dim3((unsigned)((n4 + 255) / 256)), dim3(256), 0, st, a->partial, S, numel, a->bias, a->out_scale, a->out_shift,
                            a->res, a->relu_out, n4, a->N / 4, a->out);
         return check_launch("splitk_reduce_kernel");
@@ -354,6 +408,17 @@ static int conv_gemm_one(const awr_conv_args* a_in, void* stream) {
     else AWR_LAUNCH_GEMM(1, 1);
 #undef AWR_LAUNCH_GEMM
     return check_launch("conv_gemm_kernel");
+}
+
+int awr_conv_split_depth(const awr_conv_args* a, int* depth) {
+    AWR_REQUIRE(a && depth, "conv_split_depth: null pointer");
+    *depth = 1;
+    if (a->w2 || !a->partial || a->split_max <= 1) return AWR_OK;
+    AWR_REQUIRE(a->Cin > 0 && a->Cin % BK == 0 && a->nphase >= 1 && a->nphase <= 4 && a->N > 0, "conv_split_depth: bad geometry");
+    int TM, TN, S;
+    if (int e = conv_tile_and_depth(a, TM, TN, S)) return e;
+    *depth = S;
+    return AWR_OK;
 }
 
 }  // extern "C"

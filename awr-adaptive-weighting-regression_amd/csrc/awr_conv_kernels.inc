@@ -617,9 +617,13 @@ __device__ __forceinline__ void gemm_epilogue_direct(const awr_conv_args& a, con
 // applied in registers, the tile goes to LDS as the A operand of a second, 1x1 GEMM (w2: [N][128]) whose result gets the ordinary epilogue
 // (bias2, residual) -- the hourglass residual's conv2 (3x3) -> bn3 -> ReLU -> conv3 (1x1) + skip (hourglass.py:44-59) in one launch at
 // inference: the 128-channel intermediate is never written or re-read (0.54 GB per full-resolution residual at batch 128).
-template <int TM, int TN, int NP, bool AFF, bool DUAL = false, bool SPLIT = false, bool FUSE2 = false, bool EPRE = false>
+// SPLIT + ACCB (awr_conv_args.accum = 1 on a split launch: the training forward launches with a long K extent): every K range is accumulated
+// BLOCKED -- every 128 k, counted from the range's first slice, the running sum is folded into a second accumulator set -- and the ordered sum
+// over the copies in the reduce kernel is the outermost fold: chains of 128 + range / 128 + S terms (DESIGN.md 4.13 / 5).
+template <int TM, int TN, int NP, bool AFF, bool DUAL = false, bool SPLIT = false, bool FUSE2 = false, bool EPRE = false, bool ACCB = false>
 __device__ __forceinline__ void conv_gemm_body(const awr_conv_args& a) {
     static_assert(!FUSE2 || (NP == 0 && !DUAL && !SPLIT), "FUSE2: FP32-MFMA mode");
+    static_assert(!ACCB || (SPLIT && NP == 0), "ACCB: the split-K form only (the unsplit blocked kernel is conv_gemm_dma_body)");
     constexpr int BM = 64 * TM, BN = 64 * TN;
     constexpr int RA = BM / 32, RB = BN / 32;   // float4 rows per thread for the A / B slices
     constexpr int ROWB = NP ? LDR : LDK * 4;    // LDS row pitch in bytes
@@ -791,6 +795,17 @@ __device__ __forceinline__ void conv_gemm_body(const awr_conv_args& a) {
     if constexpr (SPLIT) {
         const int per = (ksteps + (int)gridDim.z - 1) / (int)gridDim.z;
         const int ks0 = (int)blockIdx.z * per, ks1 = ks0 + per < ksteps ? ks0 + per : ksteps;
+        constexpr int ACC_SLICES = 128 / BK;      // blocked accumulation: fold every 128 k
+        f32x16 tot[ACCB ? TM : 1][ACCB ? TN : 1];
+        if constexpr (ACCB) {
+#pragma unroll
+            for (int i = 0; i < TM; ++i)
+#pragma unroll
+                for (int j = 0; j < TN; ++j)
+#pragma unroll
+                    for (int r = 0; r < 16; ++r) tot[i][j][r] = 0.f;
+        }
+        int since = 0;
         if (ks0 < ks1) {       // (uniform per workgroup; an empty range stores a zero tile)
             tap = ks0 / cslices;
             c0 = (ks0 - tap * cslices) * BK;
@@ -819,12 +834,31 @@ __device__ __forceinline__ void conv_gemm_body(const awr_conv_args& a) {
                             for (int j = 0; j < TN; ++j)
                                 acc[i][j] = __builtin_amdgcn_mfma_f32_32x32x2f32((&fa[i].x)[k], (&fb[j].x)[k], acc[i][j], 0, 0, 0);
                 }
+                if constexpr (ACCB) {
+                    if (++since == ACC_SLICES) {
+                        since = 0;
+#pragma unroll
+                        for (int i = 0; i < TM; ++i)
+#pragma unroll
+                            for (int j = 0; j < TN; ++j)
+#pragma unroll
+                                for (int r = 0; r < 16; ++r) { tot[i][j][r] += acc[i][j][r]; acc[i][j][r] = 0.f; }
+                    }
+                }
                 __syncthreads();
                 if (more) {
                     store_slice();
                     __syncthreads();
                 }
             }
+        }
+        if constexpr (ACCB) {      // the last (possibly partial) block
+#pragma unroll
+            for (int i = 0; i < TM; ++i)
+#pragma unroll
+                for (int j = 0; j < TN; ++j)
+#pragma unroll
+                    for (int r = 0; r < 16; ++r) acc[i][j][r] += tot[i][j][r];
         }
         awr_conv_args b = a;      // raw partial sums: the epilogue proper runs in splitk_reduce_kernel
         b.out = a.partial + (size_t)blockIdx.z * ((size_t)a.B * a.Hout * a.Wout * a.N);
@@ -1857,6 +1891,11 @@ template <int TM, int TN, int NP, bool AFF, bool DUAL = false, bool SPLIT = fals
 __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(2))) void conv_gemm_kernel(const awr_conv_args a) {
     conv_gemm_body<TM, TN, NP, AFF, DUAL, SPLIT, FUSE2, EPRE>(a);
 }
+// the split-K form whose K ranges accumulate blocked (awr_conv_args.accum = 1)
+template <int TM, int TN>
+__global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(2))) void conv_gemm_split_blocked_kernel(const awr_conv_args a) {
+    conv_gemm_body<TM, TN, 0, false, false, true, false, false, true>(a);
+}
 // The plain 64x64 tile at SIX waves per SIMD: 80 registers and two spilled dwords instead of 87 (five waves).  Same-box A/B: ResNet18 step
 // 13.83-13.86 vs 13.91-13.93 ms, Hourglass-1 train 25.20 vs 25.29 ms, config 3 13.32 vs 13.34 ms.  (The 64x128 tile at five waves -- 96
 // registers, twelve spilled dwords -- is no faster: 13.85-13.91 ms, Hourglass-1 slower.)  AWR_NO_OCC6=1 is the A/B hook.
@@ -1867,8 +1906,8 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(6))) void c
 
 // out = epilogue(sum over the split-K copies, in order): bias, folded-BN affine, residual, ReLU
 __global__ __launch_bounds__(256) void splitk_reduce_kernel(const float* __restrict__ partial, int nsplit, int64_t stride, const float* __restrict__ bias,
-                                                            const float* __restrict__ osc, const float* __restrict__ osh, const float* __restrict__ res,
-                                                            int relu, int64_t n4, int N4, float* __restrict__ out) {
+                                                            const float* __restrict__ osc, const float* __restrict__ osh, const float* res,
+                                                            int relu, int64_t n4, int N4, float* out) {      // (res may alias out: an accumulating data gradient)
     const int64_t i = (int64_t)blockIdx.x * 256 + threadIdx.x;
     if (i >= n4) return;
     float4 v = ld4(partial + i * 4);
@@ -1885,6 +1924,128 @@ __global__ __launch_bounds__(256) void splitk_reduce_kernel(const float* __restr
     if (res) { const float4 r = ld4(res + i * 4); v.x += r.x; v.y += r.y; v.z += r.z; v.w += r.w; }
     if (relu) { v.x = relu1(v.x); v.y = relu1(v.y); v.z = relu1(v.z); v.w = relu1(v.w); }
     st4(out + i * 4, v);
+}
+
+// The split-K reduce of TRAINING launches: out = epilogue(sum over the copies, in index order) with everything gemm_epilogue gives an unsplit
+// launch (include/awr_hip.h: awr_conv_args) --
+//   DGRAD = false: bias, output affine, residual; per-channel sum / sum of squares of that value into stats[slot][2][N]; ReLU; store
+//   DGRAD = true : + res (in place when res == out); the ReLU mask from bnr_act or from y * scale + shift > 0; the masked gradient stored;
+//                  sum g, sum g * (y - mean) * invstd into stats, and sum g, sum g * (y2 - mean2) * invstd2 into stats2 (bnr2_y)
+// An HBM-bound pass over S + 1 (+ operands) small tensors: grid (ceil(npix / 64), ceil(N / 64)), 256 threads = 16 row lanes x 16 channel quads,
+// four rows per thread, every access 16 bytes; a thread keeps its channel quad, so its statistics stay in fp64 registers across its rows, the
+// sixteen row lanes meet in LDS (fixed order) and the workgroup issues ONE add per (slot, statistic, channel): workgroup i = blockIdx.y *
+// gridDim.x + blockIdx.x adds into copy (stat_slot_base + i) % stat_slots.  The grid never exceeds the launch's 64x64-tile workgroup count, so
+// stat_slots >= that count (the deterministic sizing of the unsplit launch) gives every address exactly one add.  All loads of a thread are
+// issued before its first store (res may alias out).
+template <bool DGRAD>
+__global__ __launch_bounds__(256) void splitk_reduce_epi_kernel(const awr_conv_args a, int nsplit, int npix) {
+    __shared__ double red[3][16][64];
+    const int tid = threadIdx.x, q = tid & 15, rl = tid >> 4;
+    const int n0 = (int)blockIdx.y * 64 + 4 * q;
+    const bool nok = n0 < a.N;                                // N % 4 == 0: the whole quad is in or out
+    const int64_t stride = (int64_t)npix * a.N;
+    const bool act_on = DGRAD && a.bnr_act != nullptr, y2_on = DGRAD && a.bnr2_y != nullptr;
+    const bool stats2_on = DGRAD && a.stats2 != nullptr;      // (as in gemm_epilogue: sum g goes to stats2 whenever it is given)
+    const float4 z4 = make_float4(0, 0, 0, 0), o4 = make_float4(1, 1, 1, 1);
+    float4 v[4], rr[4], yy[4], aa[4], y2[4];
+    bool ok[4];
+#pragma unroll
+    for (int i = 0; i < 4; ++i) {
+        const int row = (int)blockIdx.x * 64 + rl + 16 * i;
+        ok[i] = nok && row < npix;
+        const int64_t off = (int64_t)row * a.N + n0;
+        v[i] = ok[i] ? ld4(a.partial + off) : z4;
+        rr[i] = (ok[i] && a.res) ? ld4(a.res + off) : z4;
+        yy[i] = (DGRAD && ok[i]) ? ld4(a.bnr_y + off) : z4;
+        aa[i] = (act_on && ok[i]) ? ld4(a.bnr_act + off) : z4;
+        y2[i] = (y2_on && ok[i]) ? ld4(a.bnr2_y + off) : z4;
+    }
+    for (int z = 1; z < nsplit; ++z) {
+#pragma unroll
+        for (int i = 0; i < 4; ++i) {
+            const int row = (int)blockIdx.x * 64 + rl + 16 * i;
+            const float4 p = ok[i] ? ld4(a.partial + (int64_t)z * stride + (int64_t)row * a.N + n0) : z4;
+            v[i].x += p.x; v[i].y += p.y; v[i].z += p.z; v[i].w += p.w;
+        }
+    }
+    double s1[4] = {0, 0, 0, 0}, s2[4] = {0, 0, 0, 0}, s3[4] = {0, 0, 0, 0};
+    if constexpr (!DGRAD) {
+        const float4 bias = (a.bias && nok) ? ld4(a.bias + n0) : z4;
+        const float4 osc = (a.out_scale && nok) ? ld4(a.out_scale + n0) : o4, osh = (a.out_shift && nok) ? ld4(a.out_shift + n0) : z4;
+#pragma unroll
+        for (int i = 0; i < 4; ++i) {
+            float4 t = v[i];
+            if (a.bias) { t.x += bias.x; t.y += bias.y; t.z += bias.z; t.w += bias.w; }
+            if (a.out_scale) { t.x = t.x * osc.x + osh.x; t.y = t.y * osc.y + osh.y; t.z = t.z * osc.z + osh.z; t.w = t.w * osc.w + osh.w; }
+            t.x += rr[i].x; t.y += rr[i].y; t.z += rr[i].z; t.w += rr[i].w;
+            if (ok[i]) {
+                const float* tp = &t.x;
+#pragma unroll
+                for (int e = 0; e < 4; ++e) { const double d = (double)tp[e]; s1[e] += d; s2[e] += d * d; }
+            }
+            if (a.relu_out) { t.x = relu1(t.x); t.y = relu1(t.y); t.z = relu1(t.z); t.w = relu1(t.w); }
+            v[i] = t;
+        }
+    } else {
+        float4 ksc = o4, ksh = z4, kmu = z4, kis = o4, kmu2 = z4, kis2 = o4;
+        if (nok) {
+            ksc = ld4(a.bnr_coef + n0); ksh = ld4(a.bnr_coef + a.N + n0);
+            kmu = ld4(a.bnr_coef + 2 * a.N + n0); kis = ld4(a.bnr_coef + 3 * a.N + n0);
+            if (y2_on) { kmu2 = ld4(a.bnr2_coef + 2 * a.N + n0); kis2 = ld4(a.bnr2_coef + 3 * a.N + n0); }
+        }
+#pragma unroll
+        for (int i = 0; i < 4; ++i) {
+            float4 t = v[i];
+            t.x += rr[i].x; t.y += rr[i].y; t.z += rr[i].z; t.w += rr[i].w;
+            if (act_on) {
+                t.x = aa[i].x > 0.f ? t.x : 0.f; t.y = aa[i].y > 0.f ? t.y : 0.f; t.z = aa[i].z > 0.f ? t.z : 0.f; t.w = aa[i].w > 0.f ? t.w : 0.f;
+            } else {
+                t.x = yy[i].x * ksc.x + ksh.x > 0.f ? t.x : 0.f; t.y = yy[i].y * ksc.y + ksh.y > 0.f ? t.y : 0.f;
+                t.z = yy[i].z * ksc.z + ksh.z > 0.f ? t.z : 0.f; t.w = yy[i].w * ksc.w + ksh.w > 0.f ? t.w : 0.f;
+            }
+            if (ok[i]) {
+                const float *tp = &t.x, *yp = &yy[i].x, *y2p = &y2[i].x, *mu = &kmu.x, *is = &kis.x, *mu2 = &kmu2.x, *is2 = &kis2.x;
+#pragma unroll
+                for (int e = 0; e < 4; ++e) {
+                    const double g = (double)tp[e];
+                    s1[e] += g;
+                    s2[e] += g * (((double)yp[e] - (double)mu[e]) * (double)is[e]);
+                    if (y2_on) s3[e] += g * (((double)y2p[e] - (double)mu2[e]) * (double)is2[e]);
+                }
+            }
+            if (a.relu_out) { t.x = relu1(t.x); t.y = relu1(t.y); t.z = relu1(t.z); t.w = relu1(t.w); }
+            v[i] = t;
+        }
+    }
+#pragma unroll
+    for (int i = 0; i < 4; ++i) {
+        const int row = (int)blockIdx.x * 64 + rl + 16 * i;
+        if (ok[i]) st4(a.out + (int64_t)row * a.N + n0, v[i]);
+    }
+    if (!a.stats) return;      // (uniform)
+#pragma unroll
+    for (int e = 0; e < 4; ++e) {
+        red[0][rl][4 * q + e] = s1[e];
+        red[1][rl][4 * q + e] = s2[e];
+        red[2][rl][4 * q + e] = s3[e];
+    }
+    __syncthreads();
+    const int k = tid >> 6, c = tid & 63, n = (int)blockIdx.y * 64 + c;
+    if (k < 3 && n < a.N && (k < 2 || (y2_on && stats2_on))) {
+        double t = red[k][0][c];
+#pragma unroll
+        for (int r = 1; r < 16; ++r) t += red[k][r][c];
+        const unsigned nslots = a.stat_slots > 0 ? (unsigned)a.stat_slots : (unsigned)AWR_STAT_SLOTS;
+        const size_t slot = (size_t)(((unsigned)a.stat_slot_base + blockIdx.y * gridDim.x + blockIdx.x) % nslots) * 2 * a.N;
+        if (k == 0) {
+            atomicAdd(a.stats + slot + n, t);
+            if (stats2_on) atomicAdd(a.stats2 + slot + n, t);      // the second BatchNorm sees the same masked gradient
+        } else if (k == 1) {
+            atomicAdd(a.stats + slot + a.N + n, t);
+        } else {
+            atomicAdd(a.stats2 + slot + a.N + n, t);
+        }
+    }
 }
 #endif
 

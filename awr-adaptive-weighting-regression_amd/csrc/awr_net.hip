@@ -670,6 +670,7 @@ struct awr_plan {
     awr_net* net = nullptr;
     int B = 0, H = 0;
     bool training = false, det = false;
+    bool train_split = false;                  // awr_get_train_split_k() when the plan was built
     int bn_repeat = 1, n_buckets = 1;
     unsigned supervised = 0;
     std::vector<Op> fwd, bwd, pack_ops;
@@ -785,6 +786,30 @@ struct Builder {
         return (int)(((int64_t)B * Hq * Wq + 63) / 64) * ((Nn + 63) / 64) * nphase;
     }
     int reduce_slots() const { return P.det ? AWR_REDUCE_MAX_BLOCKS : AWR_STAT_SLOTS; }
+
+    // Training split-K (awr_set_train_split_k): a forward / data-gradient launch of a few workgroups with a long K loop gets scratch
+    // for up to `smax` raw copies of its output -- the inference rule and its constants (conv() below): 64x64-tile workgroups x phases x copies
+    // below 2048, at least 4 K slices per range at the deepest split; awr_conv_gemm picks the depth (fill ~2 workgroups per CU, >= 8 slices per
+    // range), the tuner refines it with depth 1 among its candidates.  Changed against the inference rule: at most 8 copies and TRAIN_SPLIT_MAX_BYTES
+    // (8 MiB) of scratch per launch -- a training plan has five times the launches of an evaluation plan, the rule's 16 copies / 32 MiB cost a
+    // ResNet18 batch-8 plan 962 MB -- counted in the plan's bytes.  Not for launches with a
+    // second input tensor, an un-materialised BatchNorm-backward input, partial-coverage data gradients (the reduce pass reads whole copies), the
+    // split-operand product mode, or launches a Winograd form has taken (the callers).
+    static constexpr int64_t TRAIN_SPLIT_MAX_BYTES = 8ll << 20;
+    void train_split_scratch(awr_conv_args* a) {
+        if (!P.training || !P.train_split || awr_get_gemm_products() != 1 || a->in2 || a->w2 || a->in_bnb_y || a->partial) return;
+        if (a->so != 1 && a->nphase != a->so * a->so) return;
+        const int64_t numel = (int64_t)a->B * a->Hout * a->Wout * a->N;
+        const int64_t wgs = ((int64_t)a->B * a->Hq * a->Wq + 63) / 64 * ((a->N + 63) / 64) * (int64_t)a->nphase;
+        int minsteps = 1 << 30;
+        for (int p = 0; p < a->nphase; ++p) minsteps = std::min(minsteps, a->ph[p].ntaps * (a->Cin / 32));
+        int smax = 1;
+        while (smax < 8 && wgs * smax < 2048 && minsteps / (smax * 2) >= 4 && numel * 4 * (smax * 2) <= TRAIN_SPLIT_MAX_BYTES) smax *= 2;
+        if (smax > 1) {
+            a->partial = alloc<float>((int64_t)smax * numel);
+            a->split_max = smax;
+        }
+    }
 
     float* scratch(int64_t n) {        // slice of the split-K scratch arena (zeroed by ONE fill per step)
         n = round_up(n, 4);
@@ -978,6 +1003,7 @@ struct Builder {
                 a->split_max = smax;
             }
         }
+        train_split_scratch(a);
         const std::string name = "awr_conv_gemm:" + layer->name;
         Op& op = f(name, [a](void* s) { return awr_conv_gemm(a, s); });
         op.gemm = true;
@@ -1269,6 +1295,7 @@ struct Builder {
                     }
                     P.wino_dg.push_back({da, layer_macs});
                 }
+                if (!Ud) train_split_scratch(da);      // (in_bnb_y / partial-coverage launches are refused inside)
                 Op& dop = Ud ? b(dname, [da, Ud](void* s) { return awr_wino_dgrad_or_direct(da, Ud, s); }) : b(dname, [da](void* s) { return awr_conv_gemm(da, s); });
                 dop.gemm = true;
                 dop.macs = layer_macs;
@@ -2276,8 +2303,14 @@ static int autotune(awr_plan& P, int reps, void* stream) {
             if (g.ca->N > 64) { cands.push_back({1, 2, 0}); cands.push_back({2, 2, 0}); }
             if (g.ca->partial && g.ca->split_max > 1 && awr_get_gemm_products() == 1) {      // (tile, split-K depth) pairs; tb = depth
                 std::vector<Cand> withk;
+                int minsteps = 1 << 30;
+                for (int p = 0; p < g.ca->nphase; ++p) minsteps = std::min(minsteps, g.ca->ph[p].ntaps * (g.ca->Cin / 32));
                 for (auto& c : cands)
-                    for (int sk = 1; sk <= g.ca->split_max; sk *= 2) withk.push_back({c.tm, c.tn, sk});
+                    for (int sk = 1; sk <= g.ca->split_max; sk *= 2) {
+                        // blocked accumulation: only depths the accumulation rule admits (a whole 128-k block per K range, awr_hip.h)
+                        if (sk > 1 && g.ca->accum == 1 && (minsteps + sk - 1) / sk < 4) continue;
+                        withk.push_back({c.tm, c.tn, sk});
+                    }
                 cands.swap(withk);
             }
         } else {
@@ -2421,6 +2454,7 @@ int awr_plan_create(awr_net* n, int B, int H, int training, unsigned supervised_
     p->H = H;
     p->training = training != 0;
     p->det = awr_get_deterministic() != 0;
+    p->train_split = awr_get_train_split_k() != 0;
     p->bn_repeat = bn_repeat;
     p->n_buckets = n_buckets;
     p->supervised = supervised_mask;
@@ -2741,7 +2775,13 @@ int awr_plan_gemm(const awr_plan* p, int i, const char** name, int* tile_m, int*
     if (name) *name = g.name.c_str();
     if (tile_m) *tile_m = g.tm;
     if (tile_n) *tile_n = g.tn;
-    if (target_blocks) *target_blocks = g.tb;
+    if (target_blocks) {
+        *target_blocks = g.tb;
+        if (!g.tb && g.ca && g.ca->partial && g.ca->split_max > 1) {      // conv launches with scratch, not tuned: the heuristic depth they run with
+            int depth = 0;
+            if (awr_conv_split_depth(g.ca, &depth) == AWR_OK) *target_blocks = depth;
+        }
+    }
     if (us) *us = g.us;
     if (tuned) *tuned = g.tuned ? 1 : 0;
     return AWR_OK;

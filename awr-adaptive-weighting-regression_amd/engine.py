@@ -55,10 +55,11 @@ def plan_buckets(writes, n_active, n_buckets):
     return [tuple(b) for b in out]
 
 
-def tile_cache_key(base, products, staging, accum, winograd):
+def tile_cache_key(base, products, staging, accum, winograd, split_k=0):
     """AWR_TUNE_CACHE key of a plan's tile choices: tile choices differ between the modes (products, staging, the plan's accumulation order --
-    blocked doubles the accumulators -- and its Winograd code: a Winograd plan has other launches, and its direct ones run beside other neighbours)."""
-    return base + "/x%d/s%d/a%d/w%d" % (products, staging, accum, winograd)
+    blocked doubles the accumulators -- its Winograd code: a Winograd plan has other launches, and its direct ones run beside other neighbours --
+    and training split-K: its launches carry a depth beside the tile; plans without it keep the key they always had)."""
+    return base + "/x%d/s%d/a%d/w%d" % (products, staging, accum, winograd) + ("/k1" if split_k else "")
 
 
 def cached_tiles(cache_file, key, names):
@@ -353,7 +354,7 @@ class Plan:
         cache_file = os.environ.get("AWR_TUNE_CACHE")
         if cache_key:
             cache_key = tile_cache_key(cache_key, L.lib.awr_get_gemm_products(), L.lib.awr_get_gemm_staging(), int(getattr(self, "accum", 0)),
-                                       int(getattr(self, "winograd", 0)))
+                                       int(getattr(self, "winograd", 0)), int(getattr(self, "train_split_k", 0)))
         names = [self._gemm(i)[0] for i in range(self.n_gemm)]
         if cache_file and cache_key:
             ent = cached_tiles(cache_file, cache_key, names)

@@ -23,7 +23,7 @@ import numpy as np
 import torch
 
 from . import _lib as L
-from . import _engine_winograd, _winograd_code
+from . import _engine_winograd, _split_k_flag, _winograd_code
 from . import winograd_auto as WA
 
 HUBER_DELTA = 0.01
@@ -76,6 +76,8 @@ class _WinogradAuto:
             return "direct"
         self._wino_key = WA.decision_key(training, type(self.net).__name__ + str(self.net.nstage), self.J, self.B, self.H,
                                          int(L.lib.awr_get_gemm_products()), int(L.lib.awr_get_gemm_staging()), acc)
+        if training and (getattr(self, "_split_k", False) or L.lib.awr_get_train_split_k()):
+            self._wino_key += "/k1"           # training split-K changes the direct launches every candidate is timed against
         ent = WA.load_decision(self._wino_key, self._wino_candidates)
         mode = WA.agree(ent["mode"] if ent else None, self._wino_candidates, process_group, self.net.device)
         if mode is not None:
@@ -133,8 +135,12 @@ class _WinogradAuto:
 class TrainEngine(_WinogradAuto):
     def __init__(self, net, batch_size, img_size, kernel_size, coord_weight=0.0, dense_weight=1.0, lr=1e-3, weight_decay=0.0,
                  optimizer="adam", momentum=0.9, process_group=None, use_graph=False, n_buckets=4, autotune=True, wgrad_streams=2,
-                 nhwc_boundary=None, trace_buckets=False, native_rccl=None, accum="auto", winograd=None, _share=None):
-        """accum: "auto" (default) | "ordered" | "blocked" | None (the process-wide mode, awr_amd.set_gemm_accum) -- accumulation order of the
+                 nhwc_boundary=None, trace_buckets=False, native_rccl=None, accum="auto", winograd=None, split_k=False, _share=None):
+        """split_k: False (default: the process-wide mode, off unless awr_amd.set_train_split_k / $AWR_TRAIN_SPLIT_K set it) | True -- the small
+        forward / data-gradient launches of this engine's plan (few workgroups, a long K loop: low batches, the deep levels) split their K loop
+        and take the BatchNorm statistics / fused BatchNorm-backward reductions from the reduce kernel (include/awr_hip.h: awr_set_train_split_k;
+        DESIGN.md 4.13).  Any other value raises ValueError.
+        accum: "auto" (default) | "ordered" | "blocked" | None (the process-wide mode, awr_amd.set_gemm_accum) -- accumulation order of the
         forward / data-gradient GEMMs of this engine's plan.  "blocked" is the parity mode (a conv's rounding error at torch-CPU's level, a few %
         slower); "auto" blocks only the launches with a long K extent (include/awr_hip.h: awr_set_gemm_accum), where an ordered chain's error
         is largest and blocking is cheapest; "ordered" is one chain per output element everywhere.
@@ -142,6 +148,7 @@ class TrainEngine(_WinogradAuto):
         forward, or forward + weight gradient, or forward + data gradient + weight gradient, of the eligible stride-1 3x3 convolutions (include/awr_hip.h)
         | "auto" -- the fastest of those for this plan, timed by compile() (winograd_auto.py); `winograd_mode` names what the plan runs,
         `winograd_timings` holds the candidates' ms per step."""
+        self._split_k = _split_k_flag(split_k)
         if not next(net.parameters()).is_cuda:
             raise L.AwrError("TrainEngine needs the network on the GPU")
         self.net, self.B, self.H = net, batch_size, img_size
@@ -157,7 +164,8 @@ class TrainEngine(_WinogradAuto):
         self.dp = world > 1 or (process_group is not None and os.environ.get("AWR_FORCE_DP") == "1")   # test hook: 1-rank group
         # (single GPU: scattering the packed weight gradients bucket by bucket during the backward, like the data-parallel plans do, instead
         # of in one launch at the tail of the step was measured slower: 14.28-14.32 vs 14.00-14.05 ms, profiles/r03_summary.md)
-        self._plan_kw = dict(supervised=(self.stage,), bn_repeat=net.nstage, n_buckets=n_buckets if self.dp else 1, accum=accum)
+        self._plan_kw = dict(supervised=(self.stage,), bn_repeat=net.nstage, n_buckets=n_buckets if self.dp else 1, accum=accum,
+                             split_k=True if self._split_k else None)
         self._wgrad_streams = wgrad_streams
         # head + losses on the backbone's own NHWC layout (no transposes at the boundary, the dense map read once per step when
         # coord_weight == 0); AWR_NCHW_BOUNDARY=1 / nhwc_boundary=False keeps the reference-layout kernels (same-box A/B)
@@ -367,7 +375,7 @@ class TrainEngine(_WinogradAuto):
                 self.compile()
             eng = TrainEngine(self.net, b, self.H, self.ks, self.cw, self.dw, self.lr, self.wd, self.opt, self.momentum,
                               process_group=self.sync.pg, use_graph=False, n_buckets=self._n_buckets, autotune=False,
-                              wgrad_streams=0, accum=self._accum, winograd=self._winograd, _share=self)
+                              wgrad_streams=0, accum=self._accum, winograd=self._winograd, split_k=self._split_k, _share=self)
             self._children[b] = eng
         eng.lr, eng.step_count = self.lr, self.step_count
         return eng
@@ -714,7 +722,7 @@ class Trainer:
         self.engine = TrainEngine(self.net, config.batch_size, config.img_size, config.kernel_size, config.coord_weight, config.dense_weight,
                                   config.lr, config.weight_decay, config.optimizer, process_group=process_group,
                                   use_graph=getattr(config, "use_hipgraph", False), accum=getattr(config, "accum", "auto"),
-                                  winograd=getattr(config, "winograd", None))
+                                  winograd=getattr(config, "winograd", None), split_k=getattr(config, "train_split_k", False))
         # winograd="auto": the training step's choice is logged once; the scoring engine's is reused by every later test pass
         self._wino_logged, self._infer_winograd = False, None
         if config.load_model and os.path.exists(config.load_model):

@@ -216,8 +216,16 @@ typedef struct awr_conv_args {
     int Cin1;
     float* partial;         /* optional scratch of split_max * B*Hout*Wout*N floats: enables split-K (small launches whose few workgroups
                                would each walk a long K loop -- low-batch inference): blockIdx.z takes a contiguous range of the K
-                               slices and stores its raw partial tile, a second kernel sums the copies in order and applies the
-                               epilogue (bias, folded BN, residual, ReLU).  FP32-MFMA mode, no `stats` / `bnr_y` / `in2` */
+                               slices and stores its raw partial tile, a second kernel sums the copies in index order and applies the
+                               launch's whole epilogue: bias, output affine, residual, ReLU, and -- training launches -- the `stats`
+                               sums or the fused BatchNorm-backward reductions (bnr_y / bnr_act / in-place `res` / bnr2_y), exactly as
+                               defined above, accumulated in fp64.  Reduce workgroup i (one per 64 output pixels x 64 channels) adds
+                               into statistics copy (stat_slot_base + i) % stat_slots, one add per (slot, statistic, channel): with
+                               stat_slots >= ceil(B*Hout*Wout / 64) * ceil(N / 64) (never more than the unsplit launch's 64x64-tile
+                               workgroup count) every address receives exactly one add.  FP32-MFMA mode; no in2 / fused pair (w2) /
+                               in_bnb_y / in_split, and every output pixel must belong to a phase (so == 1, or so * so phases).
+                               With accum = 1 every K range is accumulated blocked and the sum over the copies is the outer fold;
+                               a depth whose nominal range, ceil(slices / S), is shorter than one 128-k block is refused (see `accum`) */
     int split_k;            /* K ranges (1 = off, 0 = heuristic from the workgroup count and K depth), <= split_max */
     int split_max;
     const float* bnr_act;   /* with bnr_y: take the ReLU mask from this stored activation (act > 0) instead of re-deriving it from y -- the
@@ -239,7 +247,12 @@ typedef struct awr_conv_args {
                             /* taps stay zero.  Replaces the awr_bn_bwd_apply pass between two dependent data-gradient GEMMs.  LDS-DMA staging only */
     int accum;              /* 0 = one k-ordered accumulation chain over the whole K extent (v_mfma_f32_32x32x2_f32 after v_mfma ...); 1 = BLOCKED: every */
                             /* 128 k the running sum is folded into a second accumulator set and restarted (chains of 128 + K / 128 terms, the */
-                            /* rounding behaviour of oneDNN's blocked kernels that the reference's CPU numbers come from).  LDS-DMA staging, K > 256 */
+                            /* rounding behaviour of oneDNN's blocked kernels that the reference's CPU numbers come from).  LDS-DMA staging, K > 256. */
+                            /* A SPLIT-K launch (partial / split_k) honours accum = 1 in its own kernel: each K range folds every 128 k counted from its */
+                            /* first slice, the ordered sum over the S copies is the outermost fold (chains of 128 + range / 128 + S terms).  Admissible */
+                            /* while the NOMINAL range holds at least one whole 128-k block (ceil(slices / S) * 32 >= 128; the last range is what is left */
+                            /* over and may be shorter -- a shorter chain): the split then adds no more outer terms than blocking itself has.  A depth that breaks the rule is an ERROR (never a silent downgrade to ordered sums); */
+                            /* the heuristic depth (>= 8 slices per range) always satisfies it */
     const void* in_split;   /* optional (split-operand mode): the PRE-CUT image of `in` -- [pixel][Cin / 32][h | m | l][32] bf16, 6 bytes per element, written */
                             /* by awr_split_act (or a producer's epilogue): both operands then travel global -> LDS by DMA and the K loop holds no cutting */
                             /* arithmetic.  Excludes in_scale / relu_in (the producer applies them before it cuts), in2, in_bnb_y, split-K */
@@ -313,6 +326,18 @@ int awr_get_gemm_accum(void);
 int awr_set_gemm_accum_auto(int min_k, int dgrad);
 int awr_get_gemm_accum_auto(int* min_k, int* dgrad);
 int awr_resolve_gemm_accum(int k_extent, int kind);
+/* the split-K depth awr_conv_gemm runs the launch `a` with (1 = unsplit): the explicit split_k, or the heuristic from the workgroup count and the K
+ * depth -- a pure function of the argument block and the process-wide modes; the same errors as awr_conv_gemm for a depth the launch cannot honour */
+int awr_conv_split_depth(const awr_conv_args* a, int* depth);
+/* Split-K for TRAINING plans (process-wide, read when a plan is built; default 0, or $AWR_TRAIN_SPLIT_K): 1 = the forward and data-gradient launches
+ * of a training plan that have few workgroups and a long K loop (64x64-tile workgroups x phases well below two per CU, at least 8 K slices per
+ * range) get `partial` scratch (capped per launch, counted in awr_plan_info's bytes) and run split: the BatchNorm statistics / fused
+ * BatchNorm-backward reductions then come from the reduce kernel (awr_conv_args.partial).  awr_plan_autotune times depth 1 against the split depths
+ * per launch; deterministic plans take the heuristic depth.  Launches taken by a Winograd form, fused pairs, in2 / in_bnb_y launches, partial-coverage
+ * data gradients and the split-operand product mode stay unsplit.  0: a plan is launch-for-launch what it was without the mode.  Replaces nothing in the
+ * reference (a scheduling choice for its batch_size = 32 default, train.py). */
+int awr_set_train_split_k(int on);
+int awr_get_train_split_k(void);
 
 /* weight gradient:  R[cd][t][cg] += sum_m D[m][cd] * G[pix(m,t)][cg]
  * D: dense operand (B,Hd,Wd,Cd); G: gathered operand (B,Hg,Wg,Cg) read at (y*sg+dy[t], x*sg+dx[t]).
@@ -536,7 +561,8 @@ int awr_plan_backward(awr_plan* plan, void* stream);
 /* serial replay with a HIP-event pair around every launch: ms[i] per op, 0 for fills / copies / markers (synchronises the stream) */
 int awr_plan_run_timed(awr_plan* plan, int list, void* stream, float* ms);
 /* time the tile / split-K candidates of every GEMM launch in place (no-op in deterministic mode); read / preset choices
- * (target_blocks: weight gradients = workgroup target of the split over pixels; conv launches with `partial` scratch = split-K depth) */
+ * (target_blocks: weight gradients = workgroup target of the split over pixels; conv launches with `partial` scratch = split-K depth -- the tuned
+ * one, or, before / without tuning, the depth the heuristic gives the launch: awr_conv_split_depth) */
 int awr_plan_autotune(awr_plan* plan, int reps, void* stream);
 int awr_plan_gemm(const awr_plan* plan, int i, const char** name, int* tile_m, int* tile_n, int* target_blocks,
                   float* us, int* tuned);
