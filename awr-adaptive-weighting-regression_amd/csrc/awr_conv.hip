@@ -31,6 +31,13 @@ extern template void launch_dma_tile<1, 1>(const awr_conv_args*, dim3, hipStream
 extern template void launch_dma_tile<1, 2>(const awr_conv_args*, dim3, hipStream_t, int, int, bool, int);
 extern template void launch_dma_tile<2, 1>(const awr_conv_args*, dim3, hipStream_t, int, int, bool, int);
 extern template void launch_dma_tile<2, 2>(const awr_conv_args*, dim3, hipStream_t, int, int, bool, int);
+// ... and its form that also writes the 2x2 max-pool of the output (awr_conv_args.pool_out without w2)
+template <int TM, int TN>
+void launch_dma_pool_tile(const awr_conv_args* a, dim3 grid, hipStream_t st);
+extern template void launch_dma_pool_tile<1, 1>(const awr_conv_args*, dim3, hipStream_t);
+extern template void launch_dma_pool_tile<1, 2>(const awr_conv_args*, dim3, hipStream_t);
+extern template void launch_dma_pool_tile<2, 1>(const awr_conv_args*, dim3, hipStream_t);
+extern template void launch_dma_pool_tile<2, 2>(const awr_conv_args*, dim3, hipStream_t);
 }  // namespace awr
 
 using namespace awr;
@@ -279,7 +286,7 @@ static int conv_gemm_one(const awr_conv_args* a_in, void* stream) {
     AWR_REQUIRE(!a->bnr2_y || (a->bnr_y && a->bnr2_coef && a->stats2), "conv_gemm: a second fused reduction (bnr2_y) needs bnr_y, bnr2_coef and stats2");
     AWR_REQUIRE((a->in_scale == nullptr) == (a->in_shift == nullptr), "conv_gemm: in_scale/in_shift must come together");
     AWR_REQUIRE((a->out_scale == nullptr) == (a->out_shift == nullptr), "conv_gemm: out_scale/out_shift must come together");
-    AWR_REQUIRE(!a->pool_out || a->w2, "conv_gemm: pool_out belongs to the fused pair (w2)");
+    // (pool_out: the fused pair checks its own conditions below; every other launch those of the pooled 1x1 form, once its tile and depth are known)
     AWR_REQUIRE(!a->in2 || a->w2 || (g_products == 1 && a->nphase == 1 && a->ph[0].ntaps == 1 && a->T == 1 && a->Cin1 > 0 && a->Cin1 < a->Cin && a->Cin1 % BK == 0),
                 "conv_gemm: a second input tensor needs the FP32-MFMA mode, one tap and 0 < Cin1 < Cin, Cin1 %% 32 == 0");
     for (int p = 0; p < a->nphase; ++p) {
@@ -325,6 +332,30 @@ static int conv_gemm_one(const awr_conv_args* a_in, void* stream) {
     if (int e = conv_tile_and_depth(a, TM, TN, S)) return e;
     auto blocks = [&](int tm, int tn) { return ((M + 64 * tm - 1) / (64 * tm)) * ((a->N + 64 * tn - 1) / (64 * tn)) * a->nphase; };
     hipStream_t st = as_stream(stream);
+    if (a->pool_out) {
+        // A launch that is not a fused pair writes the 2x2 / stride-2 max-pool of its output itself when it is a plain or two-tensor 1x1 convolution on the
+        // shipped LDS-DMA kernel form: 2D workgroup tiles (two image rows x 32 tile_m columns), the windows reduced in the epilogue.  Everything else
+        // is an error -- pool_out is never left unwritten.
+        AWR_REQUIRE(g_products == 1 && g_staging != 0, "conv_gemm: pool_out needs the FP32-MFMA mode with LDS-DMA staging");
+        AWR_REQUIRE(a->nphase == 1 && a->ph[0].ntaps == 1 && (a->ph[0].tap[0] & 0xffff) == 0 && a->T == 1 && a->si == 1 && a->so == 1 &&
+                        a->Hin == a->Hq && a->Win == a->Wq && a->Hout == a->Hq && a->Wout == a->Wq,
+                    "conv_gemm: pool_out outside the fused pair needs a 1x1 convolution at stride 1 (one phase, one tap; this launch: %d phase(s), %d tap(s), "
+                    "T=%d, stride in %d / out %d)", a->nphase, a->ph[0].ntaps, a->T, a->si, a->so);
+        AWR_REQUIRE(!a->in_scale && !a->relu_in && !a->in_bnb_y && !a->in_split, "conv_gemm: pool_out needs a plain input (no in_scale / relu_in / in_bnb_y / in_split)");
+        AWR_REQUIRE(!a->stats && !a->bnr_y && !a->out_scale && !a->relu_out,
+                    "conv_gemm: pool_out needs the plain epilogue (bias, optional res): no stats / bnr_y / output affine / ReLU");
+        AWR_REQUIRE(a->accum == 0, "conv_gemm: pool_out needs ordered accumulation (accum = 0)");
+        AWR_REQUIRE(S == 1, "conv_gemm: pool_out excludes split-K (this launch resolves to a depth of %d)", S);
+        AWR_REQUIRE(a->Hq % 2 == 0 && a->Wq % (32 * TM) == 0,
+                    "conv_gemm: pool_out needs an even map height and a width that is a multiple of %d for tile_m = %d (map %d x %d)", 32 * TM, TM, a->Hq, a->Wq);
+        AWR_REQUIRE(M % (64 * TM) == 0, "conv_gemm: pool_out: M=%lld is not a whole number of %d-row tiles", (long long)M, 64 * TM);
+        const dim3 pgrid((unsigned)blocks(TM, TN), 1);
+        if (TM == 2 && TN == 2) launch_dma_pool_tile<2, 2>(a, pgrid, st);
+        else if (TM == 2 && TN == 1) launch_dma_pool_tile<2, 1>(a, pgrid, st);
+        else if (TM == 1 && TN == 2) launch_dma_pool_tile<1, 2>(a, pgrid, st);
+        else launch_dma_pool_tile<1, 1>(a, pgrid, st);
+        return check_launch("conv_gemm_dma_pool_kernel");
+    }
     if (S > 1) {
         const dim3 grid((unsigned)(blocks(TM, TN) / a->nphase), a->nphase, S);
         if (a->accum == 1) {

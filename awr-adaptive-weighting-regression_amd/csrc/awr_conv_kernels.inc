@@ -1175,7 +1175,8 @@ __device__ __forceinline__ unsigned lds_addr(const void* p) {
 // bounce rows), 2 = swapped and, for the PLAIN epilogue, stored straight from the accumulators (no LDS in the epilogue at all)
 // FUSE2 (round 5): the fused conv pair of conv_gemm_body (a.w2: conv2 3x3 -> bn3 -> ReLU -> conv3 1x1 + skip in one launch, inference) with the FIRST GEMM on
 // LDS-DMA staging -- that GEMM is 80 % of the pair's work and was the last big launch family still on the register-staged kernel.
-// POOL (FUSE2 only, round 5): the pair also writes the 2x2 / stride-2 max-pool of its output (awr_conv_args.pool_out).  A workgroup tile is then a 2D patch --
+// POOL (round 5: the fused pair; round 7: also a plain or two-tensor 1x1 launch -- one phase, one tap, stride 1, plain input, plain epilogue, ordered
+// accumulation): the launch also writes the 2x2 / stride-2 max-pool of its output (awr_conv_args.pool_out).  A workgroup tile is then a 2D patch --
 // two image rows x BM / 2 columns (tile2d_pixel) -- so the two M-waves hold vertically adjacent row segments and the four pixels of every window meet in
 // the epilogue's own LDS tiles: the separate pooling pass that re-reads the full-resolution tensor (1.07 GB at 128x128 x 128 channels x batch 128)
 // disappears.
@@ -1187,11 +1188,14 @@ __device__ __forceinline__ int tile2d_pixel(const awr_conv_args& a, int m) {
     const int y2 = q % hy, b = q / hy;
     return (b * a.Hq + 2 * y2 + r / CX) * a.Wq + tx * CX + (r % CX);
 }
-// epilogue of one output-channel half (hf) of the pair's second GEMM with the pool: bias2 (+ identity skip) -> full-resolution rows as usual, the final
-// values written back into the wave's transpose tile, and -- once both M-waves of a column are there -- the 2x2 windows (row pair = the two M-waves, column
-// pair = neighbouring tile rows) reduced in the SAME comparison order as maxpool_fwd_kernel (first maximum wins) and stored to pool_out.
+// epilogue of one N tile with the pool -- one output-channel half of the pair's second GEMM (tile_n = the half), or the N tile of a plain / two-tensor 1x1
+// launch (round 7): bias (+ residual) -> full-resolution rows as usual, the final values written back into the wave's transpose tile, and -- once both
+// M-waves of a column are there -- the 2x2 windows (row pair = the two M-waves, column pair = neighbouring tile rows) reduced in the SAME comparison
+// order as maxpool_fwd_kernel (first maximum wins) and stored to pool_out.  Columns beyond N (the ragged last N tile) get the out-of-range offset:
+// their loads return zeros, their stores are dropped.  `nt`: streaming stores / residual loads for `out` (awr_conv_args.out_nt); pool_out is read
+// next and always takes the default policy.
 template <int TM, int TN>
-__device__ __forceinline__ void pair_pool_epilogue(const awr_conv_args& e, f32x16 (&acc)[TM][TN], float* smem, int M, int tile_m, int hf) {
+__device__ __forceinline__ void pool_epilogue(const awr_conv_args& e, f32x16 (&acc)[TM][TN], float* smem, int M, int tile_m, int tile_n, bool nt) {
     constexpr int BM = 64 * TM, BN = 64 * TN, CX = BM / 2;
     const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6, wm = wave >> 1, wn = wave & 1, half = lane >> 5, l31 = lane & 31;
     const int c4 = lane & 7, rbase = lane >> 3;
@@ -1204,11 +1208,12 @@ __device__ __forceinline__ void pair_pool_epilogue(const awr_conv_args& e, f32x1
     const int t = tile_m, tpr = e.Wq / CX, tx = t % tpr, q = t / tpr;      // q = b * (Hq / 2) + row pair: the pooled map's row index over the batch
     const float* const t0 = smem + wn * (32 * LDK);                        // transpose tiles of the wm = 0 / wm = 1 waves of this column
     const float* const t1 = smem + (2 + wn) * (32 * LDK);
-    __syncthreads();                    // every wave is done with the staged w2 slices
+    __syncthreads();                    // every wave is done with the staged slices
 #pragma unroll
     for (int j = 0; j < TN; ++j) {
-        const int n0 = hf * BN + wn * 32 * TN + j * 32 + 4 * c4;
-        const float4 bias = e.bias ? ld4(e.bias + n0) : make_float4(0, 0, 0, 0);
+        const int n0 = tile_n * BN + wn * 32 * TN + j * 32 + 4 * c4;
+        const bool nok = n0 < e.N;                                         // N % 4 == 0: the whole float4 is in or out
+        const float4 bias = (e.bias && nok) ? ld4(e.bias + n0) : make_float4(0, 0, 0, 0);
 #pragma unroll
         for (int i = 0; i < TM; ++i) {
 #pragma unroll
@@ -1218,13 +1223,13 @@ __device__ __forceinline__ void pair_pool_epilogue(const awr_conv_args& e, f32x1
             for (int qq = 0; qq < 4; ++qq) {
                 const int row = rbase + 8 * qq, m = tile_m * BM + wm * 32 * TM + i * 32 + row;
                 float4 v = ld4(tbuf + row * LDK + 4 * c4);
-                const unsigned off = m < M ? (unsigned)tile2d_pixel<BM>(e, m) * (unsigned)e.N * 4u + (unsigned)n0 * 4u : OOB;
+                const unsigned off = (nok && m < M) ? (unsigned)tile2d_pixel<BM>(e, m) * (unsigned)e.N * 4u + (unsigned)n0 * 4u : OOB;
                 v.x += bias.x; v.y += bias.y; v.z += bias.z; v.w += bias.w;
                 if (e.res) {
-                    const float4 rr = buf_ld4(rs_res, off);
+                    const float4 rr = nt ? buf_ld4_nt(rs_res, off) : buf_ld4(rs_res, off);
                     v.x += rr.x; v.y += rr.y; v.z += rr.z; v.w += rr.w;
                 }
-                buf_st4(rs_out, off, v);
+                if (nt) buf_st4_nt(rs_out, off, v); else buf_st4(rs_out, off, v);
                 st4(tbuf + row * LDK + 4 * c4, v);       // the final value, for the windows
             }
             __syncthreads();                              // both row segments of the column are final
@@ -1236,8 +1241,8 @@ __device__ __forceinline__ void pair_pool_epilogue(const awr_conv_args& e, f32x1
                 mx.x = b0.x > mx.x ? b0.x : mx.x; mx.y = b0.y > mx.y ? b0.y : mx.y; mx.z = b0.z > mx.z ? b0.z : mx.z; mx.w = b0.w > mx.w ? b0.w : mx.w;
                 mx.x = b1.x > mx.x ? b1.x : mx.x; mx.y = b1.y > mx.y ? b1.y : mx.y; mx.z = b1.z > mx.z ? b1.z : mx.z; mx.w = b1.w > mx.w ? b1.w : mx.w;
                 const int xp = tx * (CX / 2) + i * 16 + ppx;                              // pooled column; the pooled row over the batch is q
-                const int pn0 = hf * BN + wn * 32 * TN + j * 32 + 4 * pc4;
-                const bool ok = tile_m * BM < M;
+                const int pn0 = tile_n * BN + wn * 32 * TN + j * 32 + 4 * pc4;
+                const bool ok = tile_m * BM < M && pn0 < e.N;
                 buf_st4(rs_pool, ok ? ((unsigned)(q * (e.Wq / 2) + xp) * (unsigned)e.N + (unsigned)pn0) * 4u : OOB, mx);
             }
             __syncthreads();                              // the tiles are rewritten by the next (i, j)
@@ -1246,7 +1251,8 @@ __device__ __forceinline__ void pair_pool_epilogue(const awr_conv_args& e, f32x1
 }
 template <int TM, int TN, int KB, int NBUF, int AFF, bool EPRE = false, int EM = 0, bool DUAL = false, bool ACCB = false, int SW = 0, bool FUSE2 = false, bool POOL = false>
 __device__ __forceinline__ void conv_gemm_dma_body(const awr_conv_args& a) {
-    static_assert(!POOL || FUSE2, "POOL belongs to the fused pair");
+    static_assert(!POOL || FUSE2 || (KB == 16 && NBUF == 2 && AFF == 0 && !EPRE && EM == 1 && !ACCB && SW == 0),
+                  "POOL: the fused pair, or a plain-input, plain-epilogue, ordered launch of the shipped stage shape");
     static_assert((KB == 16 || KB == 32) && (NBUF == 1 || NBUF == 2 || NBUF == 4), "stage shape");
     static_assert(AFF != 4 || (KB == 16 && NBUF == 2), "the in-LDS affine pass belongs to the shipped stage shape");
     static_assert(NBUF != 4 || (KB == 16 && !FUSE2), "deep pipeline: 16-float stages");      // (round 6: blocked accumulation too -- the launches that take the
@@ -1718,12 +1724,14 @@ __device__ __forceinline__ void conv_gemm_dma_body(const awr_conv_args& a) {
                 compute2(st + 1, 1, 1);
                 if (more) landed();
             }
-            if constexpr (POOL) pair_pool_epilogue<TM, TN>(e, acc, reinterpret_cast<float*>(B2), M, tile_m, hf);
+            if constexpr (POOL) pool_epilogue<TM, TN>(e, acc, reinterpret_cast<float*>(B2), M, tile_m, hf, false);
             else gemm_epilogue<TM, TN>(e, ph, acc, reinterpret_cast<float*>(B2), M, tile_m, hf);
         }
         return;
     }
-    if constexpr (DIRECT) {
+    if constexpr (POOL) {      // (the launcher admits a single 1x1 tap at stride 1 only: M is a whole number of 2D tiles)
+        pool_epilogue<TM, TN>(a, acc, smem, M, tile_m, tile_n, a.out_nt == 2);
+    } else if constexpr (DIRECT) {
         if constexpr (EPRE) gemm_epilogue_direct<TM, TN, true>(a, ph, acc, M, tile_m, tile_n, &epre, eoffd);
         else gemm_epilogue_direct<TM, TN, false>(a, ph, acc, M, tile_m, tile_n);
     } else {
@@ -1738,6 +1746,11 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(2))) void c
 template <int TM, int TN, bool POOL = false>
 __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(2))) void conv_gemm_dma_pair_kernel(const awr_conv_args a) {
     conv_gemm_dma_body<TM, TN, 16, 2, 0, false, 1, false, false, 0, true, POOL>(a);
+}
+// a 1x1 launch (DUAL: over two input tensors) that also writes the 2x2 max-pool of its output
+template <int TM, int TN, bool DUAL>
+__global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(2))) void conv_gemm_dma_pool_kernel(const awr_conv_args a) {
+    conv_gemm_dma_body<TM, TN, 16, 2, 0, false, 1, DUAL, false, 0, false, true>(a);
 }
 
 #ifdef AWR_STUDY

@@ -117,4 +117,11 @@ void launch_dma_tile(const awr_conv_args* a, dim3 grid, hipStream_t st, int mode
     else if (aff == 1) launch_dma_em<TM, TN, 16, 2, 1>(a, grid, st, epre, em);
     else launch_dma_em<TM, TN, 16, 2, 0>(a, grid, st, epre, em);
 }
+// A plain (or, with in2, two-tensor) 1x1 launch that also writes the 2x2 max-pool of its output (awr_conv_args.pool_out): the shipped stage shape only.
+// The launcher has checked every condition of the form (conv_gemm_one).
+template <int TM, int TN>
+void launch_dma_pool_tile(const awr_conv_args* a, dim3 grid, hipStream_t st) {
+    if (a->in2) hipLaunchKernelGGL((conv_gemm_dma_pool_kernel<TM, TN, true>), grid, dim3(256), 0, st, *a);
+    else hipLaunchKernelGGL((conv_gemm_dma_pool_kernel<TM, TN, false>), grid, dim3(256), 0, st, *a);
+}
 }  // namespace awr

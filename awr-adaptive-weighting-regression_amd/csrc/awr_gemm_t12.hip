@@ -4,4 +4,5 @@
 
 namespace awr {
 template void launch_dma_tile<1, 2>(const awr_conv_args*, dim3, hipStream_t, int, int, bool, int);
+template void launch_dma_pool_tile<1, 2>(const awr_conv_args*, dim3, hipStream_t);
 }  // namespace awr

@@ -617,6 +617,10 @@ struct Tn {
     // d(y) is still written -- by an apply launch that travels with the weight gradient on its side stream
     bool conv_out = false;
     awr_conv_args* pair_args = nullptr;       // written by a fused inference pair (conv_pair): a 2x2 max-pool of it can ride in that launch (pool_out)
+    // ... or by a plain / two-tensor 1x1 inference launch whose form admits pool_out (Builder::note_pool_producer); its op and tunable-launch entry get
+    // the "+pool" suffix when a max-pool takes the offer
+    awr_conv_args* pool_args = nullptr;
+    size_t pool_op = 0, pool_gemm = 0;
     struct FusedStats* fstats = nullptr;      // produced by a max-pool / up-sampling add that can accumulate the next BatchNorm's statistics itself
     bool half_ok = false;     // conv output whose data gradient may run as two half-batch parts (set by conv())
     bool half_dy = false;     // ... and whose BatchNorm backward writes d(y) half by half: the second half on the weight gradient's stream
@@ -917,6 +921,18 @@ struct Builder {
     }
 
     // ---- ops ----
+    // The launch just emitted (P.fwd.back() / P.gemms.back()) produces y: remember it when a 2x2 max-pool of y could ride in it -- an inference launch that
+    // is a 1x1 convolution at stride 1 with a plain input, the plain epilogue (bias, optional residual), ordered accumulation, the FP32-MFMA product
+    // mode and no split-K scratch (awr_conv_args.pool_out, include/awr_hip.h).  maxpool() checks the map's shape and the switches.
+    void note_pool_producer(Tn* y, awr_conv_args* a) {
+        if (P.training || awr_get_gemm_products() != 1 || a->nphase != 1 || a->ph[0].ntaps != 1 || (a->ph[0].tap[0] & 0xffff) != 0 || a->T != 1 || a->si != 1 ||
+            a->so != 1 || a->in_scale || a->relu_in || a->stats || a->out_scale || a->relu_out || a->accum != 0 || a->partial)
+            return;
+        y->pool_args = a;
+        y->pool_op = P.fwd.size() - 1;
+        y->pool_gemm = P.gemms.size() - 1;
+    }
+
     // y = conv(x) [+bias] [*s+t] [+res] [relu]
     Tn* conv(Tn* x, ConvLayer* layer, ConvOpt o = ConvOpt()) {
         use_layer(layer);
@@ -1009,6 +1025,7 @@ struct Builder {
         op.gemm = true;
         op.macs = gemm_macs(prob, B, spec);
         P.gemms.push_back({a, nullptr, name});
+        note_pool_producer(y, a);
         if (P.training) {
             Tn* res = o.res;
             const bool has_bias = bias != nullptr;
@@ -1123,6 +1140,7 @@ struct Builder {
         op.gemm = true;
         op.macs = gemm_macs(fwd_problem(d->c3->spec, a->H, a->W), B, d->c3->spec) + gemm_macs(fwd_problem(d->sk->spec, x->H, x->W), B, d->sk->spec);
         P.gemms.push_back({ca, nullptr, name});
+        note_pool_producer(y, ca);
         if (P.training) {
             ConvLayer *c3 = d->c3, *sk = d->sk;
             P.nodes.push_back([=]() {
@@ -1496,6 +1514,16 @@ struct Builder {
         return err;
     }
 
+    // May the 2x2 max-pool of x be written by the 1x1 launch that produces x?  The width rule is checked against the widest tile the launch can run
+    // with before it is tuned (the launcher's heuristic takes 128-row tiles -- 64 columns -- for K extents of at most 64); the tuner and
+    // awr_plan_set_gemm keep to the tiles the map's width admits.
+    bool gemm_pool_ok(Tn* x, int k, int s_, int p) const {
+        const awr_conv_args* a = x->pool_args;
+        if (P.training || !a || a->pool_out || k != 2 || s_ != 2 || p != 0 || x->lazy || x->H % 2 != 0) return false;
+        const int tm = a->tile_m ? a->tile_m : a->Cin <= 64 ? 2 : 1;
+        return x->W % (32 * tm) == 0 && env_or("AWR_PAIR_POOL", 1) && env_or("AWR_GEMM_POOL", 1) && awr_get_gemm_staging() != 0;
+    }
+
     Tn* maxpool(Tn* x, int k, int s_, int p) {
         const int B = x->B, H = x->H, W = x->W, C = x->C;
         const int Ho = (H + 2 * p - k) / s_ + 1, Wo = (W + 2 * p - k) / s_ + 1;
@@ -1519,6 +1547,12 @@ struct Builder {
             if (!P.training && pa && !pa->pool_out && k == 2 && s_ == 2 && p == 0 && !x->lazy && H % 2 == 0 && W % (pbm / 2) == 0 && env_or("AWR_PAIR_POOL", 1) &&
                 awr_get_gemm_staging() != 0 && env_or("AWR_FUSE2_DMA", 1) && !pa->in_scale && !pa->relu_in) {
                 pa->pool_out = ob;
+            } else if (gemm_pool_ok(x, k, s_, p)) {
+                // ... and so is the pool of a plain / two-tensor 1x1 launch's output (conv3 (+ skip) of a residual whose pair did not form: Winograd plans, low
+                // batches, AWR_NO_FUSE2).  AWR_GEMM_POOL=0: this form off (A/B hook, read per plan); AWR_PAIR_POOL=0: no pool rides in any GEMM launch
+                x->pool_args->pool_out = ob;
+                P.fwd[x->pool_op].name += "+pool";
+                P.gemms[x->pool_gemm].name += "+pool";
             } else {
                 f("awr_maxpool_fwd", [=](void* s) {
                     return fs && fs->sp ? awr_maxpool_fwd_stats(xb, ls, lt, lr, B, H, W, C, k, s_, p, ob, arg, fs->sp, fs->ns, s)
@@ -2301,6 +2335,8 @@ static int autotune(awr_plan& P, int reps, void* stream) {
         } else if (g.ca) {
             cands = {{1, 1, 0}, {2, 1, 0}};
             if (g.ca->N > 64) { cands.push_back({1, 2, 0}); cands.push_back({2, 2, 0}); }
+            if (g.ca->pool_out)      // a launch that carries a max-pool: only tiles whose 2D patch (32 tile_m columns) divides the map's width
+                cands.erase(std::remove_if(cands.begin(), cands.end(), [&](const Cand& c) { return g.ca->Wq % (32 * c.tm) != 0; }), cands.end());
             if (g.ca->partial && g.ca->split_max > 1 && awr_get_gemm_products() == 1) {      // (tile, split-K depth) pairs; tb = depth
                 std::vector<Cand> withk;
                 int minsteps = 1 << 30;
@@ -2793,6 +2829,9 @@ int awr_plan_set_gemm(awr_plan* p, int i, int tile_m, int tile_n, int target_blo
     GemmRef& g = p->gemms[i];
     AWR_REQUIRE(!(p->det && g.wa), "plan_set_gemm: a deterministic plan sizes the per-chunk copies of its weight gradients for the default geometry");
     if (g.ca) {
+        AWR_REQUIRE(!(g.ca->pool_out && !g.ca->w2) || g.ca->Wq % (32 * tile_m) == 0,
+                    "plan_set_gemm: launch %d (%s) also writes the max-pool of its output: tile_m = %d needs a map width that is a multiple of %d (it is %d)",
+                    i, g.name.c_str(), tile_m, 32 * tile_m, g.ca->Wq);
         g.ca->tile_m = tile_m; g.ca->tile_n = tile_n;
         if (target_blocks && g.ca->partial && target_blocks <= g.ca->split_max) g.ca->split_k = target_blocks;      // conv launches: split-K depth
     } else {

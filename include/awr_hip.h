@@ -256,9 +256,13 @@ typedef struct awr_conv_args {
     const void* in_split;   /* optional (split-operand mode): the PRE-CUT image of `in` -- [pixel][Cin / 32][h | m | l][32] bf16, 6 bytes per element, written */
                             /* by awr_split_act (or a producer's epilogue): both operands then travel global -> LDS by DMA and the K loop holds no cutting */
                             /* arithmetic.  Excludes in_scale / relu_in (the producer applies them before it cuts), in2, in_bnb_y, split-K */
-    float* pool_out;        /* optional, fused pair only (w2): also write MaxPool2d(2, 2) of the pair's output, (B, Hout / 2, Wout / 2, N) -- the workgroup */
-                            /* tiles become 2D patches (two image rows x 32 / 64 columns) so that every window meets in the epilogue; needs an even map */
-                            /* height and a width that is a multiple of the patch width.  model/hourglass.py:65-70: every level's input feeds up1 AND a pool */
+    float* pool_out;        /* optional: also write MaxPool2d(2, 2) of the launch's output, (B, Hout / 2, Wout / 2, N), bit-identical to awr_maxpool_fwd -- the */
+                            /* workgroup tiles become 2D patches (two image rows x 32 / 64 columns) so that every window meets in the epilogue.  Accepted on a  */
+                            /* fused pair (w2), or on a plain / two-tensor (in2) 1x1 launch: FP32-MFMA mode with LDS-DMA staging, one phase, one tap, stride 1, */
+                            /* plain input (no in_scale / relu_in / in_bnb_y / in_split), plain epilogue (bias, optional res: no stats / bnr_y / output affine  */
+                            /* / ReLU), accum = 0, no split-K (a resolved depth of 1).  Both need an even map height and a width that is a multiple of the      */
+                            /* patch width (32 tile_m for the 1x1 form, with the tile the launch actually runs).  Anything else with pool_out set is an error:  */
+                            /* it is never left unwritten.  model/hourglass.py:65-70: every level's input feeds up1 AND a pool                                  */
     int out_nt;             /* cache policy of the output stores and of the epilogue's operand loads (res / bnr_y / bnr_act): 0 = automatic, 1 = cached, */
                             /* 2 = streaming (`buffer_store ... nt`: a short-K launch's 32 KB tile per workgroup does not evict the operand lines the K loops */
                             /* of its neighbours still want -- DESIGN.md 4.2) */
