@@ -88,6 +88,11 @@ class WinoArgs(C.Structure):
                 ("out_scale", C.c_void_p), ("out_shift", C.c_void_p)]
 
 
+class PlanModes(C.Structure):
+    """awr_plan_modes (include/awr_hip.h): the build modes of one plan"""
+    _fields_ = [("accum", C.c_int), ("accum_auto_k", C.c_int), ("accum_auto_dgrad", C.c_int), ("winograd", C.c_int), ("train_split_k", C.c_int)]
+
+
 class NyuSample(C.Structure):
     """awr_nyu_sample (include/awr_hip.h): one image of a device-side NYU batch."""
     _fields_ = [("frame", C.c_int64), ("ustart", C.c_int32), ("vstart", C.c_int32), ("cw", C.c_int32), ("ch", C.c_int32),
@@ -174,6 +179,7 @@ _SIGS = {
     "awr_net_tensor_info": ([_P, _L, C.POINTER(C.c_char_p), C.POINTER(_I), C.POINTER(_I), C.POINTER(_L), C.POINTER(_L), C.POINTER(_I)], C.c_int),
     "awr_net_bind": ([_P, _P, _P, _P], C.c_int),
     "awr_plan_create": ([_P, _I, _I, _I, C.c_uint, _I, _I, _P, _PP, _PP, _PP], C.c_int),
+    "awr_plan_create_modes": ([_P, _I, _I, _I, C.c_uint, _I, _I, _P, _PP, _PP, C.POINTER(PlanModes), _PP], C.c_int),
     "awr_plan_destroy": ([_P], C.c_int),
     "awr_plan_info": ([_P, C.POINTER(_L), C.POINTER(_I), C.POINTER(_I), C.POINTER(_I), C.POINTER(_I), C.POINTER(_I), C.POINTER(_I)], C.c_int),
     "awr_plan_bucket": ([_P, _I, C.POINTER(_L), C.POINTER(_L), C.POINTER(_I)], C.c_int),

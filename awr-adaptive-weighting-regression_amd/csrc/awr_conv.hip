@@ -38,6 +38,24 @@ extern template void launch_dma_pool_tile<1, 1>(const awr_conv_args*, dim3, hipS
 extern template void launch_dma_pool_tile<1, 2>(const awr_conv_args*, dim3, hipStream_t);
 extern template void launch_dma_pool_tile<2, 1>(const awr_conv_args*, dim3, hipStream_t);
 extern template void launch_dma_pool_tile<2, 2>(const awr_conv_args*, dim3, hipStream_t);
+
+int check_gemm_accum(int mode) {
+    AWR_REQUIRE(mode >= 0 && mode <= 2, "gemm_accum: 0 (ordered), 1 (blocked: restart every 128 k) or 2 (auto: blocked where the K extent is long)");
+    return AWR_OK;
+}
+int check_gemm_accum_auto(int min_k) {
+    AWR_REQUIRE(min_k >= 256, "gemm_accum_auto: the threshold is a K extent >= 256 (shorter extents are one block anyway)");
+    return AWR_OK;
+}
+int check_train_split_k(int on) {
+    AWR_REQUIRE(on == 0 || on == 1, "train_split_k: 0 (off) or 1 (on)");
+    return AWR_OK;
+}
+int resolve_gemm_accum(const awr_plan_modes& m, int k_extent, int kind) {
+    if (m.accum != 2) return m.accum;
+    if (kind != AWR_GEMM_FORWARD && !(kind == AWR_GEMM_DGRAD && m.accum_auto_dgrad)) return 0;
+    return (g_products == 1 && g_staging != 0 && k_extent >= m.accum_auto_k) ? 1 : 0;
+}
 }  // namespace awr
 
 using namespace awr;
@@ -89,7 +107,7 @@ int awr_set_gemm_staging(int mode) {
 int awr_get_gemm_staging(void) { return g_staging; }
 
 int awr_set_gemm_accum(int mode) {
-    AWR_REQUIRE(mode >= 0 && mode <= 2, "gemm_accum: 0 (ordered), 1 (blocked: restart every 128 k) or 2 (auto: blocked where the K extent is long)");
+    if (int e = check_gemm_accum(mode)) return e;
     g_accum = mode;
     return AWR_OK;
 }
@@ -97,7 +115,7 @@ int awr_set_gemm_accum(int mode) {
 int awr_get_gemm_accum(void) { return g_accum; }
 
 int awr_set_gemm_accum_auto(int min_k, int dgrad) {
-    AWR_REQUIRE(min_k >= 256, "gemm_accum_auto: the threshold is a K extent >= 256 (shorter extents are one block anyway)");
+    if (int e = check_gemm_accum_auto(min_k)) return e;
     g_accum_auto_k = min_k;
     g_accum_auto_dgrad = dgrad != 0;
     return AWR_OK;
@@ -110,7 +128,7 @@ int awr_get_gemm_accum_auto(int* min_k, int* dgrad) {
 }
 
 int awr_set_train_split_k(int on) {
-    AWR_REQUIRE(on == 0 || on == 1, "train_split_k: 0 (off) or 1 (on)");
+    if (int e = check_train_split_k(on)) return e;
     g_train_split_k = on;
     return AWR_OK;
 }
@@ -118,9 +136,7 @@ int awr_set_train_split_k(int on) {
 int awr_get_train_split_k(void) { return g_train_split_k; }
 
 int awr_resolve_gemm_accum(int k_extent, int kind) {
-    if (g_accum != 2) return g_accum;
-    if (kind != AWR_GEMM_FORWARD && !(kind == AWR_GEMM_DGRAD && g_accum_auto_dgrad)) return 0;
-    return (g_products == 1 && g_staging != 0 && k_extent >= g_accum_auto_k) ? 1 : 0;
+    return resolve_gemm_accum(awr_plan_modes{g_accum, g_accum_auto_k, g_accum_auto_dgrad, 0, 0}, k_extent, kind);
 }
 
 static int conv_gemm_one(const awr_conv_args* a, void* stream);

@@ -28,11 +28,13 @@
 #include <vector>
 
 #include "awr_common.h"
+#include "awr_conv_modes.h"
 
 extern "C" unsigned long long awr_dp_generation(const awr_dp* d);      // csrc/awr_dp.hip: generation of a communicator that has not been destroyed, else 0
 
 namespace awrnet {
 
+using awr::env_int;
 using awr::set_error;
 
 constexpr float BN_EPS = 1e-5f;
@@ -277,6 +279,11 @@ struct Prob {
     int Hin, Win, Cin, Hout, Wout, N, Hq, Wq, so, si;
     std::vector<PhaseT> phases;
     bool full;
+    int k_extent() const {      // terms one output element sums: taps x input channels of the longest phase
+        size_t taps = 0;
+        for (auto& ph : phases) taps = std::max(taps, ph.taps.size());
+        return (int)taps * Cin;
+    }
 };
 
 static std::vector<PhaseT> gather_taps(const Spec& s) {       // conv-type gather: one phase, taps (ky-p, kx-p, ky*k+kx)
@@ -331,19 +338,15 @@ static Prob dgrad_problem(const Spec& s, int hin, int win) {
     return Prob{ho, wo, s.cout_pad, hin, win, s.cin_pad, hin / 2, win / 2, 2, 1, ph, full};
 }
 
-static void fill_conv_args(awr_conv_args& a, const Prob& p, int B, const float* in, const float* w, const void* w_split, float* out, int T,
-                           int kind = AWR_GEMM_OTHER) {
+// accum: the launch's accumulation order (0 / 1), resolved by the builder from the plan's modes (Builder::accum)
+static void fill_conv_args(awr_conv_args& a, const Prob& p, int B, const float* in, const float* w, const void* w_split, float* out, int T, int accum) {
     memset(&a, 0, sizeof a);
     a.in = in; a.w = w; a.out = out; a.w_split = w_split;
     a.B = B; a.Hin = p.Hin; a.Win = p.Win; a.Cin = p.Cin;
     a.Hq = p.Hq; a.Wq = p.Wq; a.Hout = p.Hout; a.Wout = p.Wout; a.N = p.N;
     a.so = p.so; a.si = p.si; a.T = T;
     a.nphase = (int)p.phases.size();
-    {   // the accumulation order is captured when the plan is built, like the deterministic mode; AUTO resolves per launch by its K extent
-        size_t taps = 0;
-        for (auto& ph : p.phases) taps = std::max(taps, ph.taps.size());
-        a.accum = awr_resolve_gemm_accum((int)taps * p.Cin, kind);
-    }
+    a.accum = accum;
     for (int i = 0; i < a.nphase; ++i) {
         a.ph[i].py = p.phases[i].py;
         a.ph[i].px = p.phases[i].px;
@@ -674,7 +677,7 @@ struct awr_plan {
     awr_net* net = nullptr;
     int B = 0, H = 0;
     bool training = false, det = false;
-    bool train_split = false;                  // awr_get_train_split_k() when the plan was built
+    awr_plan_modes modes{};                    // what the plan was built with (awr_plan_create_modes); every build-time decision reads these
     int bn_repeat = 1, n_buckets = 1;
     unsigned supervised = 0;
     std::vector<Op> fwd, bwd, pack_ops;
@@ -739,10 +742,6 @@ namespace awrnet {
 
 // ---- plan building -------------------------------------------------------------------------------------------
 struct Tn;
-static int env_or(const char* name, int dflt) {
-    const char* e = getenv(name);
-    return e ? atoi(e) : dflt;
-}
 
 struct ConvOpt {
     const float *in_scale = nullptr, *in_shift = nullptr;
@@ -790,6 +789,8 @@ struct Builder {
         return (int)(((int64_t)B * Hq * Wq + 63) / 64) * ((Nn + 63) / 64) * nphase;
     }
     int reduce_slots() const { return P.det ? AWR_REDUCE_MAX_BLOCKS : AWR_STAT_SLOTS; }
+    // the accumulation order (awr_conv_args.accum) of a launch of this K extent and kind under the plan's mode; AUTO resolves per launch
+    int accum(int k_extent, int kind) const { return awr::resolve_gemm_accum(P.modes, k_extent, kind); }
 
     // Training split-K (awr_set_train_split_k): a forward / data-gradient launch of a few workgroups with a long K loop gets scratch
     // for up to `smax` raw copies of its output -- the inference rule and its constants (conv() below): 64x64-tile workgroups x phases x copies
@@ -801,7 +802,7 @@ struct Builder {
     // split-operand product mode, or launches a Winograd form has taken (the callers).
     static constexpr int64_t TRAIN_SPLIT_MAX_BYTES = 8ll << 20;
     void train_split_scratch(awr_conv_args* a) {
-        if (!P.training || !P.train_split || awr_get_gemm_products() != 1 || a->in2 || a->w2 || a->in_bnb_y || a->partial) return;
+        if (!P.training || !P.modes.train_split_k || awr_get_gemm_products() != 1 || a->in2 || a->w2 || a->in_bnb_y || a->partial) return;
         if (a->so != 1 && a->nphase != a->so * a->so) return;
         const int64_t numel = (int64_t)a->B * a->Hout * a->Wout * a->N;
         const int64_t wgs = ((int64_t)a->B * a->Hq * a->Wq + 63) / 64 * ((a->N + 63) / 64) * (int64_t)a->nphase;
@@ -830,8 +831,8 @@ struct Builder {
 
     // the forward of this stride-1 3x3 layer may run as Winograd F(2x2, 3x3) (mode, kernel constraints, launch-size rule)
     bool wino_fwd_ok(const Spec& spec, int B, int H, int W) const {
-        return awr_get_conv_winograd() && !P.det && awr_get_gemm_products() == 1 && !spec.deconv && spec.k == 3 && spec.stride == 1 && spec.pad == 1 &&
-               awr_wino_eligible(B, H, W, spec.cin_pad, spec.cout_pad);
+        return P.modes.winograd && !P.det && awr_get_gemm_products() == 1 && !spec.deconv && spec.k == 3 && spec.stride == 1 && spec.pad == 1 &&
+               awr::wino_eligible(P.modes.winograd, B, H, W, spec.cin_pad, spec.cout_pad);
     }
 
     Op& push(std::vector<Op>& list, const std::string& name, std::function<int(void*)> fn) {
@@ -947,7 +948,7 @@ struct Builder {
             // hidden apply pass wins; profiles/r05_half_batch_wavefront.txt).  AWR_HALF_BNB_MIN_ROWS = rows of the data-gradient GEMM per half from
             // which a layer takes part (read per plan); 0 = off, the default.
 #ifdef AWR_STUDY
-            const int64_t half_min = env_or("AWR_HALF_BNB_MIN_ROWS", 0);
+            const int64_t half_min = env_int("AWR_HALF_BNB_MIN_ROWS", 0);
 #else
             const int64_t half_min = 0;      // (the wavefront's scheduling states exist in study builds only: ADVICE r5)
 #endif
@@ -997,7 +998,7 @@ struct Builder {
         }
         P.cargs.emplace_back();
         awr_conv_args* a = &P.cargs.back();
-        fill_conv_args(*a, prob, B, x->buf, layer->p_fwd.p, layer->p_fwd.split, y->buf, spec.T(), P.training ? AWR_GEMM_FORWARD : AWR_GEMM_OTHER);
+        fill_conv_args(*a, prob, B, x->buf, layer->p_fwd.p, layer->p_fwd.split, y->buf, spec.T(), accum(prob.k_extent(), P.training ? AWR_GEMM_FORWARD : AWR_GEMM_OTHER));
         a->in_scale = o.in_scale; a->in_shift = o.in_shift; a->bias = bias;
         a->out_scale = o.out_scale; a->out_shift = o.out_shift;
         a->res = o.res ? o.res->buf : nullptr;
@@ -1039,13 +1040,13 @@ struct Builder {
     // nullptr when the pair does not qualify (shape, product mode, too few workgroups to fill the chip without split-K).
     Tn* conv_pair(Tn* x, ConvLayer* c2, const ConvOpt& o, ConvLayer* c3, Tn* res, DualLayer* dual = nullptr, Tn* xin = nullptr) {
         const bool off = getenv("AWR_NO_FUSE2") != nullptr;                    // same-box A/B hook (read per plan)
-        const int min_wgs = env_or("AWR_FUSE2_MIN_WGS", 1024);                 // (tests force the fused form on small batches)
+        const int min_wgs = env_int("AWR_FUSE2_MIN_WGS", 1024);                 // (tests force the fused form on small batches)
         const bool no_dual = getenv("AWR_NO_FUSE2_DUAL") != nullptr;
         if (dual) c3 = dual->c3;
         const Spec &s2 = c2->spec, &s3 = c3->spec;
         const int64_t wgs = ((int64_t)x->B * x->H * x->W + 63) / 64;
         const int n1 = s2.cout;
-        if (off || P.training || awr_resolve_gemm_accum(s2.T() * s2.cin_pad, AWR_GEMM_OTHER) != 0 || awr_resolve_gemm_accum(s3.cin_pad, AWR_GEMM_OTHER) != 0 || awr_get_gemm_products() != 1 || s2.deconv || s3.deconv || s2.stride != 1 || s3.k != 1 || s3.stride != 1 ||
+        if (off || P.training || accum(s2.T() * s2.cin_pad, AWR_GEMM_OTHER) != 0 || accum(s3.cin_pad, AWR_GEMM_OTHER) != 0 || awr_get_gemm_products() != 1 || s2.deconv || s3.deconv || s2.stride != 1 || s3.k != 1 || s3.stride != 1 ||
             (n1 != 128 && n1 != 64) || s3.cin != n1 || s3.cout != 2 * n1 || wgs < min_wgs || x->lazy || (dual && no_dual))
             return nullptr;
         if (dual && (dual->sk->spec.k != 1 || dual->sk->spec.stride != 1 || dual->sk->spec.cout != s3.cout || dual->sk->spec.cin_pad % 32 != 0 ||
@@ -1072,7 +1073,7 @@ struct Builder {
         join_if(res);
         P.cargs.emplace_back();
         awr_conv_args* a = &P.cargs.back();
-        fill_conv_args(*a, prob, B, x->buf, c2->p_fwd.p, c2->p_fwd.split, y->buf, s2.T());
+        fill_conv_args(*a, prob, B, x->buf, c2->p_fwd.p, c2->p_fwd.split, y->buf, s2.T(), accum(prob.k_extent(), AWR_GEMM_OTHER));
         a->N1 = n1;
         a->N = 2 * n1;
         a->w2 = w2;
@@ -1082,7 +1083,7 @@ struct Builder {
         a->out_scale = o.out_scale; a->out_shift = o.out_shift; a->relu_out = o.relu_out;
         a->res = res ? res->buf : nullptr;
         if (dual) { a->in2 = xin->buf; a->N1x = n1x; }
-        if (n1 == 64) a->tile_m = env_or("AWR_FUSE2_TM64", 2), a->tile_n = 1;      // 128x64 tile (what the tuner picks for this conv on its own)
+        if (n1 == 64) a->tile_m = env_int("AWR_FUSE2_TM64", 2), a->tile_n = 1;      // 128x64 tile (what the tuner picks for this conv on its own)
         y->pair_args = a;
         const std::string tail = dual ? "conv3+skip_layer" : c3->name.substr(c3->name.rfind('.', c3->name.rfind('.') - 1) + 1);
         const std::string name = "awr_conv_gemm:" + c2->name + "+" + tail;
@@ -1128,7 +1129,7 @@ struct Builder {
         if (want_stats) y->stats = stat_buf(gemm_slots(B, prob.Hq, prob.Wq, prob.N, 1), prob.N);
         P.cargs.emplace_back();
         awr_conv_args* ca = &P.cargs.back();
-        fill_conv_args(*ca, prob, B, a->buf, d->p.p, nullptr, y->buf, 1, P.training ? AWR_GEMM_FORWARD : AWR_GEMM_OTHER);
+        fill_conv_args(*ca, prob, B, a->buf, d->p.p, nullptr, y->buf, 1, accum(prob.k_extent(), P.training ? AWR_GEMM_FORWARD : AWR_GEMM_OTHER));
         ca->in2 = x->buf;
         ca->Cin1 = cin1;
         if (a->lazy) { ca->in_scale = a->lz_scale; ca->in_shift = a->lz_shift; ca->relu_in = a->lz_relu; }
@@ -1216,8 +1217,8 @@ struct Builder {
         }
         // Winograd-domain weight gradient (winograd = "full"; csrc/awr_wino.hip): stride-1 3x3 layers with channel counts in multiples of 64 whose K loop
         // is long enough to pay for the per-split copies; writes the same packed R (and slot 0 of the bias column sums) the direct kernel accumulates into
-        const bool wino_w = (awr_get_conv_winograd() & 3) >= 2 && !P.det && awr_get_wgrad_products() == 1 && spec.k == 3 && spec.stride == 1 && spec.pad == 1 &&
-                            !spec.deconv && !layer->head && wp.d_is_dy && awr_wino_wgrad_eligible(B, H, W, spec.cin_pad, spec.cout_pad);
+        const bool wino_w = (P.modes.winograd & 3) >= 2 && !P.det && awr_get_wgrad_products() == 1 && spec.k == 3 && spec.stride == 1 && spec.pad == 1 &&
+                            !spec.deconv && !layer->head && wp.d_is_dy && awr::wino_wgrad_eligible(P.modes.winograd, B, H, W, spec.cin_pad, spec.cout_pad);
         float* wscratch = nullptr;
         if (wino_w) {
             wscratch = alloc<float>(awr_wino_wgrad_scratch(B, H, W, spec.cin_pad, spec.cout_pad));
@@ -1277,7 +1278,7 @@ struct Builder {
             }
             P.cargs.emplace_back();
             awr_conv_args* da = &P.cargs.back();
-            fill_conv_args(*da, dp, B, y->lz_g ? y->lz_g : dy, layer->p_dgrad.p, layer->p_dgrad.split, gx, spec.T(), AWR_GEMM_DGRAD);
+            fill_conv_args(*da, dp, B, y->lz_g ? y->lz_g : dy, layer->p_dgrad.p, layer->p_dgrad.split, gx, spec.T(), accum(dp.k_extent(), AWR_GEMM_DGRAD));
             if (y->lz_g) { da->in_bnb_y = y->buf; da->in_bnb_coef = y->lz_lin4; }
             da->res = acc ? gx : nullptr;
             // remember who wrote d(x), in order: a full-coverage dgrad that is the LAST producer can host the fused BN-backward reduction
@@ -1303,8 +1304,8 @@ struct Builder {
                 // Winograd data gradient (round 6): same eligibility as the forward; the launch decides from the COMPLETED argument block whether it
                 // implements its epilogue (plain, accumulate, BatchNorm-backward reduction) and runs the direct kernel otherwise
                 float* Ud = nullptr;
-                if ((awr_get_conv_winograd() & 3) == 2 && !P.det && awr_get_gemm_products() == 1 && !spec.deconv && spec.k == 3 && spec.stride == 1 && spec.pad == 1 &&
-                    dp.full && !y->lz_g && awr_wino_eligible(B, dp.Hin, dp.Win, spec.cout_pad, spec.cin_pad)) {
+                if ((P.modes.winograd & 3) == 2 && !P.det && awr_get_gemm_products() == 1 && !spec.deconv && spec.k == 3 && spec.stride == 1 && spec.pad == 1 &&
+                    dp.full && !y->lz_g && awr::wino_eligible(P.modes.winograd, B, dp.Hin, dp.Win, spec.cout_pad, spec.cin_pad)) {
                     for (auto& wl : P.wino_d)
                         if (wl.first == layer) Ud = wl.second;
                     if (!Ud) {
@@ -1467,7 +1468,7 @@ struct Builder {
         // with every eligible BatchNorm); restricted to single-tap (1x1) convolutions it is a wash (Hourglass-1 23.9 vs 24.1 ms).  The upper
         // bound -- the step with the apply passes simply left out -- is 12.76 / 21.7 ms, so the pass IS exposed, but the consumer is the
         // wrong place to hide it.  AWR_LAZY_BNB: 0 = never (default), 1 = 1x1 convolutions, 2 = every eligible BatchNorm.
-        const int lazy_mode = env_or("AWR_LAZY_BNB", 0);
+        const int lazy_mode = env_int("AWR_LAZY_BNB", 0);
         const bool lazy_bnb = lazy_mode > 0 && fused && relu && !res && !acc && !g_out && y->conv_out && (lazy_mode > 1 || y->conv_taps == 1) && y->needs_grad &&
                               C <= 512 && awr_get_gemm_products() == 1 && awr_get_gemm_staging() == 2;
         {
@@ -1521,7 +1522,7 @@ struct Builder {
         const awr_conv_args* a = x->pool_args;
         if (P.training || !a || a->pool_out || k != 2 || s_ != 2 || p != 0 || x->lazy || x->H % 2 != 0) return false;
         const int tm = a->tile_m ? a->tile_m : a->Cin <= 64 ? 2 : 1;
-        return x->W % (32 * tm) == 0 && env_or("AWR_PAIR_POOL", 1) && env_or("AWR_GEMM_POOL", 1) && awr_get_gemm_staging() != 0;
+        return x->W % (32 * tm) == 0 && env_int("AWR_PAIR_POOL", 1) && env_int("AWR_GEMM_POOL", 1) && awr_get_gemm_staging() != 0;
     }
 
     Tn* maxpool(Tn* x, int k, int s_, int p) {
@@ -1535,7 +1536,7 @@ struct Builder {
             const int lr = x->lazy && x->lz_relu ? 1 : 0;
             float* ob = y->buf;
             FusedStats* fs = nullptr;
-            if (P.training && env_or("AWR_FUSED_POOL_STATS", 1) && C % 4 == 0 && (C <= 1024 || C % 1024 == 0)) {
+            if (P.training && env_int("AWR_FUSED_POOL_STATS", 1) && C % 4 == 0 && (C <= 1024 || C % 1024 == 0)) {
                 P.fstats.emplace_back();
                 fs = &P.fstats.back();
                 y->fstats = fs;
@@ -1544,8 +1545,8 @@ struct Builder {
             // windows reduced in the epilogue) -- no pass that re-reads the full-resolution tensor.  AWR_PAIR_POOL=0: the separate pass (A/B hook)
             awr_conv_args* pa = x->pair_args;
             const int pbm = pa && pa->N1 == 64 && pa->tile_m == 2 ? 128 : 64;
-            if (!P.training && pa && !pa->pool_out && k == 2 && s_ == 2 && p == 0 && !x->lazy && H % 2 == 0 && W % (pbm / 2) == 0 && env_or("AWR_PAIR_POOL", 1) &&
-                awr_get_gemm_staging() != 0 && env_or("AWR_FUSE2_DMA", 1) && !pa->in_scale && !pa->relu_in) {
+            if (!P.training && pa && !pa->pool_out && k == 2 && s_ == 2 && p == 0 && !x->lazy && H % 2 == 0 && W % (pbm / 2) == 0 && env_int("AWR_PAIR_POOL", 1) &&
+                awr_get_gemm_staging() != 0 && env_int("AWR_FUSE2_DMA", 1) && !pa->in_scale && !pa->relu_in) {
                 pa->pool_out = ob;
             } else if (gemm_pool_ok(x, k, s_, p)) {
                 // ... and so is the pool of a plain / two-tensor 1x1 launch's output (conv3 (+ skip) of a residual whose pair did not form: Winograd plans, low
@@ -1583,7 +1584,7 @@ struct Builder {
             const float *ub = up1->buf, *lb = low->buf;
             float* ob = y->buf;
             FusedStats* fs = nullptr;
-            if (P.training && env_or("AWR_FUSED_POOL_STATS", 1) && C % 4 == 0 && (C <= 1024 || C % 1024 == 0)) {
+            if (P.training && env_int("AWR_FUSED_POOL_STATS", 1) && C % 4 == 0 && (C <= 1024 || C % 1024 == 0)) {
                 P.fstats.emplace_back();
                 fs = &P.fstats.back();
                 y->fstats = fs;
@@ -2479,6 +2480,25 @@ int awr_net_bind(awr_net* n, float* params, float* grads, float* buffers) {
 
 int awr_plan_create(awr_net* n, int B, int H, int training, unsigned supervised_mask, int bn_repeat, int n_buckets, float* img, float* const* outs,
                     float* const* grad_outs, awr_plan** out) {
+    return awr_plan_create_modes(n, B, H, training, supervised_mask, bn_repeat, n_buckets, img, outs, grad_outs, nullptr, out);
+}
+
+int awr_plan_create_modes(awr_net* n, int B, int H, int training, unsigned supervised_mask, int bn_repeat, int n_buckets, float* img, float* const* outs,
+                          float* const* grad_outs, const awr_plan_modes* modes, awr_plan** out) {
+    awr_plan_modes m;
+    if (modes) {
+        m = *modes;
+    } else {      // the process-wide modes (awr_set_gemm_accum[_auto], awr_set_conv_winograd, awr_set_train_split_k)
+        m.accum = awr_get_gemm_accum();
+        awr_get_gemm_accum_auto(&m.accum_auto_k, &m.accum_auto_dgrad);
+        m.winograd = awr_get_conv_winograd();
+        m.train_split_k = awr_get_train_split_k();
+    }
+    if (int e = awr::check_gemm_accum(m.accum)) return e;
+    if (m.accum == 2)
+        if (int e = awr::check_gemm_accum_auto(m.accum_auto_k)) return e;
+    if (int e = awr::check_conv_winograd(m.winograd)) return e;
+    if (int e = awr::check_train_split_k(m.train_split_k)) return e;
     AWR_REQUIRE(n && out && img && outs, "plan_create: null pointer");
     AWR_REQUIRE(n->params, "plan_create: bind the parameter arenas first (awr_net_bind)");
     AWR_REQUIRE(B >= 1 && H >= 16 && H % 16 == 0, "plan_create: B=%d, H=%d (multiples of 16)", B, H);
@@ -2490,7 +2510,7 @@ int awr_plan_create(awr_net* n, int B, int H, int training, unsigned supervised_
     p->H = H;
     p->training = training != 0;
     p->det = awr_get_deterministic() != 0;
-    p->train_split = awr_get_train_split_k() != 0;
+    p->modes = m;
     p->bn_repeat = bn_repeat;
     p->n_buckets = n_buckets;
     p->supervised = supervised_mask;

@@ -16,6 +16,7 @@
 #include <string.h>
 
 #include "awr_common.h"
+#include "awr_conv_modes.h"
 
 namespace awr {
 
@@ -786,6 +787,44 @@ __global__ __launch_bounds__(1024) void wino_wgrad_reduce_kernel(const float* __
     }
 }
 
+// ---- what a plan builder asks (csrc/awr_net.hip): the mode checks and launch-size rules, as functions of the Winograd code -----------------
+static int g_winograd = env_int("AWR_WINOGRAD", 0);
+
+int check_conv_winograd(int code) {
+    AWR_REQUIRE(code >= 0 && code < 16, "conv_winograd: 0 (direct implicit GEMM everywhere), 1 (Winograd F(2x2, 3x3) forward where it is eligible), 2 (forward, data "
+                                        "and weight gradient), 3 (forward and weight gradient); + 4 (tests: wherever the kernels can run, whatever the launch size); "
+                                        "+ 8 (A/B: never the 64-channel tile form)");
+    return AWR_OK;
+}
+
+int wino_eligible(int code, int B, int H, int W, int C, int N) {
+    const int minside = (code & 4) ? 4 : 8;      // (8 x 8 maps: only where the batch still gives 256 workgroups -- ResNet18 layer4 at batch 128 and up)
+    if (H < minside || W < minside || (H & (H - 1)) || (W & (W - 1)) || C % 8 || N % 32) return 0;
+    if ((int64_t)B * H * W * C >= (1LL << 31)) return 0;
+    const int PH = H / 2, PW = W / 2, PCt = PW < 32 ? PW : 32, PRt = PH < W_TP / PCt ? PH : W_TP / PCt, nimg = W_TP / (PRt * PCt);
+    const int64_t wgs = (int64_t)(PW / PCt) * (PH / PRt) * ((B + nimg - 1) / nimg) * (N / W_TN);
+    return (code & 4) || wgs >= 256;      // (fewer workgroups than half the chip's slots: the direct kernel's smaller tiles win, profiles/r06_winograd.txt)
+}
+
+static int wino_wgrad_splits(int B, int H, int W, int C, int N) {
+    // ONE round of workgroups, one per CU (a second round costs a second 256 KB copy per CU and buys nothing: 433 -> 401 us on 128 -> 128 @ 64 x 64 x 64)
+    const int nblocks = B * (H / 4) * (W / 8), tiles = (C / 64) * (N / 64);
+    int S = (256 + tiles - 1) / tiles;
+    if (S > nblocks / 2) S = nblocks / 2;      // every split owns at least one PAIR of stages (the loop body of wino_wgrad_kernel)
+    return S < 1 ? 1 : S;
+}
+
+int wino_wgrad_eligible(int code, int B, int H, int W, int C, int N) {
+    auto pow2 = [](int v) { return v > 0 && (v & (v - 1)) == 0; };
+    if (C % 64 || N % 64 || !pow2(H) || !pow2(W) || H < 8 || W < 8) return 0;
+    if ((int64_t)B * H * W * (C > N ? C : N) >= (1LL << 31)) return 0;
+    if (code & 4) return 1;
+    // every split stores a 256 KB copy of its tile (67 MB per launch whatever the layer): it takes a K loop of 8 stages to pay for it
+    // (profiles/r06_winograd.txt: 64 -> 64 @ 32 x 32 x 64 = 8 stages per split: 1.32x the direct kernel; 256 -> 256 @ 8 x 8 x 64: 1.06-1.17x)
+    const int stages = B * (H / 4) * (W / 8) / wino_wgrad_splits(B, H, W, C, N);
+    return stages >= 8;
+}
+
 }  // namespace awr
 
 using namespace awr;
@@ -799,26 +838,15 @@ int awr_wino_weights(const float* w, int N, int C, int Npad, int Cpad, int mirro
     return check_launch("wino_weight_kernel");
 }
 
-static int g_winograd = []() { const char* e = getenv("AWR_WINOGRAD"); return e ? atoi(e) : 0; }();
-
 int awr_set_conv_winograd(int on) {
-    AWR_REQUIRE(on >= 0 && on < 16, "conv_winograd: 0 (direct implicit GEMM everywhere), 1 (Winograd F(2x2, 3x3) forward where it is eligible), 2 (forward, data "
-                                    "and weight gradient), 3 (forward and weight gradient); + 4 (tests: wherever the kernels can run, whatever the launch size); "
-                                    "+ 8 (A/B: never the 64-channel tile form)");
+    if (int e = check_conv_winograd(on)) return e;
     g_winograd = on;
     return AWR_OK;
 }
 
 int awr_get_conv_winograd(void) { return g_winograd; }
 
-int awr_wino_eligible(int B, int H, int W, int C, int N) {
-    const int minside = (g_winograd & 4) ? 4 : 8;      // (8 x 8 maps: only where the batch still gives 256 workgroups -- ResNet18 layer4 at batch 128 and up)
-    if (H < minside || W < minside || (H & (H - 1)) || (W & (W - 1)) || C % 8 || N % 32) return 0;
-    if ((int64_t)B * H * W * C >= (1LL << 31)) return 0;
-    const int PH = H / 2, PW = W / 2, PCt = PW < 32 ? PW : 32, PRt = PH < W_TP / PCt ? PH : W_TP / PCt, nimg = W_TP / (PRt * PCt);
-    const int64_t wgs = (int64_t)(PW / PCt) * (PH / PRt) * ((B + nimg - 1) / nimg) * (N / W_TN);
-    return (g_winograd & 4) || wgs >= 256;      // (fewer workgroups than half the chip's slots: the direct kernel's smaller tiles win, profiles/r06_winograd.txt)
-}
+int awr_wino_eligible(int B, int H, int W, int C, int N) { return wino_eligible(g_winograd, B, H, W, C, N); }
 
 int awr_wino_conv3x3(const float* in, const float* U, const float* bias, float* out, int B, int H, int W, int C, int N, int relu, int kb, void* stream) {
     AWR_REQUIRE(in && U && out, "wino_conv3x3: NULL pointer");
@@ -919,24 +947,7 @@ int awr_wino_dgrad_or_direct(const awr_conv_args* d, const float* U, void* strea
 
 // Weight gradient of a stride-1 3x3 convolution in the Winograd domain (see wino_wgrad_kernel).  R[N][9][ld] (ld >= C) and bias_grad[N] are ASSIGNED.
 // scratch: awr_wino_wgrad_scratch() floats.  Deterministic (ordered sums over the split copies).
-static int wino_wgrad_splits(int B, int H, int W, int C, int N) {
-    // ONE round of workgroups, one per CU (a second round costs a second 256 KB copy per CU and buys nothing: 433 -> 401 us on 128 -> 128 @ 64 x 64 x 64)
-    const int nblocks = B * (H / 4) * (W / 8), tiles = (C / 64) * (N / 64);
-    int S = (256 + tiles - 1) / tiles;
-    if (S > nblocks / 2) S = nblocks / 2;      // every split owns at least one PAIR of stages (the loop body of wino_wgrad_kernel)
-    return S < 1 ? 1 : S;
-}
-
-int awr_wino_wgrad_eligible(int B, int H, int W, int C, int N) {
-    auto pow2 = [](int v) { return v > 0 && (v & (v - 1)) == 0; };
-    if (C % 64 || N % 64 || !pow2(H) || !pow2(W) || H < 8 || W < 8) return 0;
-    if ((int64_t)B * H * W * (C > N ? C : N) >= (1LL << 31)) return 0;
-    if (g_winograd & 4) return 1;
-    // every split stores a 256 KB copy of its tile (67 MB per launch whatever the layer): it takes a K loop of 8 stages to pay for it
-    // (profiles/r06_winograd.txt: 64 -> 64 @ 32 x 32 x 64 = 8 stages per split: 1.32x the direct kernel; 256 -> 256 @ 8 x 8 x 64: 1.06-1.17x)
-    const int stages = B * (H / 4) * (W / 8) / wino_wgrad_splits(B, H, W, C, N);
-    return stages >= 8;
-}
+int awr_wino_wgrad_eligible(int B, int H, int W, int C, int N) { return wino_wgrad_eligible(g_winograd, B, H, W, C, N); }
 
 int64_t awr_wino_wgrad_scratch(int B, int H, int W, int C, int N) {
     const int S = wino_wgrad_splits(B, H, W, C, N);

@@ -155,9 +155,11 @@ class DpComm:
 
 
 class Plan:
-    """awr_plan + its boundary tensors.  Building allocates every buffer; replaying allocates nothing and never synchronises."""
+    """awr_plan + its boundary tensors.  Building allocates every buffer; replaying allocates nothing and never synchronises.
+    accum (0 ordered, 1 blocked, 2 auto), auto_rule (K-extent threshold, data gradients too), winograd (the code of awr_set_conv_winograd) and
+    train_split_k (0 / 1) are the plan's RESOLVED build modes (awr_plan_modes); AwrBackbone.get_plan resolves them from its arguments."""
 
-    def __init__(self, net, B, H, F, J, training, supervised, bn_repeat=1, n_buckets=1):
+    def __init__(self, net, B, H, F, J, training, supervised, bn_repeat=1, n_buckets=1, *, accum, auto_rule, winograd, train_split_k):
         dev = net.device
         self.net, self.B, self.H, self.dev, self.training = net, B, H, dev, bool(training)
         self.bn_repeat, self.n_buckets = bn_repeat, n_buckets
@@ -172,7 +174,13 @@ class Plan:
         outs = (C.c_void_p * nstage)(*[o.data_ptr() for o in self.outputs])
         gouts = (C.c_void_p * nstage)(*[g.data_ptr() for g in self.grad_outs]) if training else None
         self.h = C.c_void_p()
-        L.call("awr_plan_create", net._handle.h, B, H, int(bool(training)), mask, bn_repeat, n_buckets, L.ptr(self.img), outs, gouts, C.byref(self.h))
+        self.accum, self.winograd, self.train_split_k = int(accum), int(winograd), int(train_split_k)
+        modes = L.PlanModes(self.accum, int(auto_rule[0]), int(auto_rule[1]), self.winograd, self.train_split_k)
+        L.call("awr_plan_create_modes", net._handle.h, B, H, int(bool(training)), mask, bn_repeat, n_buckets, L.ptr(self.img), outs, gouts, C.byref(modes),
+               C.byref(self.h))
+        nw, wm = C.c_int(0), C.c_double(0)
+        L.call("awr_plan_winograd", self.h, C.byref(nw), C.byref(wm))
+        self.n_winograd, self.winograd_macs = nw.value, wm.value       # launches that run as Winograd F(2x2, 3x3) (forward, data / weight gradients); their algorithmic MACs
         nbytes, det, nf, nb, nbk, ng, nbn = C.c_int64(), C.c_int(), C.c_int(), C.c_int(), C.c_int(), C.c_int(), C.c_int()
         L.call("awr_plan_info", self.h, C.byref(nbytes), C.byref(det), C.byref(nf), C.byref(nb), C.byref(nbk), C.byref(ng), C.byref(nbn))
         self.bytes = nbytes.value + sum(t.numel() * 4 for t in [self.img] + self.outputs + [g for g in self.grad_outs if g is not None])
@@ -353,8 +361,7 @@ class Plan:
             return
         cache_file = os.environ.get("AWR_TUNE_CACHE")
         if cache_key:
-            cache_key = tile_cache_key(cache_key, L.lib.awr_get_gemm_products(), L.lib.awr_get_gemm_staging(), int(getattr(self, "accum", 0)),
-                                       int(getattr(self, "winograd", 0)), int(getattr(self, "train_split_k", 0)))
+            cache_key = tile_cache_key(cache_key, L.lib.awr_get_gemm_products(), L.lib.awr_get_gemm_staging(), self.accum, self.winograd, self.train_split_k)
         names = [self._gemm(i)[0] for i in range(self.n_gemm)]
         if cache_file and cache_key:
             ent = cached_tiles(cache_file, cache_key, names)

@@ -158,28 +158,15 @@ class AwrBackbone(nn.Module):
         if not self._arena.is_cuda:
             raise L.AwrError("the AWR backbone runs on the MI355X only: call .cuda() first (there is no CPU path)")
         acc = self.plan_accum(accum, training)
-        wino = int(L.lib.awr_get_conv_winograd()) if winograd is None else _winograd_code(winograd)      # captured when the plan is built, like accum
+        wino = int(L.lib.awr_get_conv_winograd()) if winograd is None else _winograd_code(winograd)
         tsk = (int(L.lib.awr_get_train_split_k()) if split_k is None else int(_split_k_flag(split_k))) if training else 0
+        rule = _auto_rule()
         key = (B, H, bool(training), supervised if isinstance(supervised, str) else tuple(supervised), bn_repeat, n_buckets, L.lib.awr_get_deterministic(), acc,
-               _auto_rule() if acc == 2 else 0, wino, tsk)
+               rule if acc == 2 else 0, wino, tsk)
         plan = self._plans.get(key)
         if plan is None:
-            was, was_w, was_k = int(L.lib.awr_get_gemm_accum()), int(L.lib.awr_get_conv_winograd()), int(L.lib.awr_get_train_split_k())
-            L.call("awr_set_gemm_accum", acc)          # plans capture the modes when they are built
-            L.call("awr_set_conv_winograd", wino)
-            L.call("awr_set_train_split_k", tsk)
-            try:
-                plan = Plan(self, B, H, H // getattr(self, "downsample", 2), self.J, training, supervised, bn_repeat, n_buckets)
-            finally:
-                L.call("awr_set_gemm_accum", was)
-                L.call("awr_set_conv_winograd", was_w)
-                L.call("awr_set_train_split_k", was_k)
-            nw, wm = L.C.c_int(0), L.C.c_double(0)
-            L.call("awr_plan_winograd", plan.h, L.C.byref(nw), L.C.byref(wm))
-            plan.n_winograd, plan.winograd_macs = nw.value, wm.value       # launches that run as Winograd F(2x2, 3x3) (forward, data / weight gradients); their algorithmic MACs
-            plan.accum = acc          # 0 = ordered, 1 = blocked, 2 = auto (blocked per launch by K extent): what the plan's GEMM launches captured
-            plan.winograd = wino      # the Winograd code the plan was built with (awr_set_conv_winograd)
-            plan.train_split_k = tsk  # 1: built under awr_set_train_split_k (training plans)
+            plan = Plan(self, B, H, H // getattr(self, "downsample", 2), self.J, training, supervised, bn_repeat, n_buckets,
+                        accum=acc, auto_rule=rule, winograd=wino, train_split_k=tsk)
             self._plans[key] = plan
         return plan
 

@@ -309,7 +309,9 @@ int awr_get_wgrad_products(void);
 int awr_debug_set_knob(const char* name, int value);
 int awr_set_gemm_staging(int mode);
 int awr_get_gemm_staging(void);
-/* Accumulation order of the forward / data-gradient GEMMs of plans created from now on (process-wide; default 2, or $AWR_ACCUM):
+/* Accumulation order of the forward / data-gradient GEMMs of a plan.  awr_set_gemm_accum / awr_set_gemm_accum_auto set the process-wide DEFAULT
+ * (2, or $AWR_ACCUM), which a plan created without a modes block captures (awr_plan_create, awr_plan_create_modes(..., NULL, ...)); a plan
+ * created with one takes awr_plan_modes.accum / accum_auto_k / accum_auto_dgrad and never looks at the default.
  * 0 = ordered, 1 = blocked (awr_conv_args.accum), 2 = AUTO (the default): a plain FORWARD launch of a TRAINING plan (FP32-MFMA, LDS-DMA
  * staging, no fused pair / split-K: what the blocked kernel exists for) is blocked when its K extent (taps x input channels of its longest
  * phase) reaches min_k terms (default 576: every 3x3 convolution from 64 channels up and the transposed convolutions), everything else --
@@ -320,8 +322,8 @@ int awr_get_gemm_staging(void);
  * training forward alone (profiles/r06_accum_modes.txt) -- for which the joints of the two-image training-mode fixtures land CLOSER to
  * float64 than the fp32 oracle's own.  awr_set_gemm_accum_auto(min_k, dgrad): the threshold, and whether data-gradient launches follow the
  * same rule (default no).  Blocked = every launch the blocked kernel exists for: the parity mode (InferEngine(parity=True),
- * TrainEngine(accum="blocked")).  awr_resolve_gemm_accum: what a launch of that K extent and kind gets under the current mode (what plan
- * builders store in awr_conv_args.accum, which itself only takes 0 / 1). */
+ * TrainEngine(accum="blocked")).  awr_resolve_gemm_accum: what a launch of that K extent and kind gets under the process-wide default (plan
+ * builders apply the same rule to their plan's modes and store the result in awr_conv_args.accum, which itself only takes 0 / 1). */
 #define AWR_GEMM_OTHER 0        /* evaluation-plan forward, fused pairs, anything else */
 #define AWR_GEMM_FORWARD 1      /* forward launch of a training plan */
 #define AWR_GEMM_DGRAD 2        /* data gradient */
@@ -333,7 +335,8 @@ int awr_resolve_gemm_accum(int k_extent, int kind);
 /* the split-K depth awr_conv_gemm runs the launch `a` with (1 = unsplit): the explicit split_k, or the heuristic from the workgroup count and the K
  * depth -- a pure function of the argument block and the process-wide modes; the same errors as awr_conv_gemm for a depth the launch cannot honour */
 int awr_conv_split_depth(const awr_conv_args* a, int* depth);
-/* Split-K for TRAINING plans (process-wide, read when a plan is built; default 0, or $AWR_TRAIN_SPLIT_K): 1 = the forward and data-gradient launches
+/* Split-K for TRAINING plans (awr_plan_modes.train_split_k; awr_set_train_split_k sets the process-wide default -- 0, or $AWR_TRAIN_SPLIT_K -- that a plan
+ * created without a modes block captures): 1 = the forward and data-gradient launches
  * of a training plan that have few workgroups and a long K loop (64x64-tile workgroups x phases well below two per CU, at least 8 K slices per
  * range) get `partial` scratch (capped per launch, counted in awr_plan_info's bytes) and run split: the BatchNorm statistics / fused
  * BatchNorm-backward reductions then come from the reduce kernel (awr_conv_args.partial).  awr_plan_autotune times depth 1 against the split depths
@@ -523,6 +526,23 @@ int awr_net_bind(awr_net* net, float* params, float* grads, float* buffers);
  * hands out gradient-arena ranges through the bucket callback as soon as they are final. */
 int awr_plan_create(awr_net* net, int B, int H, int training, unsigned supervised_mask, int bn_repeat,
                     int n_buckets, float* img, float* const* outs, float* const* grad_outs, awr_plan** out);
+/* The build modes of ONE plan: passed in, stored in the plan, and read from the plan by every decision its builder takes.
+ * NOT in the block, because the launch dispatchers (awr_conv_gemm, awr_conv_wgrad, the head and loss kernels) read them at every launch and not
+ * only the builder, so a per-plan value would have to travel in awr_conv_args / awr_wgrad_args: the product mode (awr_set_gemm_products), the
+ * staging mode (awr_set_gemm_staging), the deterministic mode (captured from the process when the plan is created; awr_plan_info reports it)
+ * and the awr_debug_set_knob knobs.  For the same reason bits 4 and 8 of `winograd` decide a plan's launch LIST from this block, while
+ * awr_wino_conv still picks its tile form (64-channel or not) from the process-wide code when it launches (awr_wino_args has no field for it). */
+typedef struct awr_plan_modes {
+    int accum;             /* 0 ordered, 1 blocked, 2 auto  (awr_set_gemm_accum) */
+    int accum_auto_k;      /* accum == 2: K extent from which a launch blocks (>= 256, awr_set_gemm_accum_auto) ... */
+    int accum_auto_dgrad;  /* ... forward launches only (0) or data gradients too (1) */
+    int winograd;          /* code of awr_set_conv_winograd, 0 ... 15 */
+    int train_split_k;     /* 0 / 1 (awr_set_train_split_k); ignored by evaluation plans */
+} awr_plan_modes;
+/* awr_plan_create with the plan's modes given by the caller; modes == NULL: the process-wide defaults, which is what awr_plan_create passes.
+ * The block is validated (the setters' ranges) before anything else. */
+int awr_plan_create_modes(awr_net* net, int B, int H, int training, unsigned supervised_mask, int bn_repeat, int n_buckets,
+                          float* img, float* const* outs, float* const* grad_outs, const awr_plan_modes* modes, awr_plan** out);
 int awr_plan_destroy(awr_plan* plan);
 int awr_plan_info(const awr_plan* plan, int64_t* bytes, int* deterministic, int* n_fwd, int* n_bwd,
                   int* n_buckets, int* n_gemm, int* n_bn);
@@ -617,7 +637,8 @@ int awr_plan_set_dp(awr_plan* plan, awr_dp* dp);
  * rounding differs -- measured 0.3-0.6x the direct kernel's error against float64 (chains of Cin terms instead of 9 Cin).
  * awr_wino_conv3x3 is the first form (windows gathered from global memory; kb = channels per stage, + 100 = 256-thread workgroups), kept for the
  * measurements in profiles/r06_winograd.txt.
- * Plans: awr_set_conv_winograd(1 | 2) (process-wide, captured when a plan is built, default $AWR_WINOGRAD or 0; 2 = also the data and weight
+ * Plans: the Winograd code 1 | 2 (awr_plan_modes.winograd; awr_set_conv_winograd sets the process-wide default -- $AWR_WINOGRAD or 0 -- that a plan
+ * created without a modes block captures, and that awr_wino_eligible / awr_wino_wgrad_eligible answer for; 2 = also the data and weight
  * gradients, + 4 = ignore the launch-size rules: tests, + 8 = never the 64-channel tile form: A/B) makes plan builders run the FORWARD
  * of every eligible layer (awr_wino_eligible: maps >= 8 x 8, at least 256 workgroups; epilogue = bias / ReLU / statistics) through
  * awr_wino2_conv3x3, the DATA GRADIENT of those layers (mirrored transform, accumulate / BatchNorm-backward-reduction epilogues) through

@@ -182,3 +182,34 @@ def test_winograd_entry_points_without_gpu(lib):
     assert L.lib.awr_wino_wgrad(None, None, None, None, 0, 1, 8, 8, 64, 64, None, None, 64, None, None) == -1 and "NULL" in L.last_error()
     assert L.lib.awr_wino_weights(None, 64, 64, 64, 64, 0, None, None) == -1
     assert L.lib.awr_wino_conv(None, None) == -1
+
+
+def test_plan_modes_block_and_its_validation_without_gpu(lib):
+    """awr_plan_modes is five ints in the header's order, and awr_plan_create_modes checks them (the setters' ranges) before the pointer and
+    "bind first" checks and before any HIP call: an out-of-range mode on an unbound net is refused by the name of the mode."""
+    import ctypes as C
+    L = lib
+    assert C.sizeof(L.PlanModes) == 5 * 4
+    assert [f[0] for f in L.PlanModes._fields_] == ["accum", "accum_auto_k", "accum_auto_dgrad", "winograd", "train_split_k"]
+    assert [getattr(L.PlanModes, f).offset for f, _ in L.PlanModes._fields_] == [0, 4, 8, 12, 16]
+    header = re.sub(r"/\*.*?\*/", "", open(os.path.join(REPO, "include", "awr_hip.h")).read(), flags=re.S)
+    body = re.search(r"typedef struct awr_plan_modes \{(.*?)\} awr_plan_modes;", header, flags=re.S).group(1)
+    assert re.findall(r"int\s+(\w+)\s*;", body) == [f[0] for f in L.PlanModes._fields_]
+    h = C.c_void_p()
+    assert L.lib.awr_net_create(0, 1, 14, 2, C.byref(h)) == 0, L.last_error()
+    was = (L.lib.awr_get_gemm_accum(), L.lib.awr_get_conv_winograd(), L.lib.awr_get_train_split_k())
+
+    def create(**kw):
+        m = L.PlanModes(accum=0, accum_auto_k=576, accum_auto_dgrad=0, winograd=0, train_split_k=0)
+        for k, v in kw.items():
+            setattr(m, k, v)
+        return L.lib.awr_plan_create_modes(h, 2, 128, 0, 1, 1, 1, None, None, None, C.byref(m), C.byref(C.c_void_p()))
+    for field, bad, word in (("accum", 3, "accum"), ("accum", -1, "accum"), ("winograd", 16, "winograd"), ("winograd", -1, "winograd"),
+                             ("train_split_k", 2, "train_split_k")):
+        assert create(**{field: bad}) == -1 and word in L.last_error(), (field, bad, L.last_error())
+    assert create(accum=2, accum_auto_k=128) == -1 and "accum_auto" in L.last_error()
+    assert create(accum=1, accum_auto_k=0) == -1 and "null pointer" in L.last_error()      # the threshold only matters to accum = 2; valid modes: on to the pointers
+    assert create() == -1 and "null pointer" in L.last_error()
+    assert L.lib.awr_plan_create_modes(h, 2, 128, 0, 1, 1, 1, None, None, None, None, C.byref(C.c_void_p())) == -1 and "null pointer" in L.last_error()
+    assert (L.lib.awr_get_gemm_accum(), L.lib.awr_get_conv_winograd(), L.lib.awr_get_train_split_k()) == was
+    assert L.lib.awr_net_destroy(h) == 0

@@ -182,3 +182,105 @@ def test_hourglass2_inference_through_the_c_abi_only(golden_dir):
         assert float(d.mean()) <= 2e-2, (st, float(d.mean()))      # (stage 1 of these procedural weights is ill-conditioned: test_nets_gpu.py holds the yardstick)
     ok(lib.awr_plan_destroy(plan))
     ok(lib.awr_net_destroy(net))
+
+
+def _ok(rc):
+    from awr_amd import _lib as L
+    assert rc == 0, L.last_error()
+
+
+def _bound_resnet18(lib, J, dev):
+    """ResNet18-deconv through awr_net_*: arenas (parameters / gradients / BatchNorm buffers) filled from a state_dict through
+    awr_net_tensor_info (the checkpoint layout) and bound.  -> net, (params, grads, bufs), {key: (kind, offset, numel)}, n_active"""
+    ok = _ok
+    net = C.c_void_p()
+    ok(lib.awr_net_create(0, 1, J, 2, C.byref(net)))
+    nt, npar, nact, nbuf, ncnt, nst = C.c_int64(), C.c_int64(), C.c_int64(), C.c_int64(), C.c_int(), C.c_int()
+    ok(lib.awr_net_sizes(net, C.byref(nt), C.byref(npar), C.byref(nact), C.byref(nbuf), C.byref(ncnt), C.byref(nst)))
+    params, grads, bufs = torch.zeros(npar.value, device=dev), torch.zeros(npar.value, device=dev), torch.zeros(nbuf.value, device=dev)
+    sd = O.procedural_state(O.manifest_for("resnet_18", J), seed=1)
+    key, kd, nd, off, un = C.c_char_p(), C.c_int(), C.c_int(), C.c_int64(), C.c_int()
+    shape = (C.c_int64 * 4)()
+    where = {}
+    for i in range(nt.value):
+        ok(lib.awr_net_tensor_info(net, i, C.byref(key), C.byref(kd), C.byref(nd), shape, C.byref(off), C.byref(un)))
+        k = key.value.decode()
+        if kd.value == 7:
+            continue
+        arena = params if kd.value <= 4 else bufs
+        n = sd[k].numel()
+        arena[off.value:off.value + n].copy_(sd[k].reshape(-1))
+        where[k] = (kd.value, off.value, n)
+    ok(lib.awr_net_bind(net, params.data_ptr(), grads.data_ptr(), bufs.data_ptr()))
+    return net, (params, grads, bufs), where, nact
+
+
+def test_plan_modes_through_the_c_abi_only(golden_dir):
+    """awr_plan_create_modes: a training plan with blocked accumulation (accum = 1) built on raw pointers while the process-wide mode stays what
+    it was.  It has the launch list of a plan created by awr_plan_create under awr_set_gemm_accum(1), runs a forward / loss / backward step whose
+    loss meets the golden bar of the first test (blocked accumulation only lowers the rounding error), and leaves activations behind
+    (awr_plan_tensor)."""
+    import awr_amd  # noqa: F401
+    from awr_amd import _lib as L
+    lib, ok = L.lib, _ok
+    dev = torch.device("cuda:0")
+    g = np.load(os.path.join(golden_dir, "resnet_18_train.npz"))
+    img_h, jt_h = torch.from_numpy(g["img"]), torch.from_numpy(g["jt_gt"])
+    B, J, H, F, ks = img_h.shape[0], int(g["J"]), 128, 64, float(g["ks"])
+    net, (params, grads, bufs), where, nact = _bound_resnet18(lib, J, dev)
+    img, out, gout = img_h.to(dev), torch.zeros(B, 4 * J, F, F, device=dev), torch.zeros(B, 4 * J, F, F, device=dev)
+    outs, gouts = (C.c_void_p * 1)(out.data_ptr()), (C.c_void_p * 1)(gout.data_ptr())
+
+    def op_names(plan):
+        nf, nb, name = C.c_int(), C.c_int(), C.c_char_p()
+        ok(lib.awr_plan_info(plan, None, None, C.byref(nf), C.byref(nb), None, None, None))
+        names = []
+        for lst, n in ((0, nf.value), (1, nb.value)):
+            for i in range(n):
+                ok(lib.awr_plan_op(plan, lst, i, C.byref(name), None, None))
+                names.append((lst, name.value.decode()))
+        return names
+
+    was = lib.awr_get_gemm_accum()
+    assert was != 1
+    modes = L.PlanModes(accum=1, accum_auto_k=0, accum_auto_dgrad=0, winograd=0, train_split_k=0)
+    plan, plan_g = C.c_void_p(), C.c_void_p()
+    ok(lib.awr_plan_create_modes(net, B, H, 1, 1, 1, 1, img.data_ptr(), outs, gouts, C.byref(modes), C.byref(plan)))
+    assert lib.awr_get_gemm_accum() == was
+    try:
+        ok(lib.awr_set_gemm_accum(1))
+        ok(lib.awr_plan_create(net, B, H, 1, 1, 1, 1, img.data_ptr(), outs, gouts, C.byref(plan_g)))
+    finally:
+        ok(lib.awr_set_gemm_accum(was))
+    names = op_names(plan)
+    assert names == op_names(plan_g) and sum(n.startswith("awr_conv_gemm") for _, n in names) >= 20
+    ok(lib.awr_plan_destroy(plan_g))
+    s = torch.cuda.current_stream().cuda_stream
+    jt_gt, jt, stat, g_jt = jt_h.to(dev), torch.zeros(B, J, 3, device=dev), torch.zeros(B, J, 2, device=dev), torch.zeros(B, J, 3, device=dev)
+    acc, losses = torch.zeros(2, device=dev, dtype=torch.float64), torch.zeros(3, device=dev)
+    ok(lib.awr_plan_refresh_weights(plan, s))
+    ok(lib.awr_plan_forward(plan, s))
+    ok(lib.awr_head_forward(out.data_ptr(), img.data_ptr(), B, J, F, H, ks, jt.data_ptr(), stat.data_ptr(), s))
+    ok(lib.awr_zero_f64(acc.data_ptr(), 2, s))
+    ok(lib.awr_dense_loss(out.data_ptr(), jt_gt.data_ptr(), img.data_ptr(), B, J, F, H, ks, 0.01, 1.0, acc.data_ptr() + 8, gout.data_ptr(), 0, s))
+    ok(lib.awr_huber(jt.data_ptr(), jt_gt.data_ptr(), B * J * 3, 0.01, 1.0, acc.data_ptr(), g_jt.data_ptr(), 0, s))
+    ok(lib.awr_head_backward(out.data_ptr(), img.data_ptr(), jt.data_ptr(), stat.data_ptr(), g_jt.data_ptr(), B, J, F, H, ks, gout.data_ptr(), 1, s))
+    ok(lib.awr_loss_finalize(acc.data_ptr(), 2, losses.data_ptr(), s))
+    ok(lib.awr_plan_backward(plan, s))
+    torch.cuda.synchronize()
+    assert abs(float(losses[2]) - float(g["c1_loss0"])) <= 2e-4 * abs(float(g["c1_loss0"]))
+    assert float(np.abs(jt.cpu().numpy() - g["c1_jt0"]).max()) * 150 <= 5e-3
+    kd_, o_, n_ = where["layer1.0.conv1.weight"]
+    gw = grads[o_:o_ + n_]
+    assert bool(torch.isfinite(gw).all()) and float(gw.abs().max()) > 0
+    # an activation the step left behind: layer1.0.conv1's raw output
+    name, dims, buf, grad, lz, sc, sh = C.c_char_p(), (C.c_int * 4)(), C.c_void_p(), C.c_void_p(), C.c_int(), C.c_void_p(), C.c_void_p()
+    i, found = 0, None
+    while lib.awr_plan_tensor(plan, i, C.byref(name), dims, C.byref(buf), C.byref(grad), C.byref(lz), C.byref(sc), C.byref(sh)) == 0:
+        if name.value.decode() == "layer1.0.conv1.out":
+            found = (tuple(dims), buf.value)
+        i += 1
+    assert found and found[0] == (B, F, F, 64) and found[1]      # (downsample 2: layer1 runs at the dense map's resolution)
+    assert lib.awr_get_gemm_accum() == was
+    ok(lib.awr_plan_destroy(plan))
+    ok(lib.awr_net_destroy(net))

@@ -1264,3 +1264,60 @@ def test_half_batch_batchnorm_backward_wavefront(amd, dev, net, streams, monkeyp
         report("%s/half_batch_wavefront/streams%d/grad_rel_diff" % (net, streams), d)
     finally:
         amd.set_deterministic(False)
+
+
+_MODE_SETS = {"blocked": dict(accum="blocked", winograd=False, split_k=False),
+              "auto+full": dict(accum="auto", winograd="full", split_k=False),
+              "auto+force+split_k": dict(accum="auto", winograd="force", split_k=True)}
+
+
+@pytest.mark.parametrize("net", ["resnet_18", "hourglass_1"])
+@pytest.mark.parametrize("training,modes", [(True, "blocked"), (True, "auto+full"), (True, "auto+force+split_k"), (False, "blocked"), (False, "auto+full")])
+def test_plan_modes_passed_in_equal_the_process_wide_ones(amd, dev, net, training, modes):
+    """A plan's build modes are an argument of its creation (awr_plan_create_modes), not process state: plan X is built with the modes passed
+    explicitly while the process-wide modes stay where they were (checked right after the build), plan Y on a second identical network with
+    modes = None after the same modes were set process-wide.  Same launch lists, tunable launches, Winograd launch count / MACs and bytes; the
+    evaluation pair also computes bit-identical stage outputs from the same input and weights (evaluation launches use no atomics)."""
+    B, J, want = 8, 14, _MODE_SETS[modes]
+    sd = O.reference_init_state(net, J, seed=5)
+
+    def process_modes():
+        return amd.get_gemm_accum(), amd.get_conv_winograd(), amd.get_train_split_k()
+
+    def summary(p):
+        return dict(fwd=p.op_names("fwd"), bwd=p.op_names("bwd"), gemms=[p._gemm(i)[0] for i in range(p.n_gemm)], n_winograd=p.n_winograd,
+                    winograd_macs=p.winograd_macs, bytes=p.bytes, modes=(p.accum, p.winograd, p.train_split_k))
+
+    was = process_modes()
+    mx, my = make_net(amd, net, J, sd), make_net(amd, net, J, sd)
+    mx.train(training), my.train(training)
+    px = mx.get_plan(B, 128, training, accum=want["accum"], winograd=want["winograd"], split_k=want["split_k"])
+    assert process_modes() == was
+    try:
+        amd.set_gemm_accum(want["accum"])
+        amd.set_conv_winograd(want["winograd"])
+        amd.set_train_split_k(want["split_k"])
+        py = my.get_plan(B, 128, training)
+    finally:
+        amd.set_gemm_accum(was[0])
+        amd.set_conv_winograd(was[1])
+        amd.set_train_split_k(was[2])
+    sx, sy = summary(px), summary(py)
+    for k in sx:
+        assert sx[k] == sy[k], k
+    assert sx["modes"] == (mx.plan_accum(want["accum"], training), amd._winograd_code(want["winograd"]), int(want["split_k"] and training))
+    assert len(sx["fwd"]) >= 10 and (len(sx["bwd"]) >= 10) == training and sx["gemms"]
+    if want["winograd"] == "force":      # (whatever the launch size; "full" at batch 8 only takes the layers with enough workgroups)
+        assert sx["n_winograd"] > 0
+    if not training:
+        img = O.synth_batch(B, 128, J, seed=11)[0].to(dev)
+        outs = []
+        for m, p in ((mx, px), (my, py)):
+            m.sync_weights(p)
+            p.img.copy_(img)
+            p.forward()
+            torch.cuda.synchronize()
+            outs.append([o.clone() for o in p.outputs])
+        assert len(outs[0]) == mx.nstage
+        for a, b in zip(*outs):
+            assert torch.isfinite(a).all() and float(a.abs().max()) > 0 and torch.equal(a, b)
