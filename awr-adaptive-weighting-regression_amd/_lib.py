@@ -232,6 +232,8 @@ _SIGS = {
     "awr_nyu_normalize": ([_P, _P, _P, _I, _L, _P, _P], C.c_int),
     "awr_nyu_augment": ([_P, _P, _P, _I, _I, _P, _P, _P], C.c_int),
     "awr_nyu_batch": ([_P, _I, _I, _I, _P, _I, _I, _P, _P, _P, _P], C.c_int),
+    # joint scoring (csrc/awr_eval.hip)
+    "awr_eval_batch": ([_P, _P, _P, _P, _P, _I, _I, _I, _F, _D, _D, _D, _D, _I, _P, _P, _L, _L, _P, _P, _P], C.c_int),
 }
 
 # entry points of study builds only (hipcc -DAWR_STUDY, AWR_BUILD_STUDY=1 for awr_amd.build): measured-and-rejected forms that the default

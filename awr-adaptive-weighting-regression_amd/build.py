@@ -31,6 +31,7 @@ SOURCES = {
     "awr_net.hip": [],        # host-only: network-level plan builder / runner
     "awr_dp.hip": [],         # host-only: RCCL communicators through dlopen (no link-time dependency)
     "awr_nyu.hip": ["-ffp-contract=off"],     # NYU data path: numpy's / OpenCV's arithmetic, no fused multiply-adds
+    "awr_eval.hip": ["-ffp-contract=off"],    # joint scoring: the host evaluator's numpy arithmetic
 }
 
 

@@ -32,8 +32,10 @@ _MI355X = dict(use_hipgraph=False,    # True: replay each step as one hipGraph (
                                       # "auto" = each engine times the modes on its own plan and keeps the fastest (logged at the first step)
                train_split_k=False,   # True: the training plan's small forward / data-gradient launches split their K loop, BatchNorm statistics from the reduce
                                       # kernel (TrainEngine(split_k=...)).  False = the process-wide mode (off unless $AWR_TRAIN_SPLIT_K).  Nothing else is accepted
-               device_loader=True)    # NYU datasets built from this config keep their decoded frames in HBM and crop / augment / normalise on the
+               device_loader=True,    # NYU datasets built from this config keep their decoded frames in HBM and crop / augment / normalise on the
                                       # GPU (awr_amd.nyu_device: bit-identical to the host loader nyu_data.NYU, which False selects)
+               device_eval=False)     # True: the train and test loops score joints on the GPU (evaluator.DeviceEvalUtil: no download of the predictions and
+                                      # no sync per batch).  False = the host evaluator (EvalUtil), as the reference does it
 
 
 class Config(object):
@@ -49,6 +51,8 @@ class Config(object):
             setattr(self, k, v)
         if not isinstance(self.train_split_k, bool):
             raise ValueError("train_split_k is False or True, not %r" % (self.train_split_k,))
+        if not isinstance(self.device_eval, bool):
+            raise ValueError("device_eval is False or True, not %r" % (self.device_eval,))
         if self.dataset not in _DATASETS:
             raise ValueError("dataset must be one of %s" % sorted(_DATASETS))
         for k, v in zip(_DERIVED, _DATASETS[self.dataset]):

@@ -25,6 +25,7 @@ import torch
 from . import _lib as L
 from . import _engine_winograd, _split_k_flag, _winograd_code
 from . import winograd_auto as WA
+from .evaluator import DeviceEvalUtil, EvalUtil
 
 HUBER_DELTA = 0.01
 
@@ -661,6 +662,13 @@ class SyntheticHands(torch.utils.data.Dataset):
         return self.img[i], self.jt_xyz[i], self.jt_uvd[i], self.center[i], self.M[i], self.cube[i]
 
 
+def make_evaluator(config, data, device=None, **kw):
+    """The evaluator a loop over `data` scores with: the host EvalUtil, or with config.device_eval the GPU one (kw: capacity, store)."""
+    if getattr(config, "device_eval", False):
+        return DeviceEvalUtil(data.img_size, data.paras, data.flip, data.jt_num, device=device, **kw)
+    return EvalUtil(data.img_size, data.paras, data.flip, data.jt_num)
+
+
 class Trainer:
     """The reference's Trainer (train.py:27-227, test.py:20-110) on the MI355X engines: same config attributes, same
     log lines, same checkpoint files, with the per-sample host loops removed.  `train_data` / `test_data` are any
@@ -773,7 +781,8 @@ class Trainer:
         dev = self.net.device
         # train.py:102: ONE evaluator for the whole run -- the reference's `train mpe` (which drives ReduceLROnPlateau) is the
         # running mean over every frame fed since the start of training, not a per-epoch value.  Reproduced on purpose.
-        ev = self.EvalUtil(self.trainData.img_size, self.trainData.paras, self.trainData.flip, self.trainData.jt_num)
+        ev = make_evaluator(cfg, self.trainData, device=dev, store=False)
+        dev_eval = isinstance(ev, DeviceEvalUtil)      # config.device_eval: scored on the GPU, running sums only (constant memory over the run)
         for epoch in range(self.best_records["epoch"] + 1, cfg.max_epoch + 1):
             self.net.train()
             lsum, lcnt, pend, last_mean = torch.zeros(3, device=dev), 0, [], float("nan")
@@ -797,7 +806,10 @@ class Trainer:
                         "{} {:.3f} ms".format(k, v) if isinstance(v, float) else "{}: {}".format(k, v) for k, v in eng.winograd_timings.items())))
                 lsum += losses                                      # device-side meter: no loss.item() per iteration
                 lcnt += 1
-                pend.append((jt_pred.clone(), jt_xyz_gt, center_xyz, M, cube))
+                if dev_eval:            # jt_pred is valid until the next step: scored in place, on the stream the next step is issued on
+                    ev.feed_batch(jt_pred, jt_xyz_gt, center_xyz, M, cube)
+                else:
+                    pend.append((jt_pred.clone(), jt_xyz_gt, center_xyz, M, cube))
                 if (ii + 1) % cfg.print_freq == 0:
                     l = meter()
                     last_mean = l[2]
@@ -808,7 +820,9 @@ class Trainer:
             drain()
             # rank-uniform metric: every rank must feed the SAME number to its LR scheduler, or the replicas would step the
             # (identical, all-reduced) gradients with different learning rates and silently diverge
-            if ev._err:
+            if dev_eval:
+                train_mpe = eng.sync.global_mean(*ev.mean_error(), device=dev)     # (0.0, 0) for an epoch without a single batch
+            elif ev._err:
                 e = np.concatenate(ev._err, 0).astype(np.float64)
                 train_mpe = eng.sync.global_mean(e.mean(1).sum(), e.shape[0], device=dev)
             else:
@@ -845,10 +859,11 @@ class Trainer:
             wino = self._infer_winograd
         inf = self._last_infer = InferEngine(self.net, cfg.batch_size, cfg.img_size, cfg.kernel_size, use_graph=False,
                                              parity=bool(getattr(cfg, "parity_infer", False)), winograd=wino)
-        ev = self.EvalUtil(self.testData.img_size, self.testData.paras, self.testData.flip, self.testData.jt_num)
         n, bs = len(self.testData), cfg.batch_size
         mine = [b for b in range((n + bs - 1) // bs) if b % world == self.rank]
         idx = [i for b in mine for i in range(b * bs, min(n, (b + 1) * bs))]
+        ev = make_evaluator(cfg, self.testData, device=self.net.device, capacity=len(idx))
+        dev_eval = isinstance(ev, DeviceEvalUtil)      # config.device_eval: no download and no sync inside the batch loop
         loader = torch.utils.data.DataLoader(torch.utils.data.Subset(self.testData, idx), batch_size=bs, shuffle=False,
                                              num_workers=int(getattr(cfg, "num_workers", 0)), drop_last=False)
         pad = None
@@ -863,16 +878,26 @@ class Trainer:
                 pad.zero_()
                 pad[:nb] = x
                 x = pad
-            jt = inf(x)[:nb].cpu().numpy()
-            ev.feed_batch(jt, jt_xyz_gt.numpy(), center_xyz.numpy(), M.numpy(), cube.numpy())
+            if dev_eval:
+                jt = inf(x)
+                ev.feed_batch(jt, jt_xyz_gt, center_xyz, M, cube, n_valid=nb)
+            else:
+                jt = inf(x)[:nb].cpu().numpy()
+                ev.feed_batch(jt, jt_xyz_gt.numpy(), center_xyz.numpy(), M.numpy(), cube.numpy())
             ib = mine[k] + 1
             if getattr(cfg, "vis_freq", 0) and ib % cfg.vis_freq == 0 and self._vis is not None:    # train.py:203-213
                 half = cfg.img_size / 2.0
+                if dev_eval:             # the one joint set this iteration draws
+                    jt = jt[:1].cpu().numpy()
                 self._vis.plot(img[0].numpy(), os.path.join(self.result_dir, "test_epoch_{}_iter_{}.png".format(epoch, ib)),
                                (jt[0] + 1) * half, (jt_uvd_gt[0].numpy() + 1) * half)
         self.net.train()
         if inf.winograd_source is not None and not inf._wino_pending:
             self._infer_winograd = inf.winograd_mode
+        if dev_eval:           # one download of the error and uvd rows; from here on it is the host evaluator's code
+            rows = ev.jt_uvd_pred
+            ev = ev.host()
+            ev.jt_uvd_pred = rows
         if world > 1:          # every rank ends up with the whole test set, in dataset order
             J = self.testData.jt_num
             err = np.concatenate(ev._err, 0) if ev._err else np.zeros((0, J), np.float32)

@@ -732,6 +732,41 @@ int awr_nyu_augment(const float* crop, const float* stats, const awr_nyu_sample*
 int awr_nyu_batch(const void* frames, int frame_type, int fh, int fw, const awr_nyu_sample* samples, int B, int dsize, float* out,
                   int* status, float* scratch, void* stream);
 
+/* ------------------------------------------------------------------------------------------
+ * Joint scoring on the device (csrc/awr_eval.hip).  Replaces EvalUtil.feed (util/eval_tool.py:20-46) with its pinhole back-projection
+ * uvd2xyz (util/util.py:13-20) -- per sample, on the host, behind a device sync in train.py:141-148 / test.py:67-86 -- for a whole batch
+ * per launch, with the running sums the epoch metric needs kept on the device.  One workgroup scores the batch.
+ *   jt_pred     (B, J, 3)  predicted joints, normalised uvd in [-1, 1]: the head's output as it is
+ *   jt_xyz_gt   (n, J, 3)  ground truth, cube-normalised xyz          center_xyz (n, 3)  crop centre, mm
+ *   M           (n, 3, 3)  crop matrix, original-image -> crop pixels  cube       (n, 3)  cube extent, mm
+ *   n = n_valid <= B: only rows [0, n_valid) of ANY argument are read (a padded last batch keeps its padding rows out of everything).
+ *   img_size: crop side in pixels; fx, fy, u0, v0: the camera intrinsics; flip: +1 / -1, the sign of the camera's y axis.
+ * Arithmetic, step by step as numpy does it on the host (awr_amd.evaluator.EvalUtil.feed_batch; no fused multiply-adds):
+ *   float32  u, v = (p + 1) * img_size / 2;  d = p_z * cube_z / 2 + center_z                         (eval_tool.py:38-39)
+ *   float64  (u, v) <- rows 0, 1 of inv(M) . (u, v, 1), stored as float32.  inv(M) is the adjugate of the float32 M over its determinant
+ *            in float64 (the host inverts in float32 with LAPACK: the device form is the closer one to exact)   (:40-41)
+ *   float64  x = (u - u0) * d / fx, y = (v - v0) * d / fy, stored as float32; y *= flip; z = d        (util.py:13-20)
+ *   float32  gt_mm = gt * (cube / 2) + center;  err = sqrt((dx^2 + dy^2) + dz^2)                      (:46)
+ * Outputs (uvd_out and err_out may each be NULL: nothing per frame is written; `capacity` = rows of the result buffers):
+ *   uvd_out  rows [row, row + n_valid) of a (capacity, J, 3) buffer: original-image uvd, what test.py:105-108 writes to the results file
+ *   err_out  rows [row, row + n_valid) of a (capacity, J) buffer: errors in mm
+ *   acc      J + 2 doubles the call ADDS onto (zero them with awr_zero_f64 before the first batch of a run):
+ *            acc[0..J) per-joint error sum, acc[J] frames scored, acc[J + 1] sum over frames of the frame's mean error over its joints.
+ *            Ordered in-workgroup reduction, one writer per word, no floating-point atomics: bitwise reproducible run to run.
+ *   status   2 ints, zero before the first batch of a run: {code, frame}.  Where numpy raises (np.linalg.inv of a singular matrix) the
+ *            kernel writes NaN to the frame's rows, leaves it out of `acc`, and records the FIRST such frame of the run: code
+ *            AWR_EVAL_SINGULAR (determinant zero, or an inverse that overflows) or AWR_EVAL_NONFINITE (M holds Inf / NaN), frame = row + its
+ *            position in the batch.  The other frames of the batch are scored as usual.  The caller reads status when it reads results.
+ * J <= AWR_EVAL_MAX_JOINTS.  Nothing synchronises; batches fed on one stream accumulate in feed order.
+ * -----------------------------------------------------------------------------------------*/
+#define AWR_EVAL_OK 0
+#define AWR_EVAL_SINGULAR 1
+#define AWR_EVAL_NONFINITE 2
+#define AWR_EVAL_MAX_JOINTS 256
+int awr_eval_batch(const float* jt_pred, const float* jt_xyz_gt, const float* center_xyz, const float* M, const float* cube, int B, int J,
+                   int n_valid, float img_size, double fx, double fy, double u0, double v0, int flip, float* uvd_out, float* err_out,
+                   int64_t row, int64_t capacity, double* acc, int* status, void* stream);
+
 #ifdef __cplusplus
 }
 #endif
