@@ -34,8 +34,13 @@ _MI355X = dict(use_hipgraph=False,    # True: replay each step as one hipGraph (
                                       # kernel (TrainEngine(split_k=...)).  False = the process-wide mode (off unless $AWR_TRAIN_SPLIT_K).  Nothing else is accepted
                device_loader=True,    # NYU datasets built from this config keep their decoded frames in HBM and crop / augment / normalise on the
                                       # GPU (awr_amd.nyu_device: bit-identical to the host loader nyu_data.NYU, which False selects)
-               device_eval=False)     # True: the train and test loops score joints on the GPU (evaluator.DeviceEvalUtil: no download of the predictions and
+               device_eval=False,     # True: the train and test loops score joints on the GPU (evaluator.DeviceEvalUtil: no download of the predictions and
                                       # no sync per batch).  False = the host evaluator (EvalUtil), as the reference does it
+               test_loss=False,       # True: Trainer.test also computes the validation loss of test.py:73-88 (coord_weight / dense_weight, the mean over the
+                                      # batches of the per-batch mean) in the same pass over the dense map that decodes the joints, and logs it in a
+                                      # second line (InferEngine(loss_weights=...)).  False = joints only
+               test_loss_stages="last")   # "last": the stage the training loss supervises (what the [train loss] lines report) | "all": the sum over the
+                                      # Hourglass stacks, as test.py:74-80 adds them up.  Only read with test_loss = True
 
 
 class Config(object):
@@ -53,6 +58,10 @@ class Config(object):
             raise ValueError("train_split_k is False or True, not %r" % (self.train_split_k,))
         if not isinstance(self.device_eval, bool):
             raise ValueError("device_eval is False or True, not %r" % (self.device_eval,))
+        if not isinstance(self.test_loss, bool):
+            raise ValueError("test_loss is False or True, not %r" % (self.test_loss,))
+        if not (isinstance(self.test_loss_stages, str) and self.test_loss_stages in ("last", "all")):
+            raise ValueError("test_loss_stages is \"last\" or \"all\", not %r" % (self.test_loss_stages,))
         if self.dataset not in _DATASETS:
             raise ValueError("dataset must be one of %s" % sorted(_DATASETS))
         for k, v in zip(_DERIVED, _DATASETS[self.dataset]):

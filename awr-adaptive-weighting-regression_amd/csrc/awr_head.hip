@@ -325,8 +325,11 @@ __global__ __launch_bounds__(256) void huber_kernel(const float* __restrict__ x,
 // map is fetched once, whatever the per-joint reduction needs.  MODE bits: 1 = online-softmax partials of offset2joint_softmax
 // (util/feature_tool.py:41-65) per (image, chunk, joint), merged by head_finish_kernel; 2 = GT map + dense Huber value and gradient
 // (util/feature_tool.py:12-39, model/loss.py:8-25), written in place into the tile and streamed out as the NHWC gradient;
-// 4 = the head's backward (closed form, see head_bwd_kernel) added onto that gradient.  One launch does 1|2 (coord_weight == 0: the
-// reference default) -- the dense map is read ONCE per step -- or 1, then 2|4 once the joints exist.
+// 4 = the head's backward (closed form, see head_bwd_kernel) added onto that gradient; 8 = GT map + dense Huber VALUE only (test.py:73-86:
+// the loss of a scoring pass) -- bit 2's arithmetic into the same accumulator, no gradient, the tile is never rewritten and nothing is
+// streamed out (`grad` is not dereferenced).  One launch does 1|2 (coord_weight == 0: the reference default) -- the dense map is read ONCE
+// per step -- or 1, then 2|4 once the joints exist; an eval pass does 1|8.  Images b >= n_valid (the zero padding of a ragged last batch) add
+// nothing to the accumulator; their softmax partials are written like everyone's.
 constexpr int TPX = 64;      // pixels per tile
 
 // exp(x) for x <= 0 (softmax terms after the max subtraction): two-term range reduction with explicit FMAs (x log2 e = n + r,
@@ -344,17 +347,18 @@ __device__ __forceinline__ float exp_nonpos(float x) {
 struct nhwc_args {
     const float* pred;       // (B, P, Cp)
     const float* img;        // (B, 1, H, H)
-    const float* jt_gt;      // (B, J, 3)     MODE & 2
+    const float* jt_gt;      // (B, J, 3)     MODE & 10
     const float* jt;         // (B, J, 3)     MODE & 4: the head's output
     const float* stat;       // (B, J, 2)     MODE & 4: softmax max / sum
     const float* g_jt;       // (B, J, 3)     MODE & 4: upstream gradient
     float* partial;          // (B, chunks, J, 5)   MODE & 1
     float* grad;             // (B, P, Cp)    MODE & 6
-    double* acc;             // dense-loss accumulator   MODE & 2
+    double* acc;             // dense-loss accumulator   MODE & 10
     int J, F, H, Cp, tiles_per_wg, lgF;      // lgF: log2(F) when F is a power of two (every map of both backbones), else -1
     float ks, delta, gscale;
     double lscale;
     int fixed_point;
+    int n_valid;             // images [0, n_valid) count towards acc   MODE & 8 (the training forms are launched with n_valid == B)
 };
 
 template <int JS, int MODE, int DEPTH, bool POW2>
@@ -383,7 +387,7 @@ __global__ __launch_bounds__(256) void dense_nhwc_kernel(const nhwc_args a) {
     float mx = 0.f, inv_s = 0.f, g0 = 0.f, g1 = 0.f, g2 = 0.f, o0 = 0.f, o1 = 0.f, o2 = 0.f;
     if (active) {
         const int bj = b * J + j;
-        if (MODE & 2) { gj0 = a.jt_gt[bj * 3]; gj1 = a.jt_gt[bj * 3 + 1]; gj2 = a.jt_gt[bj * 3 + 2]; }
+        if (MODE & 10) { gj0 = a.jt_gt[bj * 3]; gj1 = a.jt_gt[bj * 3 + 1]; gj2 = a.jt_gt[bj * 3 + 2]; }
         if (MODE & 4) {
             mx = a.stat[2 * bj]; inv_s = 1.0f / a.stat[2 * bj + 1];
             g0 = a.g_jt[bj * 3]; g1 = a.g_jt[bj * 3 + 1]; g2 = a.g_jt[bj * 3 + 2];
@@ -392,6 +396,7 @@ __global__ __launch_bounds__(256) void dense_nhwc_kernel(const nhwc_args a) {
     }
     SoftAcc sa = {-INFINITY, 0.f, 0.f, 0.f, 0.f};
     float lsum = 0.f;
+    const bool counted = !(MODE & 8) || b < a.n_valid;      // (uniform over the workgroup; the training forms count every image: n_valid == B there)
     const float inv_f = 1.0f / (float)F;
 
     // DEPTH register sets: tile t + DEPTH is requested while tile t is being worked on (DEPTH = 2 doubles the bytes a workgroup keeps
@@ -451,9 +456,9 @@ __global__ __launch_bounds__(256) void dense_nhwc_kernel(const nhwc_args a) {
                     sa.a1 += (v1 * mk * dis + cy) * e;
                     sa.a2 += (v2 * mk * dis + d) * e;
                 }
-                if (MODE & 6) {
+                if ((MODE & 6) || ((MODE & 8) && counted)) {
                     float q0 = 0.f, q1 = 0.f, q2 = 0.f, qh = 0.f;
-                    if (MODE & 2) {       // util/feature_tool.py:29-39, operation for operation (gt_map4)
+                    if (MODE & 10) {      // util/feature_tool.py:29-39, operation for operation (gt_map4)
                         // The GT map is zero wherever its mask is (background pixels; pixels farther than ks from the joint): there
                         // x - (+-0) == x exactly, so the correctly rounded sqrt / divides (~150 VALU instructions per (pixel, joint),
                         // what made the NCHW kernel compute-bound at 2.2 TB/s) only run where the mask can be 1.
@@ -465,8 +470,10 @@ __global__ __launch_bounds__(256) void dense_nhwc_kernel(const nhwc_args a) {
                             if (hm >= 0.f) { z0 = v0 - e0 / dist; z1 = v1 - e1 / dist; z2 = v2 - e2 / dist; zh = hraw - hm; }
                         }
                         lsum += huber_val(z0, a.delta); lsum += huber_val(z1, a.delta); lsum += huber_val(z2, a.delta); lsum += huber_val(zh, a.delta);
-                        q0 = huber_grad(z0, a.delta) * a.gscale; q1 = huber_grad(z1, a.delta) * a.gscale;
-                        q2 = huber_grad(z2, a.delta) * a.gscale; qh = huber_grad(zh, a.delta) * a.gscale;
+                        if (MODE & 2) {
+                            q0 = huber_grad(z0, a.delta) * a.gscale; q1 = huber_grad(z1, a.delta) * a.gscale;
+                            q2 = huber_grad(z2, a.delta) * a.gscale; qh = huber_grad(zh, a.delta) * a.gscale;
+                        }
                     }
                     if (MODE & 4) {       // head_bwd_kernel's closed form
                         const float w = expf(h * kBeta - mx) * inv_s;
@@ -478,7 +485,7 @@ __global__ __launch_bounds__(256) void dense_nhwc_kernel(const nhwc_args a) {
                         q0 += g0 * wd; q1 += g1 * wd; q2 += g2 * wd;
                         qh += mk * w * (g0 * t0 + g1 * t1 + g2 * t2);
                     }
-                    row[3 * j] = q0; row[3 * j + 1] = q1; row[3 * j + 2] = q2; row[3 * J + j] = qh;
+                    if (MODE & 6) { row[3 * j] = q0; row[3 * j + 1] = q1; row[3 * j + 2] = q2; row[3 * J + j] = qh; }
                 }
             }
         }
@@ -528,14 +535,14 @@ __global__ __launch_bounds__(256) void dense_nhwc_kernel(const nhwc_args a) {
         }
         __syncthreads();
     }
-    if (MODE & 2) block_accumulate((double)lsum, a.lscale, a.acc, a.fixed_point);
+    if ((MODE & 10) && counted) block_accumulate((double)lsum, a.lscale, a.acc, a.fixed_point);
 }
 
 // merge the per-chunk softmax partials -> joints (B, J, 3) + (max, sum) for the backward; optionally the coordinate Huber loss
 // (train.py:125: crit(jt_uvd_pred, jt_uvd_gt)) and its gradient w.r.t. the joints.  A 32-lane half-wave per (image, joint): lane c takes
 // chunks c, c + 32, ... and the halves fold with the softmax-merge operator (a thread per joint walking the chunks one after the other
-// took 16 us -- as long as the streaming pass itself).
-__global__ __launch_bounds__(256) void head_finish_kernel(const float* __restrict__ partial, int chunks, int J, int BJ, const float* __restrict__ jt_gt,
+// took 16 us -- as long as the streaming pass itself).  Images b >= n_valid get their joints but add nothing to acc.
+__global__ __launch_bounds__(256) void head_finish_kernel(const float* __restrict__ partial, int chunks, int J, int BJ, int n_valid, const float* __restrict__ jt_gt,
                                                           float delta, float gscale, double lscale, float* __restrict__ jt, float* __restrict__ stat,
                                                           float* __restrict__ g_jt, double* __restrict__ acc, int fixed_point) {
     const int i = blockIdx.x * 8 + (threadIdx.x >> 5), c0 = threadIdx.x & 31;
@@ -561,7 +568,7 @@ __global__ __launch_bounds__(256) void head_finish_kernel(const float* __restric
 #pragma unroll
         for (int c = 0; c < 3; ++c) jt[i * 3 + c] = out[c];
         if (stat) { stat[2 * i] = t.m; stat[2 * i + 1] = t.s; }
-        if (acc) {
+        if (acc && i < n_valid * J) {
 #pragma unroll
             for (int c = 0; c < 3; ++c) {
                 const float z = out[c] - jt_gt[i * 3 + c];
@@ -653,7 +660,12 @@ static int launch_dense_nhwc(const nhwc_args& a, int B, int chunks, hipStream_t 
         if (a.lgF >= 0) hipLaunchKernelGGL((dense_nhwc_kernel<js, MODE, dp, true>), grid, dim3(256), lds, st, a);          \
         else hipLaunchKernelGGL((dense_nhwc_kernel<js, MODE, dp, false>), grid, dim3(256), lds, st, a);                    \
     } while (0)
-    if (a.J <= 16 && depth == 2) AWR_NHWC_LAUNCH(16, 2);
+    bool deep = false;
+    if constexpr (!(MODE & 8)) {      // (the value-only form has no depth-2 instantiation: the hook is a training-step study)
+        deep = a.J <= 16 && depth == 2;
+        if (deep) AWR_NHWC_LAUNCH(16, 2);
+    }
+    if (deep) {}
     else if (a.J <= 16) AWR_NHWC_LAUNCH(16, 1);
     else if (a.J <= 32) AWR_NHWC_LAUNCH(32, 1);
     else AWR_NHWC_LAUNCH(64, 1);
@@ -769,7 +781,7 @@ int awr_head_forward_nhwc(const float* pred, int Cp, const float* img, int B, in
     a.pred = pred; a.img = img; a.partial = scratch; a.J = J; a.F = F; a.H = H; a.Cp = Cp; a.tiles_per_wg = per; a.ks = ks; a.lgF = log2_exact(F);
     hipStream_t st = as_stream(stream);
     if (int e = launch_dense_nhwc<1>(a, B, chunks, st)) return e;
-    hipLaunchKernelGGL(head_finish_kernel, dim3((B * J + 7) / 8), dim3(256), 0, st, scratch, chunks, J, B * J, nullptr, 0.f, 0.f, 0.0, jt, stat,
+    hipLaunchKernelGGL(head_finish_kernel, dim3((B * J + 7) / 8), dim3(256), 0, st, scratch, chunks, J, B * J, B, nullptr, 0.f, 0.f, 0.0, jt, stat,
                        nullptr, nullptr, 0);
     return check_launch("head_finish_kernel");
 }
@@ -788,13 +800,13 @@ int awr_head_loss_step_nhwc(const float* pred, int Cp, const float* img, const f
     memset(&a, 0, sizeof a);
     a.pred = pred; a.img = img; a.jt_gt = jt_gt; a.partial = scratch; a.grad = grad; a.acc = acc + 1;
     a.J = J; a.F = F; a.H = H; a.Cp = Cp; a.tiles_per_wg = per; a.ks = ks; a.delta = delta; a.lgF = log2_exact(F);
-    a.gscale = (float)((double)dense_weight / nd); a.lscale = (double)dense_weight / nd; a.fixed_point = fixed;
+    a.gscale = (float)((double)dense_weight / nd); a.lscale = (double)dense_weight / nd; a.fixed_point = fixed; a.n_valid = B;
     hipStream_t st = as_stream(stream);
     const bool coord = coord_weight != 0.f;
     // coord_weight == 0 (config.py:41, the reference default): ONE pass over the map does the softmax partials, the dense loss and its
     // gradient; otherwise the joints have to exist before the head's backward can run: partials -> finish -> dense loss + head backward
     if (int e = coord ? launch_dense_nhwc<1>(a, B, chunks, st) : launch_dense_nhwc<3>(a, B, chunks, st)) return e;
-    hipLaunchKernelGGL(head_finish_kernel, dim3((B * J + 7) / 8), dim3(256), 0, st, scratch, chunks, J, B * J, jt_gt, delta,
+    hipLaunchKernelGGL(head_finish_kernel, dim3((B * J + 7) / 8), dim3(256), 0, st, scratch, chunks, J, B * J, B, jt_gt, delta,
                        (float)((double)coord_weight / nc), (double)coord_weight / nc, jt, stat, coord ? g_jt : nullptr, acc, fixed);
     if (int e = check_launch("head_finish_kernel")) return e;
     if (coord) {
@@ -802,6 +814,30 @@ int awr_head_loss_step_nhwc(const float* pred, int Cp, const float* img, const f
         if (int e = launch_dense_nhwc<6>(a, B, chunks, st)) return e;
     }
     return AWR_OK;
+}
+
+int awr_head_eval_nhwc(const float* pred, int Cp, const float* img, const float* jt_gt, int B, int J, int F, int H, int n_valid, float ks, float delta,
+                       float coord_weight, float dense_weight, float* scratch, float* jt, float* stat, double* acc, void* stream) {
+    AWR_REQUIRE(pred && img && jt_gt && scratch && jt && acc, "head_eval_nhwc: null pointer");
+    int chunks, per;
+    if (int e = nhwc_geometry(B, J, F, H, Cp, &chunks, &per)) return e;
+    AWR_REQUIRE(n_valid >= 0 && n_valid <= B, "head_eval_nhwc: n_valid=%d outside [0, B=%d]", n_valid, B);
+    const int P = F * F;
+    // the means are over the images that count: a padded last batch scores like the ragged batch the reference's loader hands out
+    const double nd = (double)(n_valid > 0 ? n_valid : 1) * 4.0 * J * P, nc = (double)(n_valid > 0 ? n_valid : 1) * J * 3.0;
+    const int fixed = awr_get_deterministic();
+    nhwc_args a;
+    memset(&a, 0, sizeof a);
+    a.pred = pred; a.img = img; a.jt_gt = jt_gt; a.partial = scratch; a.acc = acc + 1;
+    a.J = J; a.F = F; a.H = H; a.Cp = Cp; a.tiles_per_wg = per; a.ks = ks; a.delta = delta; a.lgF = log2_exact(F);
+    a.lscale = (double)dense_weight / nd; a.fixed_point = fixed; a.n_valid = n_valid;
+    hipStream_t st = as_stream(stream);
+    // ONE read-only pass over the map: softmax partials + the dense Huber value; the merge kernel adds the coordinate term
+    if (int e = launch_dense_nhwc<9>(a, B, chunks, st)) return e;
+    const bool coord = coord_weight != 0.f && n_valid > 0;
+    hipLaunchKernelGGL(head_finish_kernel, dim3((B * J + 7) / 8), dim3(256), 0, st, scratch, chunks, J, B * J, n_valid, jt_gt, delta, 0.f,
+                       (double)coord_weight / nc, jt, stat, nullptr, coord ? acc : nullptr, fixed);
+    return check_launch("head_finish_kernel");
 }
 
 int awr_huber(const float* x, const float* y, int64_t n, float delta, float weight, double* acc, float* gx, int accumulate,

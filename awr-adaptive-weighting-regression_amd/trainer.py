@@ -514,10 +514,17 @@ TrainEngine.load_optimizer_state_dict = lambda self, sd: _load_opt_into(self, sd
 
 
 class InferEngine(_WinogradAuto):
-    """test.py:67-86 without the per-sample host loop: img -> dense map -> joints, eval-mode BN."""
+    """test.py:67-86 without the per-sample host loop: img -> dense map -> joints, eval-mode BN; with `loss_weights` also the
+    validation loss of test.py:73-88, from the same pass over the dense map (awr_head_eval_nhwc)."""
 
-    def __init__(self, net, batch_size, img_size, kernel_size, use_graph=False, autotune=True, parity=False, winograd=None):
-        """parity=True: blocked accumulation in the GEMMs of this engine's plan (awr_amd.set_gemm_accum) -- scoring passes (test.py:67-86) care
+    def __init__(self, net, batch_size, img_size, kernel_size, use_graph=False, autotune=True, parity=False, winograd=None,
+                 loss_weights=None, loss_stages="last", nhwc_boundary=None):
+        """loss_weights: None (default: joints only, nothing about the engine changes) | (coord_weight, dense_weight) -- a call that is handed
+        the ground-truth joints adds coord_weight * Huber(joints) + dense_weight * Huber(dense map - GT map) of its batch (test.py:73-86) to a
+        device accumulator; `loss_means()` reads it.  loss_stages: "last" -- the stage TrainEngine supervises, what the [train loss] lines
+        report | "all" -- the sum over the Hourglass stacks (test.py:74-80).  nhwc_boundary: None ($AWR_NCHW_BOUNDARY decides) | False: the
+        reference-layout kernels (what a net with more than 56 joints gets anyway).
+        parity=True: blocked accumulation in the GEMMs of this engine's plan (awr_amd.set_gemm_accum) -- scoring passes (test.py:67-86) care
         about the last digits of the joints, not about the last few per cent of throughput.
         winograd: None (the process-wide mode, awr_amd.set_conv_winograd) | False | True -- the eligible stride-1 3x3 convolutions of the eval plan as
         Winograd F(2x2, 3x3) with the folded BatchNorm / residual add in its epilogue (Hourglass: instead of the fused conv2 + conv3 launch) | "auto" --
@@ -535,7 +542,18 @@ class InferEngine(_WinogradAuto):
         self.J, self.F = net.J, img_size // getattr(net, "downsample", 2)
         self.stage = net.nstage - 1
         import os as _os
-        self._want_nhwc, self._scratch = _os.environ.get("AWR_NCHW_BOUNDARY") != "1", None
+        self._want_nhwc, self._scratch = (_os.environ.get("AWR_NCHW_BOUNDARY") != "1") if nhwc_boundary is None else bool(nhwc_boundary), None
+        if loss_stages not in ("last", "all"):
+            raise ValueError("loss_stages is \"last\" or \"all\", not %r" % (loss_stages,))
+        self._lw = None
+        if loss_weights is not None:
+            cw, dw = loss_weights
+            self._lw = (float(cw), float(dw))
+            self._loss_stages = list(range(net.nstage)) if loss_stages == "all" else [self.stage]
+            self.jt_gt = torch.zeros(batch_size, self.J, 3, device=net.device)
+            self._jt_aux = torch.zeros(batch_size, self.J, 3, device=net.device) if len(self._loss_stages) > 1 else None
+            self._lacc = torch.zeros(2, device=net.device, dtype=torch.float64)      # sums over stages and batches of the per-batch means
+            self._lout, self._lbatches = torch.zeros(3, device=net.device), 0
         self._accum = "blocked" if self.parity else None
         self.winograd_timings, self.winograd_source = None, None
         self._wino_pending = False
@@ -560,6 +578,8 @@ class InferEngine(_WinogradAuto):
             self._pred, _, self._cp = plan.head_nhwc(self.stage)
             if self._scratch is None:
                 self._scratch = torch.zeros(int(L.lib.awr_head_nhwc_scratch(self.B, self.J, self.F)), device=self.net.device)
+            if self._lw is not None:
+                self._preds = {st: plan.head_nhwc(st)[0] for st in self._loss_stages}
 
     def _wino_plan(self, mode):
         return self.net.get_plan(self.B, self.H, False, accum=self._accum, winograd=mode)
@@ -567,11 +587,14 @@ class InferEngine(_WinogradAuto):
     def _tune_key(self):
         return "infer/%s/J%d/B%d/H%d" % (type(self.net).__name__ + str(self.net.nstage), self.J, self.B, self.H)
 
-    def _core(self):
+    def _core(self, loss=None, n_valid=None):
+        """loss: None = whenever the engine has loss weights (what the set-up runs and the captured graph do)."""
         plan = self.plan
-        if self.nhwc and not plan.nhwc:
-            plan.set_nhwc_boundary(True)
+        if self.nhwc != plan.nhwc:          # plans are shared: another engine on this network may have left it on the other boundary
+            plan.set_nhwc_boundary(self.nhwc)
         plan.run_forward()
+        if (self._lw is not None) if loss is None else loss:
+            return self._head_and_loss(self.B if n_valid is None else n_valid)
         if self.nhwc:
             L.call("awr_head_forward_nhwc", self._pred, self._cp, L.ptr(plan.img), self.B, self.J, self.F, self.H, self.ks, L.ptr(self._scratch),
                    L.ptr(self.jt), None, L.stream())
@@ -579,7 +602,63 @@ class InferEngine(_WinogradAuto):
         L.call("awr_head_forward", L.ptr(plan.outputs[self.stage]), L.ptr(plan.img), self.B, self.J, self.F, self.H, self.ks, L.ptr(self.jt),
                None, L.stream())
 
-    def __call__(self, img):
+    def _head_and_loss(self, nv):
+        """Joints of the last stage + this batch's loss terms (means over its first nv images) of every stage in `_loss_stages`, added
+        onto the device accumulator.  NHWC: one read-only pass per stage (awr_head_eval_nhwc); NCHW boundary: head, dense loss without a
+        gradient buffer, Huber on the joints."""
+        plan, s = self.plan, L.stream()
+        B, J, F, H = self.B, self.J, self.F, self.H
+        cw, dw = self._lw
+        for st in self._loss_stages:
+            jt = self.jt if st == self.stage else self._jt_aux
+            if self.nhwc:
+                L.call("awr_head_eval_nhwc", self._preds[st], self._cp, L.ptr(plan.img), L.ptr(self.jt_gt), B, J, F, H, nv, self.ks, HUBER_DELTA, cw, dw,
+                       L.ptr(self._scratch), L.ptr(jt), None, L.ptr(self._lacc), s)
+                continue
+            out = plan.outputs[st]
+            L.call("awr_head_forward", L.ptr(out), L.ptr(plan.img), B, J, F, H, self.ks, L.ptr(jt), None, s)
+            if nv > 0:
+                L.call("awr_dense_loss", L.ptr(out), L.ptr(self.jt_gt), L.ptr(plan.img), nv, J, F, H, self.ks, HUBER_DELTA, dw, self._lacc.data_ptr() + 8,
+                       None, 0, s)
+                if cw != 0.0:
+                    L.call("awr_huber", L.ptr(jt), L.ptr(self.jt_gt), nv * J * 3, HUBER_DELTA, cw, L.ptr(self._lacc), None, 0, s)
+
+    def reset_loss(self):
+        """Clear the loss accumulator and the batch count (no synchronisation)."""
+        if self._lw is not None:
+            L.call("awr_zero_f64", L.ptr(self._lacc), 2, L.stream())
+            self._lbatches = 0
+
+    def loss_sums(self):
+        """(sum of the per-batch coord terms, sum of the per-batch dense terms, batches) fed since the last reset -- what data-parallel
+        ranks add up before dividing.  Synchronises."""
+        if self._lw is None:
+            raise L.AwrError("InferEngine was built without loss_weights: there is no loss to report")
+        L.call("awr_loss_finalize", L.ptr(self._lacc), 2, L.ptr(self._lout), L.stream())      # the only reader of the accumulator (its encoding depends on the mode)
+        c, d, _ = self._lout.tolist()
+        return c, d, self._lbatches
+
+    def loss_means(self):
+        """{"coord", "dense", "total", "batches"}: the mean over the batches fed so far of the per-batch mean loss terms -- what
+        AverageValueMeter.add(loss.item()) per batch reports (test.py:88).  The only call of the loss path that synchronises."""
+        c, d, n = self.loss_sums()
+        return _loss_dict(c, d, n)
+
+    def __call__(self, img, jt_uvd_gt=None, n_valid=None):
+        """-> joints (B, J, 3) of the last stage.  jt_uvd_gt (needs loss_weights): the batch's ground-truth joints, (B, J, 3) or the first
+        n_valid rows; the same pass adds this batch's mean loss terms over its first n_valid images (default: all B) to the accumulator and
+        counts the batch.  Images past n_valid -- the padding of a ragged last batch -- still get their joints."""
+        want = jt_uvd_gt is not None
+        if want and self._lw is None:
+            raise L.AwrError("InferEngine was built without loss_weights: it cannot score a batch against jt_uvd_gt")
+        nv = self.B if n_valid is None else int(n_valid)
+        if not 0 <= nv <= self.B:
+            raise L.AwrError("n_valid = %d outside [0, %d]" % (nv, self.B))
+        if want:
+            rows = int(jt_uvd_gt.shape[0])
+            if rows < nv or rows > self.B:
+                raise L.AwrError("jt_uvd_gt has %d rows for n_valid = %d of a batch of %d" % (rows, nv, self.B))
+            self.jt_gt[:rows].copy_(jt_uvd_gt, non_blocking=True)
         self.net.sync_weights(self.plan)
         self.plan.img.copy_(img, non_blocking=True)
         if not self._compiled:           # one-off: [winograd="auto": the candidate plans timed,] eager warm-up run, GEMM tile autotune, hipGraph capture
@@ -596,11 +675,20 @@ class InferEngine(_WinogradAuto):
                     self.graph = torch.cuda.CUDAGraph()
                     with torch.cuda.graph(self.graph):
                         self._core()
-        if self.graph is not None:
-            self.graph.replay()
+            self.reset_loss()         # the candidate timing, the warm-up and the tuner's runs are not batches of the caller's
+        if self.graph is not None and want == (self._lw is not None) and (nv == self.B or not want):
+            self.graph.replay()       # (the captured launches score all B images; a ragged call or one without its ground truth runs eagerly)
         else:
-            self._core()
+            self._core(loss=want, n_valid=nv)
+        if want and nv > 0:
+            self._lbatches += 1
         return self.jt
+
+
+def _loss_dict(coord, dense, batches):
+    n = float(batches)
+    c, d = (coord / n, dense / n) if batches else (float("nan"), float("nan"))
+    return {"coord": c, "dense": d, "total": c + d, "batches": int(batches)}
 
 
 class _Plateau:
@@ -857,8 +945,10 @@ class Trainer:
         wino = getattr(cfg, "winograd", None)
         if isinstance(wino, str) and wino == "auto" and self._infer_winograd is not None:
             wino = self._infer_winograd
+        test_loss = bool(getattr(cfg, "test_loss", False))      # test.py:73-88: the validation loss, from the pass that decodes the joints
+        loss_kw = dict(loss_weights=(cfg.coord_weight, cfg.dense_weight), loss_stages=getattr(cfg, "test_loss_stages", "last")) if test_loss else {}
         inf = self._last_infer = InferEngine(self.net, cfg.batch_size, cfg.img_size, cfg.kernel_size, use_graph=False,
-                                             parity=bool(getattr(cfg, "parity_infer", False)), winograd=wino)
+                                             parity=bool(getattr(cfg, "parity_infer", False)), winograd=wino, **loss_kw)
         n, bs = len(self.testData), cfg.batch_size
         mine = [b for b in range((n + bs - 1) // bs) if b % world == self.rank]
         idx = [i for b in mine for i in range(b * bs, min(n, (b + 1) * bs))]
@@ -878,11 +968,12 @@ class Trainer:
                 pad.zero_()
                 pad[:nb] = x
                 x = pad
+            gt = (jt_uvd_gt.cuda(non_blocking=True).float(),) if test_loss else ()      # (rows past nb of a ragged batch are not read)
             if dev_eval:
-                jt = inf(x)
+                jt = inf(x, *gt, n_valid=nb)
                 ev.feed_batch(jt, jt_xyz_gt, center_xyz, M, cube, n_valid=nb)
             else:
-                jt = inf(x)[:nb].cpu().numpy()
+                jt = inf(x, *gt, n_valid=nb)[:nb].cpu().numpy()
                 ev.feed_batch(jt, jt_xyz_gt.numpy(), center_xyz.numpy(), M.numpy(), cube.numpy())
             ib = mine[k] + 1
             if getattr(cfg, "vis_freq", 0) and ib % cfg.vis_freq == 0 and self._vis is not None:    # train.py:203-213
@@ -915,4 +1006,11 @@ class Trainer:
             jt_uvd = np.array(ev.jt_uvd_pred, dtype=np.float32)
             np.savetxt(os.path.join(self.work_dir, "test_%.3f.txt" % mpe), jt_uvd.reshape([jt_uvd.shape[0], cfg.jt_num * 3]), fmt="%.3f")
         self._msg("[epoch {:2d}], [test mpe {:.3f}], [lr {:.1e}]".format(epoch, mpe, self.engine.lr))
+        if test_loss:          # per-rank sums and batch counts are added up: every rank holds and logs the same means (like train()'s meter)
+            t = torch.tensor(inf.loss_sums(), dtype=torch.float64, device=self.net.device)
+            if world > 1:
+                torch.distributed.all_reduce(t, group=self.pg)
+            c, d, nbat = t.tolist()
+            self.last_test_loss = l = _loss_dict(c, d, int(nbat))
+            self._msg("[epoch {:2d}], [test loss {:.5f}][offset_loss {:.5f}][coord_loss {:.5f}]".format(epoch, l["total"], l["dense"], l["coord"]))
         return mpe

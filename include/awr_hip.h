@@ -111,6 +111,17 @@ int awr_head_forward_nhwc(const float* pred, int Cp, const float* img, int B, in
 int awr_head_loss_step_nhwc(const float* pred, int Cp, const float* img, const float* jt_gt, int B, int J, int F, int H, float ks,
                             float delta, float coord_weight, float dense_weight, float* scratch, float* jt, float* stat,
                             float* g_jt /* needed when coord_weight != 0 */, double* acc, float* grad, void* stream);
+/* awr_head_eval_nhwc = the loss of a scoring pass (test.py:73-86) next to its joints, in one read-only pass over the map: joints (+ the
+ * optional (max, sum) statistics) exactly as awr_head_forward_nhwc writes them, acc[0] += coord_weight * mean Huber(joints - jt_gt),
+ * acc[1] += dense_weight * mean Huber(pred - GT map), the GT map (util/feature_tool.py:12-39) computed on the fly as in
+ * awr_head_loss_step_nhwc -- but no gradient: pred is only read, nothing of the size of the map is written.  Both means are over the first
+ * n_valid images (0 <= n_valid <= B): the zero-padded tail of a ragged last batch gets its joints and adds nothing to acc (n_valid == 0: acc
+ * is untouched; coord_weight == 0: acc[0] is untouched).  Geometry rules: awr_head_forward_nhwc's.  acc ACCUMULATES: a caller sums stages
+ * (test.py:74-80) and batches on the device and reads the result with awr_loss_finalize / awr_loss_finalize_reset; the encoding of acc follows
+ * the deterministic mode as in awr_head_loss_step_nhwc.  One streaming launch + the merge launch. */
+int awr_head_eval_nhwc(const float* pred, int Cp, const float* img, const float* jt_gt, int B, int J, int F, int H, int n_valid,
+                       float ks, float delta, float coord_weight, float dense_weight, float* scratch, float* jt,
+                       float* stat /* may be NULL */, double* acc /* [0] += coord term, [1] += dense term */, void* stream);
 int awr_zero_f64(double* p, int64_t n, void* stream);
 /* out[i] = (float)acc[i] for i<n, out[n] = sum -- e.g. {coord, dense, total} */
 int awr_loss_finalize(const double* acc, int n, float* out, void* stream);
