@@ -116,6 +116,7 @@ def __getattr__(name):
         "PoseNet": ("hourglass", "PoseNet"),
         "Trainer": ("trainer", "Trainer"),
         "TrainEngine": ("trainer", "TrainEngine"),
+        "Predictor": ("predictor", "Predictor"),
         "opt": ("config", "opt"),
     }
     if name in table:

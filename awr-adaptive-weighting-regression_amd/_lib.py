@@ -235,6 +235,11 @@ _SIGS = {
     "awr_nyu_batch": ([_P, _I, _I, _I, _P, _I, _I, _P, _P, _P, _P], C.c_int),
     # joint scoring (csrc/awr_eval.hip)
     "awr_eval_batch": ([_P, _P, _P, _P, _P, _I, _I, _I, _F, _D, _D, _D, _D, _I, _P, _P, _L, _L, _P, _P, _P], C.c_int),
+    "awr_joints_unproject": ([_P, _P, _P, _P, _I, _I, _I, _F, _D, _D, _D, _D, _I, _P, _P, _P, _P], C.c_int),
+    # hand detection (csrc/awr_detect.hip)
+    "awr_detect_scratch": ([_I], C.c_int64),
+    "awr_detect": ([_P, _I, _L, _I, _I, _P, _I, _I, _P, _D, _D, _D, _P, _I, _D, _D, _I, _I, _P, _P, _P, _P], C.c_int),
+    "awr_detect_samples": ([_P, _P, _I, _L, _P, _I, _I, _I, _I, _D, _D, _D, _D, _I, _P, _P, _P, _P, _P, _P], C.c_int),
 }
 
 # entry points of study builds only (hipcc -DAWR_STUDY, AWR_BUILD_STUDY=1 for awr_amd.build): measured-and-rejected forms that the default

@@ -32,6 +32,7 @@ SOURCES = {
     "awr_dp.hip": [],         # host-only: RCCL communicators through dlopen (no link-time dependency)
     "awr_nyu.hip": ["-ffp-contract=off"],     # NYU data path: numpy's / OpenCV's arithmetic, no fused multiply-adds
     "awr_eval.hip": ["-ffp-contract=off"],    # joint scoring: the host evaluator's numpy arithmetic
+    "awr_detect.hip": ["-ffp-contract=off"],  # hand detection: center2bounds / set_crop in numpy's double arithmetic
 }
 
 

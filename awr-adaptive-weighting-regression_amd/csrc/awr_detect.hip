@@ -1,0 +1,338 @@
+// Hand detection on the device: the crop centre of a raw depth frame by an iterated centre of mass, and from a centre the
+// awr_nyu_sample block, crop matrix, camera-space centre and cube that awr_nyu_batch / awr_joints_unproject consume -- a restatement of
+// awr_amd/detect.py (detect, sample_blocks), which itself calls nyu_data.center2bounds / crop_geometry / center2transmat.
+//
+// A pass over a frame is a streaming read (480 x 640 uint16 = 614 KB; 39 MB per pass at B = 64): HBM-bound, no matrix work.  What
+// matters is (1) every sum is a 64-bit INTEGER (count, sum of columns, sum of rows, sum of raw uint16 depths): integer addition is
+// associative, so any split of a frame over workgroups and any arrival order of the 64-bit integer atomics give the bits numpy gives
+// summing in int64 -- there is no floating-point atomic in this file; (2) a frame is split over several workgroups by rows, rows are
+// read with 16-byte loads wherever an aligned group of 8 pixels lies inside the window and pixel by pixel at the two ends;
+// (3) per-workgroup partial sums meet in LDS and leave as ONE set of four atomics per workgroup; (4) each pass is its own launch and
+// keeps its own accumulator slot in the caller's scratch, so the passes are ordered by the stream alone: nothing synchronises, and
+// every workgroup of a pass derives the window from the previous pass's sums by the same three double divisions.
+// The window arithmetic is nyu_data.center2bounds in IEEE double without contraction (this file is compiled with -ffp-contract=off).
+#include <limits.h>
+#include <math.h>
+
+#include "awr_common.h"
+
+namespace awr {
+
+constexpr int DET_THREADS = 256;
+constexpr int DET_SLOTS = AWR_DET_MAX_ITERS + 2;      // slot 0: smallest depth (NEAREST), slot 1: seed pass, slots 2...: refinement passes
+constexpr int DET_MAX_PARTS = 1024;
+constexpr int DET_MAX_SIDE = 16384;                   // fh, fw: sums stay below 2^44, pixel offsets inside int32
+
+typedef unsigned long long u64;
+
+enum { PASS_MIN = 0, PASS_SEED = 1, PASS_REFINE = 2 };
+
+struct Window {
+    int u0, u1, v0, v1;       // clipped to the frame; empty when u0 >= u1 or v0 >= v1
+    int dlo, dhi;             // raw depths d with dlo <= d <= dhi (dlo >= 1: zero is "no measurement")
+};
+
+// int() of a finite double whose value may lie outside int32: every use clips to [0, 16384] afterwards, so clamping first changes nothing
+__device__ __forceinline__ int trunc_clamped(double x) {
+    return (int)fmin(fmax(trunc(x), -1073741824.0), 1073741824.0);
+}
+
+// zstart <= d <= zend and d != 0 for an integer d in [0, 65535]  <=>  dlo <= d <= dhi
+__device__ __forceinline__ void depth_bounds(double zstart, double zend, int& dlo, int& dhi) {
+    if (!(zstart <= zend)) { dlo = 1; dhi = 0; return; }                   // NaN or an empty range
+    dlo = max(1, (int)fmin(fmax(ceil(zstart), 0.0), 65536.0));
+    dhi = (int)fmin(fmax(floor(zend), -1.0), 65535.0);
+}
+
+// nyu_data.center2bounds (loader.py:181-188) clipped to the frame; a non-finite centre or bound is an empty window
+__device__ __forceinline__ Window bounds_window(const double* c, const double* cube, double fx, double fy, int fh, int fw) {
+    Window w{0, 0, 0, 0, 1, 0};
+    const double hu = (cube[0] / 2.0) / c[2] * fx, hv = (cube[1] / 2.0) / c[2] * fy;
+    const double us = c[0] - hu + 0.5, ue = c[0] + hu + 0.5, vs = c[1] - hv + 0.5, ve = c[1] + hv + 0.5;
+    if (!(isfinite(us) && isfinite(ue) && isfinite(vs) && isfinite(ve) && isfinite(c[2]))) return w;
+    w.u0 = max(trunc_clamped(us), 0); w.u1 = min(trunc_clamped(ue), fw);
+    w.v0 = max(trunc_clamped(vs), 0); w.v1 = min(trunc_clamped(ve), fh);
+    depth_bounds(c[2] - cube[2] / 2.0, c[2] + cube[2] / 2.0, w.dlo, w.dhi);
+    return w;
+}
+
+// centre of mass of an accumulator slot: three double divisions; n == 0 -> NaN
+__device__ __forceinline__ void slot_centre(const u64* s, double* c) {
+    if (s[0] == 0) { c[0] = c[1] = c[2] = __builtin_nan(""); return; }
+    const double n = (double)s[0];
+    c[0] = (double)s[1] / n; c[1] = (double)s[2] / n; c[2] = (double)s[3] / n;
+}
+
+__device__ __forceinline__ u64 wave_sum_u64(u64 v) {
+#pragma unroll
+    for (int o = 32; o > 0; o >>= 1) v += (u64)__shfl_xor((long long)v, o, 64);
+    return v;
+}
+
+__global__ __launch_bounds__(DET_THREADS) void detect_init_kernel(u64* __restrict__ slots, int64_t n) {
+    const int64_t i = (int64_t)blockIdx.x * DET_THREADS + threadIdx.x;
+    if (i < n) slots[i] = (i % (DET_SLOTS * 4) == 0) ? ~0ull : 0ull;        // slot 0 word 0 holds a minimum
+}
+
+// One pass: grid (parts, B).  kind PASS_MIN: smallest depth in [zmin, zmax] over the frame -> slot 0.  PASS_SEED: centre of mass over the
+// frame of [zmin, zmax] (RANGE) or [dmin, min(dmin + slab, zmax)] (NEAREST) -> slot 1.  PASS_REFINE r: window of the centre left by
+// pass r - 1 (r = 0: the seed) -> slot 2 + r.
+__global__ __launch_bounds__(DET_THREADS) void detect_pass_kernel(const uint16_t* __restrict__ frames, int64_t n_frames, int fh, int fw,
+                                                                  const int64_t* __restrict__ frame, int kind, int r, int seed_mode,
+                                                                  const double* __restrict__ seed, double zmin, double zmax, double slab,
+                                                                  const double* __restrict__ cube, int cube_stride, double fx, double fy,
+                                                                  u64* __restrict__ slots) {
+    __shared__ u64 red[4][DET_THREADS / 64];
+    const int b = blockIdx.y, parts = gridDim.x, part = blockIdx.x, tid = threadIdx.x;
+    const int64_t f = frame[b];
+    if (f < 0 || f >= n_frames) return;                                     // AWR_DET_BAD_FRAME: nothing of it is read
+    u64* S = slots + (int64_t)b * DET_SLOTS * 4;
+    Window w{0, fw, 0, fh, 1, 0};
+    if (kind == PASS_REFINE) {
+        double c[3];
+        if (r == 0 && seed_mode == AWR_DET_SEED_GIVEN) { c[0] = seed[3 * b]; c[1] = seed[3 * b + 1]; c[2] = seed[3 * b + 2]; }
+        else slot_centre(S + 4 * (1 + r), c);
+        w = bounds_window(c, cube + (int64_t)b * cube_stride, fx, fy, fh, fw);
+    } else if (kind == PASS_SEED && seed_mode == AWR_DET_SEED_NEAREST) {
+        const double dmin = (double)S[0];                                   // (no pixel in range: the sentinel 2^64 - 1 admits none)
+        depth_bounds(dmin, fmin(dmin + slab, zmax), w.dlo, w.dhi);
+    } else {
+        depth_bounds(zmin, zmax, w.dlo, w.dhi);
+    }
+    if (w.u0 >= w.u1 || w.v0 >= w.v1 || w.dlo > w.dhi) return;
+    const int rows = w.v1 - w.v0, per = (rows + parts - 1) / parts;
+    const int va = w.v0 + part * per, vb = min(va + per, w.v1);
+    if (part * per >= rows) return;                                         // more workgroups than rows
+    const uint16_t* F = frames + f * (int64_t)fh * fw;
+    const int mis = (int)(((uintptr_t)F >> 1) & 7);                         // pixels by which the frame's origin is past a 16-byte boundary
+    const unsigned dlo = (unsigned)w.dlo, dhi = (unsigned)w.dhi;
+    u64 n = 0, su = 0, sv = 0, sd = 0;
+    unsigned dmin = 0xFFFFFFFFu;
+    // (row, aligned group of 8 pixels) pairs of this workgroup's rows, flattened so that narrow windows still fill the lanes.  gpr bounds the
+    // groups a row touches; pixel positions count from the 16-byte boundary before the frame's origin, where groups of 8 are aligned.
+    const int gpr = ((w.u1 - w.u0) >> 3) + 2, total = (vb - va) * gpr;
+    for (int idx = tid; idx < total; idx += DET_THREADS) {
+        const int v = va + idx / gpr, gi = idx % gpr;
+        const int colbase = mis + v * fw, gs = colbase + w.u0, ge = colbase + w.u1;
+        const int g0 = ((gs >> 3) + gi) << 3;
+        if (g0 >= ge) continue;
+        unsigned rn = 0, ru = 0, rd = 0;
+        if (g0 >= gs && g0 + 8 <= ge) {
+            const uint4 q = *reinterpret_cast<const uint4*>(F + (g0 - mis));
+            const unsigned word[4] = {q.x, q.y, q.z, q.w};
+#pragma unroll
+            for (int k = 0; k < 8; ++k) {
+                const unsigned d = (word[k >> 1] >> ((k & 1) * 16)) & 0xFFFFu;
+                const bool in = d >= dlo && d <= dhi;
+                rn += in ? 1u : 0u;
+                ru += in ? (unsigned)(g0 + k - colbase) : 0u;
+                rd += in ? d : 0u;
+                dmin = in ? min(dmin, d) : dmin;
+            }
+        } else {                                                            // the two ends of a row: pixel by pixel, never outside the window
+            for (int g = max(g0, gs); g < min(g0 + 8, ge); ++g) {
+                const unsigned d = F[g - mis];
+                const bool in = d >= dlo && d <= dhi;
+                rn += in ? 1u : 0u;
+                ru += in ? (unsigned)(g - colbase) : 0u;
+                rd += in ? d : 0u;
+                dmin = in ? min(dmin, d) : dmin;
+            }
+        }
+        n += rn; su += ru; sd += rd; sv += (u64)rn * (u64)v;
+    }
+    if (kind == PASS_MIN) {
+#pragma unroll
+        for (int o = 32; o > 0; o >>= 1) dmin = min(dmin, (unsigned)__shfl_xor((int)dmin, o, 64));
+        if ((tid & 63) == 0) red[0][tid >> 6] = dmin;
+        __syncthreads();
+        if (tid == 0) {
+            u64 m = red[0][0];
+            for (int i = 1; i < DET_THREADS / 64; ++i) m = min(m, red[0][i]);
+            if (m != 0xFFFFFFFFull) atomicMin(S, m);
+        }
+        return;
+    }
+    n = wave_sum_u64(n); su = wave_sum_u64(su); sv = wave_sum_u64(sv); sd = wave_sum_u64(sd);
+    if ((tid & 63) == 0) { red[0][tid >> 6] = n; red[1][tid >> 6] = su; red[2][tid >> 6] = sv; red[3][tid >> 6] = sd; }
+    __syncthreads();
+    if (tid < 4) {
+        u64 t = 0;
+        for (int i = 0; i < DET_THREADS / 64; ++i) t += red[tid][i];
+        u64* dst = S + 4 * (kind == PASS_SEED ? 1 : 2 + r) + tid;
+        if (red[0][0] + red[0][1] + red[0][2] + red[0][3] != 0) atomicAdd(dst, t);
+    }
+}
+
+// centre and status of every frame from its slots, in pass order
+__global__ __launch_bounds__(DET_THREADS) void detect_finalize_kernel(int64_t n_frames, const int64_t* __restrict__ frame, int B, int seed_mode,
+                                                                      const double* __restrict__ seed, int iters, const u64* __restrict__ slots,
+                                                                      double* __restrict__ center, int* __restrict__ status) {
+    const int b = blockIdx.x * DET_THREADS + threadIdx.x;
+    if (b >= B) return;
+    const u64* S = slots + (int64_t)b * DET_SLOTS * 4;
+    double c[3] = {__builtin_nan(""), __builtin_nan(""), __builtin_nan("")};
+    int st = AWR_DET_OK;
+    if (frame[b] < 0 || frame[b] >= n_frames) st = AWR_DET_BAD_FRAME;
+    else {
+        if (seed_mode == AWR_DET_SEED_GIVEN) { c[0] = seed[3 * b]; c[1] = seed[3 * b + 1]; c[2] = seed[3 * b + 2]; }
+        else {
+            slot_centre(S + 4, c);
+            if (S[4] == 0) st = AWR_DET_EMPTY;
+        }
+        for (int r = 0; r < iters; ++r) {
+            slot_centre(S + 4 * (2 + r), c);
+            if (S[4 * (2 + r)] == 0) st = AWR_DET_EMPTY;
+        }
+    }
+    center[3 * b] = c[0]; center[3 * b + 1] = c[1]; center[3 * b + 2] = c[2];
+    status[b] = st;
+}
+
+// ---- centre -> awr_nyu_sample block, crop matrix, camera-space centre, cube (nyu_device.set_crop + set_normalize, center2transmat) ----
+__global__ __launch_bounds__(DET_THREADS) void detect_samples_kernel(const double* __restrict__ center, const double* __restrict__ cube,
+                                                                     int cube_stride, int64_t n_frames, const int64_t* __restrict__ frame,
+                                                                     int B, int dsize, int fh, int fw, double fx, double fy, double u0, double v0, double flip,
+                                                                     awr_nyu_sample* __restrict__ samples, float* __restrict__ M,
+                                                                     float* __restrict__ center_xyz, float* __restrict__ cube_out,
+                                                                     int* __restrict__ status) {
+    const int b = blockIdx.x * DET_THREADS + threadIdx.x;
+    if (b >= B) return;
+    const double* c = center + 3 * b;
+    const double* cb = cube + (int64_t)b * cube_stride;
+    awr_nyu_sample s;
+    // center2bounds (loader.py:181-188)
+    const double hu = (cb[0] / 2.0) / c[2] * fx, hv = (cb[1] / 2.0) / c[2] * fy;
+    const double us = c[0] - hu + 0.5, ue = c[0] + hu + 0.5, vs = c[1] - hv + 0.5, ve = c[1] + hv + 0.5;
+    bool ok = isfinite(us) && isfinite(ue) && isfinite(vs) && isfinite(ve) && isfinite(c[2]) && isfinite(cb[2]);
+    // (a bound outside int32 cannot pass set_crop's tests with a positive extent that resizes to something: refused here)
+    ok = ok && fabs(us) < 1073741824.0 && fabs(ue) < 1073741824.0 && fabs(vs) < 1073741824.0 && fabs(ve) < 1073741824.0;
+    int ustart = 0, uend = 0, vstart = 0, vend = 0, cw = 0, ch = 0, rw = 0, rh = 0;
+    double scale = 0.0;
+    if (ok) {
+        ustart = (int)us; uend = (int)ue; vstart = (int)vs; vend = (int)ve;
+        cw = uend - ustart; ch = vend - vstart;
+        ok = cw > 0 && ch > 0 && uend > 0 && vend > 0 && ustart < fw && vstart < fh;
+    }
+    if (ok) {
+        scale = fmin((double)dsize / (double)cw, (double)dsize / (double)ch);        // crop_geometry (loader.py:31-36)
+        rw = (int)((double)cw * scale); rh = (int)((double)ch * scale);
+        ok = rw > 0 && rh > 0;
+    }
+    const int64_t f = frame[b];
+    if (f < 0 || f >= n_frames) {                                                             // never a block that names a frame outside the store
+        ok = false;
+        status[b] = AWR_DET_BAD_FRAME;
+    }
+    for (int i = 0; i < 9; ++i) s.m[i] = 0.0;
+    s.op = AWR_NYU_NONE; s.norm32 = 0; s.zstart2 = 0.0; s.zend2 = 0.0;
+    if (ok) {
+        s.frame = f;
+        s.ustart = ustart; s.vstart = vstart; s.cw = cw; s.ch = ch; s.rw = rw; s.rh = rh;
+        s.ox = (int)((double)(dsize - rw) / 2.0); s.oy = (int)((double)(dsize - rh) / 2.0);
+        s.ifx = 1.0 / ((double)rw / (double)cw); s.ify = 1.0 / ((double)rh / (double)ch);      // nyu_data.resize_nearest: two divisions
+        s.zstart = c[2] - cb[2] / 2.0; s.zend = c[2] + cb[2] / 2.0;
+        const double half = cb[2] / 2.0;                                                      // set_normalize, float64
+        s.half = half; s.far = c[2] + half; s.lo = c[2] - half; s.center_z = c[2];
+        // center2transmat (loader.py:211-240): t2 . (sc . t1) in double, stored as float32
+        const double tx = floor((double)dsize / 2.0 - (double)rw / 2.0), ty = floor((double)dsize / 2.0 - (double)rh / 2.0);
+        float* m = M + 9 * b;
+        m[0] = (float)scale; m[1] = 0.f; m[2] = (float)(scale * (double)(-ustart) + tx);
+        m[3] = 0.f; m[4] = (float)scale; m[5] = (float)(scale * (double)(-vstart) + ty);
+        m[6] = 0.f; m[7] = 0.f; m[8] = 1.f;
+    } else {
+        // a window set_crop refuses (or a NaN centre): a block that reads no pixel and renders a finite all-background image (rw = rh = 0:
+        // nyu_batch_kernel's crop_pixel returns 0 before it touches cw, ch or the frame), a NaN matrix that un-projects to NaN rows
+        s.frame = 0;
+        s.ustart = s.vstart = s.cw = s.ch = s.rw = s.rh = s.ox = s.oy = 0;
+        s.ifx = s.ify = 1.0; s.zstart = 0.0; s.zend = 0.0;
+        s.lo = 0.0; s.far = 1.0; s.center_z = 0.0; s.half = 1.0;
+        for (int i = 0; i < 9; ++i) M[9 * b + i] = __builtin_nanf("");
+        if (status[b] == AWR_DET_OK) status[b] = AWR_DET_BAD_WINDOW;
+    }
+    samples[b] = s;
+    // evaluator.uvd2xyz (util.py:13-20) of the float64 centre, stored as float32
+    center_xyz[3 * b] = (float)((c[0] - u0) * c[2] / fx);
+    center_xyz[3 * b + 1] = (float)((c[1] - v0) * c[2] / fy * flip);
+    center_xyz[3 * b + 2] = (float)c[2];
+    cube_out[3 * b] = (float)cb[0]; cube_out[3 * b + 1] = (float)cb[1]; cube_out[3 * b + 2] = (float)cb[2];
+}
+
+static int detect_parts(int B, int fh) {
+    // about four workgroups per CU over the batch, never more than one per row of the frame (a workgroup's share is whole rows)
+    int p = (1024 + B - 1) / B;
+    p = p < fh ? p : fh;
+    return p < 1 ? 1 : (p > DET_MAX_PARTS ? DET_MAX_PARTS : p);
+}
+
+}  // namespace awr
+
+using namespace awr;
+
+extern "C" {
+
+int64_t awr_detect_scratch(int B) {
+    if (B <= 0 || B > AWR_DET_MAX_BATCH) {
+        set_error("awr_detect_scratch: B = %d is outside [1, %d]", B, AWR_DET_MAX_BATCH);
+        return -1;
+    }
+    return (int64_t)B * DET_SLOTS * 4 * (int64_t)sizeof(u64);
+}
+
+int awr_detect(const void* frames, int frame_type, int64_t n_frames, int fh, int fw, const int64_t* frame, int B, int seed_mode,
+               const double* seed_uvd, double zmin, double zmax, double slab, const double* cube, int cube_stride, double fx, double fy,
+               int iters, int parts, void* scratch, double* center_uvd, int* status, void* stream) {
+    AWR_REQUIRE(frames && frame && cube && scratch && center_uvd && status, "awr_detect: NULL pointer");
+    AWR_REQUIRE(frame_type == AWR_NYU_U16, "awr_detect: the frame store must be uint16 millimetres (AWR_NYU_U16): integer sums are what makes the "
+                "centre of mass independent of the summation order (got frame_type %d)", frame_type);
+    AWR_REQUIRE(B > 0 && B <= AWR_DET_MAX_BATCH, "awr_detect: B = %d is outside [1, %d]", B, AWR_DET_MAX_BATCH);
+    AWR_REQUIRE(n_frames > 0, "awr_detect: n_frames = %lld must be positive", (long long)n_frames);
+    AWR_REQUIRE(fh > 0 && fw > 0 && fh <= DET_MAX_SIDE && fw <= DET_MAX_SIDE, "awr_detect: frame of %d x %d is outside [1, %d]^2", fh, fw, DET_MAX_SIDE);
+    AWR_REQUIRE(iters >= 0 && iters <= AWR_DET_MAX_ITERS, "awr_detect: iters = %d is outside [0, %d]", iters, AWR_DET_MAX_ITERS);
+    AWR_REQUIRE(seed_mode == AWR_DET_SEED_GIVEN || seed_mode == AWR_DET_SEED_RANGE || seed_mode == AWR_DET_SEED_NEAREST,
+                "awr_detect: seed_mode %d is none of AWR_DET_SEED_GIVEN / _RANGE / _NEAREST", seed_mode);
+    AWR_REQUIRE(seed_mode != AWR_DET_SEED_GIVEN || seed_uvd, "awr_detect: AWR_DET_SEED_GIVEN needs seed_uvd (NULL pointer)");
+    AWR_REQUIRE(zmin <= zmax, "awr_detect: depth range needs zmin <= zmax (got %g, %g)", zmin, zmax);
+    AWR_REQUIRE(slab >= 0.0, "awr_detect: slab = %g must be >= 0", slab);
+    AWR_REQUIRE(cube_stride == 0 || cube_stride == 3, "awr_detect: cube_stride is 0 (one cube) or 3 (one per frame), not %d", cube_stride);
+    AWR_REQUIRE(fx != 0.0 && fy != 0.0 && isfinite(fx) && isfinite(fy), "awr_detect: bad intrinsics");
+    AWR_REQUIRE(parts >= 0 && parts <= DET_MAX_PARTS, "awr_detect: parts = %d is outside [0, %d] (0: chosen from B and the frame)", parts, DET_MAX_PARTS);
+    AWR_REQUIRE(((uintptr_t)frames & 1) == 0 && ((uintptr_t)scratch & 7) == 0, "awr_detect: misaligned frame store / scratch");
+    hipStream_t s = as_stream(stream);
+    u64* slots = (u64*)scratch;
+    const int64_t nw = (int64_t)B * DET_SLOTS * 4;
+    const int P = parts ? parts : detect_parts(B, fh);
+    const uint16_t* F = (const uint16_t*)frames;
+    detect_init_kernel<<<(unsigned)((nw + DET_THREADS - 1) / DET_THREADS), DET_THREADS, 0, s>>>(slots, nw);
+    const dim3 grid(P, B);
+    if (seed_mode == AWR_DET_SEED_NEAREST)
+        detect_pass_kernel<<<grid, DET_THREADS, 0, s>>>(F, n_frames, fh, fw, frame, PASS_MIN, 0, seed_mode, seed_uvd, zmin, zmax, slab, cube,
+                                                        cube_stride, fx, fy, slots);
+    if (seed_mode != AWR_DET_SEED_GIVEN)
+        detect_pass_kernel<<<grid, DET_THREADS, 0, s>>>(F, n_frames, fh, fw, frame, PASS_SEED, 0, seed_mode, seed_uvd, zmin, zmax, slab, cube,
+                                                        cube_stride, fx, fy, slots);
+    for (int r = 0; r < iters; ++r)
+        detect_pass_kernel<<<grid, DET_THREADS, 0, s>>>(F, n_frames, fh, fw, frame, PASS_REFINE, r, seed_mode, seed_uvd, zmin, zmax, slab, cube,
+                                                        cube_stride, fx, fy, slots);
+    detect_finalize_kernel<<<(B + DET_THREADS - 1) / DET_THREADS, DET_THREADS, 0, s>>>(n_frames, frame, B, seed_mode, seed_uvd, iters, slots,
+                                                                                      center_uvd, status);
+    return check_launch("awr_detect");
+}
+
+int awr_detect_samples(const double* center_uvd, const double* cube, int cube_stride, int64_t n_frames, const int64_t* frame, int B, int dsize,
+                       int fh, int fw, double fx, double fy, double u0, double v0, int flip, awr_nyu_sample* samples, float* M, float* center_xyz,
+                       float* cube_out, int* status, void* stream) {
+    AWR_REQUIRE(center_uvd && cube && frame && samples && M && center_xyz && cube_out && status, "awr_detect_samples: NULL pointer");
+    AWR_REQUIRE(B > 0 && B <= AWR_DET_MAX_BATCH, "awr_detect_samples: B = %d is outside [1, %d]", B, AWR_DET_MAX_BATCH);
+    AWR_REQUIRE(n_frames > 0, "awr_detect_samples: n_frames = %lld must be positive", (long long)n_frames);
+    AWR_REQUIRE(dsize > 0 && dsize <= 4096, "awr_detect_samples: dsize = %d is outside [1, 4096]", dsize);
+    AWR_REQUIRE(fh > 0 && fw > 0 && fh <= DET_MAX_SIDE && fw <= DET_MAX_SIDE, "awr_detect_samples: frame of %d x %d is outside [1, %d]^2", fh, fw,
+                DET_MAX_SIDE);
+    AWR_REQUIRE(cube_stride == 0 || cube_stride == 3, "awr_detect_samples: cube_stride is 0 (one cube) or 3 (one per frame), not %d", cube_stride);
+    AWR_REQUIRE(fx != 0.0 && fy != 0.0 && isfinite(fx) && isfinite(fy) && (flip == 1 || flip == -1), "awr_detect_samples: bad intrinsics / flip");
+    detect_samples_kernel<<<(B + DET_THREADS - 1) / DET_THREADS, DET_THREADS, 0, as_stream(stream)>>>(
+        center_uvd, cube, cube_stride, n_frames, frame, B, dsize, fh, fw, fx, fy, u0, v0, (double)flip, samples, M, center_xyz, cube_out, status);
+    return check_launch("awr_detect_samples");
+}
+
+}  // extern "C"

@@ -43,6 +43,42 @@ __device__ __forceinline__ int inverse_rows(const float* __restrict__ M, double*
     return AWR_EVAL_OK;
 }
 
+// one predicted joint, normalised uvd -> original-image uvd (u, v, d) and camera x, y in mm (z = d): eval_tool.py:38-41 + util.py:13-20
+__device__ __forceinline__ void unproject_joint(const float* __restrict__ p, const float* __restrict__ c, const float* __restrict__ cb,
+                                                const double* r, float img_size, double fx, double fy, double u0, double v0, float flip,
+                                                float& u, float& v, float& d, float& x, float& y) {
+    u = (p[0] + 1.f) * img_size / 2.0f;                          // eval_tool.py:38, float32
+    v = (p[1] + 1.f) * img_size / 2.0f;
+    d = p[2] * cb[2] / 2.0f + c[2];                              // :39
+    const double hu = (double)u, hv = (double)v;                 // :40-41, float64 against inv(M), stored as float32
+    u = (float)((r[0] * hu + r[1] * hv) + r[2]);
+    v = (float)((r[3] * hu + r[4] * hv) + r[5]);
+    x = (float)(((double)u - u0) * (double)d / fx);              // util.py:13-20, float64 against the intrinsics, stored as float32
+    y = (float)(((double)v - v0) * (double)d / fy) * flip;
+}
+
+// The label-free half of eval_batch_kernel: joints -> original-image uvd and camera xyz, one status code per frame.
+__global__ __launch_bounds__(EVAL_THREADS) void joints_unproject_kernel(const float* __restrict__ pred, const float* __restrict__ center,
+                                                                        const float* __restrict__ M, const float* __restrict__ cube, int J,
+                                                                        int n_valid, float img_size, double fx, double fy, double u0, double v0,
+                                                                        float flip, float* __restrict__ uvd_out, float* __restrict__ xyz_out,
+                                                                        int* __restrict__ status) {
+    for (int e = threadIdx.x; e < n_valid * J; e += EVAL_THREADS) {
+        const int64_t b = e / J;
+        const int j = e - (int)b * J;
+        double r[6];
+        const int code = inverse_rows(M + b * 9, r);
+        float u, v, d, x, y;
+        if (code == AWR_EVAL_OK) unproject_joint(pred + (b * J + j) * 3, center + b * 3, cube + b * 3, r, img_size, fx, fy, u0, v0, flip, u, v, d, x, y);
+        else u = v = d = x = y = __builtin_nanf("");
+        float* o = uvd_out + (b * J + j) * 3;
+        o[0] = u; o[1] = v; o[2] = d;
+        float* q = xyz_out + (b * J + j) * 3;
+        q[0] = x; q[1] = y; q[2] = d;
+        if (j == 0) status[b] = code;
+    }
+}
+
 __global__ __launch_bounds__(EVAL_THREADS) void eval_batch_kernel(const float* __restrict__ pred, const float* __restrict__ gt,
                                                                   const float* __restrict__ center, const float* __restrict__ M,
                                                                   const float* __restrict__ cube, int J, int n_valid, float img_size,
@@ -71,14 +107,8 @@ __global__ __launch_bounds__(EVAL_THREADS) void eval_batch_kernel(const float* _
             const float* cb = cube + b * 3;
             float u, v, d, err;
             if (code == AWR_EVAL_OK) {
-                u = (p[0] + 1.f) * img_size / 2.0f;                          // eval_tool.py:38, float32
-                v = (p[1] + 1.f) * img_size / 2.0f;
-                d = p[2] * cb[2] / 2.0f + c[2];                              // :39
-                const double hu = (double)u, hv = (double)v;                 // :40-41, float64 against inv(M), stored as float32
-                u = (float)((r[0] * hu + r[1] * hv) + r[2]);
-                v = (float)((r[3] * hu + r[4] * hv) + r[5]);
-                const float x = (float)(((double)u - u0) * (double)d / fx);  // util.py:13-20, float64 against the intrinsics, stored as float32
-                const float y = (float)(((double)v - v0) * (double)d / fy) * flip;
+                float x, y;
+                unproject_joint(p, c, cb, r, img_size, fx, fy, u0, v0, flip, u, v, d, x, y);
                 const float* g = gt + (b * J + j) * 3;
                 const float dx = (g[0] * (cb[0] / 2.0f) + c[0]) - x;         // :46, float32
                 const float dy = (g[1] * (cb[1] / 2.0f) + c[1]) - y;
@@ -148,6 +178,20 @@ int awr_eval_batch(const float* jt_pred, const float* jt_xyz_gt, const float* ce
     eval_batch_kernel<<<1, EVAL_THREADS, 0, as_stream(stream)>>>(jt_pred, jt_xyz_gt, center_xyz, M, cube, J, n_valid, img_size, fx, fy, u0, v0,
                                                                  (float)flip, uvd_out, err_out, row, acc, status);
     return check_launch("awr_eval_batch");
+}
+
+int awr_joints_unproject(const float* jt_pred, const float* center_xyz, const float* M, const float* cube, int B, int J, int n_valid,
+                         float img_size, double fx, double fy, double u0, double v0, int flip, float* uvd_out, float* xyz_out, int* status,
+                         void* stream) {
+    AWR_REQUIRE(jt_pred && center_xyz && M && cube && uvd_out && xyz_out && status, "awr_joints_unproject: NULL pointer");
+    AWR_REQUIRE(B > 0 && B < (1 << 20) && J > 0 && J <= AWR_EVAL_MAX_JOINTS, "awr_joints_unproject: bad sizes (B = %d, J = %d; J <= %d)", B, J,
+                AWR_EVAL_MAX_JOINTS);
+    AWR_REQUIRE(n_valid >= 0 && n_valid <= B, "awr_joints_unproject: n_valid = %d is outside [0, B = %d]", n_valid, B);
+    AWR_REQUIRE(img_size > 0.f && fx != 0.0 && fy != 0.0 && (flip == 1 || flip == -1), "awr_joints_unproject: bad img_size / intrinsics / flip");
+    if (n_valid == 0) return AWR_OK;
+    joints_unproject_kernel<<<1, EVAL_THREADS, 0, as_stream(stream)>>>(jt_pred, center_xyz, M, cube, J, n_valid, img_size, fx, fy, u0, v0, (float)flip,
+                                                                       uvd_out, xyz_out, status);
+    return check_launch("awr_joints_unproject");
 }
 
 }  // extern "C"

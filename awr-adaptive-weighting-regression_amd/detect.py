@@ -1,0 +1,200 @@
+"""Hand detection from a raw depth frame (csrc/awr_detect.hip; include/awr_hip.h "Hand detection on the device").
+
+Two things live here:
+
+  * the numpy restatement -- `center_of_mass`, `detect`, `sample_blocks` -- written to the definition in the header.  It is the
+    yardstick the kernels are tested against bit for bit, and a usable host fallback for a machine without a GPU;
+  * thin operator-level wrappers over the entry points (`detect_device`, `samples_device`, `unproject_device`) for tests and tools.
+    `awr_amd.predictor.Predictor` is the product path.
+
+Definition.  Centre of mass of a pixel set: n, sum of columns u, sum of rows v and sum of raw uint16 depths d as int64, centre =
+(su / n, sv / n, sd / n) as three double divisions.  Integer sums do not depend on the order of summation, so the device, which splits a
+frame over workgroups and combines them with 64-bit integer atomics, gives these bits exactly; that is why frames must be uint16.
+Seed: "given" | "range" (pixels of the whole frame with zmin <= d <= zmax) | "nearest" (dmin = smallest such d, then the pixels with
+dmin <= d <= min(dmin + slab, zmax)).  Refinement, `iters` times with no convergence test: window and depth range from
+nyu_data.center2bounds(centre, cube, paras), clipped to the frame; centre of mass of its pixels with zstart <= d <= zend.  A pixel with
+d == 0 never counts.  A pass that finds no pixel makes the centre NaN and the status EMPTY; later passes keep the NaN.
+"""
+import ctypes as C
+import warnings
+
+import numpy as np
+
+from . import nyu_data as ND
+from .evaluator import uvd2xyz
+
+OK, EMPTY, BAD_FRAME, BAD_WINDOW = 0, 1, 2, 3
+STATUS_NAMES = {OK: "ok", EMPTY: "no pixel in the depth range / window (AWR_DET_EMPTY)", BAD_FRAME: "frame index outside the store (AWR_DET_BAD_FRAME)",
+                BAD_WINDOW: "crop window misses the frame or resizes to nothing (AWR_DET_BAD_WINDOW)"}
+SEED_GIVEN, SEED_RANGE, SEED_NEAREST = 0, 1, 2
+SEEDS = {"given": SEED_GIVEN, "range": SEED_RANGE, "nearest": SEED_NEAREST}
+MAX_ITERS = 8
+# Engineering defaults, not measured on NYU frames (none are available where this was written): the sensor's useful range, a slab as deep
+# as a hand seen end-on, two refinement passes.
+DEPTH_RANGE, SLAB, REFINE_ITERS = (1.0, 2000.0), 150.0, 2
+_NAN3 = (float("nan"),) * 3
+
+
+def _u16(frame):
+    frame = np.asarray(frame)
+    if frame.dtype != np.uint16 or frame.ndim != 2:
+        raise ValueError("a frame is a (h, w) uint16 array of millimetres (integer sums make the centre of mass exact), not %s %s"
+                         % (frame.dtype, frame.shape))
+    return frame
+
+
+def center_of_mass(frame, window=None, zstart=-np.inf, zend=np.inf):
+    """-> ((u, v, d) float64, n).  window = (ustart, uend, vstart, vend), already clipped to the frame (None: the whole frame); pixels with
+    zstart <= d <= zend and d != 0 count.  n == 0 -> (nan, nan, nan)."""
+    frame = _u16(frame)
+    u0, u1, v0, v1 = (0, frame.shape[1], 0, frame.shape[0]) if window is None else window
+    if u0 >= u1 or v0 >= v1:
+        return _NAN3, 0
+    win = frame[v0:v1, u0:u1]
+    mask = (win >= zstart) & (win <= zend) & (win != 0)      # uint16 against a float64 scalar compares in float64
+    n = int(np.count_nonzero(mask))
+    if n == 0:
+        return _NAN3, 0
+    vv, uu = np.nonzero(mask)
+    su = int(uu.astype(np.int64).sum()) + n * u0
+    sv = int(vv.astype(np.int64).sum()) + n * v0
+    sd = int(win[mask].astype(np.int64).sum())
+    return (float(su) / float(n), float(sv) / float(n), float(sd) / float(n)), n
+
+
+def _window(center, cube, paras, fh, fw):
+    """center2bounds clipped to the frame, or None where it has no integer window (a NaN / infinite centre or bound)."""
+    try:
+        with np.errstate(all="ignore"), warnings.catch_warnings():
+            warnings.simplefilter("ignore")
+            ustart, uend, vstart, vend, zstart, zend = ND.center2bounds(center, cube, paras)
+    except (ValueError, OverflowError):
+        return None
+    if not np.isfinite(center[2]):
+        return None
+    return (max(ustart, 0), min(uend, fw), max(vstart, 0), min(vend, fh)), zstart, zend
+
+
+def detect(frame, seed="nearest", center=None, cube=(300, 300, 300), paras=ND.PARAS, depth_range=DEPTH_RANGE, slab=SLAB, iters=REFINE_ITERS):
+    """-> ((u, v, d) float64 centre, status).  seed: "given" (centre = `center`) | "range" | "nearest"."""
+    frame = _u16(frame)
+    fh, fw = frame.shape
+    if seed not in SEEDS:
+        raise ValueError("seed is one of %s, not %r" % (sorted(SEEDS), seed))
+    if not 0 <= int(iters) <= MAX_ITERS:
+        raise ValueError("iters = %r is outside [0, %d]" % (iters, MAX_ITERS))
+    zmin, zmax = float(depth_range[0]), float(depth_range[1])
+    if not zmin <= zmax:
+        raise ValueError("depth_range needs zmin <= zmax")
+    status = OK
+    if seed == "given":
+        c = tuple(float(x) for x in center)
+    else:
+        if seed == "nearest":
+            m = (frame >= zmin) & (frame <= zmax) & (frame != 0)
+            if m.any():
+                dmin = float(frame[m].min())
+                c, n = center_of_mass(frame, None, dmin, min(dmin + float(slab), zmax))
+            else:
+                c, n = _NAN3, 0
+        else:
+            c, n = center_of_mass(frame, None, zmin, zmax)
+        if n == 0:
+            status = EMPTY
+    for _ in range(int(iters)):
+        w = _window(c, cube, paras, fh, fw)
+        c, n = center_of_mass(frame, *w) if w is not None else (_NAN3, 0)
+        if n == 0:
+            status = EMPTY
+    return c, status
+
+
+def sample_blocks(centers, cube, dsize, paras=ND.PARAS, flip=-1, frame_shape=(480, 640), frames=None):
+    """The host's blocks for float64 centres: -> (list of L.NyuSample or None where set_crop refuses the window, M (B, 3, 3) float32 (NaN there),
+    center_xyz (B, 3) float32, cube (B, 3) float32, status (B,) int32).  What awr_detect_samples is tested against."""
+    from . import _lib as L
+    from . import nyu_device as DV
+    centers = np.asarray(centers, np.float64).reshape(-1, 3)
+    B = centers.shape[0]
+    cubes = np.broadcast_to(np.asarray(cube, np.float64), (B, 3))
+    fh, fw = frame_shape
+    blocks, M, status = [], np.full((B, 3, 3), np.nan, np.float32), np.zeros(B, np.int32)
+    for b in range(B):
+        blk = L.NyuSample()
+        try:
+            with np.errstate(all="ignore"), warnings.catch_warnings():
+                warnings.simplefilter("ignore")
+                M[b] = DV.set_crop(blk, b if frames is None else frames[b], centers[b], cubes[b], (dsize, dsize), paras, fh, fw)
+            DV.set_normalize(blk, centers[b], cubes[b])
+            blocks.append(blk)
+        except (ValueError, OverflowError, ZeroDivisionError):
+            blocks.append(None)
+            status[b] = BAD_WINDOW
+    with np.errstate(all="ignore"):
+        cxyz = uvd2xyz(centers, paras, flip)
+    return blocks, M, cxyz, np.ascontiguousarray(cubes, dtype=np.float32), status      # (cubes may be a broadcast view: stride 0)
+
+
+# ---- operator-level wrappers over the entry points (tests, tools) ------------------------------------------------------------------
+def _f64(x, dev):
+    import torch
+    return torch.from_numpy(np.ascontiguousarray(x, dtype=np.float64)).to(dev)
+
+
+def detect_device(store, frame_idx, seed="nearest", centers=None, cube=(300, 300, 300), paras=ND.PARAS, depth_range=DEPTH_RANGE, slab=SLAB,
+                  iters=REFINE_ITERS, parts=0):
+    """awr_detect on a nyu_device.FrameStore-like object (.data (n, fh, fw) uint16 on the device, .ftype, .fh, .fw): -> (centres (B, 3) float64,
+    status (B,) int32) on the device, nothing synchronised."""
+    import torch
+    from . import _lib as L
+    dev = store.data.device
+    idx = torch.as_tensor(np.asarray(frame_idx, np.int64)).to(dev) if not isinstance(frame_idx, torch.Tensor) else frame_idx
+    B = int(idx.shape[0])
+    cb = _f64(cube, dev)
+    seed_t = None
+    if seed == "given":
+        seed_t = centers if isinstance(centers, torch.Tensor) else _f64(centers, dev)
+    nbytes = int(L.lib.awr_detect_scratch(B))
+    if nbytes < 0:
+        raise L.AwrError(L.last_error())
+    scratch = torch.empty(nbytes // 8, dtype=torch.int64, device=dev)
+    out = torch.empty((B, 3), dtype=torch.float64, device=dev)
+    status = torch.empty(B, dtype=torch.int32, device=dev)
+    L.call("awr_detect", store.data.data_ptr(), store.ftype, int(store.data.shape[0]), store.fh, store.fw, idx.data_ptr(), B, SEEDS[seed],
+           L.ptr(seed_t), float(depth_range[0]), float(depth_range[1]), float(slab), cb.data_ptr(), 3 if cb.dim() == 2 else 0,
+           float(paras[0]), float(paras[1]), int(iters), int(parts), scratch.data_ptr(), out.data_ptr(), status.data_ptr(), L.stream())
+    return out, status
+
+
+def samples_device(centers, cube, dsize, frame_idx, n_frames, frame_shape, paras=ND.PARAS, flip=-1, status=None):
+    """awr_detect_samples: centres (B, 3) float64 on the device -> (blocks (B, BLOCK_BYTES) uint8, M (B, 3, 3), center_xyz (B, 3), cube (B, 3)
+    float32, status (B,) int32) on the device."""
+    import torch
+    from . import _lib as L
+    dev = centers.device
+    B = int(centers.shape[0])
+    idx = torch.as_tensor(np.asarray(frame_idx, np.int64)).to(dev) if not isinstance(frame_idx, torch.Tensor) else frame_idx
+    cb = _f64(cube, dev)
+    blocks = torch.empty((B, C.sizeof(L.NyuSample)), dtype=torch.uint8, device=dev)
+    M = torch.empty((B, 3, 3), dtype=torch.float32, device=dev)
+    cxyz = torch.empty((B, 3), dtype=torch.float32, device=dev)
+    cube32 = torch.empty((B, 3), dtype=torch.float32, device=dev)
+    status = torch.zeros(B, dtype=torch.int32, device=dev) if status is None else status
+    L.call("awr_detect_samples", L.ptr(centers), cb.data_ptr(), 3 if cb.dim() == 2 else 0, int(n_frames), idx.data_ptr(), B, int(dsize),
+           int(frame_shape[0]), int(frame_shape[1]), float(paras[0]), float(paras[1]), float(paras[2]), float(paras[3]), int(flip),
+           blocks.data_ptr(), L.ptr(M), L.ptr(cxyz), L.ptr(cube32), status.data_ptr(), L.stream())
+    return blocks, M, cxyz, cube32, status
+
+
+def unproject_device(jt_pred, center_xyz, M, cube, img_size, paras=ND.PARAS, flip=-1, n_valid=None, uvd_out=None, xyz_out=None, status=None):
+    """awr_joints_unproject: -> (uvd (B, J, 3), xyz (B, J, 3), status (B,)); rows >= n_valid of the outputs are left as they are."""
+    import torch
+    from . import _lib as L
+    B, J = int(jt_pred.shape[0]), int(jt_pred.shape[1])
+    n = B if n_valid is None else int(n_valid)
+    uvd = torch.empty_like(jt_pred) if uvd_out is None else uvd_out
+    xyz = torch.empty_like(jt_pred) if xyz_out is None else xyz_out
+    status = torch.zeros(B, dtype=torch.int32, device=jt_pred.device) if status is None else status
+    L.call("awr_joints_unproject", L.ptr(jt_pred), L.ptr(center_xyz), L.ptr(M), L.ptr(cube), B, J, n, float(img_size), float(paras[0]),
+           float(paras[1]), float(paras[2]), float(paras[3]), int(flip), L.ptr(uvd), L.ptr(xyz), status.data_ptr(), L.stream())
+    return uvd, xyz, status

@@ -1,0 +1,148 @@
+"""Predict hand joints from raw depth frames: no dataset index, no refined-centre file, no labels.
+
+    pred = Predictor(net, img_size=128, kernel_size=0.4, max_batch=64)
+    out = pred.predict(frames)              # (B, 480, 640) uint16 millimetres: numpy, host tensor or device tensor
+    out.xyz, out.uvd                        # (B, J, 3) camera millimetres / original-image uvd, on the device
+    pred.check()                            # synchronises; raises AwrError naming the first frame that could not be predicted
+
+Everything between the frames and the joints runs on the device, on the current stream, without a synchronisation: awr_detect (hand
+centre by iterated centre of mass) -> awr_detect_samples (crop blocks, crop matrices) -> awr_nyu_batch (crop + normalise) -> the
+inference plan and the single-pass head (InferEngine) -> awr_joints_unproject.  The host only issues launches.  There is no host
+fallback in this class: without a GPU it raises; `awr_amd.detect.detect` is the numpy statement of the detector for such a machine.
+"""
+import collections
+import types
+
+import numpy as np
+import torch
+
+from . import _lib as L
+from . import detect as D
+from . import nyu_data as ND
+
+Prediction = collections.namedtuple("Prediction", "xyz uvd center_xyz M status")
+
+
+class Predictor:
+    def __init__(self, net, img_size, kernel_size, cube=(300, 300, 300), paras=ND.PARAS, flip=-1, max_batch=1, frame_shape=(480, 640),
+                 seed="nearest", depth_range=D.DEPTH_RANGE, slab=D.SLAB, refine_iters=D.REFINE_ITERS, winograd=None, parity=False):
+        """net: an awr_amd network on the GPU with its weights loaded.  cube: the crop cube in mm.  paras = (fx, fy, u0, v0), flip: the camera.
+        max_batch: the static batch of the inference plan; smaller batches are padded, larger ones refused.  seed / depth_range / slab /
+        refine_iters: the detector (awr_amd.detect); with `centers_uvd` handed to predict() the seed is the given centre and refine_iters
+        still applies -- refine_iters=0 takes centres as they are, the dataset's behaviour.  winograd / parity: InferEngine's."""
+        if not torch.cuda.is_available():
+            raise L.AwrError("Predictor runs the detector, the crop, the network and the un-projection as HIP kernels and needs a GPU: none is "
+                             "visible -- awr_amd.detect.detect is the host statement of the detector")
+        from . import nyu_device as DV
+        from .trainer import InferEngine
+        if seed not in ("nearest", "range"):
+            raise ValueError("seed is \"nearest\" or \"range\" (pass centers_uvd to predict() for given centres), not %r" % (seed,))
+        if not 0 <= int(refine_iters) <= D.MAX_ITERS:
+            raise ValueError("refine_iters = %r is outside [0, %d]" % (refine_iters, D.MAX_ITERS))
+        if not float(depth_range[0]) <= float(depth_range[1]):
+            raise ValueError("depth_range needs zmin <= zmax")
+        self.S, self.B = int(img_size), int(max_batch)
+        self.fh, self.fw = int(frame_shape[0]), int(frame_shape[1])
+        self.paras, self.flip = tuple(float(p) for p in paras), int(flip)
+        self.seed, self.depth_range, self.slab, self.iters = seed, (float(depth_range[0]), float(depth_range[1])), float(slab), int(refine_iters)
+        dev = self.device = net.device
+        B = self.B
+        self.engine = InferEngine(net, B, self.S, kernel_size, winograd=winograd, parity=parity)
+        self.J = self.engine.J
+        # the predictor's own small frame store: the FrameStore layout, one row per image of a batch
+        self._frames = torch.empty((B, self.fh, self.fw), dtype=torch.uint16, device=dev)
+        self._frames.view(torch.int16).zero_()
+        self._stage = torch.empty((B, self.fh, self.fw), dtype=torch.uint16).pin_memory()
+        self._stage_free = None                  # event: the last upload from the staging buffer has been issued and has finished
+        self._store = types.SimpleNamespace(data=self._frames, ftype=0, fh=self.fh, fw=self.fw, n=B)
+        self._render = DV.Renderer(self._store, self.S, B)
+        self._idx = torch.arange(B, dtype=torch.int64, device=dev)
+        self._cube = torch.tensor([float(c) for c in cube], dtype=torch.float64, device=dev)
+        self._scratch = torch.empty(int(L.lib.awr_detect_scratch(B)) // 8, dtype=torch.int64, device=dev)
+        self._centers = torch.empty((B, 3), dtype=torch.float64, device=dev)
+        self._seed = torch.empty((B, 3), dtype=torch.float64, device=dev)
+        self._blocks = torch.empty((B, DV.BLOCK_BYTES), dtype=torch.uint8, device=dev)
+        self._cube32 = torch.empty((B, 3), dtype=torch.float32, device=dev)
+        self._img = torch.zeros((B, 1, self.S, self.S), dtype=torch.float32, device=dev)
+        self._last = None
+
+    def _upload(self, frames):
+        """(nb, fh, fw) uint16 -> rows [0, nb) of the frame store, without blocking"""
+        if isinstance(frames, np.ndarray):
+            if frames.dtype != np.uint16:
+                raise L.AwrError("frames must be uint16 millimetres (the sensor format; it makes the detector's sums exact), not %s" % frames.dtype)
+            frames = torch.from_numpy(np.ascontiguousarray(frames))
+        if not isinstance(frames, torch.Tensor) or frames.dtype != torch.uint16:
+            raise L.AwrError("frames must be a uint16 numpy array or tensor")
+        if frames.dim() != 3 or tuple(frames.shape[1:]) != (self.fh, self.fw):
+            raise L.AwrError("frames must be (B, %d, %d), got %s" % (self.fh, self.fw, tuple(frames.shape)))
+        nb = int(frames.shape[0])
+        if not 0 < nb <= self.B:
+            raise L.AwrError("a batch of %d frames does not fit the predictor's max_batch %d" % (nb, self.B))
+        if frames.is_cuda:
+            self._frames[:nb].copy_(frames, non_blocking=True)
+            return nb
+        if not frames.is_pinned():
+            # pageable memory -> the pinned staging buffer -> HBM.  The buffer is reused: wait for the previous upload FROM IT (a copy, not
+            # the pipeline: the launches behind it stay queued)
+            if self._stage_free is not None:
+                self._stage_free.synchronize()
+            self._stage[:nb].copy_(frames)
+            frames = self._stage[:nb]
+            self._frames[:nb].copy_(frames, non_blocking=True)
+            self._stage_free = torch.cuda.Event()
+            self._stage_free.record()
+        else:
+            self._frames[:nb].copy_(frames, non_blocking=True)
+        return nb
+
+    def predict(self, frames, centers_uvd=None, n_valid=None):
+        """-> Prediction(xyz (nb, J, 3), uvd (nb, J, 3), center_xyz (nb, 3), M (nb, 3, 3), status (nb,) int32), device tensors, nothing
+        synchronised.  centers_uvd (nb, 3): hand centres in original-image uvd (numpy or tensor) instead of the detector's seed.  n_valid:
+        frames of the batch that count (default: all of them); rows past it hold unspecified values.  status: awr_amd.detect's codes; a frame that is
+        not OK has NaN rows."""
+        nb = self._upload(frames)
+        nv = nb if n_valid is None else int(n_valid)
+        if not 0 < nv <= nb:
+            raise L.AwrError("n_valid = %d is outside [1, %d]" % (nv, nb))
+        dev, B, J, s = self.device, self.B, self.J, L.stream()
+        fx, fy, u0, v0 = self.paras
+        mode, seed = D.SEEDS[self.seed], None
+        if centers_uvd is not None:
+            c = centers_uvd if isinstance(centers_uvd, torch.Tensor) else torch.from_numpy(np.ascontiguousarray(centers_uvd, dtype=np.float64))
+            if tuple(c.shape) != (nb, 3):
+                raise L.AwrError("centers_uvd must be (%d, 3), got %s" % (nb, tuple(c.shape)))
+            self._seed[:nb].copy_(c, non_blocking=True)          # (converts to float64 on the way)
+            mode, seed = D.SEED_GIVEN, self._seed
+        M = torch.empty((B, 3, 3), dtype=torch.float32, device=dev)
+        cxyz = torch.empty((B, 3), dtype=torch.float32, device=dev)
+        status = torch.zeros(B, dtype=torch.int32, device=dev)
+        ustatus = torch.zeros(B, dtype=torch.int32, device=dev)
+        uvd = torch.empty((B, J, 3), dtype=torch.float32, device=dev)
+        xyz = torch.empty((B, J, 3), dtype=torch.float32, device=dev)
+        L.call("awr_detect", self._frames.data_ptr(), 0, B, self.fh, self.fw, self._idx.data_ptr(), nv, mode, L.ptr(seed), self.depth_range[0],
+               self.depth_range[1], self.slab, self._cube.data_ptr(), 0, fx, fy, self.iters, 0, self._scratch.data_ptr(),
+               self._centers.data_ptr(), status.data_ptr(), s)
+        L.call("awr_detect_samples", self._centers.data_ptr(), self._cube.data_ptr(), 0, B, self._idx.data_ptr(), nv, self.S, self.fh, self.fw,
+               fx, fy, u0, v0, self.flip, self._blocks.data_ptr(), L.ptr(M), L.ptr(cxyz), L.ptr(self._cube32), status.data_ptr(), s)
+        self._render(self._blocks[:nv], out=self._img[:nv])
+        if nv < B:
+            self._img[nv:].zero_()          # padding rows of the static plan: constant input, and no later stage reads their output
+        jt = self.engine(self._img)
+        L.call("awr_joints_unproject", L.ptr(jt), L.ptr(cxyz), L.ptr(M), L.ptr(self._cube32), B, J, nv, float(self.S), fx, fy, u0, v0, self.flip,
+               L.ptr(uvd), L.ptr(xyz), ustatus.data_ptr(), s)
+        self._last = (status, ustatus, nv)
+        return Prediction(xyz[:nb], uvd[:nb], cxyz[:nb], M[:nb], status[:nb])
+
+    def check(self):
+        """Synchronising: raise AwrError naming the first frame of the last batch that could not be predicted, and its status code."""
+        if self._last is None:
+            return
+        status, ustatus, nv = self._last
+        st, ust = status[:nv].tolist(), ustatus[:nv].tolist()
+        for b in range(nv):
+            if st[b] != D.OK:
+                raise L.AwrError("predict: frame %d of the batch: %s (status %d); its joints are NaN" % (b, D.STATUS_NAMES.get(st[b], "invalid"), st[b]))
+            if ust[b] != 0:
+                raise L.AwrError("predict: frame %d of the batch: its crop matrix is %s (un-projection status %d); its joints are NaN"
+                                 % (b, {1: "singular", 2: "not finite"}.get(ust[b], "invalid"), ust[b]))

@@ -778,6 +778,73 @@ int awr_eval_batch(const float* jt_pred, const float* jt_xyz_gt, const float* ce
                    int n_valid, float img_size, double fx, double fy, double u0, double v0, int flip, float* uvd_out, float* err_out,
                    int64_t row, int64_t capacity, double* acc, int* status, void* stream);
 
+/* Joints without labels: the first half of awr_eval_batch (the same device code: eval_tool.py:38-41 and uvd2xyz, util.py:13-20, in the
+ * precisions listed above) for callers that have a prediction and no ground truth -- awr_amd.predictor.Predictor.
+ *   jt_pred (B, J, 3) normalised uvd; center_xyz (B, 3), M (B, 3, 3), cube (B, 3) float32 as awr_detect_samples writes them.
+ *   Only rows [0, n_valid) of any argument are read or written.
+ *   uvd_out (B, J, 3)  original-image uvd: bit for bit what awr_eval_batch stores in its uvd_out
+ *   xyz_out (B, J, 3)  camera millimetres: evaluator.uvd2xyz(uvd_out, paras, flip) bit for bit
+ *   status  (B) int32  per frame AWR_EVAL_OK / _SINGULAR / _NONFINITE; a frame that is not OK gets NaN rows (a NaN matrix is how
+ *                      awr_detect_samples marks a frame it could not crop).
+ * One workgroup; nothing synchronises. */
+int awr_joints_unproject(const float* jt_pred, const float* center_xyz, const float* M, const float* cube, int B, int J, int n_valid,
+                         float img_size, double fx, double fy, double u0, double v0, int flip, float* uvd_out, float* xyz_out, int* status,
+                         void* stream);
+
+/* ------------------------------------------------------------------------------------------
+ * Hand detection on the device (csrc/awr_detect.hip): the crop centre of a raw depth frame by an iterated centre of
+ * mass, and from a centre everything awr_nyu_batch and awr_joints_unproject need -- so a frame without a dataset index, a refined
+ * centre file or labels goes to camera-space joints without a host round trip.  The numpy restatement is awr_amd/detect.py
+ * (detect, center_of_mass, sample_blocks); results are bit-identical to it.
+ *   frames: [n_frames][fh][fw] uint16 millimetres (the FrameStore layout; frame_type must be AWR_NYU_U16 -- float32 is refused);
+ *           frame (B) int64 addresses each image's frame.
+ * Centre of mass of a pixel set: n, sum of columns u, sum of rows v, sum of raw depths d as 64-bit INTEGERS, centre = (su / n, sv / n,
+ * sd / n) as three double divisions.  Integer sums do not depend on order: any split over workgroups and any order of the 64-bit integer
+ * atomics give numpy's int64 bits.  No floating-point atomic is involved.  A pixel with d = 0 never counts.
+ *   seed    AWR_DET_SEED_GIVEN    seed_uvd (B, 3) doubles
+ *           AWR_DET_SEED_RANGE    centre of mass of the pixels of the whole frame with zmin <= d <= zmax
+ *           AWR_DET_SEED_NEAREST  dmin = the smallest such d; centre of mass of the pixels with dmin <= d <= min(dmin + slab, zmax)
+ *   refine  `iters` times (0 ... AWR_DET_MAX_ITERS, no convergence test): window and depth range of the current centre by
+ *           nyu_data.center2bounds(centre, cube, (fx, fy)) (loader.py:181-188: IEEE double in that expression order, int() truncating),
+ *           clipped to the frame; centre of mass of the window's pixels with zstart <= d <= zend.
+ *   cube    doubles on the device: 3 (cube_stride 0) or B x 3 (cube_stride 3).
+ *   parts   workgroups per frame and pass: 0 = chosen from B and fh (about four per CU over the batch); a workgroup's share is whole
+ *           rows of the window, read with 16-byte loads between its unaligned ends.
+ *   scratch awr_detect_scratch(B) bytes, 8-byte aligned: one accumulator slot per frame and pass (the call initialises it).
+ * Outputs: center_uvd (B, 3) doubles; status (B) int32:
+ *   AWR_DET_OK
+ *   AWR_DET_EMPTY      some pass found no pixel: the centre is NaN, and stays NaN through the later passes, awr_detect_samples and
+ *                      awr_joints_unproject (NaN rows; never a fault, never a read outside the store)
+ *   AWR_DET_BAD_FRAME  frame[b] is outside [0, n_frames): nothing is read, the centre is NaN
+ * Each pass is one launch on `stream`; nothing synchronises.
+ * -----------------------------------------------------------------------------------------*/
+#define AWR_DET_OK 0
+#define AWR_DET_EMPTY 1
+#define AWR_DET_BAD_FRAME 2
+#define AWR_DET_BAD_WINDOW 3
+#define AWR_DET_SEED_GIVEN 0
+#define AWR_DET_SEED_RANGE 1
+#define AWR_DET_SEED_NEAREST 2
+#define AWR_DET_MAX_ITERS 8
+#define AWR_DET_MAX_BATCH 65535
+int64_t awr_detect_scratch(int B);        /* bytes; -1 for a B outside [1, AWR_DET_MAX_BATCH] */
+int awr_detect(const void* frames, int frame_type, int64_t n_frames, int fh, int fw, const int64_t* frame, int B, int seed_mode,
+               const double* seed_uvd, double zmin, double zmax, double slab, const double* cube, int cube_stride, double fx, double fy,
+               int iters, int parts, void* scratch, double* center_uvd, int* status, void* stream);
+/* Centres -> what the rest of the pipeline consumes, per frame:
+ *   samples     the awr_nyu_sample block nyu_device.set_crop + set_normalize write for a float64 centre (op = AWR_NYU_NONE, norm32 = 0),
+ *               field for field: window by center2bounds, rw / rh = int(w * scale), ox / oy = int((dsize - size) / 2.0), ifx / ify as
+ *               two divisions, the cube's depth range, normalize's lo / far / center_z / half
+ *   M           (3, 3) float32: nyu_data.center2transmat in double, stored as float32
+ *   center_xyz  (3) float32: evaluator.uvd2xyz of the float64 centre       cube_out (3) float32
+ * status (B) is read and updated (zero it, or hand over awr_detect's): a window set_crop refuses (it misses the frame or resizes to
+ * nothing) or a NaN centre sets AWR_DET_BAD_WINDOW on a frame that was AWR_DET_OK; a frame index outside [0, n_frames) sets
+ * AWR_DET_BAD_FRAME.  Such a frame gets a block that reads no pixel (frame 0, rw = rh = 0: awr_nyu_batch renders a constant background
+ * image) and a NaN matrix, which awr_joints_unproject turns into NaN rows. */
+int awr_detect_samples(const double* center_uvd, const double* cube, int cube_stride, int64_t n_frames, const int64_t* frame, int B, int dsize,
+                       int fh, int fw, double fx, double fy, double u0, double v0, int flip, awr_nyu_sample* samples, float* M,
+                       float* center_xyz, float* cube_out, int* status, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -1,0 +1,59 @@
+"""Joints from raw depth frames, no dataset needed:
+
+    python predict.py FRAMES.npy --load-model X.pth [--net resnet_18] [--set key=value ...]
+
+FRAMES.npy holds (n, h, w) uint16 depth frames in millimetres.  Writes pred_uvd.txt (original-image uvd, "%.3f", J * 3 columns: the format
+of the reference's results file, test.py:105-108) and pred_xyz.txt (camera millimetres) into --out (default: the current directory).
+`--set` overrides config entries as train.py does (img_size, kernel_size, cube, batch_size, jt_num, downsample, winograd ...)."""
+import argparse
+import os
+import sys
+
+sys.path.insert(0, os.path.dirname(os.path.abspath(__file__)))
+
+
+def main(argv=None):
+    ap = argparse.ArgumentParser(description=__doc__, formatter_class=argparse.RawDescriptionHelpFormatter)
+    ap.add_argument("frames")
+    ap.add_argument("--load-model", required=True)
+    ap.add_argument("--net", default=None)
+    ap.add_argument("--out", default=".")
+    ap.add_argument("--set", nargs="*", default=[], metavar="key=value")
+    args = ap.parse_args(argv)
+
+    import numpy as np
+    import torch
+    import awr_amd
+    from awr_amd import hourglass, resnet_deconv
+    from awr_amd.config import Config
+    from train import parse_overrides
+
+    over = parse_overrides(args.set)
+    if args.net:
+        over["net"] = args.net
+    cfg = Config(load_model=args.load_model, **over)
+    frames = np.load(args.frames, mmap_mode="r")
+    if "resnet" in cfg.net:
+        net = resnet_deconv.get_deconv_net(int(cfg.net.split("_")[1]), cfg.jt_num, cfg.downsample)
+    else:
+        net = hourglass.PoseNet(cfg.net, cfg.jt_num)
+    net.load_state_dict(torch.load(cfg.load_model, map_location="cpu", weights_only=False)["model"])
+    bs = min(cfg.batch_size, len(frames))
+    pred = awr_amd.Predictor(net.cuda(), cfg.img_size, cfg.kernel_size, cube=cfg.cube, max_batch=bs, frame_shape=frames.shape[1:],
+                             winograd=cfg.winograd, parity=cfg.parity_infer)
+    uvd, xyz = [], []
+    for lo in range(0, len(frames), bs):
+        out = pred.predict(np.array(frames[lo:lo + bs]))
+        uvd.append(out.uvd.cpu().numpy())
+        xyz.append(out.xyz.cpu().numpy())
+        try:
+            pred.check()
+        except awr_amd._lib.AwrError as e:
+            print("frames %d...: %s" % (lo, e), file=sys.stderr)
+    os.makedirs(args.out, exist_ok=True)
+    for name, rows in (("pred_uvd.txt", uvd), ("pred_xyz.txt", xyz)):
+        np.savetxt(os.path.join(args.out, name), np.concatenate(rows, 0).reshape(len(frames), cfg.jt_num * 3), fmt="%.3f")
+
+
+if __name__ == "__main__":
+    main()
