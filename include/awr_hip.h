@@ -156,7 +156,10 @@ int awr_unpack_wgrad(const float* packed, int d0, int d1, int T, int ld, float* 
 /* Batched forms of the two calls above: ONE launch repacks / scatters every layer of a network, one workgroup
  * per row (pack: packed row of T*ld floats; unpack: gradient row of d1*T floats).  The descriptor tables live
  * in DEVICE memory (built once per plan); `first` is the running ROW offset of each job (`rows` rows per pack
- * job, d0 rows per unpack job), `total_rows` their sum = the number of workgroups. */
+ * job, d0 rows per unpack job), `total_rows` their sum = the number of workgroups.
+ * LIMIT: T <= 255 in every job (the plans' largest is 16).  A row travels through an 8192-float LDS tile in chunks of
+ * (8192 / (T | 1)) & ~31 columns; from T = 256 on that is ZERO columns and the chunk loop of the kernel never ends.  The
+ * entry points cannot check it -- the table is in device memory -- so the caller that builds the table must. */
 typedef struct awr_pack_job {
     const float* src;
     float* dst;
@@ -176,7 +179,11 @@ typedef struct awr_unpack_job {
 /* Split image of a packed weight buffer of n fp32 elements (n % 32 == 0) for the 6- / 9-product modes of awr_conv_gemm:
  * every 32-element K-slice becomes 192 bytes [h: 32 bf16 | m: 32 bf16 | l: 32 bf16] with x == h + m + l exactly
  * (truncating 8+8+8-bit cut of the fp32 significand).  Weights are split once per optimiser step instead of once per
- * workgroup that stages them. */
+ * workgroup that stages them.
+ * DOMAIN of "exactly": x finite and a multiple of 2^-133, the smallest bf16 denormal -- in particular x == 0 and every
+ * |x| >= 2^-110 (7.7e-34), FLT_MIN included (smaller values whose lowest set bit is 2^-133 or above are exact too).  Below that a residual x - h (or x - h - m) is an fp32 denormal whose bits
+ * under 2^-133 no bf16 holds: the pieces then sum to x truncated toward zero to a multiple of 2^-133 (an fp32 denormal
+ * below 2^-133 splits into three zeros).  No weight is that small; nothing is done about it. */
 int awr_split_weight(const float* packed, void* split, int64_t n, void* stream);
 int awr_pack_weights_batched(const awr_pack_job* jobs_dev, int njobs, int64_t total_rows, void* stream);
 int awr_unpack_wgrads_batched(const awr_unpack_job* jobs_dev, int njobs, int64_t total_rows, void* stream);
