@@ -190,6 +190,9 @@ _SIGS = {
     "awr_head_forward_nhwc": ([_P, _I, _P, _I, _I, _I, _I, _F, _P, _P, _P, _P], C.c_int),
     "awr_head_loss_step_nhwc": ([_P, _I, _P, _P, _I, _I, _I, _I, _F, _F, _F, _F, _P, _P, _P, _P, _P, _P, _P], C.c_int),
     "awr_head_eval_nhwc": ([_P, _I, _P, _P, _I, _I, _I, _I, _I, _F, _F, _F, _F, _P, _P, _P, _P, _P], C.c_int),
+    "awr_head_confidence_nhwc": ([_P, _I, _P, _P, _P, _I, _I, _I, _I, _F, _P, _P, _P], C.c_int),
+    "awr_head_confidence": ([_P, _P, _P, _P, _I, _I, _I, _I, _F, _P, _P], C.c_int),
+    "awr_confidence_fields": ([_P, _P, _P, _P, _P, _I, _I, _I, _P, _P, _P, _P], C.c_int),
     "awr_plan_tensor": ([_P, _I, C.POINTER(C.c_char_p), C.POINTER(_I), _PP, _PP, C.POINTER(_I), _PP, _PP], C.c_int),
     "awr_plan_set_streams": ([_P, _I, _I], C.c_int),
     "awr_stream_pool_info": ([C.POINTER(C.c_int), C.POINTER(C.c_int)], C.c_int),

@@ -54,6 +54,18 @@ __device__ __forceinline__ Px4 load_px4(const float* __restrict__ img, int b, in
 
 __device__ __forceinline__ float comp(const float4& v, int i) { return i == 0 ? v.x : i == 1 ? v.y : i == 2 ? v.z : v.w; }
 
+// exp(x) for x <= 0 (softmax terms after the max subtraction): two-term range reduction with explicit FMAs (x log2 e = n + r,
+// |r| <= 1/2, log2 e split into a high and a low part so that r keeps full precision for |x| up to several hundred), the hardware
+// exp2 on r (1 ulp there) and an exact scaling by 2^n -- 7 instructions against ~18 for the library expf (which also guards overflow
+// and positive arguments), ~2 ulp.  The NHWC kernels are VALU-bound (ISA count: ~300 instructions per (pixel, joint)), not HBM-bound.
+__device__ __forceinline__ float exp_nonpos(float x) {
+    const float L2E_HI = 1.44269502162933349609375f, L2E_LO = 1.925963033500011e-08f;
+    const float n = rintf(x * L2E_HI);
+    float r = __builtin_fmaf(x, L2E_HI, -n);
+    r = __builtin_fmaf(x, L2E_LO, r);
+    return ldexpf(__builtin_amdgcn_exp2f(r), (int)n);
+}
+
 // ------------------------------------------------------------------------------------------
 // head forward: one workgroup per (image, joint); online softmax over all P pixels.
 // ------------------------------------------------------------------------------------------
@@ -132,6 +144,54 @@ __global__ __launch_bounds__(256) void head_fwd_kernel(const float* __restrict__
             stat[2 * bj] = t.m;
             stat[2 * bj + 1] = t.s;
         }
+    }
+}
+
+// ------------------------------------------------------------------------------------------
+// head confidence: a second pass over the map of (image, joint) with the joint and the softmax (max, sum) known.  With
+// w_p = exp(30 h_p - max) / sum (the aggregation weights of util/feature_tool.py:57-60) and vote_p the summand of :63,
+//   conf = sum_p w_p h_p,    var_c = sum_p w_p (vote_c,p - jt_c)^2      ->  out[b, j] = (conf, var_u, var_v, var_d)
+// Two-pass on purpose: the scatter about the joint the head WROTE is a sum of non-negative terms (no E[v^2] - E[v]^2 cancellation).
+// One workgroup per (image, joint) like head_fwd_kernel; per-thread sums in pixel order, xor-shuffle tree, waves 0..3 in order.
+// ------------------------------------------------------------------------------------------
+__global__ __launch_bounds__(256) void head_conf_kernel(const float* __restrict__ offset, const float* __restrict__ img,
+                                                        const float* __restrict__ jt, const float* __restrict__ stat, int J, int F, int H,
+                                                        float ks, float* __restrict__ conf) {
+    const int bj = blockIdx.x, b = bj / J, j = bj - b * J;
+    const int P = F * F;
+    const float* vec = offset + ((int64_t)b * 4 * J + 3 * j) * P;
+    const float* ht = offset + ((int64_t)b * 4 * J + 3 * J + j) * P;
+    const float mx = stat[2 * bj], inv_s = 1.0f / stat[2 * bj + 1];
+    const float o0 = jt[bj * 3], o1 = jt[bj * 3 + 1], o2 = jt[bj * 3 + 2];
+    float c[4] = {0.f, 0.f, 0.f, 0.f};
+    for (int p0 = threadIdx.x * 4; p0 < P; p0 += 256 * 4) {
+        const Px4 px = load_px4(img, b, p0, F, H);
+        const float4 h4 = ld4(ht + p0), v0 = ld4(vec + p0), v1 = ld4(vec + P + p0), v2 = ld4(vec + 2 * P + p0);
+#pragma unroll
+        for (int i = 0; i < 4; ++i) {
+            const float mk = px.d[i] < kDepthBg ? 1.f : 0.f;
+            const float h = comp(h4, i) * mk;
+            const float w = exp_nonpos(h * kBeta - mx) * inv_s;
+            const float dis = ks - h * ks;
+            const float e0 = (comp(v0, i) * mk * dis + px.cx[i]) - o0;
+            const float e1 = (comp(v1, i) * mk * dis + px.cy) - o1;
+            const float e2 = (comp(v2, i) * mk * dis + px.d[i]) - o2;
+            c[0] += w * h;
+            c[1] += w * (e0 * e0);
+            c[2] += w * (e1 * e1);
+            c[3] += w * (e2 * e2);
+        }
+    }
+    __shared__ float part[4][4];
+#pragma unroll
+    for (int k = 0; k < 4; ++k) {
+        c[k] = wave_sum(c[k]);
+        if ((threadIdx.x & 63) == 0) part[threadIdx.x >> 6][k] = c[k];
+    }
+    __syncthreads();
+    if (threadIdx.x < 4) {
+        const int k = threadIdx.x;
+        conf[(int64_t)bj * 4 + k] = ((part[0][k] + part[1][k]) + part[2][k]) + part[3][k];
     }
 }
 
@@ -332,18 +392,6 @@ __global__ __launch_bounds__(256) void huber_kernel(const float* __restrict__ x,
 // nothing to the accumulator; their softmax partials are written like everyone's.
 constexpr int TPX = 64;      // pixels per tile
 
-// exp(x) for x <= 0 (softmax terms after the max subtraction): two-term range reduction with explicit FMAs (x log2 e = n + r,
-// |r| <= 1/2, log2 e split into a high and a low part so that r keeps full precision for |x| up to several hundred), the hardware
-// exp2 on r (1 ulp there) and an exact scaling by 2^n -- 7 instructions against ~18 for the library expf (which also guards overflow
-// and positive arguments), ~2 ulp.  The NHWC kernels are VALU-bound (ISA count: ~300 instructions per (pixel, joint)), not HBM-bound.
-__device__ __forceinline__ float exp_nonpos(float x) {
-    const float L2E_HI = 1.44269502162933349609375f, L2E_LO = 1.925963033500011e-08f;
-    const float n = rintf(x * L2E_HI);
-    float r = __builtin_fmaf(x, L2E_HI, -n);
-    r = __builtin_fmaf(x, L2E_LO, r);
-    return ldexpf(__builtin_amdgcn_exp2f(r), (int)n);
-}
-
 struct nhwc_args {
     const float* pred;       // (B, P, Cp)
     const float* img;        // (B, 1, H, H)
@@ -536,6 +584,139 @@ __global__ __launch_bounds__(256) void dense_nhwc_kernel(const nhwc_args a) {
         __syncthreads();
     }
     if ((MODE & 10) && counted) block_accumulate((double)lsum, a.lscale, a.acc, a.fixed_point);
+}
+
+// The confidence pass on the NHWC map: dense_nhwc_kernel's tile staging (a workgroup walks its run of 64-pixel tiles, tile t + 1 requested
+// while tile t is worked on, the tile parked in LDS, thread (pixel slot, joint) reads its four values there) around head_conf_kernel's
+// arithmetic.  A sibling of dense_nhwc_kernel and not one more MODE bit of it: a bit changed the register allocation of the existing
+// instantiations.  Reads a.pred / img / jt / stat, writes four plain sums per (image, chunk, joint) into a.partial;
+// lanes and waves fold in the order the softmax partials use, with a plain add.  Read-only: nothing is streamed out.
+template <int JS, bool POW2>
+__global__ __launch_bounds__(256) void conf_nhwc_kernel(const nhwc_args a) {
+    constexpr int NS = 256 / JS;          // pixel slots per pass
+    constexpr int PPT = TPX / NS;         // pixels per thread per tile
+    constexpr int NLMAX = JS / 4;         // float4 loads per thread per tile
+    extern __shared__ __attribute__((aligned(16))) float smem[];
+    const int pitch = a.Cp + 4;
+    float* const tile = smem;                    // [TPX][pitch]
+    float* const dtile = smem + TPX * pitch;     // [TPX] depth of the tile's pixels
+    const int tid = threadIdx.x, j = tid % JS, slot = tid / JS;
+    const int b = blockIdx.y, chunk = blockIdx.x, J = a.J, F = a.F, P = F * F;
+    const bool active = j < J;
+    const int rs = a.H / F;
+    const int NL = a.Cp >> 4, C4 = a.Cp >> 2;
+    const int tile0 = chunk * a.tiles_per_wg;
+    int ntile = P / TPX - tile0;
+    if (ntile > a.tiles_per_wg) ntile = a.tiles_per_wg;
+    const float* src = a.pred + ((int64_t)b * P + (int64_t)tile0 * TPX) * a.Cp;
+    const float* dimg = a.img + (int64_t)b * a.H * a.H;
+    float mx = 0.f, inv_s = 0.f, o0 = 0.f, o1 = 0.f, o2 = 0.f;
+    if (active) {
+        const int bj = b * J + j;
+        mx = a.stat[2 * bj]; inv_s = 1.0f / a.stat[2 * bj + 1];
+        o0 = a.jt[bj * 3]; o1 = a.jt[bj * 3 + 1]; o2 = a.jt[bj * 3 + 2];
+    }
+    float cf[4] = {0.f, 0.f, 0.f, 0.f};          // sum w h, sum w e_c^2
+    const float inv_f = 1.0f / (float)F;
+    float4 r[NLMAX];
+    float rd = 0.f;
+    auto request = [&](int t) {                  // tile t of this workgroup: 64 * Cp contiguous floats + the 64 depth samples
+        const float* s = src + (int64_t)t * TPX * a.Cp;
+#pragma unroll
+        for (int i = 0; i < NLMAX; ++i)
+            if (i < NL) r[i] = ld4(s + ((int64_t)(tid + 256 * i) << 2));
+        if (tid < TPX) {
+            const int p = (tile0 + t) * TPX + tid, y = p / F, x = p - y * F;
+            rd = dimg[(int64_t)y * rs * a.H + x * rs];
+        }
+    };
+    request(0);
+    for (int t = 0; t < ntile; ++t) {
+#pragma unroll
+        for (int i = 0; i < NLMAX; ++i)
+            if (i < NL) {
+                const int e = tid + 256 * i, px = e / C4, c4 = e - px * C4;
+                st4(tile + px * pitch + 4 * c4, r[i]);
+            }
+        if (tid < TPX) dtile[tid] = rd;
+        __syncthreads();
+        if (t + 1 < ntile) request(t + 1);
+        if (active) {
+#pragma unroll
+            for (int k = 0; k < PPT; ++k) {
+                const int px = slot + NS * k;
+                const int p = (tile0 + t) * TPX + px;
+                int x, y;
+                float cx, cy;
+                if (POW2) {            // (see dense_nhwc_kernel: bit for bit grid_coord)
+                    y = p >> a.lgF; x = p & (F - 1);
+                    cx = (float)(2 * x + 1) * inv_f - 1.0f; cy = (float)(2 * y + 1) * inv_f - 1.0f;
+                } else {
+                    y = p / F; x = p - y * F;
+                    cx = grid_coord(x, F); cy = grid_coord(y, F);
+                }
+                const float d = dtile[px];
+                const float* row = tile + px * pitch;
+                const float v0 = row[3 * j], v1 = row[3 * j + 1], v2 = row[3 * j + 2], hraw = row[3 * J + j];
+                const float mk = d < kDepthBg ? 1.f : 0.f;
+                const float h = hraw * mk;
+                const float dis = ks_dis(a.ks, h);
+                const float w = exp_nonpos(h * kBeta - mx) * inv_s;      // 30 h <= max: the argument is never positive
+                const float e0 = (v0 * mk * dis + cx) - o0, e1 = (v1 * mk * dis + cy) - o1, e2 = (v2 * mk * dis + d) - o2;
+                cf[0] += w * h;
+                cf[1] += w * (e0 * e0);
+                cf[2] += w * (e1 * e1);
+                cf[3] += w * (e2 * e2);
+            }
+        }
+        __syncthreads();
+    }
+#pragma unroll
+    for (int k = 0; k < 4; ++k) {
+#pragma unroll
+        for (int o = 32; o >= JS; o >>= 1) cf[k] += __shfl_xor(cf[k], o, 64);
+    }
+    float4* part = reinterpret_cast<float4*>(smem);      // [4][JS] (the tile is dead)
+    const int lane = tid & 63, wave = tid >> 6;
+    if (lane < JS) part[wave * JS + lane] = make_float4(cf[0], cf[1], cf[2], cf[3]);
+    __syncthreads();
+    if (tid < JS && tid < J) {
+        const float4 p0 = part[tid], p1 = part[JS + tid], p2 = part[2 * JS + tid], p3 = part[3 * JS + tid];
+        float4 t;
+        if (JS < 64) {
+            t.x = ((p0.x + p1.x) + p2.x) + p3.x; t.y = ((p0.y + p1.y) + p2.y) + p3.y;
+            t.z = ((p0.z + p1.z) + p2.z) + p3.z; t.w = ((p0.w + p1.w) + p2.w) + p3.w;
+        } else {
+            t.x = (p0.x + p1.x) + (p2.x + p3.x); t.y = (p0.y + p1.y) + (p2.y + p3.y);
+            t.z = (p0.z + p1.z) + (p2.z + p3.z); t.w = (p0.w + p1.w) + (p2.w + p3.w);
+        }
+        st4(a.partial + (((int64_t)b * gridDim.x + chunk) * J + tid) * 4, t);
+    }
+}
+
+// merge the per-chunk confidence partials in chunk order: thread (image, joint, component)
+__global__ __launch_bounds__(256) void conf_finish_kernel(const float* __restrict__ partial, int chunks, int J, int BJ, float* __restrict__ conf) {
+    const int e = blockIdx.x * 256 + threadIdx.x;
+    if (e >= BJ * 4) return;
+    const int i = e >> 2, k = e & 3, b = i / J, j = i - b * J;
+    float t = 0.f;
+    for (int c = 0; c < chunks; ++c) t += partial[(((int64_t)b * chunks + c) * J + j) * 4 + k];
+    conf[e] = t;
+}
+
+// what a caller reads next to a joint (awr_confidence_fields): conf, peak = max / 30, spread in nominal millimetres; NaN rows for frames
+// whose detection or un-projection status is not zero, like their joints
+__global__ __launch_bounds__(256) void conf_fields_kernel(const float* __restrict__ conf4, const float* __restrict__ stat, const float* __restrict__ cube,
+                                                          const int* __restrict__ status, const int* __restrict__ ustatus, int J, int n,
+                                                          float* __restrict__ conf, float* __restrict__ peak, float* __restrict__ spread) {
+    const int i = blockIdx.x * 256 + threadIdx.x;
+    if (i >= n) return;
+    const int b = i / J;
+    float c = conf4[4 * i], pk = stat[2 * i] / kBeta, sp;
+    const float hx = cube[3 * b] * 0.5f, hy = cube[3 * b + 1] * 0.5f, hz = cube[3 * b + 2] * 0.5f;
+    sp = sqrtf((conf4[4 * i + 1] * (hx * hx) + conf4[4 * i + 2] * (hy * hy)) + conf4[4 * i + 3] * (hz * hz));
+    if ((status && status[b] != 0) || (ustatus && ustatus[b] != 0)) c = pk = sp = __builtin_nanf("");
+    conf[i] = c; peak[i] = pk; spread[i] = sp;
 }
 
 // merge the per-chunk softmax partials -> joints (B, J, 3) + (max, sum) for the backward; optionally the coordinate Huber loss
@@ -838,6 +1019,51 @@ int awr_head_eval_nhwc(const float* pred, int Cp, const float* img, const float*
     hipLaunchKernelGGL(head_finish_kernel, dim3((B * J + 7) / 8), dim3(256), 0, st, scratch, chunks, J, B * J, n_valid, jt_gt, delta, 0.f,
                        (double)coord_weight / nc, jt, stat, nullptr, coord ? acc : nullptr, fixed);
     return check_launch("head_finish_kernel");
+}
+
+int awr_head_confidence_nhwc(const float* pred, int Cp, const float* img, const float* jt, const float* stat, int B, int J, int F, int H, float ks,
+                             float* scratch, float* conf, void* stream) {
+    AWR_REQUIRE(pred && img && jt && stat && scratch && conf, "head_confidence_nhwc: null pointer");
+    int chunks, per;
+    if (int e = nhwc_geometry(B, J, F, H, Cp, &chunks, &per)) return e;
+    nhwc_args a;
+    memset(&a, 0, sizeof a);
+    a.pred = pred; a.img = img; a.jt = jt; a.stat = stat; a.partial = scratch;
+    a.J = J; a.F = F; a.H = H; a.Cp = Cp; a.tiles_per_wg = per; a.ks = ks; a.lgF = log2_exact(F);
+    hipStream_t st = as_stream(stream);
+    const dim3 grid((unsigned)chunks, (unsigned)B);
+    const size_t lds = (size_t)(TPX * (Cp + 4) + TPX) * sizeof(float);
+#define AWR_CONF_LAUNCH(js)                                                                                      \
+    do {                                                                                                          \
+        if (a.lgF >= 0) hipLaunchKernelGGL((conf_nhwc_kernel<js, true>), grid, dim3(256), lds, st, a);            \
+        else hipLaunchKernelGGL((conf_nhwc_kernel<js, false>), grid, dim3(256), lds, st, a);                      \
+    } while (0)
+    if (J <= 16) AWR_CONF_LAUNCH(16);
+    else if (J <= 32) AWR_CONF_LAUNCH(32);
+    else AWR_CONF_LAUNCH(64);
+#undef AWR_CONF_LAUNCH
+    if (int e = check_launch("conf_nhwc_kernel")) return e;
+    hipLaunchKernelGGL(conf_finish_kernel, dim3((B * J * 4 + 255) / 256), dim3(256), 0, st, scratch, chunks, J, B * J, conf);
+    return check_launch("conf_finish_kernel");
+}
+
+int awr_head_confidence(const float* offset, const float* img, const float* jt, const float* stat, int B, int J, int F, int H, float ks,
+                        float* conf, void* stream) {
+    if (int e = check_head_dims(B, J, F, H)) return e;
+    AWR_REQUIRE(offset && img && jt && stat && conf, "head_confidence: null pointer");
+    hipLaunchKernelGGL(head_conf_kernel, dim3(B * J), dim3(256), 0, as_stream(stream), offset, img, jt, stat, J, F, H, ks, conf);
+    return check_launch("head_conf_kernel");
+}
+
+int awr_confidence_fields(const float* conf4, const float* stat, const float* cube, const int* status, const int* ustatus, int B, int J, int n_valid,
+                          float* conf, float* peak, float* spread_mm, void* stream) {
+    AWR_REQUIRE(conf4 && stat && cube && conf && peak && spread_mm, "confidence_fields: null pointer");
+    AWR_REQUIRE(B > 0 && J > 0 && n_valid >= 0 && n_valid <= B, "confidence_fields: bad sizes (B = %d, J = %d, n_valid = %d)", B, J, n_valid);
+    if (n_valid == 0) return AWR_OK;
+    const int n = n_valid * J;
+    hipLaunchKernelGGL(conf_fields_kernel, dim3((n + 255) / 256), dim3(256), 0, as_stream(stream), conf4, stat, cube, status, ustatus, J, n, conf, peak,
+                       spread_mm);
+    return check_launch("conf_fields_kernel");
 }
 
 int awr_huber(const float* x, const float* y, int64_t n, float delta, float weight, double* acc, float* gx, int accumulate,

@@ -57,3 +57,19 @@ class FeatureModule:
     def offset2joint_softmax(self, offset, img, kernel_size):
         """Dense map (B,4J,F,F) + depth -> joints (B,J,3); feature_tool.py:41-65."""
         return _Offset2Joint.apply(offset, img, kernel_size)
+
+    def joint_confidence(self, offset, img, kernel_size):
+        """Dense map (B,4J,F,F) + depth -> (B,J,4) = [conf, var_u, var_v, var_d] per joint, normalised crop units: the expected closeness
+        under the softmax weights of feature_tool.py:57-60 and the weighted scatter of the per-pixel votes (the summand of :63) about the
+        joint offset2joint_softmax returns (include/awr_hip.h: awr_head_confidence).  No autograd."""
+        B, C4, F, F2 = offset.shape
+        if C4 % 4 or F != F2:
+            raise L.AwrError("offset must be (B,4J,F,F); got %s" % (tuple(offset.shape),))
+        J, H = C4 // 4, img.shape[-1]
+        off, im = _prep(offset), _prep(img)
+        jt = torch.empty(B, J, 3, device=off.device, dtype=torch.float32)
+        stat = torch.empty(B, J, 2, device=off.device, dtype=torch.float32)
+        conf = torch.empty(B, J, 4, device=off.device, dtype=torch.float32)
+        L.call("awr_head_forward", L.ptr(off), L.ptr(im), B, J, F, H, float(kernel_size), L.ptr(jt), L.ptr(stat), L.stream())
+        L.call("awr_head_confidence", L.ptr(off), L.ptr(im), L.ptr(jt), L.ptr(stat), B, J, F, H, float(kernel_size), L.ptr(conf), L.stream())
+        return conf

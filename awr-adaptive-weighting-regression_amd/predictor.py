@@ -4,6 +4,7 @@
     out = pred.predict(frames)              # (B, 480, 640) uint16 millimetres: numpy, host tensor or device tensor
     out.xyz, out.uvd                        # (B, J, 3) camera millimetres / original-image uvd, on the device
     pred.check()                            # synchronises; raises AwrError naming the first frame that could not be predicted
+    Predictor(..., confidence=True)         # out additionally carries conf, peak, spread_mm (B, J): how sure each joint is
 
 Everything between the frames and the joints runs on the device, on the current stream, without a synchronisation: awr_detect (hand
 centre by iterated centre of mass) -> awr_detect_samples (crop blocks, crop matrices) -> awr_nyu_batch (crop + normalise) -> the
@@ -21,15 +22,24 @@ from . import detect as D
 from . import nyu_data as ND
 
 Prediction = collections.namedtuple("Prediction", "xyz uvd center_xyz M status")
+ConfidentPrediction = collections.namedtuple("ConfidentPrediction", Prediction._fields + ("conf", "peak", "spread_mm"))
 
 
 class Predictor:
     def __init__(self, net, img_size, kernel_size, cube=(300, 300, 300), paras=ND.PARAS, flip=-1, max_batch=1, frame_shape=(480, 640),
-                 seed="nearest", depth_range=D.DEPTH_RANGE, slab=D.SLAB, refine_iters=D.REFINE_ITERS, winograd=None, parity=False):
+                 seed="nearest", depth_range=D.DEPTH_RANGE, slab=D.SLAB, refine_iters=D.REFINE_ITERS, winograd=None, parity=False, confidence=False):
         """net: an awr_amd network on the GPU with its weights loaded.  cube: the crop cube in mm.  paras = (fx, fy, u0, v0), flip: the camera.
         max_batch: the static batch of the inference plan; smaller batches are padded, larger ones refused.  seed / depth_range / slab /
         refine_iters: the detector (awr_amd.detect); with `centers_uvd` handed to predict() the seed is the given centre and refine_iters
-        still applies -- refine_iters=0 takes centres as they are, the dataset's behaviour.  winograd / parity: InferEngine's."""
+        still applies -- refine_iters=0 takes centres as they are, the dataset's behaviour.  winograd / parity: InferEngine's.
+        confidence: False -- predict() returns the five-field Prediction | True -- a ConfidentPrediction, the same five fields and per joint
+        conf (the expected closeness under the head's aggregation weights, in [0, 1] for a trained map), peak (the largest masked heat value)
+        and spread_mm = sqrt(var_u (cube_x / 2)^2 + var_v (cube_y / 2)^2 + var_d (cube_z / 2)^2), the scatter of the per-pixel votes about the
+        joint in NOMINAL millimetres: the crop maps the cube onto [-1, 1] by construction, so half a cube edge is one normalised unit (exact
+        in depth, and in the image plane as far as the crop's pinhole scaling is).  One more pass over the dense map and one small launch."""
+        if not isinstance(confidence, bool):
+            raise TypeError("confidence is True or False, not %r" % (confidence,))
+        self.confidence = confidence
         if not torch.cuda.is_available():
             raise L.AwrError("Predictor runs the detector, the crop, the network and the un-projection as HIP kernels and needs a GPU: none is "
                              "visible -- awr_amd.detect.detect is the host statement of the detector")
@@ -47,7 +57,7 @@ class Predictor:
         self.seed, self.depth_range, self.slab, self.iters = seed, (float(depth_range[0]), float(depth_range[1])), float(slab), int(refine_iters)
         dev = self.device = net.device
         B = self.B
-        self.engine = InferEngine(net, B, self.S, kernel_size, winograd=winograd, parity=parity)
+        self.engine = InferEngine(net, B, self.S, kernel_size, winograd=winograd, parity=parity, confidence=confidence)
         self.J = self.engine.J
         # the predictor's own small frame store: the FrameStore layout, one row per image of a batch
         self._frames = torch.empty((B, self.fh, self.fw), dtype=torch.uint16, device=dev)
@@ -98,9 +108,9 @@ class Predictor:
 
     def predict(self, frames, centers_uvd=None, n_valid=None):
         """-> Prediction(xyz (nb, J, 3), uvd (nb, J, 3), center_xyz (nb, 3), M (nb, 3, 3), status (nb,) int32), device tensors, nothing
-        synchronised.  centers_uvd (nb, 3): hand centres in original-image uvd (numpy or tensor) instead of the detector's seed.  n_valid:
+        synchronised; with confidence=True a ConfidentPrediction: these and conf, peak, spread_mm (nb, J).  centers_uvd (nb, 3): hand centres in original-image uvd (numpy or tensor) instead of the detector's seed.  n_valid:
         frames of the batch that count (default: all of them); rows past it hold unspecified values.  status: awr_amd.detect's codes; a frame that is
-        not OK has NaN rows."""
+        not OK has NaN rows (of conf / peak / spread_mm too)."""
         nb = self._upload(frames)
         nv = nb if n_valid is None else int(n_valid)
         if not 0 < nv <= nb:
@@ -132,6 +142,11 @@ class Predictor:
         L.call("awr_joints_unproject", L.ptr(jt), L.ptr(cxyz), L.ptr(M), L.ptr(self._cube32), B, J, nv, float(self.S), fx, fy, u0, v0, self.flip,
                L.ptr(uvd), L.ptr(xyz), ustatus.data_ptr(), s)
         self._last = (status, ustatus, nv)
+        if self.confidence:
+            fields = torch.empty((3, B, J), dtype=torch.float32, device=dev)
+            L.call("awr_confidence_fields", L.ptr(self.engine.conf), L.ptr(self.engine.stat), L.ptr(self._cube32), status.data_ptr(), ustatus.data_ptr(),
+                   B, J, nv, L.ptr(fields[0]), L.ptr(fields[1]), L.ptr(fields[2]), s)
+            return ConfidentPrediction(xyz[:nb], uvd[:nb], cxyz[:nb], M[:nb], status[:nb], fields[0, :nb], fields[1, :nb], fields[2, :nb])
         return Prediction(xyz[:nb], uvd[:nb], cxyz[:nb], M[:nb], status[:nb])
 
     def check(self):

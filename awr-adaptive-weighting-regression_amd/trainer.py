@@ -517,8 +517,10 @@ class InferEngine(_WinogradAuto):
     """test.py:67-86 without the per-sample host loop: img -> dense map -> joints, eval-mode BN; with `loss_weights` also the
     validation loss of test.py:73-88, from the same pass over the dense map (awr_head_eval_nhwc)."""
 
+    confidence, stat, conf = False, None, None          # an engine without confidence=True: no statistics buffer, stat = NULL in every head launch
+
     def __init__(self, net, batch_size, img_size, kernel_size, use_graph=False, autotune=True, parity=False, winograd=None,
-                 loss_weights=None, loss_stages="last", nhwc_boundary=None):
+                 loss_weights=None, loss_stages="last", nhwc_boundary=None, confidence=False):
         """loss_weights: None (default: joints only, nothing about the engine changes) | (coord_weight, dense_weight) -- a call that is handed
         the ground-truth joints adds coord_weight * Huber(joints) + dense_weight * Huber(dense map - GT map) of its batch (test.py:73-86) to a
         device accumulator; `loss_means()` reads it.  loss_stages: "last" -- the stage TrainEngine supervises, what the [train loss] lines
@@ -528,7 +530,13 @@ class InferEngine(_WinogradAuto):
         about the last digits of the joints, not about the last few per cent of throughput.
         winograd: None (the process-wide mode, awr_amd.set_conv_winograd) | False | True -- the eligible stride-1 3x3 convolutions of the eval plan as
         Winograd F(2x2, 3x3) with the folded BatchNorm / residual add in its epilogue (Hourglass: instead of the fused conv2 + conv3 launch) | "auto" --
-        "direct" or "forward", whichever the first call times faster (winograd_auto.py; `winograd_mode`, `winograd_timings`)."""
+        "direct" or "forward", whichever the first call times faster (winograd_auto.py; `winograd_mode`, `winograd_timings`).
+        confidence: False (default: the launches and stat = NULL of an engine without it) | True -- the head launch also writes its softmax
+        statistics and a second, read-only pass over the last stage's map (awr_head_confidence_nhwc / awr_head_confidence)
+        follows it: after a call `conf` (B, J, 4) = [conf, var_u, var_v, var_d] and `peak` (B, J) are valid until the next call."""
+        if not isinstance(confidence, bool):
+            raise TypeError("confidence is True or False, not %r" % (confidence,))
+        self.confidence = confidence
         self.net, self.B, self.H, self.ks = net, batch_size, img_size, float(kernel_size)
         self.parity = bool(parity)
         if self.parity and (int(L.lib.awr_get_gemm_products()) != 1 or int(L.lib.awr_get_gemm_staging()) == 0):
@@ -567,7 +575,17 @@ class InferEngine(_WinogradAuto):
         self.winograd_mode = WA.mode_name(self.plan.winograd, training=False) if self.plan.n_winograd else "direct"
         self._autotune, self._compiled = bool(autotune), False
         self.jt = torch.zeros(batch_size, self.J, 3, device=net.device)
+        if confidence:
+            self.stat = torch.zeros(batch_size, self.J, 2, device=net.device)
+            self.conf = torch.zeros(batch_size, self.J, 4, device=net.device)
         self.use_graph, self.graph = use_graph, None
+
+    @property
+    def peak(self):
+        """(B, J): the largest masked heat value of each joint's map -- the head's softmax max over 30 (needs confidence=True)."""
+        if self.stat is None:
+            raise L.AwrError("InferEngine was built without confidence=True: there are no softmax statistics to read the peak from")
+        return self.stat[..., 0] / 30.0
 
     def _attach(self, plan):
         self.plan = plan
@@ -594,13 +612,25 @@ class InferEngine(_WinogradAuto):
             plan.set_nhwc_boundary(self.nhwc)
         plan.run_forward()
         if (self._lw is not None) if loss is None else loss:
-            return self._head_and_loss(self.B if n_valid is None else n_valid)
-        if self.nhwc:
+            self._head_and_loss(self.B if n_valid is None else n_valid)
+        elif self.nhwc:
             L.call("awr_head_forward_nhwc", self._pred, self._cp, L.ptr(plan.img), self.B, self.J, self.F, self.H, self.ks, L.ptr(self._scratch),
-                   L.ptr(self.jt), None, L.stream())
-            return
-        L.call("awr_head_forward", L.ptr(plan.outputs[self.stage]), L.ptr(plan.img), self.B, self.J, self.F, self.H, self.ks, L.ptr(self.jt),
-               None, L.stream())
+                   L.ptr(self.jt), L.ptr(self.stat), L.stream())
+        else:
+            L.call("awr_head_forward", L.ptr(plan.outputs[self.stage]), L.ptr(plan.img), self.B, self.J, self.F, self.H, self.ks, L.ptr(self.jt),
+                   L.ptr(self.stat), L.stream())
+        if self.confidence:
+            self._confidence()
+
+    def _confidence(self):
+        """The second pass over the last stage's map, behind the head launch that wrote `jt` and `stat`."""
+        plan = self.plan
+        if self.nhwc:
+            L.call("awr_head_confidence_nhwc", self._pred, self._cp, L.ptr(plan.img), L.ptr(self.jt), L.ptr(self.stat), self.B, self.J, self.F, self.H,
+                   self.ks, L.ptr(self._scratch), L.ptr(self.conf), L.stream())
+        else:
+            L.call("awr_head_confidence", L.ptr(plan.outputs[self.stage]), L.ptr(plan.img), L.ptr(self.jt), L.ptr(self.stat), self.B, self.J, self.F,
+                   self.H, self.ks, L.ptr(self.conf), L.stream())
 
     def _head_and_loss(self, nv):
         """Joints of the last stage + this batch's loss terms (means over its first nv images) of every stage in `_loss_stages`, added
@@ -611,12 +641,13 @@ class InferEngine(_WinogradAuto):
         cw, dw = self._lw
         for st in self._loss_stages:
             jt = self.jt if st == self.stage else self._jt_aux
+            stat = L.ptr(self.stat) if st == self.stage else None          # (None without confidence=True)
             if self.nhwc:
                 L.call("awr_head_eval_nhwc", self._preds[st], self._cp, L.ptr(plan.img), L.ptr(self.jt_gt), B, J, F, H, nv, self.ks, HUBER_DELTA, cw, dw,
-                       L.ptr(self._scratch), L.ptr(jt), None, L.ptr(self._lacc), s)
+                       L.ptr(self._scratch), L.ptr(jt), stat, L.ptr(self._lacc), s)
                 continue
             out = plan.outputs[st]
-            L.call("awr_head_forward", L.ptr(out), L.ptr(plan.img), B, J, F, H, self.ks, L.ptr(jt), None, s)
+            L.call("awr_head_forward", L.ptr(out), L.ptr(plan.img), B, J, F, H, self.ks, L.ptr(jt), stat, s)
             if nv > 0:
                 L.call("awr_dense_loss", L.ptr(out), L.ptr(self.jt_gt), L.ptr(plan.img), nv, J, F, H, self.ks, HUBER_DELTA, dw, self._lacc.data_ptr() + 8,
                        None, 0, s)

@@ -122,6 +122,29 @@ int awr_head_loss_step_nhwc(const float* pred, int Cp, const float* img, const f
 int awr_head_eval_nhwc(const float* pred, int Cp, const float* img, const float* jt_gt, int B, int J, int F, int H, int n_valid,
                        float ks, float delta, float coord_weight, float dense_weight, float* scratch, float* jt,
                        float* stat /* may be NULL */, double* acc /* [0] += coord term, [1] += dense term */, void* stream);
+/* Per-joint confidence and vote spread from the dense map: a second pass with the joints and the softmax statistics of a
+ * head forward known.  In the reference's terms (util/feature_tool.py:57-63), for image b and joint j over the pixels i of the map:
+ *   mask_i = img_i < 0.99,  h_i = offset_ht_i * mask_i,  w_i = softmax_i(30 h_i)                       (offset_ht_norm, :57-60)
+ *   vote_i = offset_vec_i * mask_i * (ks - h_i * ks) + coords_i   (the summand of :63; jt = sum_i w_i vote_i is the head's output)
+ *   conf   = sum_i w_i h_i                        the expected closeness under the aggregation weights
+ *   var_c  = sum_i w_i (vote_i,c - jt_c)^2        c in {u, v, d}: the weighted scatter of the votes about the joint the head WROTE
+ * conf (B, J, 4) fp32 = [conf, var_u, var_v, var_d] per (b, j), normalised crop units; every entry is a sum of non-negative terms.
+ * jt (B, J, 3) and stat (B, J, 2) = (max logit, sum-exp) are the outputs of awr_head_forward / awr_head_forward_nhwc / awr_head_eval_nhwc on
+ * the SAME map and image; stat[..., 0] / 30 is the largest masked heat value ("peak").  Read-only passes: nothing of the size of the map is
+ * written.  No atomics: two runs on the same buffers give the same bits, in the deterministic mode and out of it.
+ * awr_head_confidence_nhwc: pred (B, F*F, Cp) rows and scratch (awr_head_nhwc_scratch floats; may be the head forward's) under
+ * awr_head_forward_nhwc's geometry rules; one streaming launch + a merge launch.  awr_head_confidence: the (B, 4J, F, F) layout, any J,
+ * one workgroup per (b, j). */
+int awr_head_confidence_nhwc(const float* pred, int Cp, const float* img, const float* jt, const float* stat, int B, int J, int F, int H,
+                             float ks, float* scratch, float* conf /* (B, J, 4) */, void* stream);
+int awr_head_confidence(const float* offset, const float* img, const float* jt, const float* stat, int B, int J, int F, int H, float ks,
+                        float* conf /* (B, J, 4) */, void* stream);
+/* What a caller reads next to a joint, rows [0, n_valid): conf (B, J) = conf4[..., 0]; peak (B, J) = stat[..., 0] / 30; spread_mm (B, J) =
+ * sqrt(var_u (cube_x / 2)^2 + var_v (cube_y / 2)^2 + var_d (cube_z / 2)^2) with cube (B, 3) float32 millimetres as awr_detect_samples
+ * writes it -- NOMINAL millimetres: the crop maps the cube onto [-1, 1].  status / ustatus (B) int32, each optional: a frame with a
+ * non-zero code (awr_detect's, awr_joints_unproject's) gets NaN rows, like its joints.  One small launch. */
+int awr_confidence_fields(const float* conf4, const float* stat, const float* cube, const int* status, const int* ustatus, int B, int J,
+                          int n_valid, float* conf, float* peak, float* spread_mm, void* stream);
 int awr_zero_f64(double* p, int64_t n, void* stream);
 /* out[i] = (float)acc[i] for i<n, out[n] = sum -- e.g. {coord, dense, total} */
 int awr_loss_finalize(const double* acc, int n, float* out, void* stream);

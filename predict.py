@@ -4,6 +4,8 @@
 
 FRAMES.npy holds (n, h, w) uint16 depth frames in millimetres.  Writes pred_uvd.txt (original-image uvd, "%.3f", J * 3 columns: the format
 of the reference's results file, test.py:105-108) and pred_xyz.txt (camera millimetres) into --out (default: the current directory).
+--confidence adds pred_conf.txt, pred_peak.txt and pred_spread_mm.txt (J columns each: the expected closeness under the head's weights, the
+largest masked heat value, the vote scatter in nominal millimetres).
 `--set` overrides config entries as train.py does (img_size, kernel_size, cube, batch_size, jt_num, downsample, winograd ...)."""
 import argparse
 import os
@@ -12,14 +14,19 @@ import sys
 sys.path.insert(0, os.path.dirname(os.path.abspath(__file__)))
 
 
-def main(argv=None):
+def parse_args(argv=None):
     ap = argparse.ArgumentParser(description=__doc__, formatter_class=argparse.RawDescriptionHelpFormatter)
     ap.add_argument("frames")
     ap.add_argument("--load-model", required=True)
     ap.add_argument("--net", default=None)
     ap.add_argument("--out", default=".")
     ap.add_argument("--set", nargs="*", default=[], metavar="key=value")
-    args = ap.parse_args(argv)
+    ap.add_argument("--confidence", action="store_true", help="also write per-joint conf / peak / spread_mm")
+    return ap.parse_args(argv)
+
+
+def main(argv=None):
+    args = parse_args(argv)
 
     import numpy as np
     import torch
@@ -40,12 +47,15 @@ def main(argv=None):
     net.load_state_dict(torch.load(cfg.load_model, map_location="cpu", weights_only=False)["model"])
     bs = min(cfg.batch_size, len(frames))
     pred = awr_amd.Predictor(net.cuda(), cfg.img_size, cfg.kernel_size, cube=cfg.cube, max_batch=bs, frame_shape=frames.shape[1:],
-                             winograd=cfg.winograd, parity=cfg.parity_infer)
-    uvd, xyz = [], []
+                             winograd=cfg.winograd, parity=cfg.parity_infer, confidence=args.confidence)
+    uvd, xyz, extra = [], [], {"conf": [], "peak": [], "spread_mm": []}
     for lo in range(0, len(frames), bs):
         out = pred.predict(np.array(frames[lo:lo + bs]))
         uvd.append(out.uvd.cpu().numpy())
         xyz.append(out.xyz.cpu().numpy())
+        if args.confidence:
+            for k in extra:
+                extra[k].append(getattr(out, k).cpu().numpy())
         try:
             pred.check()
         except awr_amd._lib.AwrError as e:
@@ -53,6 +63,9 @@ def main(argv=None):
     os.makedirs(args.out, exist_ok=True)
     for name, rows in (("pred_uvd.txt", uvd), ("pred_xyz.txt", xyz)):
         np.savetxt(os.path.join(args.out, name), np.concatenate(rows, 0).reshape(len(frames), cfg.jt_num * 3), fmt="%.3f")
+    if args.confidence:
+        for k, rows in extra.items():
+            np.savetxt(os.path.join(args.out, "pred_%s.txt" % k), np.concatenate(rows, 0).reshape(len(frames), cfg.jt_num), fmt="%.6g")
 
 
 if __name__ == "__main__":
