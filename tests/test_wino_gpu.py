@@ -182,7 +182,9 @@ def test_winograd_data_gradient_epilogues(env, use_res, use_bnr, use_act):
                                                                 (4, 32, 32, 128, 128, True, True, True)])
 def test_winograd_weight_gradient_matches_float64(env, B, H, W, cin, cout, affine, relu_in, bias):
     """awr_wino_wgrad: dg = G^T [sum_patches (B^T d B)(.)(A dY A^T)] G against autograd in float64 -- with the fused input affine / ReLU (padding
-    stays zero), the bias gradient, split-K ranges that do not divide the patch blocks evenly (B = 3, 5), packed rows longer than C (ld)"""
+    stays zero), the bias gradient, packed rows longer than C (ld).  Every shape here gives each split exactly ONE pair of stages (the split
+    count equals the number of stage pairs, so the ranges are even and the kernel's main loop runs once): deeper loops and split ranges of
+    different length inside one launch are tests/test_wino_wgrad_gpu.py's, on the shapes of tests/wino_wgrad_cases.py"""
     L, ops, dev = env
     g = torch.Generator().manual_seed(B * 1000 + H * 10 + cin)
     x = torch.randn(B, cin, H, W, generator=g)
