@@ -876,6 +876,8 @@ int awr_add(const float* a, const float* b, float* out, int64_t n, void* stream)
 
 int awr_bias_grad(const float* dy, int64_t npix, int C, float* db, int accumulate, void* stream) {
     AWR_REQUIRE(dy && db, "bias_grad: null pointer");
+    // (the launch checks these too; a rejected call must not have cleared db before it says so)
+    AWR_REQUIRE(C % 4 == 0 && C >= 4 && (C <= 1024 || C % 1024 == 0) && npix > 0, "bias_grad: C=%d must be a multiple of 4 up to 1024, or a multiple of 1024, and npix > 0", C);
     if (!accumulate && hipMemsetAsync(db, 0, sizeof(float) * C, as_stream(stream)) != hipSuccess) {
         set_error("bias_grad: hipMemsetAsync failed");
         return AWR_ERR_HIP;
