@@ -11,6 +11,9 @@
 // keeps its own accumulator slot in the caller's scratch, so the passes are ordered by the stream alone: nothing synchronises, and
 // every workgroup of a pass derives the window from the previous pass's sums by the same three double divisions.
 // The window arithmetic is nyu_data.center2bounds in IEEE double without contraction (this file is compiled with -ffp-contract=off).
+// Two one-thread-per-frame passes close the loop from the network's output back to a crop centre: joints_center_kernel
+// (predicted joints -> the gated next centre, detect.joints_center in IEEE double) and centers_select_kernel (a tracked centre where it is
+// usable, the detector's otherwise).  Both are launch-bound; neither is clever.
 #include <limits.h>
 #include <math.h>
 
@@ -258,6 +261,64 @@ __global__ __launch_bounds__(DET_THREADS) void detect_samples_kernel(const doubl
     cube_out[3 * b] = (float)cb[0]; cube_out[3 * b + 1] = (float)cb[1]; cube_out[3 * b + 2] = (float)cb[2];
 }
 
+// ---- joints -> the next crop centre (detect.joints_center): one thread per frame, the header's definition line by line ----
+__global__ __launch_bounds__(DET_THREADS) void joints_center_kernel(const float* __restrict__ xyz, const double* center_uvd,
+                                                                    const float* __restrict__ center_xyz, const float* __restrict__ cube,
+                                                                    const int* __restrict__ status, const int* __restrict__ ustatus, int J,
+                                                                    int n_valid, const int* __restrict__ joints, int n_sel, double fx, double fy,
+                                                                    double u0, double v0, double flip, double zmin, double zmax, double max_shift,
+                                                                    double* center_out, double* __restrict__ next_out, int* __restrict__ code) {
+    const int b = blockIdx.x * DET_THREADS + threadIdx.x;
+    if (b >= n_valid) return;
+    const double nan = __builtin_nan("");
+    const double c[3] = {center_uvd[3 * b], center_uvd[3 * b + 1], center_uvd[3 * b + 2]};      // read before center_out, which may be it
+    double nc[3] = {nan, nan, nan};
+    int cd = AWR_RECENTER_KEPT_FRAME;
+    if (status[b] == 0 && ustatus[b] == 0) {
+        const float* X = xyz + (int64_t)b * J * 3;
+        double m[3] = {0.0, 0.0, 0.0};
+        bool in_range = true;
+        for (int k = 0; k < n_sel; ++k) {                                   // sequential, in index order
+            const int j = joints ? joints[k] : k;
+            if (j < 0 || j >= J) { in_range = false; break; }               // never a read outside the frame's joints
+            m[0] += (double)X[3 * j]; m[1] += (double)X[3 * j + 1]; m[2] += (double)X[3 * j + 2];
+        }
+        const double n = (double)n_sel;
+        m[0] = m[0] / n; m[1] = m[1] / n; m[2] = m[2] / n;
+        bool near = true;
+        for (int a = 0; a < 3; ++a)
+            near = near && fabs(m[a] - (double)center_xyz[3 * b + a]) <= max_shift * ((double)cube[3 * b + a] / 2.0);
+        if (!in_range || !(isfinite(m[0]) && isfinite(m[1]) && isfinite(m[2]))) cd = AWR_RECENTER_KEPT_NONFINITE;
+        else if (!(zmin <= m[2] && m[2] <= zmax)) cd = AWR_RECENTER_KEPT_DEPTH;
+        else if (!near) cd = AWR_RECENTER_KEPT_SHIFT;
+        else {
+            cd = AWR_RECENTER_MOVED;                                        // evaluator.xyz2uvd (util.py:3-10) in double
+            const double y = m[1] * flip;
+            nc[0] = m[0] * fx / m[2] + u0; nc[1] = y * fy / m[2] + v0; nc[2] = m[2];
+        }
+    }
+    const bool moved = cd == AWR_RECENTER_MOVED;
+    for (int a = 0; a < 3; ++a) {
+        center_out[3 * b + a] = moved ? nc[a] : c[a];
+        if (next_out) next_out[3 * b + a] = nc[a];
+    }
+    code[b] = cd;
+}
+
+// ---- per frame: a where it is a usable centre, b otherwise (detect.select) ----
+__global__ __launch_bounds__(DET_THREADS) void centers_select_kernel(const double* __restrict__ a_center, const int* __restrict__ a_status,
+                                                                     const double* __restrict__ b_center, const int* __restrict__ b_status, int B,
+                                                                     double* __restrict__ out_center, int* __restrict__ out_status,
+                                                                     int* __restrict__ which) {
+    const int i = blockIdx.x * DET_THREADS + threadIdx.x;
+    if (i >= B) return;
+    const double a[3] = {a_center[3 * i], a_center[3 * i + 1], a_center[3 * i + 2]};
+    const bool take_a = a_status[i] == AWR_DET_OK && isfinite(a[0]) && isfinite(a[1]) && isfinite(a[2]);
+    for (int k = 0; k < 3; ++k) out_center[3 * i + k] = take_a ? a[k] : b_center[3 * i + k];
+    out_status[i] = take_a ? a_status[i] : b_status[i];
+    if (which) which[i] = take_a ? 0 : 1;
+}
+
 static int detect_parts(int B, int fh) {
     // about four workgroups per CU over the batch, never more than one per row of the frame (a workgroup's share is whole rows)
     int p = (1024 + B - 1) / B;
@@ -333,6 +394,36 @@ int awr_detect_samples(const double* center_uvd, const double* cube, int cube_st
     detect_samples_kernel<<<(B + DET_THREADS - 1) / DET_THREADS, DET_THREADS, 0, as_stream(stream)>>>(
         center_uvd, cube, cube_stride, n_frames, frame, B, dsize, fh, fw, fx, fy, u0, v0, (double)flip, samples, M, center_xyz, cube_out, status);
     return check_launch("awr_detect_samples");
+}
+
+int awr_joints_center(const float* xyz, const double* center_uvd, const float* center_xyz, const float* cube, const int* status,
+                      const int* ustatus, int B, int J, int n_valid, const int* joints, int n_joints, double fx, double fy, double u0, double v0,
+                      int flip, double zmin, double zmax, double max_shift, double* center_out, double* next_out, int* code, void* stream) {
+    AWR_REQUIRE(xyz && center_uvd && center_xyz && cube && status && ustatus && center_out && code, "awr_joints_center: NULL pointer");
+    AWR_REQUIRE(B > 0 && B <= AWR_DET_MAX_BATCH, "awr_joints_center: B = %d is outside [1, %d]", B, AWR_DET_MAX_BATCH);
+    AWR_REQUIRE(J > 0 && J <= AWR_RECENTER_MAX_JOINTS, "awr_joints_center: J = %d is outside [1, %d]", J, AWR_RECENTER_MAX_JOINTS);
+    AWR_REQUIRE(n_valid >= 0 && n_valid <= B, "awr_joints_center: n_valid = %d is outside [0, B = %d]", n_valid, B);
+    AWR_REQUIRE(n_joints >= 0 && n_joints <= J, "awr_joints_center: n_joints = %d is outside [0, J = %d]", n_joints, J);
+    AWR_REQUIRE(n_joints == 0 || joints, "awr_joints_center: n_joints = %d needs the index list (NULL pointer)", n_joints);
+    AWR_REQUIRE(fx != 0.0 && fy != 0.0 && isfinite(fx) && isfinite(fy) && isfinite(u0) && isfinite(v0) && (flip == 1 || flip == -1),
+                "awr_joints_center: bad intrinsics / flip");
+    AWR_REQUIRE(zmin <= zmax, "awr_joints_center: depth range needs zmin <= zmax (got %g, %g)", zmin, zmax);
+    AWR_REQUIRE(max_shift >= 0.0, "awr_joints_center: max_shift = %g must be >= 0 (infinity: no gate)", max_shift);
+    if (n_valid == 0) return AWR_OK;
+    const bool all = n_joints == 0;
+    joints_center_kernel<<<(n_valid + DET_THREADS - 1) / DET_THREADS, DET_THREADS, 0, as_stream(stream)>>>(
+        xyz, center_uvd, center_xyz, cube, status, ustatus, J, n_valid, all ? nullptr : joints, all ? J : n_joints, fx, fy, u0, v0, (double)flip,
+        zmin, zmax, max_shift, center_out, next_out, code);
+    return check_launch("awr_joints_center");
+}
+
+int awr_centers_select(const double* a_center, const int* a_status, const double* b_center, const int* b_status, int B, double* out_center,
+                       int* out_status, int* which, void* stream) {
+    AWR_REQUIRE(a_center && a_status && b_center && b_status && out_center && out_status, "awr_centers_select: NULL pointer");
+    AWR_REQUIRE(B > 0 && B <= AWR_DET_MAX_BATCH, "awr_centers_select: B = %d is outside [1, %d]", B, AWR_DET_MAX_BATCH);
+    centers_select_kernel<<<(B + DET_THREADS - 1) / DET_THREADS, DET_THREADS, 0, as_stream(stream)>>>(a_center, a_status, b_center, b_status, B,
+                                                                                                   out_center, out_status, which);
+    return check_launch("awr_centers_select");
 }
 
 }  // extern "C"

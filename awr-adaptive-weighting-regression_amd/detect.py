@@ -4,8 +4,10 @@ Two things live here:
 
   * the numpy restatement -- `center_of_mass`, `detect`, `sample_blocks` -- written to the definition in the header.  It is the
     yardstick the kernels are tested against bit for bit, and a usable host fallback for a machine without a GPU;
-  * thin operator-level wrappers over the entry points (`detect_device`, `samples_device`, `unproject_device`) for tests and tools.
-    `awr_amd.predictor.Predictor` is the product path.
+  * thin operator-level wrappers over the entry points (`detect_device`, `samples_device`, `unproject_device`, `joints_center_device`,
+    `select_device`) for tests and tools.  `awr_amd.predictor.Predictor` is the product path.
+  * `joints_center` and `select`: the statements of awr_joints_center (predicted joints -> the next crop centre, with a gate) and
+    awr_centers_select (a tracked centre where it is usable, the detector's otherwise); DESIGN.md 4.19.
 
 Definition.  Centre of mass of a pixel set: n, sum of columns u, sum of rows v and sum of raw uint16 depths d as int64, centre =
 (su / n, sv / n, sd / n) as three double divisions.  Integer sums do not depend on the order of summation, so the device, which splits a
@@ -33,6 +35,11 @@ MAX_ITERS = 8
 # as a hand seen end-on, two refinement passes.
 DEPTH_RANGE, SLAB, REFINE_ITERS = (1.0, 2000.0), 150.0, 2
 _NAN3 = (float("nan"),) * 3
+# awr_joints_center's codes (include/awr_hip.h AWR_RECENTER_*)
+KEPT_FRAME, MOVED, KEPT_NONFINITE, KEPT_DEPTH, KEPT_SHIFT = 0, 1, 2, 3, 4
+RECENTER_NAMES = {KEPT_FRAME: "kept: the frame has a status code", MOVED: "moved", KEPT_NONFINITE: "kept: the joint mean is not finite",
+                  KEPT_DEPTH: "kept: the joint mean is outside the depth range", KEPT_SHIFT: "kept: the joint mean is too far from the centre"}
+MAX_JOINTS = 256
 
 
 def _u16(frame):
@@ -135,6 +142,61 @@ def sample_blocks(centers, cube, dsize, paras=ND.PARAS, flip=-1, frame_shape=(48
     return blocks, M, cxyz, np.ascontiguousarray(cubes, dtype=np.float32), status      # (cubes may be a broadcast view: stride 0)
 
 
+def joints_center(xyz, center_uvd, center_xyz, cube, status, ustatus, paras, flip, joints=None, depth_range=DEPTH_RANGE, max_shift=1.0):
+    """The statement of awr_joints_center (include/awr_hip.h): predicted joints -> the next crop centre, per frame, with a gate.
+    xyz (B, J, 3) float32 camera mm; center_uvd (B, 3) float64, the centres this pass was cropped at; center_xyz, cube (B, 3) float32;
+    status, ustatus (B,) the detector's and the un-projection's codes; joints: indices into [0, J) (None: all of them).
+    -> (center_out (B, 3) float64: the new centre where MOVED, center_uvd's row otherwise; next (B, 3): the new centre where MOVED, NaN
+    otherwise; code (B,) int32).  An explicit loop in IEEE double, in the header's order."""
+    xyz = np.asarray(xyz, np.float32)
+    B, J = xyz.shape[0], xyz.shape[1]
+    center_uvd = np.asarray(center_uvd, np.float64).reshape(B, 3)
+    center_xyz, cube = np.asarray(center_xyz, np.float32).reshape(B, 3), np.asarray(cube, np.float32).reshape(B, 3)
+    sel = list(range(J)) if joints is None or len(joints) == 0 else [int(j) for j in joints]
+    fx, fy, u0, v0 = (np.float64(p) for p in paras)
+    zmin, zmax, max_shift, fl = np.float64(depth_range[0]), np.float64(depth_range[1]), np.float64(max_shift), np.float64(flip)
+    if not (1 <= J <= MAX_JOINTS and len(sel) <= J and int(flip) in (1, -1) and zmin <= zmax and max_shift >= 0):
+        raise ValueError("joints_center: J in [1, %d], at most J indices, flip = +-1, zmin <= zmax and max_shift >= 0 are required" % MAX_JOINTS)
+    out, nxt, code = center_uvd.copy(), np.full((B, 3), np.nan), np.zeros(B, np.int32)
+    with np.errstate(all="ignore"):
+        for b in range(B):
+            if status[b] != 0 or ustatus[b] != 0:
+                code[b] = KEPT_FRAME
+                continue
+            m, in_range = [np.float64(0.0)] * 3, True
+            for j in sel:
+                if not 0 <= j < J:
+                    in_range = False
+                    break
+                m = [m[a] + np.float64(xyz[b, j, a]) for a in range(3)]
+            m = [m[a] / np.float64(len(sel)) for a in range(3)]
+            if not in_range or not all(np.isfinite(m)):
+                code[b] = KEPT_NONFINITE
+            elif not (zmin <= m[2] <= zmax):
+                code[b] = KEPT_DEPTH
+            elif not all(abs(m[a] - np.float64(center_xyz[b, a])) <= max_shift * (np.float64(cube[b, a]) / np.float64(2.0)) for a in range(3)):
+                code[b] = KEPT_SHIFT
+            else:
+                code[b] = MOVED
+                y = m[1] * fl                                         # evaluator.xyz2uvd (util.py:3-10), kept in double
+                nxt[b] = (m[0] * fx / m[2] + u0, y * fy / m[2] + v0, m[2])
+                out[b] = nxt[b]
+    return out, nxt, code
+
+
+def select(a_center, a_status, b_center, b_status):
+    """The statement of awr_centers_select: per frame `a` where a_status == OK and a's centre is finite, otherwise `b` with b's status.
+    -> (center (B, 3) float64, status (B,) int32, which (B,) int32: 0 = a, 1 = b)."""
+    a_center, b_center = np.asarray(a_center, np.float64).reshape(-1, 3), np.asarray(b_center, np.float64).reshape(-1, 3)
+    a_status, b_status = np.asarray(a_status, np.int32), np.asarray(b_status, np.int32)
+    B = a_center.shape[0]
+    out, status, which = b_center.copy(), b_status.copy(), np.ones(B, np.int32)
+    for b in range(B):
+        if a_status[b] == OK and all(np.isfinite(a_center[b])):
+            out[b], status[b], which[b] = a_center[b], a_status[b], 0
+    return out, status, which
+
+
 # ---- operator-level wrappers over the entry points (tests, tools) ------------------------------------------------------------------
 def _f64(x, dev):
     import torch
@@ -198,3 +260,36 @@ def unproject_device(jt_pred, center_xyz, M, cube, img_size, paras=ND.PARAS, fli
     L.call("awr_joints_unproject", L.ptr(jt_pred), L.ptr(center_xyz), L.ptr(M), L.ptr(cube), B, J, n, float(img_size), float(paras[0]),
            float(paras[1]), float(paras[2]), float(paras[3]), int(flip), L.ptr(uvd), L.ptr(xyz), status.data_ptr(), L.stream())
     return uvd, xyz, status
+
+
+def joints_center_device(xyz, center_uvd, center_xyz, cube, status, ustatus, paras=ND.PARAS, flip=-1, joints=None, depth_range=DEPTH_RANGE,
+                         max_shift=1.0, n_valid=None, center_out=None, next_out=None, code=None):
+    """awr_joints_center on device tensors: -> (center_out (B, 3) float64, next (B, 3) float64, code (B,) int32); rows >= n_valid of the
+    outputs are left as they are.  joints: a device int32 tensor, a list of indices or None (all joints); center_out may be center_uvd."""
+    import torch
+    from . import _lib as L
+    B, J = int(xyz.shape[0]), int(xyz.shape[1])
+    dev = xyz.device
+    n = B if n_valid is None else int(n_valid)
+    if joints is not None and not isinstance(joints, torch.Tensor):
+        joints = torch.tensor([int(j) for j in joints], dtype=torch.int32, device=dev)
+    center_out = torch.empty((B, 3), dtype=torch.float64, device=dev) if center_out is None else center_out
+    next_out = torch.empty((B, 3), dtype=torch.float64, device=dev) if next_out is None else next_out
+    code = torch.empty(B, dtype=torch.int32, device=dev) if code is None else code
+    L.call("awr_joints_center", L.ptr(xyz), L.ptr(center_uvd), L.ptr(center_xyz), L.ptr(cube), L.ptr(status), L.ptr(ustatus), B, J, n,
+           L.ptr(joints), 0 if joints is None else int(joints.numel()), float(paras[0]), float(paras[1]), float(paras[2]), float(paras[3]),
+           int(flip), float(depth_range[0]), float(depth_range[1]), float(max_shift), L.ptr(center_out), L.ptr(next_out), L.ptr(code), L.stream())
+    return center_out, next_out, code
+
+
+def select_device(a_center, a_status, b_center, b_status):
+    """awr_centers_select on device tensors: -> (center (B, 3) float64, status (B,) int32, which (B,) int32)."""
+    import torch
+    from . import _lib as L
+    B, dev = int(a_center.shape[0]), a_center.device
+    out = torch.empty((B, 3), dtype=torch.float64, device=dev)
+    status = torch.empty(B, dtype=torch.int32, device=dev)
+    which = torch.empty(B, dtype=torch.int32, device=dev)
+    L.call("awr_centers_select", L.ptr(a_center), L.ptr(a_status), L.ptr(b_center), L.ptr(b_status), B, L.ptr(out), L.ptr(status),
+           L.ptr(which), L.stream())
+    return out, status, which

@@ -5,11 +5,24 @@
     out.xyz, out.uvd                        # (B, J, 3) camera millimetres / original-image uvd, on the device
     pred.check()                            # synchronises; raises AwrError naming the first frame that could not be predicted
     Predictor(..., confidence=True)         # out additionally carries conf, peak, spread_mm (B, J): how sure each joint is
+    Predictor(..., recenter=1)              # crop again around the predicted joints and predict again
+    Predictor(..., track=True)              # start each call's crop at the previous call's joint centre of the same batch slot
 
 Everything between the frames and the joints runs on the device, on the current stream, without a synchronisation: awr_detect (hand
 centre by iterated centre of mass) -> awr_detect_samples (crop blocks, crop matrices) -> awr_nyu_batch (crop + normalise) -> the
 inference plan and the single-pass head (InferEngine) -> awr_joints_unproject.  The host only issues launches.  There is no host
 fallback in this class: without a GPU it raises; `awr_amd.detect.detect` is the numpy statement of the detector for such a machine.
+
+Re-centring and tracking (both opt-in; with the defaults the launches and the bits are what they were).  The detector's centre is a centre
+of mass of depth pixels, biased towards the forearm and whatever else lies in the slab, while the network was trained on refined centres.
+The network's own joints are the better centre, and awr_joints_center turns them into one on the device: the float64 mean of the (selected)
+joints, projected back to uvd, accepted only where the frame has no status code, the mean is finite, its depth lies in the detector's
+depth_range and it is within max_shift half cubes of the present centre on every axis.  recenter=N appends N passes of awr_joints_center ->
+awr_detect_samples -> render -> engine -> awr_joints_unproject on the same engine and buffers; a frame that is not moved keeps its centre
+and so repeats its previous pass bit for bit.  track=True keeps one float64 centre per batch slot (NaN: lost) and runs the detector twice,
+seeded with the tracked centres and as configured, and awr_centers_select takes the tracked result where it found the hand.  Nothing of this
+synchronises.  Whether either improves accuracy on real frames is UNMEASURED: no NYU frames and no trained checkpoint exist where this was
+written.
 """
 import collections
 import types
@@ -23,11 +36,13 @@ from . import nyu_data as ND
 
 Prediction = collections.namedtuple("Prediction", "xyz uvd center_xyz M status")
 ConfidentPrediction = collections.namedtuple("ConfidentPrediction", Prediction._fields + ("conf", "peak", "spread_mm"))
+MAX_RECENTER = 4
 
 
 class Predictor:
     def __init__(self, net, img_size, kernel_size, cube=(300, 300, 300), paras=ND.PARAS, flip=-1, max_batch=1, frame_shape=(480, 640),
-                 seed="nearest", depth_range=D.DEPTH_RANGE, slab=D.SLAB, refine_iters=D.REFINE_ITERS, winograd=None, parity=False, confidence=False):
+                 seed="nearest", depth_range=D.DEPTH_RANGE, slab=D.SLAB, refine_iters=D.REFINE_ITERS, winograd=None, parity=False, confidence=False,
+                 recenter=0, track=False, center_joints=None, max_shift=1.0):
         """net: an awr_amd network on the GPU with its weights loaded.  cube: the crop cube in mm.  paras = (fx, fy, u0, v0), flip: the camera.
         max_batch: the static batch of the inference plan; smaller batches are padded, larger ones refused.  seed / depth_range / slab /
         refine_iters: the detector (awr_amd.detect); with `centers_uvd` handed to predict() the seed is the given centre and refine_iters
@@ -36,10 +51,38 @@ class Predictor:
         conf (the expected closeness under the head's aggregation weights, in [0, 1] for a trained map), peak (the largest masked heat value)
         and spread_mm = sqrt(var_u (cube_x / 2)^2 + var_v (cube_y / 2)^2 + var_d (cube_z / 2)^2), the scatter of the per-pixel votes about the
         joint in NOMINAL millimetres: the crop maps the cube onto [-1, 1] by construction, so half a cube edge is one normalised unit (exact
-        in depth, and in the image plane as far as the crop's pinhole scaling is).  One more pass over the dense map and one small launch."""
+        in depth, and in the image plane as far as the crop's pinhole scaling is).  One more pass over the dense map and one small launch.
+        recenter: 0 ... 4 extra passes, each cropped around the joints of the pass before it (awr_joints_center's gate decides per frame).
+        track: True -- a call without centers_uvd first tries the centre the previous call's joints left for the same batch slot (refined
+        by refine_iters passes, which is also what validates it against the new frame: with refine_iters=0 a tracked centre is NEVER
+        re-validated against the frame and is only dropped when the gate or a status code drops it) and falls back to the configured
+        detector per slot; the second detector run is the price of never synchronising.  center_joints: indices into [0, J) whose mean is
+        the centre (default: all joints), uploaded once.  max_shift: the gate, in half cubes per axis, of both modes; the gate's depth range
+        is depth_range.  After a predict() with recenter > 0 or track on: centers_uvd (nb, 3) float64 the final crop centres,
+        next_centers_uvd (nb, 3) the joint centre of the final pass (NaN where not moved), recenter_codes (recenter + 1, nb) int32
+        awr_amd.detect's KEPT_* / MOVED, one row per awr_joints_center call -- device tensors, nothing synchronised."""
         if not isinstance(confidence, bool):
             raise TypeError("confidence is True or False, not %r" % (confidence,))
         self.confidence = confidence
+        if isinstance(recenter, bool) or not isinstance(recenter, int):
+            raise TypeError("recenter is an int in [0, %d], not %r" % (MAX_RECENTER, recenter))
+        if not 0 <= recenter <= MAX_RECENTER:
+            raise ValueError("recenter = %d is outside [0, %d]" % (recenter, MAX_RECENTER))
+        if not isinstance(track, bool):
+            raise TypeError("track is True or False, not %r" % (track,))
+        if isinstance(max_shift, (bool, str)) or not isinstance(max_shift, (int, float)):
+            raise TypeError("max_shift is a number >= 0, not %r" % (max_shift,))
+        if not float(max_shift) >= 0.0:
+            raise ValueError("max_shift = %r must be >= 0 (infinity: no shift gate)" % (max_shift,))
+        if center_joints is not None:
+            if isinstance(center_joints, (str, bytes)) or any(isinstance(j, bool) or not isinstance(j, (int, np.integer)) for j in center_joints):
+                raise TypeError("center_joints is a list of joint indices, not %r" % (center_joints,))
+            center_joints = [int(j) for j in center_joints]
+            nj = int(net.J)
+            if not 0 < len(center_joints) <= nj or any(not 0 <= j < nj for j in center_joints):
+                raise ValueError("center_joints needs 1 ... %d indices in [0, %d), got %r" % (nj, nj, center_joints))
+        self.recenter, self.track, self.max_shift = recenter, track, float(max_shift)
+        self.centers_uvd = self.next_centers_uvd = self.recenter_codes = None
         if not torch.cuda.is_available():
             raise L.AwrError("Predictor runs the detector, the crop, the network and the un-projection as HIP kernels and needs a GPU: none is "
                              "visible -- awr_amd.detect.detect is the host statement of the detector")
@@ -75,6 +118,55 @@ class Predictor:
         self._cube32 = torch.empty((B, 3), dtype=torch.float32, device=dev)
         self._img = torch.zeros((B, 1, self.S, self.S), dtype=torch.float32, device=dev)
         self._last = None
+        if recenter or track:
+            self._joints = None if center_joints is None else torch.tensor(center_joints, dtype=torch.int32, device=dev)
+            self._moved = torch.empty((B, 3), dtype=torch.float64, device=dev)          # center_out of the call that only asks for `next`
+        if track:
+            self._track = torch.full((B, 3), float("nan"), dtype=torch.float64, device=dev)
+            self._tcenters = torch.empty((B, 3), dtype=torch.float64, device=dev)
+            self._dcenters = torch.empty((B, 3), dtype=torch.float64, device=dev)
+            self._tstatus = torch.empty(B, dtype=torch.int32, device=dev)
+            self._dstatus = torch.empty(B, dtype=torch.int32, device=dev)
+
+    def _slots(self, slots, n=None):
+        if slots is None:
+            return None
+        if isinstance(slots, torch.Tensor):
+            return slots.to(device=self.device, dtype=torch.int64, non_blocking=True)
+        idx = [int(i) for i in slots]
+        if any(not 0 <= i < self.B for i in idx) or (n is not None and len(idx) != n):
+            raise L.AwrError("slots must be %sindices in [0, max_batch = %d), got %r" % ("" if n is None else "%d " % n, self.B, slots))
+        return torch.tensor(idx, dtype=torch.int64).to(self.device, non_blocking=True)
+
+    def set_track(self, centers_uvd, slots=None):
+        """Set the tracked centres from outside: centers_uvd (n, 3), numpy or tensor, host or device, for batch slots `slots` (default:
+        slots [0, n)).  A NaN row marks its slot as lost.  Does not block."""
+        if not self.track:
+            raise L.AwrError("set_track needs a Predictor built with track=True")
+        c = centers_uvd if isinstance(centers_uvd, torch.Tensor) else torch.from_numpy(np.ascontiguousarray(centers_uvd, dtype=np.float64))
+        if c.dim() != 2 or c.shape[1] != 3 or not 0 < c.shape[0] <= self.B:
+            raise L.AwrError("centers_uvd must be (n, 3) with n in [1, max_batch = %d], got %s" % (self.B, tuple(c.shape)))
+        idx = self._slots(slots, int(c.shape[0]))
+        if idx is None:
+            self._track[:c.shape[0]].copy_(c, non_blocking=True)
+        else:
+            self._track.index_copy_(0, idx, c.to(device=self.device, dtype=torch.float64, non_blocking=True))
+
+    def reset_track(self, slots=None):
+        """Mark batch slots (default: all of them) as lost: their next call starts from the detector.  Does not block."""
+        if not self.track:
+            raise L.AwrError("reset_track needs a Predictor built with track=True")
+        idx = self._slots(slots)
+        if idx is None:
+            self._track.fill_(float("nan"))
+        else:
+            self._track.index_fill_(0, idx, float("nan"))
+
+    def _joints_center(self, xyz, cxyz, status, ustatus, nv, center_out, next_out, code):
+        fx, fy, u0, v0 = self.paras
+        L.call("awr_joints_center", L.ptr(xyz), self._centers.data_ptr(), L.ptr(cxyz), L.ptr(self._cube32), status.data_ptr(), ustatus.data_ptr(),
+               self.B, self.J, nv, L.ptr(self._joints), 0 if self._joints is None else int(self._joints.numel()), fx, fy, u0, v0, self.flip,
+               self.depth_range[0], self.depth_range[1], self.max_shift, center_out.data_ptr(), L.ptr(next_out), code.data_ptr(), L.stream())
 
     def _upload(self, frames):
         """(nb, fh, fw) uint16 -> rows [0, nb) of the frame store, without blocking"""
@@ -110,7 +202,9 @@ class Predictor:
         """-> Prediction(xyz (nb, J, 3), uvd (nb, J, 3), center_xyz (nb, 3), M (nb, 3, 3), status (nb,) int32), device tensors, nothing
         synchronised; with confidence=True a ConfidentPrediction: these and conf, peak, spread_mm (nb, J).  centers_uvd (nb, 3): hand centres in original-image uvd (numpy or tensor) instead of the detector's seed.  n_valid:
         frames of the batch that count (default: all of them); rows past it hold unspecified values.  status: awr_amd.detect's codes; a frame that is
-        not OK has NaN rows (of conf / peak / spread_mm too)."""
+        not OK has NaN rows (of conf / peak / spread_mm too).  With recenter > 0 every field is the FINAL pass's; with track=True a call
+        without centers_uvd starts from the tracked centres (see __init__), an explicit centers_uvd overrides them for this call, and either
+        way slots [0, n_valid) of the tracker take this call's next_centers_uvd."""
         nb = self._upload(frames)
         nv = nb if n_valid is None else int(n_valid)
         if not 0 < nv <= nb:
@@ -130,17 +224,42 @@ class Predictor:
         ustatus = torch.zeros(B, dtype=torch.int32, device=dev)
         uvd = torch.empty((B, J, 3), dtype=torch.float32, device=dev)
         xyz = torch.empty((B, J, 3), dtype=torch.float32, device=dev)
-        L.call("awr_detect", self._frames.data_ptr(), 0, B, self.fh, self.fw, self._idx.data_ptr(), nv, mode, L.ptr(seed), self.depth_range[0],
-               self.depth_range[1], self.slab, self._cube.data_ptr(), 0, fx, fy, self.iters, 0, self._scratch.data_ptr(),
-               self._centers.data_ptr(), status.data_ptr(), s)
-        L.call("awr_detect_samples", self._centers.data_ptr(), self._cube.data_ptr(), 0, B, self._idx.data_ptr(), nv, self.S, self.fh, self.fw,
-               fx, fy, u0, v0, self.flip, self._blocks.data_ptr(), L.ptr(M), L.ptr(cxyz), L.ptr(self._cube32), status.data_ptr(), s)
-        self._render(self._blocks[:nv], out=self._img[:nv])
-        if nv < B:
-            self._img[nv:].zero_()          # padding rows of the static plan: constant input, and no later stage reads their output
-        jt = self.engine(self._img)
-        L.call("awr_joints_unproject", L.ptr(jt), L.ptr(cxyz), L.ptr(M), L.ptr(self._cube32), B, J, nv, float(self.S), fx, fy, u0, v0, self.flip,
-               L.ptr(uvd), L.ptr(xyz), ustatus.data_ptr(), s)
+
+        def detect(mode, seed, centers, status):
+            L.call("awr_detect", self._frames.data_ptr(), 0, B, self.fh, self.fw, self._idx.data_ptr(), nv, mode, L.ptr(seed), self.depth_range[0],
+                   self.depth_range[1], self.slab, self._cube.data_ptr(), 0, fx, fy, self.iters, 0, self._scratch.data_ptr(),
+                   centers.data_ptr(), status.data_ptr(), s)
+
+        def crop_and_predict():
+            L.call("awr_detect_samples", self._centers.data_ptr(), self._cube.data_ptr(), 0, B, self._idx.data_ptr(), nv, self.S, self.fh, self.fw,
+                   fx, fy, u0, v0, self.flip, self._blocks.data_ptr(), L.ptr(M), L.ptr(cxyz), L.ptr(self._cube32), status.data_ptr(), s)
+            self._render(self._blocks[:nv], out=self._img[:nv])
+            if nv < B:
+                self._img[nv:].zero_()          # padding rows of the static plan: constant input, and no later stage reads their output
+            jt = self.engine(self._img)
+            L.call("awr_joints_unproject", L.ptr(jt), L.ptr(cxyz), L.ptr(M), L.ptr(self._cube32), B, J, nv, float(self.S), fx, fy, u0, v0, self.flip,
+                   L.ptr(uvd), L.ptr(xyz), ustatus.data_ptr(), s)
+
+        if self.track and seed is None:
+            # the tracked centres first (a lost slot's NaN seed finds nothing), the configured detector second, per slot whichever holds
+            detect(D.SEED_GIVEN, self._track, self._tcenters, self._tstatus)
+            detect(mode, None, self._dcenters, self._dstatus)
+            L.call("awr_centers_select", self._tcenters.data_ptr(), self._tstatus.data_ptr(), self._dcenters.data_ptr(), self._dstatus.data_ptr(),
+                   nv, self._centers.data_ptr(), status.data_ptr(), None, s)
+        else:
+            detect(mode, seed, self._centers, status)
+        crop_and_predict()
+        if self.recenter or self.track:
+            codes = torch.zeros((self.recenter + 1, B), dtype=torch.int32, device=dev)
+            for k in range(self.recenter):
+                # moved frames get their new centre in place, the others keep theirs: their next pass repeats this one bit for bit
+                self._joints_center(xyz, cxyz, status, ustatus, nv, self._centers, None, codes[k])
+                crop_and_predict()
+            nxt = torch.full((B, 3), float("nan"), dtype=torch.float64, device=dev)
+            self._joints_center(xyz, cxyz, status, ustatus, nv, self._moved, nxt, codes[self.recenter])
+            self.centers_uvd, self.next_centers_uvd, self.recenter_codes = self._centers[:nb].clone(), nxt[:nb], codes[:, :nb]
+            if self.track:
+                self._track[:nv].copy_(nxt[:nv])
         self._last = (status, ustatus, nv)
         if self.confidence:
             fields = torch.empty((3, B, J), dtype=torch.float32, device=dev)

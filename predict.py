@@ -6,6 +6,10 @@ FRAMES.npy holds (n, h, w) uint16 depth frames in millimetres.  Writes pred_uvd.
 of the reference's results file, test.py:105-108) and pred_xyz.txt (camera millimetres) into --out (default: the current directory).
 --confidence adds pred_conf.txt, pred_peak.txt and pred_spread_mm.txt (J columns each: the expected closeness under the head's weights, the
 largest masked heat value, the vote scatter in nominal millimetres).
+--recenter N crops again around the predicted joints and predicts again, N times; --track treats the file as ONE sequence (batch size 1, so
+batch slot 0 is the stream) and starts each frame's crop at the previous frame's joint centre, falling back to the detector when the hand is
+lost.  With either, pred_center_uvd.txt (the final crop centres) and pred_recenter_code.txt (one column per
+awr_joints_center call: 1 = moved, 0 / 2 / 3 / 4 = kept, awr_amd.detect.RECENTER_NAMES) are written too.
 `--set` overrides config entries as train.py does (img_size, kernel_size, cube, batch_size, jt_num, downsample, winograd ...)."""
 import argparse
 import os
@@ -22,6 +26,8 @@ def parse_args(argv=None):
     ap.add_argument("--out", default=".")
     ap.add_argument("--set", nargs="*", default=[], metavar="key=value")
     ap.add_argument("--confidence", action="store_true", help="also write per-joint conf / peak / spread_mm")
+    ap.add_argument("--recenter", type=int, default=0, metavar="N", help="extra passes cropped around the predicted joints (0 ... 4)")
+    ap.add_argument("--track", action="store_true", help="the file is one sequence: start each crop at the previous frame's joint centre")
     return ap.parse_args(argv)
 
 
@@ -45,9 +51,12 @@ def main(argv=None):
     else:
         net = hourglass.PoseNet(cfg.net, cfg.jt_num)
     net.load_state_dict(torch.load(cfg.load_model, map_location="cpu", weights_only=False)["model"])
-    bs = min(cfg.batch_size, len(frames))
+    bs = 1 if args.track else min(cfg.batch_size, len(frames))
     pred = awr_amd.Predictor(net.cuda(), cfg.img_size, cfg.kernel_size, cube=cfg.cube, max_batch=bs, frame_shape=frames.shape[1:],
-                             winograd=cfg.winograd, parity=cfg.parity_infer, confidence=args.confidence)
+                             winograd=cfg.winograd, parity=cfg.parity_infer, confidence=args.confidence,
+                             recenter=args.recenter, track=args.track)
+    stateful = bool(args.recenter or args.track)
+    centers, codes = [], []
     uvd, xyz, extra = [], [], {"conf": [], "peak": [], "spread_mm": []}
     for lo in range(0, len(frames), bs):
         out = pred.predict(np.array(frames[lo:lo + bs]))
@@ -56,6 +65,9 @@ def main(argv=None):
         if args.confidence:
             for k in extra:
                 extra[k].append(getattr(out, k).cpu().numpy())
+        if stateful:
+            centers.append(pred.centers_uvd.cpu().numpy())
+            codes.append(pred.recenter_codes.cpu().numpy().T)
         try:
             pred.check()
         except awr_amd._lib.AwrError as e:
@@ -66,6 +78,9 @@ def main(argv=None):
     if args.confidence:
         for k, rows in extra.items():
             np.savetxt(os.path.join(args.out, "pred_%s.txt" % k), np.concatenate(rows, 0).reshape(len(frames), cfg.jt_num), fmt="%.6g")
+    if stateful:
+        np.savetxt(os.path.join(args.out, "pred_center_uvd.txt"), np.concatenate(centers, 0), fmt="%.6f")
+        np.savetxt(os.path.join(args.out, "pred_recenter_code.txt"), np.concatenate(codes, 0), fmt="%d")
 
 
 if __name__ == "__main__":
