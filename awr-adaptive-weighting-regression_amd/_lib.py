@@ -119,6 +119,11 @@ _SIGS = {
     "awr_loss_finalize_reset": ([_P, _I, _P, _P], C.c_int),
     "awr_adam_step": ([_P, _P, _P, _P, _L, _F, _F, _F, _F, _F, _L, _F, _P], C.c_int),
     "awr_sgd_step": ([_P, _P, _P, _L, _F, _F, _F, _L, _F, _P], C.c_int),
+    "awr_adam_step_dev": ([_P, _P, _P, _P, _P, _P, _L, _F, _F, _F, _F, _F, _L, _F, _P], C.c_int),
+    "awr_sgd_step_dev": ([_P, _P, _P, _P, _P, _L, _F, _F, _F, _L, _F, _P], C.c_int),
+    "awr_grad_accumulate": ([_P, _P, _L, _I, _P], C.c_int),
+    "awr_grad_norm_scratch": ([_L], C.c_int64),
+    "awr_grad_norm": ([_P, _P, _L, _F, _D, _P, _P, _P, _P], C.c_int),
     "awr_pack_weight": ([_P, _I, _I, _I, _I, _I, _I, _P, _P], C.c_int),
     "awr_unpack_wgrad": ([_P, _I, _I, _I, _I, _P, _I, _P], C.c_int),
     "awr_pack_weights_batched": ([_P, _I, _L, _P], C.c_int),

@@ -39,6 +39,11 @@ _MI355X = dict(use_hipgraph=False,    # True: replay each step as one hipGraph (
                test_loss=False,       # True: Trainer.test also computes the validation loss of test.py:73-88 (coord_weight / dense_weight, the mean over the
                                       # batches of the per-batch mean) in the same pass over the dense map that decodes the joints, and logs it in a
                                       # second line (InferEngine(loss_weights=...)).  False = joints only
+               accum_steps=1,         # k > 1: gradient accumulation -- k micro-batches of batch_size per optimiser step, each weighing 1/k; a window the epoch leaves
+                                      # partly filled is applied at its end (TrainEngine(accum_steps=...), flush())
+               clip_grad_norm=None,   # a finite number > 0: the optimiser applies torch's clip_grad_norm_ coefficient to the global gradient norm, measured and
+                                      # applied on the device (TrainEngine(clip_grad_norm=...)); the print_freq lines gain [grad norm: ...].  None = no clipping
+               log_grad_norm=False,   # True: measure the gradient norm without clipping and add [grad norm: ...] to the print_freq lines
                test_loss_stages="last")   # "last": the stage the training loss supervises (what the [train loss] lines report) | "all": the sum over the
                                       # Hourglass stacks, as test.py:74-80 adds them up.  Only read with test_loss = True
 
@@ -62,6 +67,13 @@ class Config(object):
             raise ValueError("test_loss is False or True, not %r" % (self.test_loss,))
         if not (isinstance(self.test_loss_stages, str) and self.test_loss_stages in ("last", "all")):
             raise ValueError("test_loss_stages is \"last\" or \"all\", not %r" % (self.test_loss_stages,))
+        if isinstance(self.accum_steps, bool) or not isinstance(self.accum_steps, int) or self.accum_steps < 1:
+            raise ValueError("accum_steps is an int >= 1, not %r" % (self.accum_steps,))
+        c = self.clip_grad_norm
+        if c is not None and (isinstance(c, bool) or not isinstance(c, (int, float)) or not (0 < c < float("inf"))):
+            raise ValueError("clip_grad_norm is None or a finite number > 0, not %r" % (c,))
+        if not isinstance(self.log_grad_norm, bool):
+            raise ValueError("log_grad_norm is False or True, not %r" % (self.log_grad_norm,))
         if self.dataset not in _DATASETS:
             raise ValueError("dataset must be one of %s" % sorted(_DATASETS))
         for k, v in zip(_DERIVED, _DATASETS[self.dataset]):

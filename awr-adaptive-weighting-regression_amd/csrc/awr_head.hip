@@ -785,13 +785,21 @@ __global__ void loss_finalize_kernel(double* acc, int n, float* out, int fixed_p
 // ------------------------------------------------------------------------------------------
 // optimisers over flat arenas (torch.optim.Adam / SGD single-tensor update rules)
 // ------------------------------------------------------------------------------------------
-__global__ __launch_bounds__(256) void adam_kernel(float* __restrict__ p, const float* __restrict__ g, float* __restrict__ m,
-                                                   float* __restrict__ v, int64_t n4, int64_t n, float one_minus_b1, float b2,
-                                                   float one_minus_b2, float eps, float wd, float step_size, float bc2_sqrt,
-                                                   float gscale) {
+// One body for both forms of each rule.  HAS_G2: the gradient element is the float32 sum g[i] + g2[i] (the accumulation window's arena);
+// HAS_DS: the scale is the float32 product gscale * dev_scale[0] (the clip coefficient awr_grad_norm left on the device).  Everything after
+// the gradient load is the same instruction sequence in every instantiation (this file is compiled with -ffp-contract=off).
+template <bool HAS_G2, bool HAS_DS>
+__device__ __forceinline__ void adam_body(float* p, const float* g, float* m, float* v, int64_t n4, int64_t n, float one_minus_b1, float b2,
+                                          float one_minus_b2, float eps, float wd, float step_size, float bc2_sqrt, float gscale,
+                                          const float* g2, const float* dev_scale) {      // (the kernels' own parameters carry __restrict__)
+    if constexpr (HAS_DS) gscale = gscale * dev_scale[0];
     const int64_t i4 = (int64_t)blockIdx.x * 256 + threadIdx.x;
     if (i4 < n4) {
         float4 pp = ld4(p + i4 * 4), gg = ld4(g + i4 * 4), mm = ld4(m + i4 * 4), vv = ld4(v + i4 * 4);
+        if constexpr (HAS_G2) {
+            const float4 hh = ld4(g2 + i4 * 4);
+            gg.x = gg.x + hh.x; gg.y = gg.y + hh.y; gg.z = gg.z + hh.z; gg.w = gg.w + hh.w;
+        }
         float* pa = &pp.x; float* ga = &gg.x; float* ma = &mm.x; float* va = &vv.x;
 #pragma unroll
         for (int k = 0; k < 4; ++k) {
@@ -807,7 +815,9 @@ __global__ __launch_bounds__(256) void adam_kernel(float* __restrict__ p, const 
     // scalar tail (n not a multiple of 4)
     if (blockIdx.x == 0 && threadIdx.x < (n - n4 * 4)) {
         const int64_t i = n4 * 4 + threadIdx.x;
-        float gr = g[i] * gscale;
+        float gr = g[i];
+        if constexpr (HAS_G2) gr = gr + g2[i];
+        gr = gr * gscale;
         if (wd != 0.f) gr = gr + wd * p[i];
         const float mk = m[i] + (gr - m[i]) * one_minus_b1;
         const float vk = v[i] * b2 + one_minus_b2 * (gr * gr);
@@ -816,15 +826,133 @@ __global__ __launch_bounds__(256) void adam_kernel(float* __restrict__ p, const 
     }
 }
 
-__global__ __launch_bounds__(256) void sgd_kernel(float* __restrict__ p, const float* __restrict__ g, float* __restrict__ buf, int64_t n,
-                                                  float lr, float mom, float wd, int first, float gscale) {
+__global__ __launch_bounds__(256) void adam_kernel(float* __restrict__ p, const float* __restrict__ g, float* __restrict__ m,
+                                                   float* __restrict__ v, int64_t n4, int64_t n, float one_minus_b1, float b2,
+                                                   float one_minus_b2, float eps, float wd, float step_size, float bc2_sqrt,
+                                                   float gscale) {
+    adam_body<false, false>(p, g, m, v, n4, n, one_minus_b1, b2, one_minus_b2, eps, wd, step_size, bc2_sqrt, gscale, nullptr, nullptr);
+}
+
+template <bool HAS_G2, bool HAS_DS>
+__global__ __launch_bounds__(256) void adam_dev_kernel(float* __restrict__ p, const float* __restrict__ g, const float* __restrict__ g2,
+                                                       const float* __restrict__ dev_scale, float* __restrict__ m, float* __restrict__ v,
+                                                       int64_t n4, int64_t n, float one_minus_b1, float b2, float one_minus_b2, float eps,
+                                                       float wd, float step_size, float bc2_sqrt, float gscale) {
+    adam_body<HAS_G2, HAS_DS>(p, g, m, v, n4, n, one_minus_b1, b2, one_minus_b2, eps, wd, step_size, bc2_sqrt, gscale, g2, dev_scale);
+}
+
+template <bool HAS_G2, bool HAS_DS>
+__device__ __forceinline__ void sgd_body(float* p, const float* g, const float* g2, const float* dev_scale, float* buf, int64_t n, float lr,
+                                         float mom, float wd, int first, float gscale) {
     const int64_t i = (int64_t)blockIdx.x * 256 + threadIdx.x;
     if (i >= n) return;
-    float gr = g[i] * gscale;
+    if constexpr (HAS_DS) gscale = gscale * dev_scale[0];
+    float ge = g[i];
+    if constexpr (HAS_G2) ge = ge + g2[i];
+    float gr = ge * gscale;
     if (wd != 0.f) gr = gr + wd * p[i];
     const float b = first ? gr : buf[i] * mom + gr;
     buf[i] = b;
     p[i] = p[i] - lr * b;
+}
+
+__global__ __launch_bounds__(256) void sgd_kernel(float* __restrict__ p, const float* __restrict__ g, float* __restrict__ buf, int64_t n,
+                                                  float lr, float mom, float wd, int first, float gscale) {
+    sgd_body<false, false>(p, g, nullptr, nullptr, buf, n, lr, mom, wd, first, gscale);
+}
+
+template <bool HAS_G2, bool HAS_DS>
+__global__ __launch_bounds__(256) void sgd_dev_kernel(float* __restrict__ p, const float* __restrict__ g, const float* __restrict__ g2,
+                                                      const float* __restrict__ dev_scale, float* __restrict__ buf, int64_t n, float lr,
+                                                      float mom, float wd, int first, float gscale) {
+    sgd_body<HAS_G2, HAS_DS>(p, g, g2, dev_scale, buf, n, lr, mom, wd, first, gscale);
+}
+
+// ------------------------------------------------------------------------------------------
+// gradient accumulation and the global gradient norm (between the gradient arena and the optimiser)
+// ------------------------------------------------------------------------------------------
+// acc = g (first micro-step of a window) or acc = acc + g: one float32 add per element, HBM-bound
+__global__ __launch_bounds__(256) void grad_accumulate_kernel(float* __restrict__ acc, const float* __restrict__ g, int64_t n4, int64_t n,
+                                                              int first) {
+    const int64_t i4 = (int64_t)blockIdx.x * 256 + threadIdx.x;
+    if (i4 < n4) {
+        float4 gg = ld4(g + i4 * 4);
+        if (!first) {
+            const float4 aa = ld4(acc + i4 * 4);
+            gg.x = aa.x + gg.x; gg.y = aa.y + gg.y; gg.z = aa.z + gg.z; gg.w = aa.w + gg.w;
+        }
+        st4(acc + i4 * 4, gg);
+    }
+    if (blockIdx.x == 0 && threadIdx.x < (n - n4 * 4)) {
+        const int64_t i = n4 * 4 + threadIdx.x;
+        acc[i] = first ? g[i] : acc[i] + g[i];
+    }
+}
+
+constexpr int GRAD_NORM_MAX_BLOCKS = 1024;      // float64 partials of awr_grad_norm (awr_grad_norm_scratch: 8 KB)
+
+// the grid of the partial pass: a function of n alone
+static inline int grad_norm_blocks(int64_t n) {
+    const int64_t b = (n / 4 + 255) / 256;
+    return (int)(b < 1 ? 1 : b > GRAD_NORM_MAX_BLOCKS ? GRAD_NORM_MAX_BLOCKS : b);
+}
+
+// partial[block] = sum over the block's elements of (double)(float)(g[i] + g2[i])^2.  Every thread adds its own elements in index order, the
+// 256 thread sums are added pairwise in LDS in a fixed tree: no atomics, so the partial depends on the input and n alone.  (Four float4 loads
+// in flight per thread instead of one were measured no faster: the stream runs at the copy rate as it is)
+template <bool HAS_G2>
+__global__ __launch_bounds__(256) void grad_norm_partial_kernel(const float* __restrict__ g, const float* __restrict__ g2, int64_t n4, int64_t n,
+                                                                double* __restrict__ partial) {
+    __shared__ double s_sum[256];
+    double t = 0.0;
+    const int64_t stride = (int64_t)gridDim.x * 256;
+    for (int64_t i4 = (int64_t)blockIdx.x * 256 + threadIdx.x; i4 < n4; i4 += stride) {
+        float4 gg = ld4(g + i4 * 4);
+        if constexpr (HAS_G2) {
+            const float4 hh = ld4(g2 + i4 * 4);
+            gg.x = gg.x + hh.x; gg.y = gg.y + hh.y; gg.z = gg.z + hh.z; gg.w = gg.w + hh.w;
+        }
+        t += (double)gg.x * (double)gg.x;
+        t += (double)gg.y * (double)gg.y;
+        t += (double)gg.z * (double)gg.z;
+        t += (double)gg.w * (double)gg.w;
+    }
+    if (blockIdx.x == 0 && threadIdx.x < (n - n4 * 4)) {
+        const int64_t i = n4 * 4 + threadIdx.x;
+        float ge = g[i];
+        if constexpr (HAS_G2) ge = ge + g2[i];
+        t += (double)ge * (double)ge;
+    }
+    s_sum[threadIdx.x] = t;
+    __syncthreads();
+#pragma unroll
+    for (int o = 128; o > 0; o >>= 1) {
+        if ((int)threadIdx.x < o) s_sum[threadIdx.x] += s_sum[threadIdx.x + o];
+        __syncthreads();
+    }
+    if (threadIdx.x == 0) partial[blockIdx.x] = s_sum[0];
+}
+
+// one workgroup: the partials are added in index order by one thread; norm = grad_scale * sqrt(sum); scale = torch's clip_grad_norm_
+// coefficient max_norm / (norm + 1e-6) clamped to 1 (max_norm <= 0 or +inf: 1), NaN for a norm that is not finite
+__global__ __launch_bounds__(256) void grad_norm_finalize_kernel(const double* __restrict__ partial, int nparts, float grad_scale, double max_norm,
+                                                                 double* __restrict__ norm_out, float* __restrict__ scale_out) {
+    __shared__ double s_part[GRAD_NORM_MAX_BLOCKS];
+    for (int i = threadIdx.x; i < nparts; i += 256) s_part[i] = partial[i];
+    __syncthreads();
+    if (threadIdx.x != 0) return;
+    double t = 0.0;
+    for (int i = 0; i < nparts; ++i) t += s_part[i];
+    const double norm = (double)grad_scale * sqrt(t);
+    norm_out[0] = norm;
+    float scale = 1.0f;
+    if (!isfinite(norm)) {
+        scale = __builtin_nanf("");
+    } else if (max_norm > 0.0 && max_norm != (double)INFINITY) {
+        const double c = max_norm / (norm + 1e-6);
+        scale = c < 1.0 ? (float)c : 1.0f;
+    }
+    scale_out[0] = scale;
 }
 
 }  // namespace awr
@@ -1113,6 +1241,75 @@ int awr_sgd_step(float* p, const float* g, float* buf, int64_t n, float lr, floa
     hipLaunchKernelGGL(sgd_kernel, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, as_stream(stream), p, g, buf, n, lr, momentum,
                        weight_decay, step == 1 ? 1 : 0, grad_scale);
     return check_launch("sgd_kernel");
+}
+
+int awr_adam_step_dev(float* p, const float* g, const float* g2, const float* dev_scale, float* m, float* v, int64_t n, float lr, float beta1,
+                      float beta2, float eps, float weight_decay, int64_t step, float grad_scale, void* stream) {
+    AWR_REQUIRE(p && g && m && v && n > 0 && step >= 1, "adam_step_dev: bad arguments");
+    AWR_REQUIRE((((uintptr_t)p | (uintptr_t)g | (uintptr_t)g2 | (uintptr_t)m | (uintptr_t)v) & 15) == 0,
+                "adam_step_dev: arenas must be 16-byte aligned");
+    AWR_REQUIRE(((uintptr_t)dev_scale & 3) == 0, "adam_step_dev: dev_scale must be 4-byte aligned");
+    const double bc1 = 1.0 - pow((double)beta1, (double)step), bc2 = 1.0 - pow((double)beta2, (double)step);
+    const int64_t n4 = n / 4;
+    const int64_t blocks = (n4 + 255) / 256 > 0 ? (n4 + 255) / 256 : 1;
+#define AWR_ADAM_DEV(G2, DS)                                                                                                          \
+    hipLaunchKernelGGL((adam_dev_kernel<G2, DS>), dim3((unsigned)blocks), dim3(256), 0, as_stream(stream), p, g, g2, dev_scale, m, v, n4, n, \
+                       (float)(1.0 - (double)beta1), beta2, (float)(1.0 - (double)beta2), eps, weight_decay, (float)((double)lr / bc1),       \
+                       (float)sqrt(bc2), grad_scale)
+    if (g2 && dev_scale) AWR_ADAM_DEV(true, true);
+    else if (g2) AWR_ADAM_DEV(true, false);
+    else if (dev_scale) AWR_ADAM_DEV(false, true);
+    else AWR_ADAM_DEV(false, false);
+#undef AWR_ADAM_DEV
+    return check_launch("adam_dev_kernel");
+}
+
+int awr_sgd_step_dev(float* p, const float* g, const float* g2, const float* dev_scale, float* buf, int64_t n, float lr, float momentum,
+                     float weight_decay, int64_t step, float grad_scale, void* stream) {
+    AWR_REQUIRE(p && g && buf && n > 0 && step >= 1, "sgd_step_dev: bad arguments");
+    AWR_REQUIRE((((uintptr_t)p | (uintptr_t)g | (uintptr_t)g2 | (uintptr_t)dev_scale | (uintptr_t)buf) & 3) == 0,
+                "sgd_step_dev: arenas must be 4-byte aligned");
+    const dim3 grid((unsigned)((n + 255) / 256));
+#define AWR_SGD_DEV(G2, DS)                                                                                                       \
+    hipLaunchKernelGGL((sgd_dev_kernel<G2, DS>), grid, dim3(256), 0, as_stream(stream), p, g, g2, dev_scale, buf, n, lr, momentum, \
+                       weight_decay, step == 1 ? 1 : 0, grad_scale)
+    if (g2 && dev_scale) AWR_SGD_DEV(true, true);
+    else if (g2) AWR_SGD_DEV(true, false);
+    else if (dev_scale) AWR_SGD_DEV(false, true);
+    else AWR_SGD_DEV(false, false);
+#undef AWR_SGD_DEV
+    return check_launch("sgd_dev_kernel");
+}
+
+int awr_grad_accumulate(float* acc, const float* g, int64_t n, int first, void* stream) {
+    AWR_REQUIRE(acc && g && n > 0, "grad_accumulate: bad arguments");
+    AWR_REQUIRE((((uintptr_t)acc | (uintptr_t)g) & 15) == 0, "grad_accumulate: arenas must be 16-byte aligned");
+    const int64_t n4 = n / 4;
+    const int64_t blocks = (n4 + 255) / 256 > 0 ? (n4 + 255) / 256 : 1;
+    hipLaunchKernelGGL(grad_accumulate_kernel, dim3((unsigned)blocks), dim3(256), 0, as_stream(stream), acc, g, n4, n, first ? 1 : 0);
+    return check_launch("grad_accumulate_kernel");
+}
+
+int64_t awr_grad_norm_scratch(int64_t n) {
+    return n > 0 ? (int64_t)grad_norm_blocks(n) * (int64_t)sizeof(double) : 0;
+}
+
+int awr_grad_norm(const float* g, const float* g2, int64_t n, float grad_scale, double max_norm, double* scratch, double* norm_out,
+                  float* scale_out, void* stream) {
+    AWR_REQUIRE(g && scratch && norm_out && scale_out && n > 0, "grad_norm: bad arguments");
+    AWR_REQUIRE((((uintptr_t)g | (uintptr_t)g2) & 15) == 0, "grad_norm: arenas must be 16-byte aligned");
+    AWR_REQUIRE((((uintptr_t)scratch | (uintptr_t)norm_out) & 7) == 0 && ((uintptr_t)scale_out & 3) == 0,
+                "grad_norm: scratch / norm_out must be 8-byte aligned, scale_out 4-byte aligned");
+    AWR_REQUIRE(!(max_norm != max_norm), "grad_norm: max_norm is NaN");
+    const int64_t n4 = n / 4;
+    const int blocks = grad_norm_blocks(n);
+    if (g2) hipLaunchKernelGGL(grad_norm_partial_kernel<true>, dim3((unsigned)blocks), dim3(256), 0, as_stream(stream), g, g2, n4, n, scratch);
+    else hipLaunchKernelGGL(grad_norm_partial_kernel<false>, dim3((unsigned)blocks), dim3(256), 0, as_stream(stream), g, g2, n4, n, scratch);
+    int rc = check_launch("grad_norm_partial_kernel");
+    if (rc != AWR_OK) return rc;
+    hipLaunchKernelGGL(grad_norm_finalize_kernel, dim3(1), dim3(256), 0, as_stream(stream), scratch, blocks, grad_scale, max_norm, norm_out,
+                       scale_out);
+    return check_launch("grad_norm_finalize_kernel");
 }
 
 }  // extern "C"

@@ -133,10 +133,43 @@ class _WinogradAuto:
             WA.store_decision(self._wino_key, mode, timings, n, collapsed)
 
 
+def _grad_options(accum_steps, clip_grad_norm, grad_norm):
+    """TrainEngine's accum_steps / clip_grad_norm / grad_norm, checked (host arithmetic only) -> (accum_steps, max_norm or None, grad_norm)."""
+    import math
+    if isinstance(accum_steps, bool) or not isinstance(accum_steps, int):
+        raise TypeError("accum_steps is an int >= 1, not %r" % (accum_steps,))
+    if accum_steps < 1:
+        raise ValueError("accum_steps is an int >= 1, not %r" % (accum_steps,))
+    if clip_grad_norm is not None:
+        if isinstance(clip_grad_norm, bool) or not isinstance(clip_grad_norm, (int, float)):
+            raise TypeError("clip_grad_norm is None or a finite number > 0, not %r" % (clip_grad_norm,))
+        if not (math.isfinite(clip_grad_norm) and clip_grad_norm > 0):
+            raise ValueError("clip_grad_norm is None or a finite number > 0, not %r" % (clip_grad_norm,))
+        clip_grad_norm = float(clip_grad_norm)
+    if not isinstance(grad_norm, bool):
+        raise TypeError("grad_norm is True or False, not %r" % (grad_norm,))
+    return accum_steps, clip_grad_norm, grad_norm
+
+
+class _GradWindow:
+    """What an engine and its ragged-batch children share between the gradient arena and the optimiser: the accumulation arena, the number
+    of micro-steps pending in it, and the device words awr_grad_norm writes."""
+
+    def __init__(self, n, dev, accumulate, norm):
+        self.pending = 0
+        self.acc = torch.zeros(n, device=dev) if accumulate else None
+        self.norm = self.scale = self.scratch = None
+        if norm:
+            self.norm = torch.full((1,), float("nan"), device=dev, dtype=torch.float64)          # (NaN: no applying step yet)
+            self.scale = torch.ones(1, device=dev)
+            self.scratch = torch.zeros(int(L.lib.awr_grad_norm_scratch(n)) // 8, device=dev, dtype=torch.float64)
+
+
 class TrainEngine(_WinogradAuto):
     def __init__(self, net, batch_size, img_size, kernel_size, coord_weight=0.0, dense_weight=1.0, lr=1e-3, weight_decay=0.0,
                  optimizer="adam", momentum=0.9, process_group=None, use_graph=False, n_buckets=4, autotune=True, wgrad_streams=2,
-                 nhwc_boundary=None, trace_buckets=False, native_rccl=None, accum="auto", winograd=None, split_k=False, _share=None):
+                 nhwc_boundary=None, trace_buckets=False, native_rccl=None, accum="auto", winograd=None, split_k=False, accum_steps=1,
+                 clip_grad_norm=None, grad_norm=False, _share=None):
         """split_k: False (default: the process-wide mode, off unless awr_amd.set_train_split_k / $AWR_TRAIN_SPLIT_K set it) | True -- the small
         forward / data-gradient launches of this engine's plan (few workgroups, a long K loop: low batches, the deep levels) split their K loop
         and take the BatchNorm statistics / fused BatchNorm-backward reductions from the reduce kernel (include/awr_hip.h: awr_set_train_split_k;
@@ -148,8 +181,18 @@ class TrainEngine(_WinogradAuto):
         winograd: None (the process-wide mode, awr_amd.set_conv_winograd) | False | True ("forward") | "forward+wgrad" | "full" -- Winograd F(2x2, 3x3)
         forward, or forward + weight gradient, or forward + data gradient + weight gradient, of the eligible stride-1 3x3 convolutions (include/awr_hip.h)
         | "auto" -- the fastest of those for this plan, timed by compile() (winograd_auto.py); `winograd_mode` names what the plan runs,
-        `winograd_timings` holds the candidates' ms per step."""
+        `winograd_timings` holds the candidates' ms per step.
+        accum_steps: 1 (default) | k > 1 -- gradient accumulation: every step() is a micro-step; micro-steps 1 .. k-1 of a
+        window add their gradient into an engine-owned arena (awr_grad_accumulate) and leave the parameters and `step_count` alone, the k-th
+        applies the sum with grad_scale = 1 / (world * k).  EVERY micro-step weighs 1/k, whatever its batch size (a ragged last batch counts
+        like a full one).  `micro_step` = micro-steps pending in the window; flush() applies a partly filled window.
+        clip_grad_norm: None (default) | a finite number > 0 -- every applying step measures the global L2 norm of the gradient the optimiser
+        is about to read (awr_grad_norm: after the all-reduce, accumulated and averaged) and the optimiser multiplies by torch's
+        clip_grad_norm_ coefficient, read from the device.  grad_norm: True measures the norm without clipping.  With either, `grad_norm`
+        (float64, one element) and `clip_scale` (float32, one element) are device tensors valid until the next applying step; nothing
+        synchronises.  With all three at their defaults the step issues the launches it always did."""
         self._split_k = _split_k_flag(split_k)
+        self.accum_steps, self._max_norm, self._want_norm = _grad_options(accum_steps, clip_grad_norm, grad_norm)
         if not next(net.parameters()).is_cuda:
             raise L.AwrError("TrainEngine needs the network on the GPU")
         self.net, self.B, self.H = net, batch_size, img_size
@@ -194,11 +237,12 @@ class TrainEngine(_WinogradAuto):
         self.losses = torch.zeros(3, device=dev)          # [coord, dense, total]
         n = net.n_active
         self._children = {}
-        if _share is not None:          # ragged-batch child: optimiser state lives in the parent engine
-            self.m, self.v = _share.m, _share.v
+        if _share is not None:          # ragged-batch child: optimiser state and accumulation window live in the parent engine
+            self.m, self.v, self._win = _share.m, _share.v, _share._win
         else:
             self.m = torch.zeros(n, device=dev)
             self.v = torch.zeros(n, device=dev) if optimizer == "adam" else None
+            self._win = _GradWindow(n, dev, self.accum_steps > 1, self._want_norm or self._max_norm is not None)
         self.step_count = 0
         self.use_graph = use_graph
         self.graph = None
@@ -355,17 +399,58 @@ class TrainEngine(_WinogradAuto):
         self.acc.zero_()          # the passes above accumulated into the loss accumulators
         return res
 
-    def _optimizer(self):
+    def _optimizer(self, g=None, g2=None, micro=1):
+        """The optimiser launch of an applying step over g (default: the gradient arena) [+ g2], averaged over `micro` micro-steps."""
         net = self.net
         n = net.n_active
         s = L.stream()
         scale = self.sync.grad_scale
+        win = self._win
+        if g is None and g2 is None and micro == 1 and win.norm is None:      # the defaults: the entry points and launches of a plain step
+            if self.opt == "adam":
+                L.call("awr_adam_step", L.ptr(net.flat_params()), L.ptr(net.flat_grads()), L.ptr(self.m), L.ptr(self.v), n, self.lr, 0.9, 0.999,
+                       1e-8, self.wd, self.step_count, scale, s)
+            else:
+                L.call("awr_sgd_step", L.ptr(net.flat_params()), L.ptr(net.flat_grads()), L.ptr(self.m), n, self.lr, self.momentum, self.wd,
+                       self.step_count, scale, s)
+            return
+        g = net.flat_grads() if g is None else g
+        if micro > 1:
+            scale = 1.0 / (self.world * micro)
+        if win.norm is not None:      # norm of what the optimiser is about to read (data parallel: the all-reduce waits are behind us)
+            L.call("awr_grad_norm", L.ptr(g), L.ptr(g2), n, scale, self._max_norm or 0.0, L.ptr(win.scratch), L.ptr(win.norm), L.ptr(win.scale), s)
         if self.opt == "adam":
-            L.call("awr_adam_step", L.ptr(net.flat_params()), L.ptr(net.flat_grads()), L.ptr(self.m), L.ptr(self.v), n, self.lr, 0.9, 0.999,
-                   1e-8, self.wd, self.step_count, scale, s)
+            L.call("awr_adam_step_dev", L.ptr(net.flat_params()), L.ptr(g), L.ptr(g2), L.ptr(win.scale), L.ptr(self.m), L.ptr(self.v), n, self.lr,
+                   0.9, 0.999, 1e-8, self.wd, self.step_count, scale, s)
         else:
-            L.call("awr_sgd_step", L.ptr(net.flat_params()), L.ptr(net.flat_grads()), L.ptr(self.m), n, self.lr, self.momentum, self.wd,
-                   self.step_count, scale, s)
+            L.call("awr_sgd_step_dev", L.ptr(net.flat_params()), L.ptr(g), L.ptr(g2), L.ptr(win.scale), L.ptr(self.m), n, self.lr, self.momentum,
+                   self.wd, self.step_count, scale, s)
+
+    @property
+    def micro_step(self):
+        """Micro-steps pending in the accumulation window (a host int; always 0 with accum_steps == 1)."""
+        return self._win.pending
+
+    def _norm_tensor(self, name):
+        t = getattr(self._win, name)
+        if t is None:
+            raise L.AwrError("TrainEngine was built without clip_grad_norm / grad_norm=True: the gradient norm is not measured")
+        return t
+
+    grad_norm = property(lambda self: self._norm_tensor("norm"), doc="(1,) float64 device tensor: grad_scale * |g| of the last applying step")
+    clip_scale = property(lambda self: self._norm_tensor("scale"), doc="(1,) float32 device tensor: the coefficient the last applying step multiplied by")
+
+    def flush(self):
+        """Apply a partly filled accumulation window: one optimiser step over the accumulator with grad_scale = 1 / (world * pending).
+        Does nothing when no micro-step is pending.  Data parallel: every rank calls it at the same point (no collective is issued: every
+        micro-step's gradient was all-reduced when it ran)."""
+        win = self._win
+        if win.pending == 0:
+            return
+        self.step_count += 1
+        self._optimizer(g=win.acc, micro=win.pending)
+        win.pending = 0
+        self.net.weights_changed()
 
     def _ragged(self, b):
         """Engine for a smaller (last-of-epoch) batch: its own static plan, the SAME optimiser state and step counter
@@ -376,14 +461,17 @@ class TrainEngine(_WinogradAuto):
                 self.compile()
             eng = TrainEngine(self.net, b, self.H, self.ks, self.cw, self.dw, self.lr, self.wd, self.opt, self.momentum,
                               process_group=self.sync.pg, use_graph=False, n_buckets=self._n_buckets, autotune=False,
-                              wgrad_streams=0, accum=self._accum, winograd=self._winograd, split_k=self._split_k, _share=self)
+                              wgrad_streams=0, accum=self._accum, winograd=self._winograd, split_k=self._split_k,
+                              accum_steps=self.accum_steps, clip_grad_norm=self._max_norm, grad_norm=self._want_norm, _share=self)
             self._children[b] = eng
         eng.lr, eng.step_count = self.lr, self.step_count
         return eng
 
     def step(self, img, jt_uvd_gt):
         """One optimisation step on this rank's shard.  Returns (losses[coord,dense,total], jt_uvd_pred)
-        as device tensors that are valid until the next step; nothing is synchronised."""
+        as device tensors that are valid until the next step; nothing is synchronised.
+        accum_steps = k > 1: one micro-step -- forward, losses, backward, BatchNorm statistics and (data parallel) the gradient exchange as
+        ever; the first k-1 calls of a window end in awr_grad_accumulate, the k-th in the optimiser."""
         if img.shape[0] != self.B:
             if not 0 < img.shape[0] < self.B:
                 raise L.AwrError("TrainEngine built for batches of %d got %d images" % (self.B, img.shape[0]))
@@ -417,8 +505,17 @@ class TrainEngine(_WinogradAuto):
             for w in self._works:           # compute stream waits for the bucket all-reduces before the optimiser
                 w.wait()
             self._works.clear()
+        win = self._win
+        if win.pending + 1 < self.accum_steps:          # micro-steps 1 .. k-1: parameters and step_count stay
+            L.call("awr_grad_accumulate", L.ptr(win.acc), L.ptr(self.net.flat_grads()), self.net.n_active, 1 if win.pending == 0 else 0, L.stream())
+            win.pending += 1
+            return self.losses, self.jt_pred
         self.step_count += 1
-        self._optimizer()
+        if win.pending:
+            self._optimizer(g2=win.acc, micro=win.pending + 1)
+            win.pending = 0
+        else:
+            self._optimizer()
         self.net.weights_changed()
         return self.losses, self.jt_pred
 
@@ -466,6 +563,9 @@ class TrainEngine(_WinogradAuto):
 
     # ---- optimizer state in torch.optim layout (checkpoint compatibility, train.py:165-170) ----------------
     def optimizer_state_dict(self):
+        if self._win.pending:
+            raise L.AwrError("optimizer_state_dict() with %d micro-step(s) pending in the accumulation window: call flush() first (a checkpoint "
+                             "cannot hold a partly filled window)" % self._win.pending)
         net = self.net
         names = [k for k, _, kind in net._layout if kind in ("conv_w", "deconv_w", "conv_b", "bn_w", "bn_b")]
         state = {}
@@ -849,7 +949,10 @@ class Trainer:
         self.engine = TrainEngine(self.net, config.batch_size, config.img_size, config.kernel_size, config.coord_weight, config.dense_weight,
                                   config.lr, config.weight_decay, config.optimizer, process_group=process_group,
                                   use_graph=getattr(config, "use_hipgraph", False), accum=getattr(config, "accum", "auto"),
-                                  winograd=getattr(config, "winograd", None), split_k=getattr(config, "train_split_k", False))
+                                  winograd=getattr(config, "winograd", None), split_k=getattr(config, "train_split_k", False),
+                                  accum_steps=getattr(config, "accum_steps", 1), clip_grad_norm=getattr(config, "clip_grad_norm", None),
+                                  grad_norm=bool(getattr(config, "log_grad_norm", False)))
+        self._log_norm = bool(getattr(config, "log_grad_norm", False)) or getattr(config, "clip_grad_norm", None) is not None
         # winograd="auto": the training step's choice is logged once; the scoring engine's is reused by every later test pass
         self._wino_logged, self._infer_winograd = False, None
         if config.load_model and os.path.exists(config.load_model):
@@ -932,11 +1035,14 @@ class Trainer:
                 if (ii + 1) % cfg.print_freq == 0:
                     l = meter()
                     last_mean = l[2]
-                    self._msg("[epoch: {:02d}][train loss: {:.5f}][offset_loss: {:.5f}][coord_loss: {:.5f}]".format(epoch, l[2], l[1], l[0]))
+                    # (log_grad_norm / clip_grad_norm: the norm of the last applying step, read where the losses were just read)
+                    norm = "[grad norm: {:.5f}]".format(float(eng.grad_norm)) if self._log_norm else ""
+                    self._msg("[epoch: {:02d}][train loss: {:.5f}][offset_loss: {:.5f}][coord_loss: {:.5f}]".format(epoch, l[2], l[1], l[0]) + norm)
                     lsum.zero_()
                     lcnt = 0
                     drain()
             drain()
+            eng.flush()          # accum_steps: a window the epoch left partly filled is applied before the scheduler, the test pass and the checkpoint
             # rank-uniform metric: every rank must feed the SAME number to its LR scheduler, or the replicas would step the
             # (identical, all-reduced) gradients with different learning rates and silently diverge
             if dev_eval:

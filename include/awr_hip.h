@@ -161,6 +161,28 @@ int awr_adam_step(float* p, const float* g, float* m, float* v, int64_t n, float
 /* SGD with momentum (train.py:68-69): buf = mom*buf + g (buf = g on step 1); p -= lr*buf */
 int awr_sgd_step(float* p, const float* g, float* buf, int64_t n, float lr, float momentum,
                  float weight_decay, int64_t step, float grad_scale, void* stream);
+/* The two rules above with a second gradient source and a scale that lives on the device.  g2 (may be NULL): the
+ * gradient element is the float32 sum g[i] + g2[i].  dev_scale (may be NULL): one float on the device; the scale is the float32 product
+ * grad_scale * dev_scale[0].  Nothing else differs: every form is one kernel body, and with both NULL the result is bit for bit what
+ * awr_adam_step / awr_sgd_step write.  awr_adam_step_dev needs g2 16-byte aligned like the other arenas. */
+int awr_adam_step_dev(float* p, const float* g, const float* g2, const float* dev_scale, float* m, float* v, int64_t n, float lr,
+                      float beta1, float beta2, float eps, float weight_decay, int64_t step, float grad_scale, void* stream);
+int awr_sgd_step_dev(float* p, const float* g, const float* g2, const float* dev_scale, float* buf, int64_t n, float lr, float momentum,
+                     float weight_decay, int64_t step, float grad_scale, void* stream);
+/* Gradient accumulation: acc[i] = g[i] (first != 0: the first micro-step of a window) or acc[i] = acc[i] + g[i], one float32 add per
+ * element.  Both arenas 16-byte aligned. */
+int awr_grad_accumulate(float* acc, const float* g, int64_t n, int first, void* stream);
+/* Global gradient norm and clip coefficient, left on the device (nothing synchronises):
+ *   norm_out[0]  = (double)grad_scale * sqrt(sum_i (double)(float)(g[i] + g2[i])^2)      g2 may be NULL; the add is the float32 add the
+ *                  optimiser kernel makes, the squares and the sum are float64
+ *   scale_out[0] = 1.0f when max_norm <= 0 or +inf; otherwise, c = max_norm / (norm + 1e-6) in float64, c < 1 ? (float)c : 1.0f
+ *                  (torch.nn.utils.clip_grad_norm_'s coefficient).  A norm that is not finite gives NaN, whatever max_norm is.
+ * Two launches and no floating-point atomics: a grid that is a function of n alone writes one float64 partial per workgroup into
+ * scratch (awr_grad_norm_scratch(n) bytes, at most 8 KB), one workgroup adds the partials in index order.  Two calls on the same input
+ * leave bitwise equal results, and so do two data-parallel ranks that hold the same reduced gradient.  g / g2 16-byte aligned. */
+int64_t awr_grad_norm_scratch(int64_t n);
+int awr_grad_norm(const float* g, const float* g2, int64_t n, float grad_scale, double max_norm, double* scratch, double* norm_out,
+                  float* scale_out, void* stream);
 
 /* ------------------------------------------------------------------------------------------
  * Backbone building blocks (replace the torch.nn modules used by model/resnet_deconv.py:19-215
