@@ -122,6 +122,7 @@ _SIGS = {
     "awr_adam_step_dev": ([_P, _P, _P, _P, _P, _P, _L, _F, _F, _F, _F, _F, _L, _F, _P], C.c_int),
     "awr_sgd_step_dev": ([_P, _P, _P, _P, _P, _L, _F, _F, _F, _L, _F, _P], C.c_int),
     "awr_grad_accumulate": ([_P, _P, _L, _I, _P], C.c_int),
+    "awr_ema_update": ([_P, _P, _L, _F, _P], C.c_int),
     "awr_grad_norm_scratch": ([_L], C.c_int64),
     "awr_grad_norm": ([_P, _P, _L, _F, _D, _P, _P, _P, _P], C.c_int),
     "awr_pack_weight": ([_P, _I, _I, _I, _I, _I, _I, _P, _P], C.c_int),

@@ -44,6 +44,13 @@ _MI355X = dict(use_hipgraph=False,    # True: replay each step as one hipGraph (
                clip_grad_norm=None,   # a finite number > 0: the optimiser applies torch's clip_grad_norm_ coefficient to the global gradient norm, measured and
                                       # applied on the device (TrainEngine(clip_grad_norm=...)); the print_freq lines gain [grad norm: ...].  None = no clipping
                log_grad_norm=False,   # True: measure the gradient norm without clipping and add [grad norm: ...] to the print_freq lines
+               ema_decay=None,        # d in the open interval (0, 1), e.g. 0.999: an exponential moving average of the weights and BatchNorm statistics, kept on the
+                                      # device behind every optimiser step (TrainEngine(ema_decay=...)), scored by Trainer.test in a second pass
+                                      # ([test mpe ema ...]) and saved as "model_ema" / "ema_updates" next to "model".  None = no EMA, nothing changes
+               ema_warmup=True,       # True: the decay of update t is min(ema_decay, (1 + t) / (10 + t)) (the TF / timm rule) | False: ema_decay from the first update.
+                                      # Only read with ema_decay set
+               load_ema=False,        # True: config.load_model's "model_ema" is loaded as THE network instead of "model" (test.py on the averaged weights, or a
+                                      # run resumed from them); a checkpoint without that entry raises
                test_loss_stages="last")   # "last": the stage the training loss supervises (what the [train loss] lines report) | "all": the sum over the
                                       # Hourglass stacks, as test.py:74-80 adds them up.  Only read with test_loss = True
 
@@ -74,6 +81,13 @@ class Config(object):
             raise ValueError("clip_grad_norm is None or a finite number > 0, not %r" % (c,))
         if not isinstance(self.log_grad_norm, bool):
             raise ValueError("log_grad_norm is False or True, not %r" % (self.log_grad_norm,))
+        d = self.ema_decay
+        if d is not None and (isinstance(d, bool) or not isinstance(d, (int, float)) or not (0 < d < 1)):
+            raise ValueError("ema_decay is None or a number in the open interval (0, 1), not %r" % (d,))
+        if not isinstance(self.ema_warmup, bool):
+            raise ValueError("ema_warmup is False or True, not %r" % (self.ema_warmup,))
+        if not isinstance(self.load_ema, bool):
+            raise ValueError("load_ema is False or True, not %r" % (self.load_ema,))
         if self.dataset not in _DATASETS:
             raise ValueError("dataset must be one of %s" % sorted(_DATASETS))
         for k, v in zip(_DERIVED, _DATASETS[self.dataset]):

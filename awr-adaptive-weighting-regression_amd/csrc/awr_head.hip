@@ -889,7 +889,23 @@ __global__ __launch_bounds__(256) void grad_accumulate_kernel(float* __restrict_
     }
 }
 
-constexpr int GRAD_NORM_MAX_BLOCKS = 1024;      // float64 partials of awr_grad_norm (awr_grad_norm_scratch: 8 KB)
+// weight EMA: ema = ema + (src - ema) * w, the lerp form adam_body uses for exp_avg -- a subtract, a multiply and an add,
+// each rounded on its own (no contraction in this file).  src is only read.  Same traffic as grad_accumulate_kernel(first = 0): 12 B / element
+__global__ __launch_bounds__(256) void ema_update_kernel(float* __restrict__ ema, const float* __restrict__ src, int64_t n4, int64_t n, float w) {
+    const int64_t i4 = (int64_t)blockIdx.x * 256 + threadIdx.x;
+    if (i4 < n4) {
+        float4 ee = ld4(ema + i4 * 4);
+        const float4 ss = ld4(src + i4 * 4);
+        ee.x = ee.x + (ss.x - ee.x) * w; ee.y = ee.y + (ss.y - ee.y) * w; ee.z = ee.z + (ss.z - ee.z) * w; ee.w = ee.w + (ss.w - ee.w) * w;
+        st4(ema + i4 * 4, ee);
+    }
+    if (blockIdx.x == 0 && threadIdx.x < (n - n4 * 4)) {
+        const int64_t i = n4 * 4 + threadIdx.x;
+        ema[i] = ema[i] + (src[i] - ema[i]) * w;
+    }
+}
+
+constexpr int GRAD_NORM_MAX_BLOCKS = 1024;     // float64 partials of awr_grad_norm (awr_grad_norm_scratch: 8 KB)
 
 // the grid of the partial pass: a function of n alone
 static inline int grad_norm_blocks(int64_t n) {
@@ -1288,6 +1304,18 @@ int awr_grad_accumulate(float* acc, const float* g, int64_t n, int first, void* 
     const int64_t blocks = (n4 + 255) / 256 > 0 ? (n4 + 255) / 256 : 1;
     hipLaunchKernelGGL(grad_accumulate_kernel, dim3((unsigned)blocks), dim3(256), 0, as_stream(stream), acc, g, n4, n, first ? 1 : 0);
     return check_launch("grad_accumulate_kernel");
+}
+
+int awr_ema_update(float* ema, const float* src, int64_t n, float w, void* stream) {
+    AWR_REQUIRE(ema && src && n > 0, "ema_update: bad arguments");
+    AWR_REQUIRE((((uintptr_t)ema | (uintptr_t)src) & 15) == 0, "ema_update: arenas must be 16-byte aligned");
+    AWR_REQUIRE(w > 0.f && w <= 1.f, "ema_update: w must lie in (0, 1] (NaN is refused)");
+    const uintptr_t e0 = (uintptr_t)ema, s0 = (uintptr_t)src, bytes = (uintptr_t)n * sizeof(float);
+    AWR_REQUIRE(e0 + bytes <= s0 || s0 + bytes <= e0, "ema_update: ema and src overlap");
+    const int64_t n4 = n / 4;
+    const int64_t blocks = (n4 + 255) / 256 > 0 ? (n4 + 255) / 256 : 1;
+    hipLaunchKernelGGL(ema_update_kernel, dim3((unsigned)blocks), dim3(256), 0, as_stream(stream), ema, src, n4, n, w);
+    return check_launch("ema_update_kernel");
 }
 
 int64_t awr_grad_norm_scratch(int64_t n) {

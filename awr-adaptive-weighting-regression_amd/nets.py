@@ -124,6 +124,21 @@ class AwrBackbone(nn.Module):
     def flat_grads(self):
         return self._garena
 
+    def clone(self):
+        """A second module of the same class and constructor arguments on the same device, its parameter arena, buffer arena and counters
+        copied from this one (in the same train / eval mode).  It shares nothing with `self`: its own arenas -- an unused gradient arena of
+        n_params floats among them --, its own layout handle and no plans.  The caller's random stream is left where it was."""
+        with torch.random.fork_rng(devices=[]):          # (the constructor draws the reference's initialisation before the copy overwrites it)
+            new = type(self)(*self._ctor_args())
+        if self._arena.is_cuda:
+            new = new.to(self.device)
+        with torch.no_grad():
+            new._arena.copy_(self._arena)
+            new._barena.copy_(self._barena)
+            new._counters.copy_(self._counters)
+        new.train(self.training)
+        return new
+
     def reset_parameters(self, seed=None):
         """Reference initialisation (resnet_deconv.py:93-115 / torch defaults for hourglass)."""
         g = torch.Generator().manual_seed(seed) if seed is not None else None
@@ -273,6 +288,9 @@ class ResNetDeconv(AwrBackbone):
         self.ndeconv = 4 - int(math.log2(downsample))
         super().__init__(0, depth, J, downsample)           # (kind 0 takes the depth in the `nstack` slot of awr_net_create)
 
+    def _ctor_args(self):
+        return (self.J, self.downsample, self.depth)
+
     def _init_conv(self, key, shape, kind, g):
         if kind == "deconv_w" or key.startswith("final"):
             return torch.randn(shape, generator=g) * 0.001                           # :103-104, :108-115
@@ -286,6 +304,9 @@ class ResNet18Deconv(ResNetDeconv):
     def __init__(self, J, downsample=2):
         super().__init__(J, downsample, 18)
 
+    def _ctor_args(self):
+        return (self.J, self.downsample)
+
 
 class HourglassNet(AwrBackbone):
     """PoseNet('hourglass_<n>', J): hourglass.py:105-165 (Conv :6-25, Residual :28-59, Hourglass :62-88)."""
@@ -295,6 +316,9 @@ class HourglassNet(AwrBackbone):
         assert f == 256, "the reference's hourglass is 256 features wide (hourglass.py:106)"
         self.nstack, self.f = nstack, f
         super().__init__(1, nstack, J, 2)
+
+    def _ctor_args(self):
+        return (self.nstack, self.J, self.f)
 
     def _init_conv(self, key, shape, kind, g):
         bound = 1.0 / math.sqrt(shape[1] * shape[2] * shape[3])          # kaiming_uniform_(a=sqrt(5))

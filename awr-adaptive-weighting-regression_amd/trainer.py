@@ -151,6 +151,38 @@ def _grad_options(accum_steps, clip_grad_norm, grad_norm):
     return accum_steps, clip_grad_norm, grad_norm
 
 
+def _ema_options(ema_decay, ema_warmup):
+    """TrainEngine's ema_decay / ema_warmup, checked (host arithmetic only) -> (decay as a float or None, warm-up)."""
+    import math
+    if ema_decay is not None:
+        if isinstance(ema_decay, bool) or not isinstance(ema_decay, (int, float)):
+            raise TypeError("ema_decay is None or a number in the open interval (0, 1), not %r" % (ema_decay,))
+        if not (math.isfinite(ema_decay) and 0.0 < ema_decay < 1.0):
+            raise ValueError("ema_decay is None or a number in the open interval (0, 1), not %r" % (ema_decay,))
+        ema_decay = float(ema_decay)
+    if not isinstance(ema_warmup, bool):
+        raise TypeError("ema_warmup is True or False, not %r" % (ema_warmup,))
+    return ema_decay, ema_warmup
+
+
+def ema_decay_at(decay, updates, warmup):
+    """The decay d the NEXT weight-EMA update uses (ema = d * ema + (1 - d) * weights), `updates` = the number of updates already applied.
+    Warm-up off: `decay`.  Warm-up on: min(decay, (1 + updates) / (10 + updates)), the TF / timm rule -- the first update uses 0.1, so the
+    average forgets the initialisation at the rate it has seen weights; 0.999 is reached at updates = 8990.  Host arithmetic in double."""
+    if not warmup:
+        return decay
+    return min(decay, (1.0 + updates) / (10.0 + updates))
+
+
+class _EmaState:
+    """What an engine and its ragged-batch children share behind the optimiser: the shadow network (a clone of the trained one, in eval()
+    mode, scored and saved like any network) and the number of EMA updates applied to it (a host int: it drives the warm-up schedule)."""
+
+    def __init__(self, net):
+        self.net = net.clone().eval()
+        self.updates = 0
+
+
 class _GradWindow:
     """What an engine and its ragged-batch children share between the gradient arena and the optimiser: the accumulation arena, the number
     of micro-steps pending in it, and the device words awr_grad_norm writes."""
@@ -169,7 +201,7 @@ class TrainEngine(_WinogradAuto):
     def __init__(self, net, batch_size, img_size, kernel_size, coord_weight=0.0, dense_weight=1.0, lr=1e-3, weight_decay=0.0,
                  optimizer="adam", momentum=0.9, process_group=None, use_graph=False, n_buckets=4, autotune=True, wgrad_streams=2,
                  nhwc_boundary=None, trace_buckets=False, native_rccl=None, accum="auto", winograd=None, split_k=False, accum_steps=1,
-                 clip_grad_norm=None, grad_norm=False, _share=None):
+                 clip_grad_norm=None, grad_norm=False, ema_decay=None, ema_warmup=True, _share=None):
         """split_k: False (default: the process-wide mode, off unless awr_amd.set_train_split_k / $AWR_TRAIN_SPLIT_K set it) | True -- the small
         forward / data-gradient launches of this engine's plan (few workgroups, a long K loop: low batches, the deep levels) split their K loop
         and take the BatchNorm statistics / fused BatchNorm-backward reductions from the reduce kernel (include/awr_hip.h: awr_set_train_split_k;
@@ -190,9 +222,16 @@ class TrainEngine(_WinogradAuto):
         is about to read (awr_grad_norm: after the all-reduce, accumulated and averaged) and the optimiser multiplies by torch's
         clip_grad_norm_ coefficient, read from the device.  grad_norm: True measures the norm without clipping.  With either, `grad_norm`
         (float64, one element) and `clip_scale` (float32, one element) are device tensors valid until the next applying step; nothing
-        synchronises.  With all three at their defaults the step issues the launches it always did."""
+        synchronises.  With all three at their defaults the step issues the launches it always did.
+        ema_decay: None (default: no shadow network, no memory, no launch) | d in the open interval (0, 1) -- an exponential moving average of
+        the weights on the device: the engine keeps a shadow network (`ema_net` = net.clone(), eval mode) and every APPLYING
+        step, and flush(), ends in two awr_ema_update launches behind the optimiser -- ema += (x - ema) * float32(1 - d_t) over the whole
+        parameter arena and over the BatchNorm running statistics --, copies num_batches_tracked and counts `ema_updates`.  ema_warmup: True
+        (default) -- d_t = ema_decay_at(d, ema_updates, True) = min(d, (1 + t) / (10 + t)) | False -- d_t = d.  The training state is only
+        read; nothing synchronises.  A NaN or Inf in a parameter lands in its average and stays there."""
         self._split_k = _split_k_flag(split_k)
         self.accum_steps, self._max_norm, self._want_norm = _grad_options(accum_steps, clip_grad_norm, grad_norm)
+        self.ema_decay, self.ema_warmup = _ema_options(ema_decay, ema_warmup)
         if not next(net.parameters()).is_cuda:
             raise L.AwrError("TrainEngine needs the network on the GPU")
         self.net, self.B, self.H = net, batch_size, img_size
@@ -281,6 +320,8 @@ class TrainEngine(_WinogradAuto):
                     self._trace.append((lo, hi, e0, e1))
             if self.dpcomm is None:
                 self.plan.bucket_hook = hook
+        # the shadow is cloned behind the data-parallel broadcast above: replicas start from equal bits (a plain copy, not a kernel call)
+        self._ema = _share._ema if _share is not None else _EmaState(net) if self.ema_decay is not None else None
 
     def _attach(self, plan):
         """Make `plan` the engine's plan: side streams, NHWC boundary, head pointers (collectives: __init__ / compile())."""
@@ -426,6 +467,52 @@ class TrainEngine(_WinogradAuto):
             L.call("awr_sgd_step_dev", L.ptr(net.flat_params()), L.ptr(g), L.ptr(g2), L.ptr(win.scale), L.ptr(self.m), n, self.lr, self.momentum,
                    self.wd, self.step_count, scale, s)
 
+    def _ema_update(self):
+        """Behind the optimiser of an applying step, on its stream: the shadow's parameter arena (all n_params: the Hourglass tail past
+        n_active never moves, and e + (e - e) * w == e) and buffer arena move towards the trained ones; the host counters are copied."""
+        st = self._ema
+        if st is None:
+            return
+        net, shadow, s = self.net, st.net, L.stream()
+        # (the subtraction in Python double, rounded to float32 once)
+        w = float(np.float32(1.0 - ema_decay_at(self.ema_decay, st.updates, self.ema_warmup)))
+        L.call("awr_ema_update", L.ptr(shadow.flat_params()), L.ptr(net.flat_params()), net.n_params, w, s)
+        L.call("awr_ema_update", L.ptr(shadow._barena), L.ptr(net._barena), net._barena.numel(), w, s)
+        shadow._counters.copy_(net._counters)
+        shadow.weights_changed()
+        st.updates += 1
+
+    def _ema_state(self):
+        if self._ema is None:
+            raise L.AwrError("TrainEngine was built without ema_decay: there is no EMA network")
+        return self._ema
+
+    ema_net = property(lambda self: self._ema_state().net, doc="the shadow network: the EMA of the weights and BatchNorm statistics, in eval() mode")
+    ema_updates = property(lambda self: self._ema_state().updates, doc="EMA updates applied so far (a host int)")
+
+    def ema_state_dict(self):
+        """The shadow's state_dict() (the reference's keys, shapes and dtypes) as detached clones."""
+        return {k: v.detach().clone() for k, v in self._ema_state().net.state_dict().items()}
+
+    def load_ema_state_dict(self, sd, updates=0):
+        """Inverse of ema_state_dict(): `updates` = the number of EMA updates `sd` has seen (it positions the warm-up schedule)."""
+        if isinstance(updates, bool) or not isinstance(updates, int) or updates < 0:
+            raise ValueError("updates is an int >= 0, not %r" % (updates,))
+        st = self._ema_state()
+        st.net.load_state_dict(sd)
+        st.net.weights_changed()
+        st.updates = updates
+
+    def ema_reset(self):
+        """shadow <- the current parameters, BatchNorm statistics and counters; ema_updates = 0 (plain copies on the current stream)."""
+        st = self._ema_state()
+        with torch.no_grad():
+            st.net.flat_params().copy_(self.net.flat_params())
+            st.net._barena.copy_(self.net._barena)
+            st.net._counters.copy_(self.net._counters)
+        st.net.weights_changed()
+        st.updates = 0
+
     @property
     def micro_step(self):
         """Micro-steps pending in the accumulation window (a host int; always 0 with accum_steps == 1)."""
@@ -449,6 +536,7 @@ class TrainEngine(_WinogradAuto):
             return
         self.step_count += 1
         self._optimizer(g=win.acc, micro=win.pending)
+        self._ema_update()
         win.pending = 0
         self.net.weights_changed()
 
@@ -462,7 +550,8 @@ class TrainEngine(_WinogradAuto):
             eng = TrainEngine(self.net, b, self.H, self.ks, self.cw, self.dw, self.lr, self.wd, self.opt, self.momentum,
                               process_group=self.sync.pg, use_graph=False, n_buckets=self._n_buckets, autotune=False,
                               wgrad_streams=0, accum=self._accum, winograd=self._winograd, split_k=self._split_k,
-                              accum_steps=self.accum_steps, clip_grad_norm=self._max_norm, grad_norm=self._want_norm, _share=self)
+                              accum_steps=self.accum_steps, clip_grad_norm=self._max_norm, grad_norm=self._want_norm,
+                              ema_decay=self.ema_decay, ema_warmup=self.ema_warmup, _share=self)
             self._children[b] = eng
         eng.lr, eng.step_count = self.lr, self.step_count
         return eng
@@ -471,7 +560,8 @@ class TrainEngine(_WinogradAuto):
         """One optimisation step on this rank's shard.  Returns (losses[coord,dense,total], jt_uvd_pred)
         as device tensors that are valid until the next step; nothing is synchronised.
         accum_steps = k > 1: one micro-step -- forward, losses, backward, BatchNorm statistics and (data parallel) the gradient exchange as
-        ever; the first k-1 calls of a window end in awr_grad_accumulate, the k-th in the optimiser."""
+        ever; the first k-1 calls of a window end in awr_grad_accumulate, the k-th in the optimiser.
+        ema_decay set: an applying step ends in the EMA update of the shadow network, outside the captured graph like the optimiser."""
         if img.shape[0] != self.B:
             if not 0 < img.shape[0] < self.B:
                 raise L.AwrError("TrainEngine built for batches of %d got %d images" % (self.B, img.shape[0]))
@@ -516,6 +606,7 @@ class TrainEngine(_WinogradAuto):
             win.pending = 0
         else:
             self._optimizer()
+        self._ema_update()
         self.net.weights_changed()
         return self.losses, self.jt_pred
 
@@ -951,18 +1042,33 @@ class Trainer:
                                   use_graph=getattr(config, "use_hipgraph", False), accum=getattr(config, "accum", "auto"),
                                   winograd=getattr(config, "winograd", None), split_k=getattr(config, "train_split_k", False),
                                   accum_steps=getattr(config, "accum_steps", 1), clip_grad_norm=getattr(config, "clip_grad_norm", None),
-                                  grad_norm=bool(getattr(config, "log_grad_norm", False)))
+                                  grad_norm=bool(getattr(config, "log_grad_norm", False)), ema_decay=getattr(config, "ema_decay", None),
+                                  ema_warmup=getattr(config, "ema_warmup", True))
+        self._ema_on = self.engine.ema_decay is not None
+        if self._ema_on:
+            self._msg("weight EMA: decay {}, warm-up {}".format(self.engine.ema_decay, "on" if self.engine.ema_warmup else "off"))
         self._log_norm = bool(getattr(config, "log_grad_norm", False)) or getattr(config, "clip_grad_norm", None) is not None
         # winograd="auto": the training step's choice is logged once; the scoring engine's is reused by every later test pass
         self._wino_logged, self._infer_winograd = False, None
         if config.load_model and os.path.exists(config.load_model):
             self._msg("loading model from {}".format(config.load_model))
             pth = torch.load(config.load_model, map_location="cpu", weights_only=False)     # trusted project artefact (best_records may hold numpy scalars)
-            self.net.load_state_dict(pth["model"])
+            key = "model_ema" if getattr(config, "load_ema", False) else "model"      # load_ema: the averaged weights become the network's
+            if key not in pth:
+                raise L.AwrError("{} holds no \"{}\" entry{}".format(config.load_model, key, " (load_ema = True needs a checkpoint written with ema_decay)"
+                                                                     if key == "model_ema" else ""))
+            self.net.load_state_dict(pth[key])
             if "optimizer" in pth:
                 self.engine.load_optimizer_state_dict(pth["optimizer"])
             if "best_records" in pth:
                 self.best_records = pth["best_records"]
+            if self._ema_on:          # (the engine cloned its shadow from the freshly initialised network)
+                if "model_ema" in pth:
+                    self.engine.load_ema_state_dict(pth["model_ema"], int(pth.get("ema_updates", 0)))
+                    self._msg("weight EMA: restored from the checkpoint after {} updates".format(self.engine.ema_updates))
+                else:
+                    self.engine.ema_reset()
+                    self._msg("weight EMA: the checkpoint holds no \"model_ema\", starting from its weights")
         # train.py:94-96: the learning rate is force-reset to config.lr after loading
         self.engine.set_lr(config.lr)
         self._plateau = _Plateau(config.lr) if config.scheduler == "auto" else None
@@ -1063,8 +1169,10 @@ class Trainer:
                 self.test(epoch)
             if self.rank == 0:
                 import os
-                torch.save({"model": self.net.state_dict(), "optimizer": eng.optimizer_state_dict(), "best_records": self.best_records},
-                           os.path.join(self.work_dir, "epoch_{}.pth".format(epoch)))
+                pth = {"model": self.net.state_dict(), "optimizer": eng.optimizer_state_dict(), "best_records": self.best_records}
+                if self._ema_on:
+                    pth.update(model_ema=eng.ema_state_dict(), ema_updates=eng.ema_updates)
+                torch.save(pth, os.path.join(self.work_dir, "epoch_{}.pth".format(epoch)))
         if self.log:
             self.log.flush()
 
@@ -1073,81 +1181,103 @@ class Trainer:
         """train.py:178-227 / test.py:51-110 -- DataLoader(batch_size, shuffle=False, num_workers) like the reference (worker processes
         decode the 8 252 NYU PNGs while the GPU runs), no per-sample host loop.  Data parallel: rank r evaluates batches r, r + world, ...
         of that loader's order; the per-frame error rows and original-image uvd predictions are gathered and re-assembled in dataset order
-        on every rank, so mpe / AUC / the results txt are identical to the single-process run and rank-uniform."""
+        on every rank, so mpe / AUC / the results txt are identical to the single-process run and rank-uniform.
+        With config.ema_decay a second pass scores the engine's EMA network the same way (its own log lines tagged `ema`, its own PCK file,
+        no results txt, no skeleton overlays); the returned mpe, best_records and the LR scheduler read the raw network's numbers."""
         import os
         import numpy as np
         cfg = self.config
-        world = torch.distributed.get_world_size(self.pg) if self.pg is not None else 1
-        # config.parity_infer = True scores with blocked accumulation (eval-mode plans measure no gain from it: off by default since round 6)
-        wino = getattr(cfg, "winograd", None)
-        if isinstance(wino, str) and wino == "auto" and self._infer_winograd is not None:
-            wino = self._infer_winograd
-        test_loss = bool(getattr(cfg, "test_loss", False))      # test.py:73-88: the validation loss, from the pass that decodes the joints
-        loss_kw = dict(loss_weights=(cfg.coord_weight, cfg.dense_weight), loss_stages=getattr(cfg, "test_loss_stages", "last")) if test_loss else {}
-        inf = self._last_infer = InferEngine(self.net, cfg.batch_size, cfg.img_size, cfg.kernel_size, use_graph=False,
-                                             parity=bool(getattr(cfg, "parity_infer", False)), winograd=wino, **loss_kw)
-        n, bs = len(self.testData), cfg.batch_size
-        mine = [b for b in range((n + bs - 1) // bs) if b % world == self.rank]
-        idx = [i for b in mine for i in range(b * bs, min(n, (b + 1) * bs))]
-        ev = make_evaluator(cfg, self.testData, device=self.net.device, capacity=len(idx))
-        dev_eval = isinstance(ev, DeviceEvalUtil)      # config.device_eval: no download and no sync inside the batch loop
-        loader = torch.utils.data.DataLoader(torch.utils.data.Subset(self.testData, idx), batch_size=bs, shuffle=False,
-                                             num_workers=int(getattr(cfg, "num_workers", 0)), drop_last=False)
-        pad = None
-        for k, (img, jt_xyz_gt, jt_uvd_gt, center_xyz, M, cube) in enumerate(loader):
-            nb = img.shape[0]
-            x = self._images(img, "test")
-            if img.dtype == torch.uint8:                             # device loader: the host only ever saw parameter blocks
-                img = x[:1].cpu() if (getattr(cfg, "vis_freq", 0) and (mine[k] + 1) % cfg.vis_freq == 0 and self._vis is not None) else None
-            if nb < bs:                                              # ragged last batch: fill the static plan's batch with zeros, drop them after
-                if pad is None:
-                    pad = torch.zeros((bs,) + tuple(x.shape[1:]), device=x.device)
-                pad.zero_()
-                pad[:nb] = x
-                x = pad
-            gt = (jt_uvd_gt.cuda(non_blocking=True).float(),) if test_loss else ()      # (rows past nb of a ragged batch are not read)
-            if dev_eval:
-                jt = inf(x, *gt, n_valid=nb)
-                ev.feed_batch(jt, jt_xyz_gt, center_xyz, M, cube, n_valid=nb)
+
+        def score(net, ema):
+            """one scoring pass over `net`: the trained network, or (ema) the engine's EMA network"""
+            world = torch.distributed.get_world_size(self.pg) if self.pg is not None else 1
+            # config.parity_infer = True scores with blocked accumulation (eval-mode plans measure no gain from it: off by default since round 6)
+            wino = getattr(cfg, "winograd", None)
+            if isinstance(wino, str) and wino == "auto" and self._infer_winograd is not None:
+                wino = self._infer_winograd
+            test_loss = bool(getattr(cfg, "test_loss", False))      # test.py:73-88: the validation loss, from the pass that decodes the joints
+            loss_kw = dict(loss_weights=(cfg.coord_weight, cfg.dense_weight), loss_stages=getattr(cfg, "test_loss_stages", "last")) if test_loss else {}
+            inf = InferEngine(net, cfg.batch_size, cfg.img_size, cfg.kernel_size, use_graph=False,
+                              parity=bool(getattr(cfg, "parity_infer", False)), winograd=wino, **loss_kw)
+            if not ema:
+                self._last_infer = inf
+            n, bs = len(self.testData), cfg.batch_size
+            mine = [b for b in range((n + bs - 1) // bs) if b % world == self.rank]
+            idx = [i for b in mine for i in range(b * bs, min(n, (b + 1) * bs))]
+            ev = make_evaluator(cfg, self.testData, device=net.device, capacity=len(idx))
+            dev_eval = isinstance(ev, DeviceEvalUtil)      # config.device_eval: no download and no sync inside the batch loop
+            loader = torch.utils.data.DataLoader(torch.utils.data.Subset(self.testData, idx), batch_size=bs, shuffle=False,
+                                                 num_workers=int(getattr(cfg, "num_workers", 0)), drop_last=False)
+            pad = None
+            vis = bool(getattr(cfg, "vis_freq", 0)) and self._vis is not None and not ema
+            for k, (img, jt_xyz_gt, jt_uvd_gt, center_xyz, M, cube) in enumerate(loader):
+                nb = img.shape[0]
+                x = self._images(img, "test")
+                if img.dtype == torch.uint8:                             # device loader: the host only ever saw parameter blocks
+                    img = x[:1].cpu() if (vis and (mine[k] + 1) % cfg.vis_freq == 0) else None
+                if nb < bs:                                              # ragged last batch: fill the static plan's batch with zeros, drop them after
+                    if pad is None:
+                        pad = torch.zeros((bs,) + tuple(x.shape[1:]), device=x.device)
+                    pad.zero_()
+                    pad[:nb] = x
+                    x = pad
+                gt = (jt_uvd_gt.cuda(non_blocking=True).float(),) if test_loss else ()      # (rows past nb of a ragged batch are not read)
+                if dev_eval:
+                    jt = inf(x, *gt, n_valid=nb)
+                    ev.feed_batch(jt, jt_xyz_gt, center_xyz, M, cube, n_valid=nb)
+                else:
+                    jt = inf(x, *gt, n_valid=nb)[:nb].cpu().numpy()
+                    ev.feed_batch(jt, jt_xyz_gt.numpy(), center_xyz.numpy(), M.numpy(), cube.numpy())
+                ib = mine[k] + 1
+                if vis and ib % cfg.vis_freq == 0:    # train.py:203-213
+                    half = cfg.img_size / 2.0
+                    if dev_eval:             # the one joint set this iteration draws
+                        jt = jt[:1].cpu().numpy()
+                    self._vis.plot(img[0].numpy(), os.path.join(self.result_dir, "test_epoch_{}_iter_{}.png".format(epoch, ib)),
+                                   (jt[0] + 1) * half, (jt_uvd_gt[0].numpy() + 1) * half)
+            if not ema:          # (the EMA network is never trained: it stays in eval mode)
+                self.net.train()
+            if not ema and inf.winograd_source is not None and not inf._wino_pending:
+                self._infer_winograd = inf.winograd_mode
+            if dev_eval:           # one download of the error and uvd rows; from here on it is the host evaluator's code
+                rows = ev.jt_uvd_pred
+                ev = ev.host()
+                ev.jt_uvd_pred = rows
+            if world > 1:          # every rank ends up with the whole test set, in dataset order
+                J = self.testData.jt_num
+                err = np.concatenate(ev._err, 0) if ev._err else np.zeros((0, J), np.float32)
+                uvd = np.asarray(ev.jt_uvd_pred, np.float32).reshape(-1, J, 3)
+                parts = [None] * world
+                torch.distributed.all_gather_object(parts, (idx, err, uvd), group=self.pg)
+                full_e, full_u = np.zeros((n, J), err.dtype), np.zeros((n, J, 3), np.float32)
+                for ids, e, u in parts:
+                    full_e[ids], full_u[ids] = e, u
+                ev._err, ev.jt_uvd_pred = [full_e], list(full_u)
+            mpe, mid, auc, pck, thresh = ev.get_measures()
+            if self.rank == 0:
+                ev.plot_pck(os.path.join(self.work_dir, "test_pck_{}epoch_{}.png".format("ema_" if ema else "", epoch)), pck, thresh)      # train.py:216
+            if epoch in (0, -1) and self.rank == 0 and not ema:                    # train.py:217-221 / test.py:103-108
+                jt_uvd = np.array(ev.jt_uvd_pred, dtype=np.float32)
+                np.savetxt(os.path.join(self.work_dir, "test_%.3f.txt" % mpe), jt_uvd.reshape([jt_uvd.shape[0], cfg.jt_num * 3]), fmt="%.3f")
+            if ema:
+                self._msg("[epoch {:2d}], [test mpe ema {:.3f}]".format(epoch, mpe))
             else:
-                jt = inf(x, *gt, n_valid=nb)[:nb].cpu().numpy()
-                ev.feed_batch(jt, jt_xyz_gt.numpy(), center_xyz.numpy(), M.numpy(), cube.numpy())
-            ib = mine[k] + 1
-            if getattr(cfg, "vis_freq", 0) and ib % cfg.vis_freq == 0 and self._vis is not None:    # train.py:203-213
-                half = cfg.img_size / 2.0
-                if dev_eval:             # the one joint set this iteration draws
-                    jt = jt[:1].cpu().numpy()
-                self._vis.plot(img[0].numpy(), os.path.join(self.result_dir, "test_epoch_{}_iter_{}.png".format(epoch, ib)),
-                               (jt[0] + 1) * half, (jt_uvd_gt[0].numpy() + 1) * half)
-        self.net.train()
-        if inf.winograd_source is not None and not inf._wino_pending:
-            self._infer_winograd = inf.winograd_mode
-        if dev_eval:           # one download of the error and uvd rows; from here on it is the host evaluator's code
-            rows = ev.jt_uvd_pred
-            ev = ev.host()
-            ev.jt_uvd_pred = rows
-        if world > 1:          # every rank ends up with the whole test set, in dataset order
-            J = self.testData.jt_num
-            err = np.concatenate(ev._err, 0) if ev._err else np.zeros((0, J), np.float32)
-            uvd = np.asarray(ev.jt_uvd_pred, np.float32).reshape(-1, J, 3)
-            parts = [None] * world
-            torch.distributed.all_gather_object(parts, (idx, err, uvd), group=self.pg)
-            full_e, full_u = np.zeros((n, J), err.dtype), np.zeros((n, J, 3), np.float32)
-            for ids, e, u in parts:
-                full_e[ids], full_u[ids] = e, u
-            ev._err, ev.jt_uvd_pred = [full_e], list(full_u)
-        mpe, mid, auc, pck, thresh = ev.get_measures()
-        if self.rank == 0:
-            ev.plot_pck(os.path.join(self.work_dir, "test_pck_epoch_{}.png".format(epoch)), pck, thresh)                # train.py:216
-        if epoch in (0, -1) and self.rank == 0:                      # train.py:217-221 / test.py:103-108
-            jt_uvd = np.array(ev.jt_uvd_pred, dtype=np.float32)
-            np.savetxt(os.path.join(self.work_dir, "test_%.3f.txt" % mpe), jt_uvd.reshape([jt_uvd.shape[0], cfg.jt_num * 3]), fmt="%.3f")
-        self._msg("[epoch {:2d}], [test mpe {:.3f}], [lr {:.1e}]".format(epoch, mpe, self.engine.lr))
-        if test_loss:          # per-rank sums and batch counts are added up: every rank holds and logs the same means (like train()'s meter)
-            t = torch.tensor(inf.loss_sums(), dtype=torch.float64, device=self.net.device)
-            if world > 1:
-                torch.distributed.all_reduce(t, group=self.pg)
-            c, d, nbat = t.tolist()
-            self.last_test_loss = l = _loss_dict(c, d, int(nbat))
-            self._msg("[epoch {:2d}], [test loss {:.5f}][offset_loss {:.5f}][coord_loss {:.5f}]".format(epoch, l["total"], l["dense"], l["coord"]))
+                self._msg("[epoch {:2d}], [test mpe {:.3f}], [lr {:.1e}]".format(epoch, mpe, self.engine.lr))
+            if test_loss:          # per-rank sums and batch counts are added up: every rank holds and logs the same means (like train()'s meter)
+                t = torch.tensor(inf.loss_sums(), dtype=torch.float64, device=net.device)
+                if world > 1:
+                    torch.distributed.all_reduce(t, group=self.pg)
+                c, d, nbat = t.tolist()
+                l = _loss_dict(c, d, int(nbat))
+                if ema:
+                    self.last_test_loss_ema = l
+                else:
+                    self.last_test_loss = l
+                head = "[epoch {:2d}], [test loss ema {:.5f}]" if ema else "[epoch {:2d}], [test loss {:.5f}]"
+                self._msg((head + "[offset_loss {:.5f}][coord_loss {:.5f}]").format(epoch, l["total"], l["dense"], l["coord"]))
+            return mpe
+
+        mpe = score(self.net, False)
+        if self._ema_on:
+            self.last_test_mpe_ema = score(self.engine.ema_net, True)
         return mpe

@@ -172,6 +172,12 @@ int awr_sgd_step_dev(float* p, const float* g, const float* g2, const float* dev
 /* Gradient accumulation: acc[i] = g[i] (first != 0: the first micro-step of a window) or acc[i] = acc[i] + g[i], one float32 add per
  * element.  Both arenas 16-byte aligned. */
 int awr_grad_accumulate(float* acc, const float* g, int64_t n, int first, void* stream);
+/* Weight EMA: ema[i] = ema[i] + (src[i] - ema[i]) * w for i < n: three float32 operations, each rounded on its own (no
+ * contraction), the lerp form awr_adam_step uses for exp_avg.  src is only read.  w in (0, 1] (w = 1 copies src; an element with
+ * src[i] == ema[i] keeps its bits for every w).  ema / src 16-byte aligned, n > 0, the ranges must not overlap; anything else -- a NULL
+ * pointer, w outside (0, 1] or NaN included -- returns AWR_ERR_ARG before any launch.  Non-finite inputs are not guarded: a NaN or Inf in
+ * src[i] or ema[i] makes ema[i] non-finite and it stays so. */
+int awr_ema_update(float* ema, const float* src, int64_t n, float w, void* stream);
 /* Global gradient norm and clip coefficient, left on the device (nothing synchronises):
  *   norm_out[0]  = (double)grad_scale * sqrt(sum_i (double)(float)(g[i] + g2[i])^2)      g2 may be NULL; the add is the float32 add the
  *                  optimiser kernel makes, the squares and the sum are float64

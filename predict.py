@@ -10,6 +10,7 @@ largest masked heat value, the vote scatter in nominal millimetres; DESIGN.md 4.
 batch slot 0 is the stream) and starts each frame's crop at the previous frame's joint centre, falling back to the detector when the hand is
 lost.  With either, pred_center_uvd.txt (the final crop centres) and pred_recenter_code.txt (one column per
 awr_joints_center call: 1 = moved, 0 / 2 / 3 / 4 = kept, awr_amd.detect.RECENTER_NAMES) are written too.
+--ema predicts with the checkpoint's averaged weights ("model_ema", written by a run with config.ema_decay) instead of "model".
 `--set` overrides config entries as train.py does (img_size, kernel_size, cube, batch_size, jt_num, downsample, winograd ...)."""
 import argparse
 import os
@@ -28,6 +29,7 @@ def parse_args(argv=None):
     ap.add_argument("--confidence", action="store_true", help="also write per-joint conf / peak / spread_mm")
     ap.add_argument("--recenter", type=int, default=0, metavar="N", help="extra passes cropped around the predicted joints (0 ... 4)")
     ap.add_argument("--track", action="store_true", help="the file is one sequence: start each crop at the previous frame's joint centre")
+    ap.add_argument("--ema", action="store_true", help="load the checkpoint's \"model_ema\" (the EMA of the weights) instead of \"model\"")
     return ap.parse_args(argv)
 
 
@@ -50,7 +52,11 @@ def main(argv=None):
         net = resnet_deconv.get_deconv_net(int(cfg.net.split("_")[1]), cfg.jt_num, cfg.downsample)
     else:
         net = hourglass.PoseNet(cfg.net, cfg.jt_num)
-    net.load_state_dict(torch.load(cfg.load_model, map_location="cpu", weights_only=False)["model"])
+    pth = torch.load(cfg.load_model, map_location="cpu", weights_only=False)
+    key = "model_ema" if args.ema else "model"
+    if key not in pth:
+        raise awr_amd._lib.AwrError("{} holds no \"{}\" entry{}".format(cfg.load_model, key, " (--ema needs a checkpoint written with ema_decay)" if args.ema else ""))
+    net.load_state_dict(pth[key])
     bs = 1 if args.track else min(cfg.batch_size, len(frames))
     pred = awr_amd.Predictor(net.cuda(), cfg.img_size, cfg.kernel_size, cube=cfg.cube, max_batch=bs, frame_shape=frames.shape[1:],
                              winograd=cfg.winograd, parity=cfg.parity_infer, confidence=args.confidence,
