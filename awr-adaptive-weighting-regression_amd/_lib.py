@@ -251,6 +251,10 @@ _SIGS = {
     "awr_detect_samples": ([_P, _P, _I, _L, _P, _I, _I, _I, _I, _D, _D, _D, _D, _I, _P, _P, _P, _P, _P, _P], C.c_int),
     "awr_joints_center": ([_P, _P, _P, _P, _P, _P, _I, _I, _I, _P, _I, _D, _D, _D, _D, _I, _D, _D, _D, _P, _P, _P, _P], C.c_int),
     "awr_centers_select": ([_P, _P, _P, _P, _I, _P, _P, _P, _P], C.c_int),
+    # test-time views (csrc/awr_detect.hip)
+    "awr_view_centers": ([_P, _P, _P, _I, _P, _I, _I, _I, _D, _D, _D, _D, _I, _P, _P, _P, _P, _P], C.c_int),
+    "awr_view_rotate": ([_P, _P, _P, _P, _I, _I, _I, _P], C.c_int),
+    "awr_views_fuse": ([_P, _P, _P, _P, _I, _I, _I, _I, _I, _D, _D, _D, _D, _I, _P, _P, _P, _P, _P], C.c_int),
 }
 
 # entry points of study builds only (hipcc -DAWR_STUDY, AWR_BUILD_STUDY=1 for awr_amd.build): measured-and-rejected forms that the default

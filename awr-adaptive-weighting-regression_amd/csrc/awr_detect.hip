@@ -14,6 +14,11 @@
 // Two one-thread-per-frame passes close the loop from the network's output back to a crop centre: joints_center_kernel
 // (predicted joints -> the gated next centre, detect.joints_center in IEEE double) and centers_select_kernel (a tracked centre where it is
 // usable, the detector's otherwise).  Both are launch-bound; neither is clever.
+// Three more of the same kind carry test-time views: view_centers_kernel expands each frame's centre into one centre, cube
+// and frame index per view, view_rotate_kernel turns the crop block and crop matrix of a rotating view into the rotated ones, and
+// views_fuse_kernel fuses the views' camera-space joints per frame and joint.  Their arithmetic is detect.view_centers / view_rotate /
+// fuse_views in IEEE double, in that order of operations; the rotation matrices come ready-made from the host (detect.view_table): no
+// kernel here evaluates a transcendental.
 #include <limits.h>
 #include <math.h>
 
@@ -319,6 +324,146 @@ __global__ __launch_bounds__(DET_THREADS) void centers_select_kernel(const doubl
     if (which) which[i] = take_a ? 0 : 1;
 }
 
+// ---- test-time views (detect.view_centers, view_rotate, fuse_views) ----
+// One table row per view, AWR_VIEW_TABLE_DOUBLES doubles (160 bytes: rows stay 16-byte aligned)
+enum { VT_R = 0, VT_IR = 9, VT_SCALE = 15, VT_SHIFT = 16, VT_ROTATES = 19 };
+
+// one thread per (view, frame): row v * B + b of the outputs
+__global__ __launch_bounds__(DET_THREADS) void view_centers_kernel(const double* __restrict__ center, const int* __restrict__ status,
+                                                                   const double* __restrict__ cube, int cube_stride,
+                                                                   const double* __restrict__ table, int V, int B, int n_valid, double fx,
+                                                                   double fy, double u0, double v0, double flip,
+                                                                   double* __restrict__ centers_out, double* __restrict__ cubes_out,
+                                                                   int64_t* __restrict__ frame_out, int* __restrict__ status_out) {
+    const int i = blockIdx.x * DET_THREADS + threadIdx.x;
+    if (i >= V * n_valid) return;
+    const int v = i / n_valid, b = i % n_valid;
+    const int64_t r = (int64_t)v * B + b;
+    const double* T = table + (int64_t)v * AWR_VIEW_TABLE_DOUBLES;
+    const double* cb = cube + (int64_t)b * cube_stride;
+    const double sx = T[VT_SHIFT], sy = T[VT_SHIFT + 1], sz = T[VT_SHIFT + 2], sc = T[VT_SCALE];
+    double c[3] = {center[3 * b], center[3 * b + 1], center[3 * b + 2]};
+    if (!(sx == 0.0 && sy == 0.0 && sz == 0.0)) {
+        // evaluator.uvd2xyz (util.py:13-20), the shift, evaluator.xyz2uvd (util.py:3-10): loader.py:112 in double
+        const double x = (c[0] - u0) * c[2] / fx + sx;
+        const double y = (c[1] - v0) * c[2] / fy * flip + sy;
+        const double z = c[2] + sz;
+        const double yf = y * flip;
+        c[0] = x * fx / z + u0; c[1] = yf * fy / z + v0; c[2] = z;
+    }
+    centers_out[3 * r] = c[0]; centers_out[3 * r + 1] = c[1]; centers_out[3 * r + 2] = c[2];
+    cubes_out[3 * r] = cb[0] * sc; cubes_out[3 * r + 1] = cb[1] * sc; cubes_out[3 * r + 2] = cb[2] * sc;
+    frame_out[r] = b;
+    status_out[r] = status[b];
+}
+
+// one thread per (view, frame): the block and the matrix of a rotating view's AWR_DET_OK row, in place
+__global__ __launch_bounds__(DET_THREADS) void view_rotate_kernel(awr_nyu_sample* __restrict__ samples, float* __restrict__ M,
+                                                                  const int* __restrict__ status, const double* __restrict__ table, int V,
+                                                                  int B, int n_valid) {
+    const int i = blockIdx.x * DET_THREADS + threadIdx.x;
+    if (i >= V * n_valid) return;
+    const int v = i / n_valid, b = i % n_valid;
+    const int64_t r = (int64_t)v * B + b;
+    const double* T = table + (int64_t)v * AWR_VIEW_TABLE_DOUBLES;
+    if (T[VT_ROTATES] == 0.0 || status[r] != AWR_DET_OK) return;
+    awr_nyu_sample* s = samples + r;
+    s->op = AWR_NYU_AFFINE;
+    for (int k = 0; k < 6; ++k) s->m[k] = T[VT_IR + k];
+    s->m[6] = 0.0; s->m[7] = 0.0; s->m[8] = 1.0;
+    float* m = M + 9 * r;
+    double a[9];
+    for (int k = 0; k < 9; ++k) a[k] = (double)m[k];
+    for (int row = 0; row < 3; ++row)
+        for (int col = 0; col < 3; ++col)
+            m[3 * row + col] = (float)(((T[VT_R + 3 * row] * a[col]) + (T[VT_R + 3 * row + 1] * a[3 + col])) + (T[VT_R + 3 * row + 2] * a[6 + col]));
+}
+
+// the middle of the n smallest of eight values (the unused ones are +infinity): a stable bubble network over registers
+__device__ __forceinline__ double median8(double (&a)[AWR_VIEWS_MAX], int n) {
+#pragma unroll
+    for (int pass = 0; pass < AWR_VIEWS_MAX - 1; ++pass)
+#pragma unroll
+        for (int k = 0; k < AWR_VIEWS_MAX - 1 - pass; ++k) {
+            const double lo = a[k], hi = a[k + 1];
+            const bool swap = lo > hi;
+            a[k] = swap ? hi : lo; a[k + 1] = swap ? lo : hi;
+        }
+    double mid = 0.0, below = 0.0;
+#pragma unroll
+    for (int k = 0; k < AWR_VIEWS_MAX; ++k) {
+        mid = (k == n / 2) ? a[k] : mid;
+        below = (k + 1 == n / 2) ? a[k] : below;
+    }
+    return (n & 1) ? mid : (below + mid) / 2.0;
+}
+
+// one thread per (frame, joint)
+__global__ __launch_bounds__(DET_THREADS) void views_fuse_kernel(const float* __restrict__ xyz, const int* __restrict__ status,
+                                                                 const int* __restrict__ ustatus, const float* __restrict__ weights, int mode,
+                                                                 int V, int B, int J, int n_valid, double fx, double fy, double u0, double v0,
+                                                                 double flip, float* __restrict__ xyz_out, float* __restrict__ uvd_out,
+                                                                 float* __restrict__ spread_out, int* __restrict__ used_out) {
+    const int64_t i = (int64_t)blockIdx.x * DET_THREADS + threadIdx.x;
+    if (i >= (int64_t)n_valid * J) return;
+    const int b = (int)(i / J), j = (int)(i % J);
+    const double nan = __builtin_nan("");
+    double X[3][AWR_VIEWS_MAX], W[AWR_VIEWS_MAX];
+    int used = 0;
+    const bool frame_ok = status[b] == 0 && ustatus[b] == 0;                // view 0's codes
+#pragma unroll
+    for (int v = 0; v < AWR_VIEWS_MAX; ++v) {
+        X[0][v] = X[1][v] = X[2][v] = INFINITY; W[v] = 0.0;
+        if (v < V && frame_ok) {
+            const int64_t r = (int64_t)v * B + b;
+            const float* p = xyz + (r * J + j) * 3;
+            const double x = (double)p[0], y = (double)p[1], z = (double)p[2];
+            double w = 1.0;
+            bool ok = status[r] == 0 && ustatus[r] == 0 && isfinite(x) && isfinite(y) && isfinite(z);
+            if (mode == AWR_FUSE_CONF) {
+                w = (double)weights[r * J + j];
+                ok = ok && isfinite(w) && w > 0.0;
+            }
+            if (ok) { X[0][v] = x; X[1][v] = y; X[2][v] = z; W[v] = w; ++used; }
+        }
+    }
+    double m[3] = {nan, nan, nan}, spread = nan;
+    if (used > 0) {
+        double sw = 0.0, s[3] = {0.0, 0.0, 0.0};
+#pragma unroll
+        for (int v = 0; v < AWR_VIEWS_MAX; ++v)
+            if (W[v] > 0.0) {                                               // sequentially in view order
+                s[0] = s[0] + W[v] * X[0][v]; s[1] = s[1] + W[v] * X[1][v]; s[2] = s[2] + W[v] * X[2][v];
+                sw = sw + W[v];
+            }
+        if (mode == AWR_FUSE_MEDIAN) {
+            for (int a = 0; a < 3; ++a) {
+                double t[AWR_VIEWS_MAX];
+#pragma unroll
+                for (int v = 0; v < AWR_VIEWS_MAX; ++v) t[v] = X[a][v];
+                m[a] = median8(t, used);
+            }
+        } else {
+            m[0] = s[0] / sw; m[1] = s[1] / sw; m[2] = s[2] / sw;
+        }
+        double q = 0.0;
+#pragma unroll
+        for (int v = 0; v < AWR_VIEWS_MAX; ++v)
+            if (W[v] > 0.0) {
+                const double dx = X[0][v] - m[0], dy = X[1][v] - m[1], dz = X[2][v] - m[2];
+                q = q + W[v] * ((dx * dx + dy * dy) + dz * dz);
+            }
+        spread = sqrt(q / sw);
+    }
+    const double yf = m[1] * flip;                                          // evaluator.xyz2uvd (util.py:3-10) in double
+    float* xo = xyz_out + i * 3;
+    float* uo = uvd_out + i * 3;
+    xo[0] = (float)m[0]; xo[1] = (float)m[1]; xo[2] = (float)m[2];
+    uo[0] = (float)(used ? m[0] * fx / m[2] + u0 : nan); uo[1] = (float)(used ? yf * fy / m[2] + v0 : nan); uo[2] = (float)m[2];
+    spread_out[i] = (float)spread;
+    used_out[i] = used;
+}
+
 static int detect_parts(int B, int fh) {
     // about four workgroups per CU over the batch, never more than one per row of the frame (a workgroup's share is whole rows)
     int p = (1024 + B - 1) / B;
@@ -424,6 +569,54 @@ int awr_centers_select(const double* a_center, const int* a_status, const double
     centers_select_kernel<<<(B + DET_THREADS - 1) / DET_THREADS, DET_THREADS, 0, as_stream(stream)>>>(a_center, a_status, b_center, b_status, B,
                                                                                                    out_center, out_status, which);
     return check_launch("awr_centers_select");
+}
+
+static int check_views(const char* who, int V, int B, int n_valid) {
+    AWR_REQUIRE(V > 0 && V <= AWR_VIEWS_MAX, "%s: V = %d is outside [1, %d]", who, V, AWR_VIEWS_MAX);
+    AWR_REQUIRE(B > 0 && (int64_t)V * B <= AWR_DET_MAX_BATCH, "%s: V * B = %d * %d is outside [1, %d]", who, V, B, AWR_DET_MAX_BATCH);
+    AWR_REQUIRE(n_valid >= 0 && n_valid <= B, "%s: n_valid = %d is outside [0, B = %d]", who, n_valid, B);
+    return AWR_OK;
+}
+
+int awr_view_centers(const double* center_uvd, const int* status, const double* cube, int cube_stride, const double* table, int V, int B,
+                     int n_valid, double fx, double fy, double u0, double v0, int flip, double* centers_out, double* cubes_out,
+                     int64_t* frame_out, int* status_out, void* stream) {
+    AWR_REQUIRE(center_uvd && status && cube && table && centers_out && cubes_out && frame_out && status_out, "awr_view_centers: NULL pointer");
+    if (check_views("awr_view_centers", V, B, n_valid) != AWR_OK) return AWR_ERR_ARG;
+    AWR_REQUIRE(cube_stride == 0 || cube_stride == 3, "awr_view_centers: cube_stride is 0 (one cube) or 3 (one per frame), not %d", cube_stride);
+    AWR_REQUIRE(fx != 0.0 && fy != 0.0 && isfinite(fx) && isfinite(fy) && isfinite(u0) && isfinite(v0) && (flip == 1 || flip == -1),
+                "awr_view_centers: bad intrinsics / flip");
+    if (n_valid == 0) return AWR_OK;
+    view_centers_kernel<<<(V * n_valid + DET_THREADS - 1) / DET_THREADS, DET_THREADS, 0, as_stream(stream)>>>(
+        center_uvd, status, cube, cube_stride, table, V, B, n_valid, fx, fy, u0, v0, (double)flip, centers_out, cubes_out, frame_out, status_out);
+    return check_launch("awr_view_centers");
+}
+
+int awr_view_rotate(awr_nyu_sample* samples, float* M, const int* status, const double* table, int V, int B, int n_valid, void* stream) {
+    AWR_REQUIRE(samples && M && status && table, "awr_view_rotate: NULL pointer");
+    if (check_views("awr_view_rotate", V, B, n_valid) != AWR_OK) return AWR_ERR_ARG;
+    if (n_valid == 0) return AWR_OK;
+    view_rotate_kernel<<<(V * n_valid + DET_THREADS - 1) / DET_THREADS, DET_THREADS, 0, as_stream(stream)>>>(samples, M, status, table, V, B,
+                                                                                                           n_valid);
+    return check_launch("awr_view_rotate");
+}
+
+int awr_views_fuse(const float* xyz, const int* status, const int* ustatus, const float* weights, int mode, int V, int B, int J, int n_valid,
+                   double fx, double fy, double u0, double v0, int flip, float* xyz_out, float* uvd_out, float* spread_out, int* used_out,
+                   void* stream) {
+    AWR_REQUIRE(xyz && status && ustatus && xyz_out && uvd_out && spread_out && used_out, "awr_views_fuse: NULL pointer");
+    if (check_views("awr_views_fuse", V, B, n_valid) != AWR_OK) return AWR_ERR_ARG;
+    AWR_REQUIRE(J > 0 && J <= AWR_RECENTER_MAX_JOINTS, "awr_views_fuse: J = %d is outside [1, %d]", J, AWR_RECENTER_MAX_JOINTS);
+    AWR_REQUIRE(mode == AWR_FUSE_MEAN || mode == AWR_FUSE_CONF || mode == AWR_FUSE_MEDIAN,
+                "awr_views_fuse: mode %d is none of AWR_FUSE_MEAN / _CONF / _MEDIAN", mode);
+    AWR_REQUIRE(mode != AWR_FUSE_CONF || weights, "awr_views_fuse: AWR_FUSE_CONF needs the weights (NULL pointer)");
+    AWR_REQUIRE(fx != 0.0 && fy != 0.0 && isfinite(fx) && isfinite(fy) && isfinite(u0) && isfinite(v0) && (flip == 1 || flip == -1),
+                "awr_views_fuse: bad intrinsics / flip");
+    if (n_valid == 0) return AWR_OK;
+    const int64_t n = (int64_t)n_valid * J;
+    views_fuse_kernel<<<(unsigned)((n + DET_THREADS - 1) / DET_THREADS), DET_THREADS, 0, as_stream(stream)>>>(
+        xyz, status, ustatus, weights, mode, V, B, J, n_valid, fx, fy, u0, v0, (double)flip, xyz_out, uvd_out, spread_out, used_out);
+    return check_launch("awr_views_fuse");
 }
 
 }  // extern "C"

@@ -8,6 +8,8 @@ Two things live here:
     `select_device`) for tests and tools.  `awr_amd.predictor.Predictor` is the product path.
   * `joints_center` and `select`: the statements of awr_joints_center (predicted joints -> the next crop centre, with a gate) and
     awr_centers_select (a tracked centre where it is usable, the detector's otherwise); DESIGN.md 4.19.
+  * `make_views`, `check_views`, `view_table`, `view_centers`, `view_rotate` and `fuse_views`: test-time views -- the host
+    table of the views' rotations and the statements of awr_view_centers, awr_view_rotate and awr_views_fuse.
 
 Definition.  Centre of mass of a pixel set: n, sum of columns u, sum of rows v and sum of raw uint16 depths d as int64, centre =
 (su / n, sv / n, sd / n) as three double divisions.  Integer sums do not depend on the order of summation, so the device, which splits a
@@ -40,6 +42,10 @@ KEPT_FRAME, MOVED, KEPT_NONFINITE, KEPT_DEPTH, KEPT_SHIFT = 0, 1, 2, 3, 4
 RECENTER_NAMES = {KEPT_FRAME: "kept: the frame has a status code", MOVED: "moved", KEPT_NONFINITE: "kept: the joint mean is not finite",
                   KEPT_DEPTH: "kept: the joint mean is outside the depth range", KEPT_SHIFT: "kept: the joint mean is too far from the centre"}
 MAX_JOINTS = 256
+# test-time views (include/awr_hip.h AWR_VIEWS_MAX, AWR_VIEW_TABLE_DOUBLES, AWR_FUSE_*)
+MAX_VIEWS, VIEW_TABLE_DOUBLES = 8, 20
+FUSE_MEAN, FUSE_CONF, FUSE_MEDIAN = 0, 1, 2
+FUSE_MODES = {"mean": FUSE_MEAN, "conf": FUSE_CONF, "median": FUSE_MEDIAN}
 
 
 def _u16(frame):
@@ -197,6 +203,192 @@ def select(a_center, a_status, b_center, b_status):
     return out, status, which
 
 
+# ---- test-time views: the same hand under rotations, cube scales and centre shifts ----------------------------------
+def _number(x, what):
+    if isinstance(x, (bool, str, bytes)) or not isinstance(x, (int, float, np.integer, np.floating)):
+        raise TypeError("%s is a number, not %r" % (what, x))
+    x = float(x)
+    if not np.isfinite(x):
+        raise ValueError("%s = %r is not finite" % (what, x))
+    return x
+
+
+def check_views(views, fuse="mean"):
+    """Validate what Predictor(views=..., fuse=...) is handed: -> a list of (rot, scale, (sx, sy, sz)) floats.  views: 2 ... MAX_VIEWS views,
+    each a dict with any of the keys rot / scale / shift or a (rot, scale, shift) tuple; view 0 must be the identity."""
+    if fuse not in FUSE_MODES:
+        raise ValueError("fuse is one of %s, not %r" % (sorted(FUSE_MODES), fuse))
+    if isinstance(views, (str, bytes, dict)) or not hasattr(views, "__len__"):
+        raise TypeError("views is a sequence of views (awr_amd.detect.make_views builds one), not %r" % (views,))
+    if not 2 <= len(views) <= MAX_VIEWS:
+        raise ValueError("views holds %d views: 2 ... %d are possible (views=None predicts from the one identity view)" % (len(views), MAX_VIEWS))
+    out = []
+    for i, v in enumerate(views):
+        if isinstance(v, dict):
+            extra = set(v) - {"rot", "scale", "shift"}
+            if extra:
+                raise ValueError("view %d has unknown keys %s (rot, scale and shift exist)" % (i, sorted(extra)))
+            rot, scale, shift = v.get("rot", 0.0), v.get("scale", 1.0), v.get("shift", (0.0, 0.0, 0.0))
+        elif isinstance(v, (tuple, list)) and len(v) == 3:
+            rot, scale, shift = v
+        else:
+            raise TypeError("view %d is a dict or a (rot, scale, shift) tuple, not %r" % (i, v))
+        rot, scale = _number(rot, "view %d: rot" % i), _number(scale, "view %d: scale" % i)
+        if not scale > 0.0:
+            raise ValueError("view %d: scale = %r must be > 0" % (i, scale))
+        if isinstance(shift, (str, bytes)) or not hasattr(shift, "__len__") or len(shift) != 3:
+            raise TypeError("view %d: shift is 3 numbers (camera millimetres), not %r" % (i, shift))
+        shift = tuple(_number(x, "view %d: shift" % i) for x in shift)
+        out.append((rot, scale, shift))
+    if out[0] != (0.0, 1.0, (0.0, 0.0, 0.0)):
+        raise ValueError("view 0 must be the identity (rot = 0, scale = 1, shift = 0): center_xyz, M and status of a prediction are its, got %r"
+                         % (out[0],))
+    return out
+
+
+def make_views(rot=(), scale=(), shift=()):
+    """The identity view, then one view per rotation (degrees), per cube scale and per centre shift (3 camera millimetres each):
+    make_views(rot=(-15, 15), scale=(0.9, 1.1)) -> five views, as a list of dicts for Predictor(views=...)."""
+    views = [dict(rot=0.0, scale=1.0, shift=(0.0, 0.0, 0.0))]
+    views += [dict(rot=r, scale=1.0, shift=(0.0, 0.0, 0.0)) for r in rot]
+    views += [dict(rot=0.0, scale=s, shift=(0.0, 0.0, 0.0)) for s in scale]
+    views += [dict(rot=0.0, scale=1.0, shift=tuple(t) if hasattr(t, "__len__") else t) for t in shift]
+    return [dict(rot=r, scale=s, shift=t) for r, s, t in check_views(views)]
+
+
+def parse_views(spec):
+    """predict.py's --views: "rot=-15,15;scale=0.9,1.1;shift=0:0:10,5:0:0" -> make_views(...) (a shift is three numbers joined by colons)"""
+    kw = {}
+    for part in filter(None, (p.strip() for p in spec.split(";"))):
+        key, _, vals = part.partition("=")
+        key = key.strip()
+        if key not in ("rot", "scale", "shift") or key in kw or not vals.strip():
+            raise ValueError("--views is like \"rot=-15,15;scale=0.9,1.1;shift=0:0:10\", not %r" % (spec,))
+        items = [v.strip() for v in vals.split(",")]
+        kw[key] = [tuple(float(x) for x in v.split(":")) for v in items] if key == "shift" else [float(v) for v in items]
+    return make_views(**kw)
+
+
+def view_table(views, dsize):
+    """-> (V, VIEW_TABLE_DOUBLES) float64, the table the three view kernels read (include/awr_hip.h "Test-time views"): per view R (9), the
+    forward rotation in crop pixels exactly as Augmenter.rotate builds it (loader.py:140-160) with the row 0 0 1; iR (6), cv2.warpAffine's
+    inverse of it; scale; shift (3); rotates (1.0 / 0.0: the reference's own `not np.allclose(rot, 0)`).  cos and sin are evaluated here and
+    nowhere else."""
+    views = check_views(views)
+    table = np.zeros((len(views), VIEW_TABLE_DOUBLES), np.float64)
+    for i, (rot, scale, shift) in enumerate(views):
+        rotates = not np.allclose(rot, 0.0)
+        R2 = ND.rotation_matrix_2d((int(dsize) // 2, int(dsize) // 2), -np.mod(rot, 360), 1) if rotates else np.array([[1.0, 0.0, 0.0], [0.0, 1.0, 0.0]])
+        table[i, 0:6], table[i, 6:9] = R2.ravel(), (0.0, 0.0, 1.0)
+        table[i, 9:15] = ND._invert_affine(R2).ravel()
+        table[i, 15], table[i, 16:19], table[i, 19] = scale, shift, float(rotates)
+    return table
+
+
+def view_centers(centers_uvd, status, cube, table, paras, flip):
+    """The statement of awr_view_centers: centres (n, 3) float64, status (n,), cube (3,) or (n, 3) -> view-major (V * n, ...) arrays:
+    centres float64, cubes float64, frame rows int64, status int32.  Scalar IEEE double, in the header's order."""
+    c_in = np.asarray(centers_uvd, np.float64).reshape(-1, 3)
+    n, V = c_in.shape[0], table.shape[0]
+    cubes = np.broadcast_to(np.asarray(cube, np.float64), (n, 3))
+    status = np.asarray(status, np.int32)
+    fx, fy, u0, v0 = (np.float64(p) for p in paras)
+    fl = np.float64(flip)
+    centers, cubes_out = np.empty((V * n, 3), np.float64), np.empty((V * n, 3), np.float64)
+    frame, st = np.empty(V * n, np.int64), np.empty(V * n, np.int32)
+    with np.errstate(all="ignore"):
+        for v in range(V):
+            scale, (sx, sy, sz) = np.float64(table[v, 15]), (np.float64(t) for t in table[v, 16:19])
+            for b in range(n):
+                r = v * n + b
+                u, w, d = c_in[b]
+                if sx == 0.0 and sy == 0.0 and sz == 0.0:
+                    centers[r] = c_in[b]
+                else:
+                    x = (u - u0) * d / fx + sx                      # evaluator.uvd2xyz, the shift, evaluator.xyz2uvd: loader.py:112 in double
+                    y = (w - v0) * d / fy * fl + sy
+                    z = d + sz
+                    yf = y * fl
+                    centers[r] = (x * fx / z + u0, yf * fy / z + v0, z)
+                cubes_out[r] = (cubes[b, 0] * scale, cubes[b, 1] * scale, cubes[b, 2] * scale)
+                frame[r], st[r] = b, status[b]
+    return centers, cubes_out, frame, st
+
+
+def view_rotate(blocks, M, status, table):
+    """The statement of awr_view_rotate: blocks, a list of V * n L.NyuSample (None where there is none), is patched in place; -> M (V * n, 3, 3)
+    float32, a copy with the rotating views' AWR_DET_OK rows replaced by float32(R . float64(M))."""
+    M = np.array(M, np.float32).reshape(-1, 3, 3)
+    V, n = table.shape[0], M.shape[0] // table.shape[0]
+    for v in range(V):
+        if table[v, 19] == 0.0:
+            continue
+        R, iR = table[v, 0:9], table[v, 9:15]
+        for b in range(n):
+            r = v * n + b
+            if status[r] != OK:
+                continue
+            if blocks is not None and blocks[r] is not None:
+                blocks[r].op = 2                                        # AWR_NYU_AFFINE
+                blocks[r].m[:] = [float(x) for x in iR] + [0.0, 0.0, 1.0]
+            a = M[r].astype(np.float64)
+            for i in range(3):
+                for k in range(3):
+                    M[r, i, k] = np.float32(((R[3 * i] * a[0, k]) + (R[3 * i + 1] * a[1, k])) + (R[3 * i + 2] * a[2, k]))
+    return M
+
+
+def fuse_views(xyz, status, ustatus, weights, mode, paras, flip):
+    """The statement of awr_views_fuse: xyz (V, n, J, 3) float32, status / ustatus (V, n), weights (V, n, J) float32 or None (read by "conf"
+    only), mode "mean" | "conf" | "median" -> (xyz (n, J, 3) float32, uvd (n, J, 3) float32, view_spread_mm (n, J) float32, views_used (n, J)
+    int32).  The header's steps 1 ... 8 in IEEE double: every line below is ONE elementwise operation over the (n, J) joints at a time (numpy
+    fuses nothing across ufuncs), and the views are walked sequentially in view order."""
+    mode = FUSE_MODES[mode] if mode in FUSE_MODES else int(mode)
+    xyz = np.asarray(xyz, np.float32)
+    V, n, J = xyz.shape[:3]
+    status, ustatus = np.asarray(status).reshape(V, n), np.asarray(ustatus).reshape(V, n)
+    x = xyz.astype(np.float64)
+    fx, fy, u0, v0 = (np.float64(p) for p in paras)
+    with np.errstate(all="ignore"):
+        frame_ok = ((status[0] == 0) & (ustatus[0] == 0))[:, None]
+        used_v, w_v = [], []
+        for v in range(V):
+            ok = frame_ok & ((status[v] == 0) & (ustatus[v] == 0))[:, None] & np.isfinite(x[v]).all(-1)
+            w = np.ones((n, J), np.float64)
+            if mode == FUSE_CONF:
+                w = np.asarray(weights, np.float32).reshape(V, n, J)[v].astype(np.float64)
+                ok = ok & np.isfinite(w) & (w > 0.0)
+            used_v.append(ok)
+            w_v.append(w)
+        used = np.zeros((n, J), np.int32)
+        sw, s = np.zeros((n, J)), [np.zeros((n, J)) for _ in range(3)]
+        for v in range(V):
+            used = used + used_v[v]
+            sw = np.where(used_v[v], sw + w_v[v], sw)
+            for a in range(3):
+                s[a] = np.where(used_v[v], s[a] + w_v[v] * x[v, :, :, a], s[a])
+        if mode == FUSE_MEDIAN:
+            m = []
+            for a in range(3):
+                t = np.sort(np.stack([np.where(used_v[v], x[v, :, :, a], np.inf) for v in range(V)]), axis=0, kind="stable")
+                mid = np.take_along_axis(t, np.minimum(used // 2, V - 1)[None], 0)[0]
+                below = np.take_along_axis(t, np.maximum(used // 2 - 1, 0)[None], 0)[0]
+                m.append(np.where(used % 2 == 1, mid, (below + mid) / 2.0))
+        else:
+            m = [s[a] / sw for a in range(3)]
+        q = np.zeros((n, J))
+        for v in range(V):
+            dx, dy, dz = x[v, :, :, 0] - m[0], x[v, :, :, 1] - m[1], x[v, :, :, 2] - m[2]
+            q = np.where(used_v[v], q + w_v[v] * ((dx * dx + dy * dy) + dz * dz), q)
+        spread = np.sqrt(q / sw)
+        none = used == 0
+        m = [np.where(none, np.nan, m[a]) for a in range(3)]
+        spread = np.where(none, np.nan, spread)
+        yf = m[1] * np.float64(flip)                                    # evaluator.xyz2uvd (util.py:3-10), in double
+        uvd = np.stack([np.where(none, np.nan, m[0] * fx / m[2] + u0), np.where(none, np.nan, yf * fy / m[2] + v0), m[2]], -1)
+    return np.stack(m, -1).astype(np.float32), uvd.astype(np.float32), spread.astype(np.float32), used.astype(np.int32)
+
+
 # ---- operator-level wrappers over the entry points (tests, tools) ------------------------------------------------------------------
 def _f64(x, dev):
     import torch
@@ -293,3 +485,51 @@ def select_device(a_center, a_status, b_center, b_status):
     L.call("awr_centers_select", L.ptr(a_center), L.ptr(a_status), L.ptr(b_center), L.ptr(b_status), B, L.ptr(out), L.ptr(status),
            L.ptr(which), L.stream())
     return out, status, which
+
+
+def view_centers_device(centers, status, cube, table, B=None, n_valid=None, paras=ND.PARAS, flip=-1, out=None):
+    """awr_view_centers on device tensors: centres (B, 3) float64, status (B,) int32, cube 3 or (B, 3) numbers, table (V, VIEW_TABLE_DOUBLES)
+    float64 -> (centres (V * B, 3) float64, cubes (V * B, 3) float64, frame (V * B,) int64, status (V * B,) int32); out: these four, to write
+    into (rows with b >= n_valid are left as they are)."""
+    import torch
+    from . import _lib as L
+    dev = centers.device
+    B = int(centers.shape[0]) if B is None else int(B)
+    n = B if n_valid is None else int(n_valid)
+    table = table if isinstance(table, torch.Tensor) else _f64(table, dev)
+    V = int(table.shape[0])
+    cb = cube if isinstance(cube, torch.Tensor) else _f64(cube, dev)
+    if out is None:
+        out = (torch.empty((V * B, 3), dtype=torch.float64, device=dev), torch.empty((V * B, 3), dtype=torch.float64, device=dev),
+               torch.empty(V * B, dtype=torch.int64, device=dev), torch.empty(V * B, dtype=torch.int32, device=dev))
+    L.call("awr_view_centers", L.ptr(centers), L.ptr(status), L.ptr(cb), 3 if cb.dim() == 2 else 0, L.ptr(table), V, B, n, float(paras[0]),
+           float(paras[1]), float(paras[2]), float(paras[3]), int(flip), L.ptr(out[0]), L.ptr(out[1]), L.ptr(out[2]), L.ptr(out[3]), L.stream())
+    return out
+
+
+def view_rotate_device(blocks, M, status, table, n_valid=None):
+    """awr_view_rotate: blocks (V * B, BLOCK_BYTES) uint8 and M (V * B, 3, 3) float32 are patched in place; status (V * B,) int32 the rows' codes
+    after awr_detect_samples."""
+    import torch
+    from . import _lib as L
+    table = table if isinstance(table, torch.Tensor) else _f64(table, M.device)
+    V = int(table.shape[0])
+    B = int(M.shape[0]) // V
+    L.call("awr_view_rotate", L.ptr(blocks), L.ptr(M), L.ptr(status), L.ptr(table), V, B, B if n_valid is None else int(n_valid), L.stream())
+    return blocks, M
+
+
+def fuse_views_device(xyz, status, ustatus, weights, mode, paras=ND.PARAS, flip=-1, n_valid=None, out=None):
+    """awr_views_fuse: xyz (V, B, J, 3) float32, status / ustatus (V, B) or (V * B,) int32, weights (V, B, J) float32 or None ->
+    (xyz (B, J, 3), uvd (B, J, 3), view_spread_mm (B, J) float32, views_used (B, J) int32); rows >= n_valid are left as they are."""
+    import torch
+    from . import _lib as L
+    V, B, J = (int(x) for x in xyz.shape[:3])
+    dev = xyz.device
+    if out is None:
+        out = (torch.empty((B, J, 3), dtype=torch.float32, device=dev), torch.empty((B, J, 3), dtype=torch.float32, device=dev),
+               torch.empty((B, J), dtype=torch.float32, device=dev), torch.empty((B, J), dtype=torch.int32, device=dev))
+    L.call("awr_views_fuse", L.ptr(xyz), L.ptr(status), L.ptr(ustatus), L.ptr(weights), FUSE_MODES[mode] if mode in FUSE_MODES else int(mode), V, B, J,
+           B if n_valid is None else int(n_valid), float(paras[0]), float(paras[1]), float(paras[2]), float(paras[3]), int(flip),
+           L.ptr(out[0]), L.ptr(out[1]), L.ptr(out[2]), L.ptr(out[3]), L.stream())
+    return out

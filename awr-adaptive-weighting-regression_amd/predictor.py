@@ -7,6 +7,7 @@
     Predictor(..., confidence=True)         # out additionally carries conf, peak, spread_mm (B, J): how sure each joint is
     Predictor(..., recenter=1)              # crop again around the predicted joints and predict again
     Predictor(..., track=True)              # start each call's crop at the previous call's joint centre of the same batch slot
+    Predictor(..., views=make_views(rot=(-15, 15)), fuse="mean")      # the same hand under several views in ONE pass, fused
 
 Everything between the frames and the joints runs on the device, on the current stream, without a synchronisation: awr_detect (hand
 centre by iterated centre of mass) -> awr_detect_samples (crop blocks, crop matrices) -> awr_nyu_batch (crop + normalise) -> the
@@ -23,6 +24,15 @@ and so repeats its previous pass bit for bit.  track=True keeps one float64 cent
 seeded with the tracked centres and as configured, and awr_centers_select takes the tracked result where it found the hand.  Nothing of this
 synchronises.  Whether either improves accuracy on real frames is UNMEASURED: no NYU frames and no trained checkpoint exist where this was
 written.
+
+Views (opt-in; views=None issues the launches and gives the bits it always did).  Test-time ensembling over the three augmentations the
+network was trained with (loader.py:75-86): in-plane rotations, cube scales and shifts of the crop centre.  The plan holds max_batch x V
+images, view-major (view v of batch slot b is row v * max_batch + b, so view 0 sits where a plain predictor's rows do).  awr_view_centers
+expands the centres, the unchanged awr_detect_samples builds V * max_batch blocks with a cube per row, awr_view_rotate turns the rotating
+views' blocks into AWR_NYU_AFFINE ones and their crop matrices into M_v = R . M; the renderer, the engine and awr_joints_unproject then run
+once over all rows -- un-projection inverts whatever matrix it is given, so a rotated view needs no arithmetic of its own -- and
+awr_views_fuse fuses the views' camera-space joints per frame and joint.  Whether fusing views lowers the joint error on real frames is
+UNMEASURED too, for the same reason.
 """
 import collections
 import types
@@ -36,13 +46,18 @@ from . import nyu_data as ND
 
 Prediction = collections.namedtuple("Prediction", "xyz uvd center_xyz M status")
 ConfidentPrediction = collections.namedtuple("ConfidentPrediction", Prediction._fields + ("conf", "peak", "spread_mm"))
+ViewPrediction = collections.namedtuple("ViewPrediction", Prediction._fields + ("view_spread_mm", "views_used"))
+ConfidentViewPrediction = collections.namedtuple("ConfidentViewPrediction", ConfidentPrediction._fields + ("view_spread_mm", "views_used"))
 MAX_RECENTER = 4
+MAX_VIEWS = D.MAX_VIEWS
 
 
 class Predictor:
+    views, fuse, V = None, "mean", 1          # a predictor without views: one identity view, no view table, no per-view buffers
+
     def __init__(self, net, img_size, kernel_size, cube=(300, 300, 300), paras=ND.PARAS, flip=-1, max_batch=1, frame_shape=(480, 640),
                  seed="nearest", depth_range=D.DEPTH_RANGE, slab=D.SLAB, refine_iters=D.REFINE_ITERS, winograd=None, parity=False, confidence=False,
-                 recenter=0, track=False, center_joints=None, max_shift=1.0):
+                 recenter=0, track=False, center_joints=None, max_shift=1.0, views=None, fuse="mean"):
         """net: an awr_amd network on the GPU with its weights loaded.  cube: the crop cube in mm.  paras = (fx, fy, u0, v0), flip: the camera.
         max_batch: the static batch of the inference plan; smaller batches are padded, larger ones refused.  seed / depth_range / slab /
         refine_iters: the detector (awr_amd.detect); with `centers_uvd` handed to predict() the seed is the given centre and refine_iters
@@ -60,7 +75,17 @@ class Predictor:
         the centre (default: all joints), uploaded once.  max_shift: the gate, in half cubes per axis, of both modes; the gate's depth range
         is depth_range.  After a predict() with recenter > 0 or track on: centers_uvd (nb, 3) float64 the final crop centres,
         next_centers_uvd (nb, 3) the joint centre of the final pass (NaN where not moved), recenter_codes (recenter + 1, nb) int32
-        awr_amd.detect's KEPT_* / MOVED, one row per awr_joints_center call -- device tensors, nothing synchronised."""
+        awr_amd.detect's KEPT_* / MOVED, one row per awr_joints_center call -- device tensors, nothing synchronised.
+        views: None | 2 ... 8 views (awr_amd.detect.make_views), each a dict or tuple of rot (degrees, in the image plane), scale (a factor
+        on the cube's three edges, > 0) and shift (3 camera millimetres added to the crop centre); view 0 must be the identity.  The plan
+        then holds max_batch * len(views) images; predict() still takes at most max_batch frames.  fuse: "mean" (every used view weighs 1) |
+        "conf" (the weight is max(conf, 0) of DESIGN.md 4.18's conf per view and joint; the engine computes it whether or not confidence=True
+        asks for the fields) | "median" (per axis).  predict() then returns a ViewPrediction / ConfidentViewPrediction: xyz and uvd are the
+        FUSED joints, center_xyz / M / status (and conf / peak / spread_mm) are view 0's, and view_spread_mm (nb, J) float32 -- the weighted
+        RMS distance of the used views' joints from the fused one -- and views_used (nb, J) int32 follow.  view_outputs holds the per-view
+        device tensors of the last call: xyz, uvd (V, nb, J, 3), M (V, nb, 3, 3), center_xyz, cube (V, nb, 3), status, ustatus (V, nb) and,
+        with an engine that has it, conf (V, nb, J) -- views into the call's buffers, nothing copied or synchronised.  With recenter / track
+        the fused joints and view 0's centre and cube are what awr_joints_center reads, and each pass expands its views anew."""
         if not isinstance(confidence, bool):
             raise TypeError("confidence is True or False, not %r" % (confidence,))
         self.confidence = confidence
@@ -81,6 +106,12 @@ class Predictor:
             nj = int(net.J)
             if not 0 < len(center_joints) <= nj or any(not 0 <= j < nj for j in center_joints):
                 raise ValueError("center_joints needs 1 ... %d indices in [0, %d), got %r" % (nj, nj, center_joints))
+        if fuse not in D.FUSE_MODES:
+            raise ValueError("fuse is one of %s, not %r" % (sorted(D.FUSE_MODES), fuse))
+        if views is not None:
+            self.views, self.fuse = D.check_views(views, fuse), fuse
+            self.V = len(self.views)
+        self.view_outputs = None
         self.recenter, self.track, self.max_shift = recenter, track, float(max_shift)
         self.centers_uvd = self.next_centers_uvd = self.recenter_codes = None
         if not torch.cuda.is_available():
@@ -100,7 +131,10 @@ class Predictor:
         self.seed, self.depth_range, self.slab, self.iters = seed, (float(depth_range[0]), float(depth_range[1])), float(slab), int(refine_iters)
         dev = self.device = net.device
         B = self.B
-        self.engine = InferEngine(net, B, self.S, kernel_size, winograd=winograd, parity=parity, confidence=confidence)
+        V = self.V
+        P = B * V                                # rows of the plan: view-major, view 0 first
+        self.engine = InferEngine(net, P, self.S, kernel_size, winograd=winograd, parity=parity,
+                                  confidence=confidence or (V > 1 and fuse == "conf"))
         self.J = self.engine.J
         # the predictor's own small frame store: the FrameStore layout, one row per image of a batch
         self._frames = torch.empty((B, self.fh, self.fw), dtype=torch.uint16, device=dev)
@@ -108,16 +142,21 @@ class Predictor:
         self._stage = torch.empty((B, self.fh, self.fw), dtype=torch.uint16).pin_memory()
         self._stage_free = None                  # event: the last upload from the staging buffer has been issued and has finished
         self._store = types.SimpleNamespace(data=self._frames, ftype=0, fh=self.fh, fw=self.fw, n=B)
-        self._render = DV.Renderer(self._store, self.S, B)
+        self._render = DV.Renderer(self._store, self.S, P)
         self._idx = torch.arange(B, dtype=torch.int64, device=dev)
         self._cube = torch.tensor([float(c) for c in cube], dtype=torch.float64, device=dev)
         self._scratch = torch.empty(int(L.lib.awr_detect_scratch(B)) // 8, dtype=torch.int64, device=dev)
         self._centers = torch.empty((B, 3), dtype=torch.float64, device=dev)
         self._seed = torch.empty((B, 3), dtype=torch.float64, device=dev)
-        self._blocks = torch.empty((B, DV.BLOCK_BYTES), dtype=torch.uint8, device=dev)
-        self._cube32 = torch.empty((B, 3), dtype=torch.float32, device=dev)
-        self._img = torch.zeros((B, 1, self.S, self.S), dtype=torch.float32, device=dev)
+        self._blocks = torch.empty((P, DV.BLOCK_BYTES), dtype=torch.uint8, device=dev)
+        self._cube32 = torch.empty((P, 3), dtype=torch.float32, device=dev)
+        self._img = torch.zeros((P, 1, self.S, self.S), dtype=torch.float32, device=dev)
         self._last = None
+        if V > 1:
+            self._vtable = torch.from_numpy(D.view_table(self.views, self.S)).to(dev)          # cos / sin are the host's: uploaded once
+            self._vcenters = torch.full((P, 3), float("nan"), dtype=torch.float64, device=dev)
+            self._vcubes = torch.ones((P, 3), dtype=torch.float64, device=dev)
+            self._vframe = torch.zeros(P, dtype=torch.int64, device=dev)
         if recenter or track:
             self._joints = None if center_joints is None else torch.tensor(center_joints, dtype=torch.int32, device=dev)
             self._moved = torch.empty((B, 3), dtype=torch.float64, device=dev)          # center_out of the call that only asks for `next`
@@ -218,12 +257,21 @@ class Predictor:
                 raise L.AwrError("centers_uvd must be (%d, 3), got %s" % (nb, tuple(c.shape)))
             self._seed[:nb].copy_(c, non_blocking=True)          # (converts to float64 on the way)
             mode, seed = D.SEED_GIVEN, self._seed
-        M = torch.empty((B, 3, 3), dtype=torch.float32, device=dev)
-        cxyz = torch.empty((B, 3), dtype=torch.float32, device=dev)
+        V, P = self.V, self.B * self.V
+        M = torch.empty((P, 3, 3), dtype=torch.float32, device=dev)
+        cxyz = torch.empty((P, 3), dtype=torch.float32, device=dev)
         status = torch.zeros(B, dtype=torch.int32, device=dev)
-        ustatus = torch.zeros(B, dtype=torch.int32, device=dev)
-        uvd = torch.empty((B, J, 3), dtype=torch.float32, device=dev)
-        xyz = torch.empty((B, J, 3), dtype=torch.float32, device=dev)
+        ustatus = torch.zeros(P, dtype=torch.int32, device=dev)
+        uvd = torch.empty((P, J, 3), dtype=torch.float32, device=dev)
+        xyz = torch.empty((P, J, 3), dtype=torch.float32, device=dev)
+        if V > 1:
+            # status: the frames' (the detector's); vstatus: one per row, view 0's first -- what every later stage and check() read
+            vstatus = torch.zeros(P, dtype=torch.int32, device=dev)
+            fxyz = torch.empty((B, J, 3), dtype=torch.float32, device=dev)
+            fuvd = torch.empty((B, J, 3), dtype=torch.float32, device=dev)
+            vspread = torch.empty((B, J), dtype=torch.float32, device=dev)
+            vused = torch.empty((B, J), dtype=torch.int32, device=dev)
+            weights = [None]
 
         def detect(mode, seed, centers, status):
             L.call("awr_detect", self._frames.data_ptr(), 0, B, self.fh, self.fw, self._idx.data_ptr(), nv, mode, L.ptr(seed), self.depth_range[0],
@@ -240,6 +288,28 @@ class Predictor:
             L.call("awr_joints_unproject", L.ptr(jt), L.ptr(cxyz), L.ptr(M), L.ptr(self._cube32), B, J, nv, float(self.S), fx, fy, u0, v0, self.flip,
                    L.ptr(uvd), L.ptr(xyz), ustatus.data_ptr(), s)
 
+        def views_and_predict():
+            # centres -> one centre, cube and frame row per view; the rows past n_valid of each view hold NaN centres: blocks without pixels
+            if nv < B:
+                self._vcenters.fill_(float("nan"))
+            L.call("awr_view_centers", self._centers.data_ptr(), status.data_ptr(), self._cube.data_ptr(), 0, self._vtable.data_ptr(), V, B, nv,
+                   fx, fy, u0, v0, self.flip, self._vcenters.data_ptr(), self._vcubes.data_ptr(), self._vframe.data_ptr(), vstatus.data_ptr(), s)
+            L.call("awr_detect_samples", self._vcenters.data_ptr(), self._vcubes.data_ptr(), 3, B, self._vframe.data_ptr(), P, self.S, self.fh,
+                   self.fw, fx, fy, u0, v0, self.flip, self._blocks.data_ptr(), L.ptr(M), L.ptr(cxyz), L.ptr(self._cube32), vstatus.data_ptr(), s)
+            L.call("awr_view_rotate", self._blocks.data_ptr(), L.ptr(M), vstatus.data_ptr(), self._vtable.data_ptr(), V, B, nv, s)
+            self._render(self._blocks, out=self._img)
+            jt = self.engine(self._img)
+            L.call("awr_joints_unproject", L.ptr(jt), L.ptr(cxyz), L.ptr(M), L.ptr(self._cube32), P, J, P, float(self.S), fx, fy, u0, v0, self.flip,
+                   L.ptr(uvd), L.ptr(xyz), ustatus.data_ptr(), s)
+            if self.fuse == "conf":
+                weights[0] = self.engine.conf[..., 0].contiguous()          # (P, J): the head's conf of every row, packed
+            L.call("awr_views_fuse", L.ptr(xyz), vstatus.data_ptr(), ustatus.data_ptr(), L.ptr(weights[0]), D.FUSE_MODES[self.fuse], V, B, J, nv,
+                   fx, fy, u0, v0, self.flip, L.ptr(fxyz), L.ptr(fuvd), L.ptr(vspread), L.ptr(vused), s)
+
+        if V > 1:
+            crop_and_predict, out_xyz, out_uvd, out_status = views_and_predict, fxyz, fuvd, vstatus
+        else:
+            out_xyz, out_uvd, out_status = xyz, uvd, status
         if self.track and seed is None:
             # the tracked centres first (a lost slot's NaN seed finds nothing), the configured detector second, per slot whichever holds
             detect(D.SEED_GIVEN, self._track, self._tcenters, self._tstatus)
@@ -253,18 +323,31 @@ class Predictor:
             codes = torch.zeros((self.recenter + 1, B), dtype=torch.int32, device=dev)
             for k in range(self.recenter):
                 # moved frames get their new centre in place, the others keep theirs: their next pass repeats this one bit for bit
-                self._joints_center(xyz, cxyz, status, ustatus, nv, self._centers, None, codes[k])
+                self._joints_center(out_xyz, cxyz, out_status, ustatus, nv, self._centers, None, codes[k])
                 crop_and_predict()
             nxt = torch.full((B, 3), float("nan"), dtype=torch.float64, device=dev)
-            self._joints_center(xyz, cxyz, status, ustatus, nv, self._moved, nxt, codes[self.recenter])
+            self._joints_center(out_xyz, cxyz, out_status, ustatus, nv, self._moved, nxt, codes[self.recenter])
             self.centers_uvd, self.next_centers_uvd, self.recenter_codes = self._centers[:nb].clone(), nxt[:nb], codes[:, :nb]
             if self.track:
                 self._track[:nv].copy_(nxt[:nv])
-        self._last = (status, ustatus, nv)
+        self._last = (out_status, ustatus, nv)
         if self.confidence:
+            # (with views: view 0's rows are the first B of every per-row buffer)
             fields = torch.empty((3, B, J), dtype=torch.float32, device=dev)
-            L.call("awr_confidence_fields", L.ptr(self.engine.conf), L.ptr(self.engine.stat), L.ptr(self._cube32), status.data_ptr(), ustatus.data_ptr(),
-                   B, J, nv, L.ptr(fields[0]), L.ptr(fields[1]), L.ptr(fields[2]), s)
+            L.call("awr_confidence_fields", L.ptr(self.engine.conf), L.ptr(self.engine.stat), L.ptr(self._cube32), out_status.data_ptr(),
+                   ustatus.data_ptr(), B, J, nv, L.ptr(fields[0]), L.ptr(fields[1]), L.ptr(fields[2]), s)
+        if V > 1:
+            per_view = dict(xyz=xyz.view(V, B, J, 3)[:, :nb], uvd=uvd.view(V, B, J, 3)[:, :nb], M=M.view(V, B, 3, 3)[:, :nb],
+                            center_xyz=cxyz.view(V, B, 3)[:, :nb], cube=self._cube32.view(V, B, 3)[:, :nb], status=vstatus.view(V, B)[:, :nb],
+                            ustatus=ustatus.view(V, B)[:, :nb])
+            if self.engine.conf is not None:
+                per_view["conf"] = (self.engine.conf[..., 0] if weights[0] is None else weights[0]).view(V, B, J)[:, :nb]
+            self.view_outputs = types.SimpleNamespace(**per_view)
+            if self.confidence:
+                return ConfidentViewPrediction(fxyz[:nb], fuvd[:nb], cxyz[:nb], M[:nb], vstatus[:nb], fields[0, :nb], fields[1, :nb], fields[2, :nb],
+                                               vspread[:nb], vused[:nb])
+            return ViewPrediction(fxyz[:nb], fuvd[:nb], cxyz[:nb], M[:nb], vstatus[:nb], vspread[:nb], vused[:nb])
+        if self.confidence:
             return ConfidentPrediction(xyz[:nb], uvd[:nb], cxyz[:nb], M[:nb], status[:nb], fields[0, :nb], fields[1, :nb], fields[2, :nb])
         return Prediction(xyz[:nb], uvd[:nb], cxyz[:nb], M[:nb], status[:nb])
 

@@ -939,6 +939,61 @@ int awr_joints_center(const float* xyz, const double* center_uvd, const float* c
 int awr_centers_select(const double* a_center, const int* a_status, const double* b_center, const int* b_status, int B, double* out_center,
                        int* out_status, int* which, void* stream);
 
+/* Test-time views (the numpy statements are awr_amd/detect.py view_table, view_centers, view_rotate and fuse_views, results
+ * are bit-identical to them): the same hand under V <= AWR_VIEWS_MAX in-plane rotations, cube scales and centre shifts -- the three
+ * augmentations of loader.py:75-86 -- carried in the batch dimension of one plan, VIEW-MAJOR: view v of frame b is row v * B + b of every
+ * (V * B, ...) array below, so view 0 occupies the rows a batch without views would.
+ *   table (V, AWR_VIEW_TABLE_DOUBLES) doubles, built on the host by detect.view_table and uploaded once; per view
+ *     [0, 9)   R       the forward rotation in crop pixels, cv2.getRotationMatrix2D((dsize / 2, dsize / 2), -mod(rot, 360), 1) as
+ *                      loader.py:140-160 calls it, extended by the row 0 0 1
+ *     [9, 15)  iR      its inverse as cv2.warpAffine takes it (nyu_data._invert_affine): the destination -> source map of AWR_NYU_AFFINE
+ *     [15]     scale   factor on the three cube edges          [16, 19) shift, camera millimetres added to the centre
+ *     [19]     rotates 1.0 where the view rotates (the reference's own test, not allclose(rot, 0)), else 0.0
+ *   The device evaluates no cosine or sine: device libm and the host's need not agree in the last bit, the table's bits are the host's.
+ * All arithmetic below is IEEE double without contraction, in the order written.
+ *
+ * awr_view_centers: one thread per (view, frame b < n_valid); rows with b >= n_valid are not written.
+ *   centers_out (V * B, 3) doubles: center_uvd[b]'s bits where the view's shift is (0, 0, 0); otherwise evaluator.xyz2uvd(uvd2xyz(c) + shift)
+ *     in their expression order (util.py:3-20, loader.py:112): x = (u - u0) * d / fx + sx;  y = (v - v0) * d / fy * flip + sy;  z = d + sz;
+ *     u' = x * fx / z + u0;  v' = (y * flip) * fy / z + v0;  d' = z
+ *   cubes_out (V * B, 3) doubles = cube[b] * scale (cube: 3 doubles with cube_stride 0, B x 3 with cube_stride 3)
+ *   frame_out (V * B) int64 = b           status_out (V * B) int32 = status[b]
+ *   These are awr_detect_samples' center_uvd, cube (cube_stride 3), frame and status over V * B rows.
+ *
+ * awr_view_rotate, after awr_detect_samples: one thread per (view, frame b < n_valid), in place.  A row of a rotating view whose status is
+ *   AWR_DET_OK gets op = AWR_NYU_AFFINE, m[0..5] = iR, m[6..8] = 0, 0, 1 in its block, and its crop matrix becomes M_v = float32(R . float64(M)),
+ *   row times column, each element ((a * b) + (c * d)) + (e * f): original-image pixels -> pixels of the rotated crop, which is all that
+ *   awr_joints_unproject needs to undo the rotation.  Every other row is left as it is (an AWR_DET_BAD_WINDOW row keeps its pixel-free block
+ *   and NaN matrix).
+ *
+ * awr_views_fuse: one thread per (frame b < n_valid, joint j); the <= 8 values per axis stay in registers.
+ *   xyz (V * B, J, 3) camera mm as awr_joints_unproject writes xyz_out; status, ustatus (V * B) the rows' codes; weights (V * B, J) float32,
+ *   read only by AWR_FUSE_CONF (may be NULL otherwise): the head's conf (awr_confidence_fields' first output before its NaN masking).
+ *   1. status or ustatus of view 0's row is non-zero -> the joint is NaN, views_used = 0, the spread is NaN
+ *   2. view v is used iff both its codes are zero, its three coordinates are finite and, for AWR_FUSE_CONF, its weight is finite and > 0
+ *      (the weight max(conf, 0), with zero weights dropped); w_v = 1 for AWR_FUSE_MEAN and AWR_FUSE_MEDIAN, the weight for AWR_FUSE_CONF
+ *   3. no view used -> the joint is NaN, views_used = 0, the spread is NaN
+ *   4. AWR_FUSE_MEAN / _CONF: m = (sum w_v x_v) / (sum w_v), both sums sequentially in view order from 0.0, one division per axis
+ *   5. AWR_FUSE_MEDIAN: per axis the middle of the used views' values in ascending order (a stable sort), or (lower + upper) / 2.0 of the
+ *      middle two
+ *   6. spread_out = float32(sqrt((sum w_v ((dx^2 + dy^2) + dz^2)) / (sum w_v))) with d = x_v - m, sequentially in view order
+ *   7. uvd_out = float32 of evaluator.xyz2uvd(m) as awr_joints_center's step 6 spells it      8. xyz_out = float32(m)
+ *   xyz_out, uvd_out (B, J, 3) float32; spread_out (B, J) float32; used_out (B, J) int32.  Rows >= n_valid are neither read nor written.
+ * V <= AWR_VIEWS_MAX, V * B <= AWR_DET_MAX_BATCH, J <= AWR_RECENTER_MAX_JOINTS: anything else returns AWR_ERR_ARG with a message, before
+ * any launch.  Each entry is one small launch on `stream`, without atomics; nothing synchronises. */
+#define AWR_VIEWS_MAX 8
+#define AWR_VIEW_TABLE_DOUBLES 20
+#define AWR_FUSE_MEAN 0
+#define AWR_FUSE_CONF 1
+#define AWR_FUSE_MEDIAN 2
+int awr_view_centers(const double* center_uvd, const int* status, const double* cube, int cube_stride, const double* table, int V, int B,
+                     int n_valid, double fx, double fy, double u0, double v0, int flip, double* centers_out, double* cubes_out,
+                     int64_t* frame_out, int* status_out, void* stream);
+int awr_view_rotate(awr_nyu_sample* samples, float* M, const int* status, const double* table, int V, int B, int n_valid, void* stream);
+int awr_views_fuse(const float* xyz, const int* status, const int* ustatus, const float* weights, int mode, int V, int B, int J, int n_valid,
+                   double fx, double fy, double u0, double v0, int flip, float* xyz_out, float* uvd_out, float* spread_out, int* used_out,
+                   void* stream);
+
 #ifdef __cplusplus
 }
 #endif

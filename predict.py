@@ -10,6 +10,10 @@ largest masked heat value, the vote scatter in nominal millimetres; DESIGN.md 4.
 batch slot 0 is the stream) and starts each frame's crop at the previous frame's joint centre, falling back to the detector when the hand is
 lost.  With either, pred_center_uvd.txt (the final crop centres) and pred_recenter_code.txt (one column per
 awr_joints_center call: 1 = moved, 0 / 2 / 3 / 4 = kept, awr_amd.detect.RECENTER_NAMES) are written too.
+--views "rot=-15,15;scale=0.9,1.1;shift=0:0:10" predicts every frame from several views in one pass -- the identity, then one view per
+in-plane rotation (degrees), per cube scale and per centre shift (x:y:z camera millimetres) -- and fuses their joints with --fuse mean |
+conf | median; pred_uvd.txt / pred_xyz.txt then hold the fused joints, and pred_view_spread_mm.txt and pred_views_used.txt
+(J columns each) are written too.
 --ema predicts with the checkpoint's averaged weights ("model_ema", written by a run with config.ema_decay) instead of "model".
 `--set` overrides config entries as train.py does (img_size, kernel_size, cube, batch_size, jt_num, downsample, winograd ...)."""
 import argparse
@@ -29,6 +33,8 @@ def parse_args(argv=None):
     ap.add_argument("--confidence", action="store_true", help="also write per-joint conf / peak / spread_mm")
     ap.add_argument("--recenter", type=int, default=0, metavar="N", help="extra passes cropped around the predicted joints (0 ... 4)")
     ap.add_argument("--track", action="store_true", help="the file is one sequence: start each crop at the previous frame's joint centre")
+    ap.add_argument("--views", default=None, metavar="SPEC", help="test-time views, e.g. \"rot=-15,15;scale=0.9,1.1;shift=0:0:10\" (the identity view comes first by itself)")
+    ap.add_argument("--fuse", default="mean", choices=("mean", "conf", "median"), help="how the views' joints are fused (with --views)")
     ap.add_argument("--ema", action="store_true", help="load the checkpoint's \"model_ema\" (the EMA of the weights) instead of \"model\"")
     return ap.parse_args(argv)
 
@@ -39,7 +45,7 @@ def main(argv=None):
     import numpy as np
     import torch
     import awr_amd
-    from awr_amd import hourglass, resnet_deconv
+    from awr_amd import detect, hourglass, resnet_deconv
     from awr_amd.config import Config
     from train import parse_overrides
 
@@ -58,12 +64,14 @@ def main(argv=None):
         raise awr_amd._lib.AwrError("{} holds no \"{}\" entry{}".format(cfg.load_model, key, " (--ema needs a checkpoint written with ema_decay)" if args.ema else ""))
     net.load_state_dict(pth[key])
     bs = 1 if args.track else min(cfg.batch_size, len(frames))
+    views = None if args.views is None else detect.parse_views(args.views)
     pred = awr_amd.Predictor(net.cuda(), cfg.img_size, cfg.kernel_size, cube=cfg.cube, max_batch=bs, frame_shape=frames.shape[1:],
                              winograd=cfg.winograd, parity=cfg.parity_infer, confidence=args.confidence,
-                             recenter=args.recenter, track=args.track)
+                             recenter=args.recenter, track=args.track, views=views, fuse=args.fuse)
     stateful = bool(args.recenter or args.track)
     centers, codes = [], []
     uvd, xyz, extra = [], [], {"conf": [], "peak": [], "spread_mm": []}
+    fused = {"view_spread_mm": [], "views_used": []}
     for lo in range(0, len(frames), bs):
         out = pred.predict(np.array(frames[lo:lo + bs]))
         uvd.append(out.uvd.cpu().numpy())
@@ -71,6 +79,9 @@ def main(argv=None):
         if args.confidence:
             for k in extra:
                 extra[k].append(getattr(out, k).cpu().numpy())
+        if views is not None:
+            for k in fused:
+                fused[k].append(getattr(out, k).cpu().numpy())
         if stateful:
             centers.append(pred.centers_uvd.cpu().numpy())
             codes.append(pred.recenter_codes.cpu().numpy().T)
@@ -84,6 +95,9 @@ def main(argv=None):
     if args.confidence:
         for k, rows in extra.items():
             np.savetxt(os.path.join(args.out, "pred_%s.txt" % k), np.concatenate(rows, 0).reshape(len(frames), cfg.jt_num), fmt="%.6g")
+    if views is not None:
+        np.savetxt(os.path.join(args.out, "pred_view_spread_mm.txt"), np.concatenate(fused["view_spread_mm"], 0), fmt="%.6g")
+        np.savetxt(os.path.join(args.out, "pred_views_used.txt"), np.concatenate(fused["views_used"], 0), fmt="%d")
     if stateful:
         np.savetxt(os.path.join(args.out, "pred_center_uvd.txt"), np.concatenate(centers, 0), fmt="%.6f")
         np.savetxt(os.path.join(args.out, "pred_recenter_code.txt"), np.concatenate(codes, 0), fmt="%d")
