@@ -9,6 +9,6 @@ from .nets import ResNetDeconv
 def get_deconv_net(layers, num_classes, downsample):
     if layers not in (18, 50, 101, 152):
         raise L.AwrError("get_deconv_net(%r, ...): the reference builds ResNet 18 / 50 / 101 / 152 (resnet_deconv.py:9-13)" % (layers,))
-    if downsample not in (1, 2, 4, 8):
-        raise L.AwrError("downsample must be one of 1,2,4,8")
+    if downsample not in (1, 2, 4):         # (awr_net_create refuses 8 too: no plan was ever built or checked at one deconvolution stage)
+        raise L.AwrError("get_deconv_net(..., downsample=%r): downsample must be 1, 2 or 4 (config.py:31)" % (downsample,))
     return ResNetDeconv(num_classes, downsample, layers)

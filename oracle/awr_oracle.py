@@ -154,10 +154,12 @@ def hourglass_manifest(nstack=1, J=14, f=256):
     return m
 
 
-def manifest_for(net, J):
-    """net: 'resnet_<18|50|101|152>' | 'hourglass_<n>' (train.py:51-57)."""
+def manifest_for(net, J, downsample=2):
+    """net: 'resnet_<18|50|101|152>' | 'hourglass_<n>' (train.py:51-57); downsample: config.downsample (config.py:31) of a ResNet --
+    the hourglass has one map size, H / 2."""
     if net.startswith("resnet"):
-        return resnet_manifest(int(net.split("_")[-1]), J, 2)
+        return resnet_manifest(int(net.split("_")[-1]), J, downsample)
+    assert downsample == 2, "the hourglass backbones have no down-sampling rate"
     return hourglass_manifest(int(net.split("_")[-1]), J)
 
 
@@ -204,14 +206,14 @@ def procedural_state(manifest, seed=0):
     return sd
 
 
-def reference_init_state(net, J, seed=0):
+def reference_init_state(net, J, seed=0, downsample=2):
     """Random init with the reference's distributions (resnet_deconv.py:93-115; torch defaults for
     hourglass, hourglass.py:10).  Values differ from the reference's RNG stream; distributions match."""
     g = torch.Generator().manual_seed(seed)
     resnet = net.startswith("resnet")
     sd = OrderedDict()
     last_w = None
-    for key, shape, kind in manifest_for(net, J):
+    for key, shape, kind in manifest_for(net, J, downsample):
         if kind == "counter":
             sd[key] = torch.zeros((), dtype=torch.int64)
         elif kind in ("bn_w", "bn_var"):
@@ -342,10 +344,10 @@ def hourglass_forward(sd, x, nstack, training=False):
     return outs
 
 
-def backbone_forward(net, sd, x, training=False):
+def backbone_forward(net, sd, x, training=False, downsample=2):
     """Returns a list of per-stage dense maps (length 1 for resnet)."""
     if net.startswith("resnet"):
-        return [resnet_forward(sd, x, training)]
+        return [resnet_forward(sd, x, training, downsample)]
     return hourglass_forward(sd, x, int(net.split("_")[-1]), training)
 
 
@@ -459,20 +461,20 @@ def params_of(sd, manifest):
     return [k for k, _, kind in manifest if kind in PARAM_KINDS]
 
 
-def loss_and_grads(net, sd, img, jt_gt, ks, coord_w, dense_w, J=None):
+def loss_and_grads(net, sd, img, jt_gt, ks, coord_w, dense_w, J=None, downsample=2):
     """Training-mode forward + backward.  Returns (loss, loss_coord, loss_dense, {key: grad|None},
     jt_pred).  Hourglass quirk (train.py:116-121): the net is run once per stage and only the LAST
     stage's loss survives; BN running stats therefore update `stacks` times."""
     J = J or jt_gt.shape[1]
-    man = manifest_for(net, J)
+    man = manifest_for(net, J, downsample)
     pkeys = params_of(sd, man)
     leaves = {k: sd[k].detach().clone().requires_grad_(True) for k in pkeys}
     work = OrderedDict((k, leaves[k] if k in leaves else sd[k]) for k in sd)
-    F = img.shape[-1] // 2
+    F = img.shape[-1] // downsample
     gt = joint2offset(jt_gt, img, ks, F)
     nstage = 1 if net.startswith("resnet") else int(net.split("_")[-1])
     for stage in range(nstage):
-        pred = backbone_forward(net, work, img, True)[stage]
+        pred = backbone_forward(net, work, img, True, downsample)[stage]
         jt = offset2joint_softmax(pred, img, ks)
         l_coord = coord_w * huber(jt, jt_gt)
         l_dense = dense_w * huber(pred, gt)

@@ -1,5 +1,6 @@
 """GPU parity of the full backbones and the fused train step (HIP path through the C ABI) against
 the oracle and the committed golden vectors (procedural weights, so nothing large is shipped)."""
+import gc
 import json
 import os
 
@@ -42,8 +43,8 @@ def amd():
     return awr_amd
 
 
-def make_net(amd, net, J, sd):
-    m = amd.get_deconv_net(int(net.split("_")[1]), J, 2) if net.startswith("resnet") else amd.PoseNet(net, J)
+def make_net(amd, net, J, sd, downsample=2):
+    m = amd.get_deconv_net(int(net.split("_")[1]), J, downsample) if net.startswith("resnet") else amd.PoseNet(net, J)
     m.load_state_dict(sd, strict=True)
     return m.cuda()
 
@@ -516,34 +517,57 @@ def test_gradients_elementwise_against_the_fp64_yardstick(amd, dev, net, cw):
     activations carry 1.8-2.6x oneDNN's rounding error on the same inputs: tools/diag_parity.py, profiles/r03_diag_parity.txt).
     Decisions may only differ from float64's where the float64 pre-activation is within 1e-4 of zero (relative to 1 + the tensor's
     largest magnitude)."""
+    gradients_against_the_fp64_yardstick(amd, dev, net, cw, 2)
+
+
+@pytest.mark.parametrize("ds,cw", [(1, 0.0), (1, 1.0), (4, 0.0), (4, 1.0)])
+def test_gradients_elementwise_at_the_other_downsample_rates(amd, dev, ds, cw):
+    """ResNet-18 at config.downsample 1 and 4 (five / three deconvolution stages, F = 128 / 32: the head kernels sample the depth image at
+    rs = 1 / 4): every parameter gradient on test_gradients_elementwise_against_the_fp64_yardstick's criterion, unchanged."""
+    gradients_against_the_fp64_yardstick(amd, dev, "resnet_18", cw, ds)
+    gc.collect()        # (the engine sits in a reference cycle: its F = 128 plan is freed here, not in the middle of a later test)
+
+
+def test_downsample_8_is_refused(amd):
+    """The reference documents config.downsample in [1, 2, 4] (config.py:31).  get_deconv_net's own check used to let 8 through, but run once
+    at 8 the gradient test above never got a network: awr_net_create refuses the rate.  Both layers say so now, in the same words."""
+    from awr_amd import _lib as L
+    from awr_amd.nets import ResNet18Deconv
+    with pytest.raises(L.AwrError, match="downsample must be 1, 2 or 4"):
+        amd.get_deconv_net(18, 14, 8)
+    with pytest.raises(L.AwrError, match="downsample must be 1, 2 or 4"):
+        ResNet18Deconv(14, 8)              # past the Python check: the library's
+
+
+def gradients_against_the_fp64_yardstick(amd, dev, net, cw, ds):
     import yardstick as Y
     from awr_amd.trainer import TrainEngine
     J, B = 14, 2
     ks = 1.0 if net.startswith("resnet") else 0.4
     img, jt_gt = O.synth_batch(B, 128, J, seed=23)
-    sd = O.reference_init_state(net, J, seed=9)
-    if (net, cw) not in _YARD_CACHE:      # (the float64 / fp32-oracle traces do not depend on the kernel mode under test: the Winograd wrapper reuses them)
-        ref = Y.trace(net, sd, img, jt_gt, ks, cw, True)
-        f32 = Y.trace(net, sd, img, jt_gt, ks, cw, False)
+    sd = O.reference_init_state(net, J, seed=9, downsample=ds)
+    if (net, cw, ds) not in _YARD_CACHE:      # (the float64 / fp32-oracle traces do not depend on the kernel mode under test: the Winograd wrapper reuses them)
+        ref = Y.trace(net, sd, img, jt_gt, ks, cw, True, downsample=ds)
+        f32 = Y.trace(net, sd, img, jt_gt, ks, cw, False, downsample=ds)
         fl32, pl32 = Y.decisions_from_trace(ref, f32)
-        ent = (ref, f32, fl32, pl32, Y.trace(net, sd, img, jt_gt, ks, cw, True, flips=fl32, pools=pl32))
-        if (net, cw) in _YARD_KEEP:       # (a trace holds every activation in float64 -- gigabytes: only the one combination that is used twice stays)
-            _YARD_CACHE[(net, cw)] = ent
+        ent = (ref, f32, fl32, pl32, Y.trace(net, sd, img, jt_gt, ks, cw, True, flips=fl32, pools=pl32, downsample=ds))
+        if (net, cw) in _YARD_KEEP and ds == 2:       # (a trace holds every activation in float64 -- gigabytes: only the one combination that is used twice stays)
+            _YARD_CACHE[(net, cw, ds)] = ent
     else:
-        ent = _YARD_CACHE[(net, cw)]
+        ent = _YARD_CACHE[(net, cw, ds)]
     ref, f32, fl32, pl32, ref_f32 = ent
-    m = make_net(amd, net, J, sd)
+    m = make_net(amd, net, J, sd, ds)
     eng = TrainEngine(m, B, 128, ks, coord_weight=cw, dense_weight=1.0, lr=1e-3, autotune=False)
     eng.step(img.to(dev), jt_gt.to(dev))
     torch.cuda.synchronize()
     flips, pools, rep = Y.decisions_from_plan(ref, eng.plan.tensors(lazy=True))
     for tag, n, mx in rep:
         assert mx < 1e-4, ("ReLU / max-pool decision differs from float64 away from a kink", tag, n, mx)
-    ref_hip = Y.trace(net, sd, img, jt_gt, ks, cw, True, flips=flips, pools=pools)
+    ref_hip = Y.trace(net, sd, img, jt_gt, ks, cw, True, flips=flips, pools=pools, downsample=ds)
     # the fused ResNet stem never materialises its ReLU / pooling decisions: they stay float64's, their near-kinks stay a (small) allowance
     # for the tensors upstream of them: the stem's own parameters
     stem_kink = Y.stem_allowance(ref) if net.startswith("resnet") else 0.0
-    pkeys = O.params_of(sd, O.manifest_for(net, J))
+    pkeys = O.params_of(sd, O.manifest_for(net, J, ds))
     gmax = max(float(ref["grads"][k].norm()) for k in pkeys if ref["grads"][k] is not None)
     rows, bad = [], []
     for k in pkeys:
@@ -559,7 +583,7 @@ def test_gradients_elementwise_against_the_fp64_yardstick(amd, dev, net, cw):
         if not e_hip <= 3.0 * e_f32 + allow + 2e-5:
             bad.append((k, e_hip, e_f32, stem_kink))
     ratios = [r[0] for r in rows]
-    tagp = "%s/cw%d/grad_vs_fp64/" % (net, int(cw))
+    tagp = "%s%s/cw%d/grad_vs_fp64/" % (net, "" if ds == 2 else "/ds%d" % ds, int(cw))
     report(tagp + "median_ratio_hip_over_fp32_oracle", float(np.median(ratios)))
     report(tagp + "max_rel_l2_err_hip", max(r[2] for r in rows))
     report(tagp + "max_rel_l2_err_fp32_oracle", max(r[3] for r in rows))

@@ -1,6 +1,7 @@
 """GPU: winograd="auto" -- the engines time their candidate plans (winograd_auto.py) and run the chosen one.  The search leaves no trace (parameters,
 BatchNorm running statistics, optimiser state, inputs), frees every candidate it built, runs exactly the plan an explicit engine of the chosen mode
 runs, meets the golden bars, and a second engine with the same AWR_TUNE_CACHE reuses the stored decision without building a candidate."""
+import gc
 import os
 
 import numpy as np
@@ -90,6 +91,7 @@ def test_forced_choice_runs_the_explicit_modes_plan(amd, monkeypatch):
     img, jt_gt = O.synth_batch(B, 128, J, seed=5)
     sd = O.reference_init_state("resnet_18", J, seed=4)
     ma, mf = make_net(amd, "resnet_18", J, sd), make_net(amd, "resnet_18", J, sd)
+    gc.collect()        # engines of earlier tests that sit in reference cycles are freed now, not by a collection inside the windows measured below
     torch.cuda.synchronize()
     a0, f0 = torch.cuda.memory_allocated(), torch.cuda.mem_get_info()[0]
     ea = TrainEngine(ma, B, 128, ks, coord_weight=1.0, use_graph=False, autotune=False, winograd="auto")

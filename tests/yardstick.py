@@ -13,7 +13,7 @@ import torch
 import awr_oracle as O
 
 
-def trace(net, sd, img, jt_gt, ks, cw, f64=True, flips=None, pools=None):
+def trace(net, sd, img, jt_gt, ks, cw, f64=True, flips=None, pools=None, downsample=2):
     """One forward + backward of the oracle.  Returns dict(acts, grads, relus, loss):
     acts  {name: tensor}    raw conv outputs "<layer>.out", hourglass residual outputs "<block>.resout", "pred" (.grad retained)
     grads {param key: grad}
@@ -22,14 +22,15 @@ def trace(net, sd, img, jt_gt, ks, cw, f64=True, flips=None, pools=None):
     pools {tag: (input (detached), argmax indices)} of every max-pool, tag = name of the pooled tensor ("pre.1.resout", ...)
     flips {tag: bool mask}  elements whose ReLU derivative is flipped (value unchanged).
     pools (argument) {tag: indices}: max-pools whose gradient is routed to THESE window elements (the other decision a rounding-level
-          perturbation can change: two window elements within 1e-6 of each other; the forward value moves by that much, which is noise)."""
+          perturbation can change: two window elements within 1e-6 of each other; the forward value moves by that much, which is noise).
+    downsample: config.downsample of a ResNet (the manifest, the deconvolution stages and the F = H / downsample of the GT map)."""
     TF = O.TF
     acts, relus, tags, alive, pooled = {}, {}, {}, [], {}
     last_bn = [None]
     o_conv, o_convt, o_relu, o_res, o_bn, o_pool = TF.conv2d, TF.conv_transpose2d, TF.relu, O._hg_res, O._bn, TF.max_pool2d
     dt = torch.float64 if f64 else torch.float32
     work = {k: (v.to(dt) if v.is_floating_point() else v.clone()) for k, v in sd.items()}
-    pkeys = O.params_of(work, O.manifest_for(net, jt_gt.shape[1]))
+    pkeys = O.params_of(work, O.manifest_for(net, jt_gt.shape[1], downsample))
     leaves = {k: work[k].detach().clone().requires_grad_(True) for k in pkeys}
     for k in pkeys:
         work[k] = leaves[k]
@@ -85,8 +86,8 @@ def trace(net, sd, img, jt_gt, ks, cw, f64=True, flips=None, pools=None):
     O.HIGH_PRECISION = bool(f64)
     try:
         im, jg = img.to(dt), jt_gt.to(dt)
-        gt = O.joint2offset(jg, im, ks, img.shape[-1] // 2)
-        pred = keep("pred", O.backbone_forward(net, work, im, True)[-1])
+        gt = O.joint2offset(jg, im, ks, img.shape[-1] // downsample)
+        pred = keep("pred", O.backbone_forward(net, work, im, True, downsample)[-1])
         loss = cw * O.huber(O.offset2joint_softmax(pred, im, ks), jg) + O.huber(pred, gt)
         loss.backward()
     finally:
