@@ -135,6 +135,19 @@ class FrameStore:
             hi = min(self.n, lo + chunk)
             self.data[lo:hi].copy_(torch.from_numpy(np.array(frames[lo:hi])), non_blocking=False)      # (np.array: a writable copy of the memmap chunk)
 
+    @classmethod
+    def from_device(cls, tensor):
+        """A store over an (n, fh, fw) uint16 or float32 device tensor that is already there (rendered frames, say): no host copy."""
+        if not isinstance(tensor, torch.Tensor) or not tensor.is_cuda or tensor.dim() != 3 or not tensor.is_contiguous():
+            raise L.AwrError("from_device takes a contiguous (n, h, w) device tensor")
+        if tensor.dtype not in (torch.uint16, torch.float32):
+            raise ValueError("frame store holds uint16 or float32 frames, not %s" % tensor.dtype)
+        self = cls.__new__(cls)
+        self.ftype = 0 if tensor.dtype == torch.uint16 else 1
+        self.n, self.fh, self.fw = (int(v) for v in tensor.shape)
+        self.data = tensor
+        return self
+
     @property
     def nbytes(self):
         return self.data.numel() * self.data.element_size()

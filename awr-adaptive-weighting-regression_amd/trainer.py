@@ -1012,6 +1012,11 @@ class Trainer:
             test_data = NYU(root, "test", **kw)
         self.trainData, self.testData, self.pg = train_data, test_data, process_group
         self._render = getattr(self, "_render", {})
+        for phase, data in (("train", train_data), ("test", test_data)):      # a device dataset handed in as an object brings its frames along
+            store = getattr(data, "frame_store", None)
+            if store is not None and phase not in self._render:
+                from . import nyu_device as DV
+                self._render[phase] = DV.Renderer(store, config.img_size, config.batch_size)
         self.rank = torch.distributed.get_rank(process_group) if process_group is not None else 0
         self.work_dir = os.path.join(config.output_dir, config.dataset, "checkpoint_" + config.exp_id)
         self.result_dir = os.path.join(self.work_dir, "results")

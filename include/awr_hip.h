@@ -994,6 +994,38 @@ int awr_views_fuse(const float* xyz, const int* status, const int* ustatus, cons
                    double fx, double fy, double u0, double v0, int flip, float* xyz_out, float* uvd_out, float* spread_out, int* used_out,
                    void* stream);
 
+/* ------------------------------------------------------------------------------------------
+ * Synthetic hand frames (csrc/awr_synth.hip; statement: awr_amd/synth.py render)
+ *
+ * awr_synth_render casts one depth ray per pixel against a union of capsules and writes raw uint16 millimetre frames -- the input of
+ * awr_detect and awr_nyu_batch -- into rows [row, row + n) of `out`, a (capacity, fh, fw) uint16 frame store.
+ *   prims (n, K, 8) doubles, rows `ax ay az bx by bz r 0` in camera millimetres: the segment a -> b swept by a sphere of radius r; r <= 0
+ *     marks an unused row; a == b is a sphere.  All trigonometry is the host's: the device evaluates + - * / and square roots only.
+ *   bbox (n, 4) int32 `u_lo v_lo u_hi v_hi`: pixels outside [u_lo, u_hi) x [v_lo, v_hi) are background; the box is clipped to the frame.
+ *   Pixel (u, v) of frame i: the ray t * ((u - u0) / fx, flip * ((v - v0) / fy), 1); the depth is the smallest t at which it ENTERS a used
+ *     capsule (the operation order, capsule by capsule, is written out at the top of awr_amd/synth.py and repeated in the kernel: every
+ *     dot product (x x' + y y') + z z', no fused multiply-add; whether a capsule counts is decided by signs of polynomials in the inputs,
+ *     square roots only place the hit).  Value: floor(t + 0.5) clipped to [1, 65535]; with background_mm > 0 (a wall) a value >=
+ *     background_mm is the wall's.  Background: 0 or the wall.  noise_mm = a > 0 adds hash(seed, frame0 + i, v * fw + u) % (2 a + 1) - a
+ *     (a uint32 hash, the same in awr_amd.synth.hash_u32) to hit pixels and to the wall and clips to [1, 65535] again: the GLOBAL frame
+ *     index enters the hash, so a store rendered in chunks equals one rendered by a single call.
+ *   status (n) int32: AWR_SYNTH_OK, AWR_SYNTH_EMPTY (no pixel was hit: the frame is all background) or AWR_SYNTH_BAD_PRIM (a used row holds
+ *     Inf / NaN: the frame is all background; the other frames of the call are not affected).  Nothing in the table can fault.
+ * Two launches on `stream` (one thread per frame writes the status, then one workgroup per 64 x 16 pixel tile; a workgroup that hit
+ * something clears the EMPTY bit with one integer atomic); no float atomics, nothing synchronises.  NULL pointers, n outside
+ * [1, AWR_SYNTH_MAX_FRAMES], K outside [1, AWR_SYNTH_MAX_PRIMS], fh or fw outside [1, AWR_SYNTH_MAX_EDGE], flip not +-1, a zero focal
+ * length, background_mm outside [0, 65535], noise_mm outside [0, 32767], a negative frame0 and rows that do not fit `capacity` return
+ * AWR_ERR_ARG with a message, before any launch. */
+#define AWR_SYNTH_OK 0
+#define AWR_SYNTH_EMPTY 1
+#define AWR_SYNTH_BAD_PRIM 2
+#define AWR_SYNTH_MAX_PRIMS 32
+#define AWR_SYNTH_MAX_FRAMES 65535
+#define AWR_SYNTH_MAX_EDGE 16384
+int awr_synth_render(const double* prims, const int* bbox, int n, int K, int fh, int fw, double fx, double fy, double u0, double v0, int flip,
+                     int background_mm, int noise_mm, unsigned int seed, int64_t frame0, uint16_t* out, int64_t row, int64_t capacity,
+                     int* status, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -7,6 +7,8 @@ MI355X engines.
 
 `--set key=value ...` overrides config entries for this run (values are parsed as Python literals when possible);
 `--synthetic N` trains on N procedurally generated hands instead of NYU (no dataset on this machine);
+`--synthetic-frames N [--synthetic-seed S]` trains on N articulated procedural hands rendered on the GPU as raw 480 x 640 depth frames
+(awr_amd.synth.SyntheticFrames: frame store, device loader and augmentation as for NYU) and tests on max(batch_size, N // 8) others;
 `--test-only` runs the evaluation pass of test.py on the loaded checkpoint.
 """
 import argparse
@@ -32,6 +34,8 @@ def main(argv=None, test_only=False):
     ap = argparse.ArgumentParser(description=__doc__, formatter_class=argparse.RawDescriptionHelpFormatter)
     ap.add_argument("--set", nargs="*", default=[], metavar="key=value")
     ap.add_argument("--synthetic", type=int, default=0, metavar="N")
+    ap.add_argument("--synthetic-frames", type=int, default=0, metavar="N")
+    ap.add_argument("--synthetic-seed", type=int, default=1, metavar="S")
     ap.add_argument("--test-only", action="store_true")
     args = ap.parse_args(argv)
 
@@ -52,6 +56,14 @@ def main(argv=None, test_only=False):
     if args.synthetic:
         data = (SyntheticHands(args.synthetic, seed=1, img_size=cfg.img_size, jt_num=cfg.jt_num),
                 SyntheticHands(max(cfg.batch_size, args.synthetic // 8), seed=2, img_size=cfg.img_size, jt_num=cfg.jt_num))
+    if args.synthetic_frames:
+        if args.synthetic:
+            ap.error("--synthetic and --synthetic-frames are two different stand-ins for the data: pick one")
+        from awr_amd.synth import SyntheticFrames
+        kw = dict(jt_num=cfg.jt_num, img_size=cfg.img_size, cube=cfg.cube)
+        frames = (SyntheticFrames(args.synthetic_frames, args.synthetic_seed, "train", aug_para=cfg.augment_para, **kw),
+                  SyntheticFrames(max(cfg.batch_size, args.synthetic_frames // 8), args.synthetic_seed + 1, "test", **kw))
+        data = (frames[0].dataset, frames[1].dataset)
     trainer = Trainer(cfg, data[0], data[1], process_group=pg)
     if test_only or args.test_only:
         trainer.test(-1)
