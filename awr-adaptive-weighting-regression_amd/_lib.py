@@ -251,6 +251,9 @@ _SIGS = {
     "awr_detect_samples": ([_P, _P, _I, _L, _P, _I, _I, _I, _I, _D, _D, _D, _D, _I, _P, _P, _P, _P, _P, _P], C.c_int),
     "awr_joints_center": ([_P, _P, _P, _P, _P, _P, _I, _I, _I, _P, _I, _D, _D, _D, _D, _I, _D, _D, _D, _P, _P, _P, _P], C.c_int),
     "awr_centers_select": ([_P, _P, _P, _P, _I, _P, _P, _P, _P], C.c_int),
+    # palm centre from an exact distance transform (csrc/awr_palm.hip)
+    "awr_detect_palm_scratch": ([_I, _I, _I], C.c_int64),
+    "awr_detect_palm": ([_P, _I, _L, _I, _I, _P, _I, _P, _P, _D, _D, _P, _I, _D, _D, _D, _I, _I, _I, _I, _P, _P, _P, _P, _P], C.c_int),
     # test-time views (csrc/awr_detect.hip)
     "awr_view_centers": ([_P, _P, _P, _I, _P, _I, _I, _I, _D, _D, _D, _D, _I, _P, _P, _P, _P, _P], C.c_int),
     "awr_view_rotate": ([_P, _P, _P, _P, _I, _I, _I, _P], C.c_int),

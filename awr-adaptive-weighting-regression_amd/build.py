@@ -33,6 +33,7 @@ SOURCES = {
     "awr_nyu.hip": ["-ffp-contract=off"],     # NYU data path: numpy's / OpenCV's arithmetic, no fused multiply-adds
     "awr_eval.hip": ["-ffp-contract=off"],    # joint scoring: the host evaluator's numpy arithmetic
     "awr_detect.hip": ["-ffp-contract=off"],  # hand detection: center2bounds / set_crop in numpy's double arithmetic
+    "awr_palm.hip": ["-ffp-contract=off"],    # palm centre: integer distance transform; center2bounds' double arithmetic for the window
     "awr_synth.hip": ["-ffp-contract=off"],   # synthetic hand frames: the ray / capsule arithmetic of synth.render, operation by operation
 }
 

@@ -8,6 +8,8 @@ Two things live here:
     `select_device`) for tests and tools.  `awr_amd.predictor.Predictor` is the product path.
   * `joints_center` and `select`: the statements of awr_joints_center (predicted joints -> the next crop centre, with a gate) and
     awr_centers_select (a tracked centre where it is usable, the detector's otherwise); DESIGN.md 4.19.
+  * `palm_center` and `distance_transform`: the statement of awr_detect_palm (csrc/awr_palm.hip) -- a detector centre ->
+    the centre of the palm disc of an exact integer distance transform, which a forearm does not drag up the arm; `palm_device` wraps it.
   * `make_views`, `check_views`, `view_table`, `view_centers`, `view_rotate` and `fuse_views`: test-time views -- the host
     table of the views' rotations and the statements of awr_view_centers, awr_view_rotate and awr_views_fuse.
 
@@ -201,6 +203,125 @@ def select(a_center, a_status, b_center, b_status):
         if a_status[b] == OK and all(np.isfinite(a_center[b])):
             out[b], status[b], which[b] = a_center[b], a_status[b], 0
     return out, status, which
+
+
+# ---- forearm-robust palm centre from an exact distance transform (include/awr_hip.h awr_detect_palm) -------------------
+# Integers only: with frame sides up to PALM_MAX_SIDE = 16384, D2 <= 2^28, L <= 2^29, |t|, |s| <= 2^30, so s * s <= 2^60, m * L <= 2^57 and
+# tau * D2, rho2 * |p - p*|^2 (tau, rho2 below 2^31) <= 2^60: every product stays below 2^62 in int64.
+PALM_SEARCH, PALM_TAU, PALM_RHO2, PALM_MAX_SIDE = 2.0, (1, 3), (25, 4), 16384
+_NO_INFO = (-1, -1, 0, 0)
+
+
+def _ratio(x, what, order):
+    """(a, b) ints in [1, 2^31): order "le" needs a <= b (tau), "ge" needs a >= b (rho2)"""
+    if isinstance(x, (str, bytes)) or not hasattr(x, "__len__") or len(x) != 2 or any(isinstance(t, bool) or not isinstance(t, (int, np.integer)) for t in x):
+        raise TypeError("%s is a pair of ints (numerator, denominator), not %r" % (what, x))
+    a, b = int(x[0]), int(x[1])
+    if not (0 < a < 2 ** 31 and 0 < b < 2 ** 31 and (a <= b if order == "le" else a >= b)):
+        raise ValueError("%s = %r needs %s, both below 2^31" % (what, x, "0 < %s[0] <= %s[1]" % (what, what) if order == "le" else "0 < %s[1] <= %s[0]" % (what, what)))
+    return a, b
+
+
+def check_palm(search=PALM_SEARCH, tau=PALM_TAU, rho2=PALM_RHO2):
+    """Validate palm_center's three knobs: -> (search float, (tau0, tau1), (rho0, rho1))."""
+    search = _number(search, "search")
+    if not search > 0.0:
+        raise ValueError("search = %r must be > 0" % (search,))
+    return search, _ratio(tau, "tau", "le"), _ratio(rho2, "rho2", "ge")
+
+
+def distance_transform(mask):
+    """Exact squared Euclidean distance transform of a (h, w) boolean window, int64: D2(p) = min over background q of |p - q|^2, where
+    everything outside the window -- the one-pixel ring around it and beyond -- is background; 0 on background.  Two passes: g, the
+    distance along the column to the nearest background row (the ring rows count), then D2(v, u) = min over u' of (u - u')^2 + g(v, u')^2
+    (g = 0 on the ring columns and beyond).  Only |u - u'| < max g can lower a pixel's own g^2, and rows without foreground stay 0."""
+    mask = np.asarray(mask, bool)
+    h, w = mask.shape
+    g = np.zeros((h, w), np.int64)
+    run = np.zeros(w, np.int64)
+    for i in range(h):
+        run = np.where(mask[i], run + 1, 0)
+        g[i] = run
+    run = np.zeros(w, np.int64)
+    for i in range(h - 1, -1, -1):
+        run = np.where(mask[i], run + 1, 0)
+        np.minimum(g[i], run, out=g[i])
+    d2 = g * g
+    rows = np.nonzero(mask.any(axis=1))[0]
+    if rows.size:
+        gm = int(g.max())
+        G = np.zeros((rows.size, w + 2 * gm), np.int64)
+        G[:, gm:gm + w] = d2[rows]
+        best = d2[rows]
+        for k in range(1, gm):
+            np.minimum(best, G[:, gm - k:gm - k + w] + k * k, out=best)
+            np.minimum(best, G[:, gm + k:gm + k + w] + k * k, out=best)
+        d2[rows] = best
+    return d2
+
+
+def _first_argmax(values, where):
+    """(row, col) of the first maximum of the non-negative `values` over `where`, in raster order"""
+    return np.unravel_index(int(np.argmax(np.where(where, values, -1))), values.shape)
+
+
+def palm_center(frame, center, status=OK, cube=(300, 300, 300), paras=ND.PARAS, depth_range=DEPTH_RANGE, search=PALM_SEARCH, tau=PALM_TAU,
+                rho2=PALM_RHO2):
+    """The statement of awr_detect_palm (include/awr_hip.h): a detector centre -> the centre of the palm disc, which a
+    forearm does not drag up the arm.  -> ((u, v, d) float64, status, info = (pu, pv, r2, n_disc) ints: the palm point in frame pixels,
+    its squared distance to the background and the pixels of the disc; (-1, -1, 0, 0) where there is none).
+      1. status != OK: centre and status pass through.
+      2. window W = center2bounds(centre, search * cube, paras) clipped to the frame; mask = pixels of W with d != 0 whose depth lies in
+         that call's [zstart, zend] and in depth_range.  No window or no pixel: NaN, EMPTY.
+      3. D2 = distance_transform(mask).     4. m = max D2; S = {tau[1] * D2 >= tau[0] * m}, the medial set.
+      5. every argmax takes the first maximum in raster order: e0 = argmax_S D2, e1 = argmax_S |p - e0|^2, e2 = argmax_S |p - e1|^2,
+         a = e2 - e1, L = |a|^2.
+      6. L == 0: p* = e0.  Otherwise t(p) = (p - e1) . a, b1 = mask pixels with t < 0, b2 = mask pixels with t > L (what lies beyond
+         either end: fingers beyond the hand's), s = L - t if b2 >= b1 else t, N = {p in S: s <= 0 or s * s <= m * L}, p* = argmax_N D2.
+      7. r2 = D2(p*); disc = mask pixels with rho2[1] * |p - p*|^2 <= rho2[0] * r2; centre = (su / n, sv / n, sd / n) of the disc.
+    All arithmetic is int64 up to the last three double divisions."""
+    frame = _u16(frame)
+    fh, fw = frame.shape
+    if fh > PALM_MAX_SIDE or fw > PALM_MAX_SIDE:
+        raise ValueError("a frame of %d x %d is outside [1, %d]^2" % (fh, fw, PALM_MAX_SIDE))
+    search, (tau0, tau1), (rho0, rho1) = check_palm(search, tau, rho2)
+    zmin, zmax = float(depth_range[0]), float(depth_range[1])
+    if not zmin <= zmax:
+        raise ValueError("depth_range needs zmin <= zmax")
+    c = tuple(float(x) for x in center)
+    if int(status) != OK:
+        return c, int(status), _NO_INFO
+    w = _window(c, tuple(search * float(x) for x in cube), paras, fh, fw)
+    if w is None or w[0][0] >= w[0][1] or w[0][2] >= w[0][3]:
+        return _NAN3, EMPTY, _NO_INFO
+    (u0, u1, v0, v1), zstart, zend = w
+    win = frame[v0:v1, u0:u1]
+    mask = (win >= zstart) & (win <= zend) & (win >= zmin) & (win <= zmax) & (win != 0)
+    if not mask.any():
+        return _NAN3, EMPTY, _NO_INFO
+    D2 = distance_transform(mask)
+    m = int(D2.max())
+    S = tau1 * D2 >= tau0 * m
+    vv, uu = np.indices(mask.shape, dtype=np.int64)
+    e0 = _first_argmax(D2, S)
+    e1 = _first_argmax((vv - e0[0]) ** 2 + (uu - e0[1]) ** 2, S)
+    e2 = _first_argmax((vv - e1[0]) ** 2 + (uu - e1[1]) ** 2, S)
+    av, au = int(e2[0]) - int(e1[0]), int(e2[1]) - int(e1[1])
+    L = av * av + au * au
+    if L == 0:
+        pv, pu = int(e0[0]), int(e0[1])
+    else:
+        t = (vv - e1[0]) * av + (uu - e1[1]) * au
+        b1, b2 = int(np.count_nonzero(mask & (t < 0))), int(np.count_nonzero(mask & (t > L)))
+        s = L - t if b2 >= b1 else t
+        N = S & ((s <= 0) | (s * s <= m * L))
+        pv, pu = (int(x) for x in _first_argmax(D2, N))
+    r2 = int(D2[pv, pu])
+    disc = mask & (rho1 * ((vv - pv) ** 2 + (uu - pu) ** 2) <= rho0 * r2)
+    n = int(np.count_nonzero(disc))
+    su, sv = int(uu[disc].sum()) + n * u0, int(vv[disc].sum()) + n * v0
+    sd = int(win[disc].astype(np.int64).sum())
+    return (float(su) / float(n), float(sv) / float(n), float(sd) / float(n)), OK, (pu + u0, pv + v0, r2, n)
 
 
 # ---- test-time views: the same hand under rotations, cube scales and centre shifts (DESIGN.md 4.22) ----------------------------------
@@ -418,6 +539,36 @@ def detect_device(store, frame_idx, seed="nearest", centers=None, cube=(300, 300
            L.ptr(seed_t), float(depth_range[0]), float(depth_range[1]), float(slab), cb.data_ptr(), 3 if cb.dim() == 2 else 0,
            float(paras[0]), float(paras[1]), int(iters), int(parts), scratch.data_ptr(), out.data_ptr(), status.data_ptr(), L.stream())
     return out, status
+
+
+def palm_device(store, frame_idx, centers, status, cube=(300, 300, 300), paras=ND.PARAS, depth_range=DEPTH_RANGE, search=PALM_SEARCH,
+                tau=PALM_TAU, rho2=PALM_RHO2, center_out=None, status_out=None, info=True, scratch=None):
+    """awr_detect_palm on a FrameStore-like object: centres (B, 3) float64 and status (B,) int32 on the device, as detect_device returns them
+    -> (centres (B, 3) float64, status (B,) int32, info (B, 4) int32 or None) on the device, nothing synchronised.  center_out / status_out:
+    tensors to write into (they may be the inputs); info: True (allocated), False (NULL) or a tensor; scratch: an int32 tensor of at least
+    awr_detect_palm_scratch(B, fh, fw) bytes."""
+    import torch
+    from . import _lib as L
+    search, (tau0, tau1), (rho0, rho1) = check_palm(search, tau, rho2)
+    dev = store.data.device
+    idx = torch.as_tensor(np.asarray(frame_idx, np.int64)).to(dev) if not isinstance(frame_idx, torch.Tensor) else frame_idx
+    B = int(idx.shape[0])
+    cb = cube if isinstance(cube, torch.Tensor) else _f64(cube, dev)
+    if scratch is None:
+        nbytes = int(L.lib.awr_detect_palm_scratch(B, store.fh, store.fw))
+        if nbytes < 0:
+            raise L.AwrError(L.last_error())
+        scratch = torch.empty(nbytes // 4, dtype=torch.int32, device=dev)
+    center_out = torch.empty((B, 3), dtype=torch.float64, device=dev) if center_out is None else center_out
+    status_out = torch.empty(B, dtype=torch.int32, device=dev) if status_out is None else status_out
+    if info is True:
+        info = torch.empty((B, 4), dtype=torch.int32, device=dev)
+    elif info is False:
+        info = None
+    L.call("awr_detect_palm", store.data.data_ptr(), store.ftype, int(store.data.shape[0]), store.fh, store.fw, idx.data_ptr(), B, L.ptr(centers),
+           L.ptr(status), float(depth_range[0]), float(depth_range[1]), cb.data_ptr(), 3 if cb.dim() == 2 else 0, float(paras[0]),
+           float(paras[1]), search, tau0, tau1, rho0, rho1, scratch.data_ptr(), L.ptr(center_out), L.ptr(status_out), L.ptr(info), L.stream())
+    return center_out, status_out, info
 
 
 def samples_device(centers, cube, dsize, frame_idx, n_frames, frame_shape, paras=ND.PARAS, flip=-1, status=None):

@@ -8,6 +8,7 @@
     Predictor(..., recenter=1)              # crop again around the predicted joints and predict again
     Predictor(..., track=True)              # start each call's crop at the previous call's joint centre of the same batch slot
     Predictor(..., views=make_views(rot=(-15, 15)), fuse="mean")      # the same hand under several views in ONE pass, fused
+    Predictor(..., palm=True)               # move the detector's centre to the palm disc, away from the forearm
 
 Everything between the frames and the joints runs on the device, on the current stream, without a synchronisation: awr_detect (hand
 centre by iterated centre of mass) -> awr_detect_samples (crop blocks, crop matrices) -> awr_nyu_batch (crop + normalise) -> the
@@ -33,6 +34,14 @@ views' blocks into AWR_NYU_AFFINE ones and their crop matrices into M_v = R . M;
 once over all rows -- un-projection inverts whatever matrix it is given, so a rotated view needs no arithmetic of its own -- and
 awr_views_fuse fuses the views' camera-space joints per frame and joint.  Whether fusing views lowers the joint error on real frames is
 UNMEASURED too, for the same reason.
+
+Palm centre (opt-in; palm=False issues the launches and gives the bits it always did).  The detector's centre of mass is dragged up a
+forearm that lies at the hand's depth, and no later pass repairs a first crop that misses the hand.  palm=True sends the configured
+detector's centres through awr_detect_palm (nine small launches, a frame split over several workgroups: the exact integer distance transform of the silhouette in a
+window of palm_search cubes, its medial set, the end of it with the fingers beyond, the palm disc's centre of mass) before
+awr_detect_samples.  With track=True only the detector branch is refined, before awr_centers_select: a tracked centre is the joints' own.
+With centers_uvd handed to predict() it does not apply.  Measured on procedural hands only (profiles/synth_accuracy.txt); behaviour on real
+depth frames -- sleeves, a body within the search depth, NYU -- is UNMEASURED.
 """
 import collections
 import types
@@ -57,7 +66,7 @@ class Predictor:
 
     def __init__(self, net, img_size, kernel_size, cube=(300, 300, 300), paras=ND.PARAS, flip=-1, max_batch=1, frame_shape=(480, 640),
                  seed="nearest", depth_range=D.DEPTH_RANGE, slab=D.SLAB, refine_iters=D.REFINE_ITERS, winograd=None, parity=False, confidence=False,
-                 recenter=0, track=False, center_joints=None, max_shift=1.0, views=None, fuse="mean"):
+                 recenter=0, track=False, center_joints=None, max_shift=1.0, views=None, fuse="mean", palm=False, palm_search=D.PALM_SEARCH):
         """net: an awr_amd network on the GPU with its weights loaded.  cube: the crop cube in mm.  paras = (fx, fy, u0, v0), flip: the camera.
         max_batch: the static batch of the inference plan; smaller batches are padded, larger ones refused.  seed / depth_range / slab /
         refine_iters: the detector (awr_amd.detect); with `centers_uvd` handed to predict() the seed is the given centre and refine_iters
@@ -85,7 +94,14 @@ class Predictor:
         RMS distance of the used views' joints from the fused one -- and views_used (nb, J) int32 follow.  view_outputs holds the per-view
         device tensors of the last call: xyz, uvd (V, nb, J, 3), M (V, nb, 3, 3), center_xyz, cube (V, nb, 3), status, ustatus (V, nb) and,
         with an engine that has it, conf (V, nb, J) -- views into the call's buffers, nothing copied or synchronised.  With recenter / track
-        the fused joints and view 0's centre and cube are what awr_joints_center reads, and each pass expands its views anew."""
+        the fused joints and view 0's centre and cube are what awr_joints_center reads, and each pass expands its views anew.
+        palm: True -- the configured detector's centres go through awr_detect_palm (awr_amd.detect.palm_center) before the
+        crop; not applied to centers_uvd handed to predict() nor to a tracked centre.  palm_search: the side of its window in cubes.  After
+        such a predict(), palm_info (nb, 4) int32 holds awr_detect_palm's info rows (palm point u, v, its squared radius, pixels of the disc)."""
+        if not isinstance(palm, bool):
+            raise TypeError("palm is True or False, not %r" % (palm,))
+        self.palm, self.palm_search = palm, D.check_palm(palm_search)[0]
+        self.palm_info = None
         if not isinstance(confidence, bool):
             raise TypeError("confidence is True or False, not %r" % (confidence,))
         self.confidence = confidence
@@ -160,6 +176,12 @@ class Predictor:
         if recenter or track:
             self._joints = None if center_joints is None else torch.tensor(center_joints, dtype=torch.int32, device=dev)
             self._moved = torch.empty((B, 3), dtype=torch.float64, device=dev)          # center_out of the call that only asks for `next`
+        if palm:
+            nbytes = int(L.lib.awr_detect_palm_scratch(B, self.fh, self.fw))
+            if nbytes < 0:
+                raise L.AwrError(L.last_error())
+            self._palm_scratch = torch.empty(nbytes // 4, dtype=torch.int32, device=dev)
+            self._palm_info = torch.empty((B, 4), dtype=torch.int32, device=dev)
         if track:
             self._track = torch.full((B, 3), float("nan"), dtype=torch.float64, device=dev)
             self._tcenters = torch.empty((B, 3), dtype=torch.float64, device=dev)
@@ -278,6 +300,14 @@ class Predictor:
                    self.depth_range[1], self.slab, self._cube.data_ptr(), 0, fx, fy, self.iters, 0, self._scratch.data_ptr(),
                    centers.data_ptr(), status.data_ptr(), s)
 
+        def palm(centers, status):
+            # in place: a frame that is not OK keeps its centre and status
+            L.call("awr_detect_palm", self._frames.data_ptr(), 0, B, self.fh, self.fw, self._idx.data_ptr(), nv, centers.data_ptr(),
+                   status.data_ptr(), self.depth_range[0], self.depth_range[1], self._cube.data_ptr(), 0, fx, fy, self.palm_search,
+                   D.PALM_TAU[0], D.PALM_TAU[1], D.PALM_RHO2[0], D.PALM_RHO2[1], self._palm_scratch.data_ptr(), centers.data_ptr(),
+                   status.data_ptr(), self._palm_info.data_ptr(), s)
+            self.palm_info = self._palm_info[:nb]
+
         def crop_and_predict():
             L.call("awr_detect_samples", self._centers.data_ptr(), self._cube.data_ptr(), 0, B, self._idx.data_ptr(), nv, self.S, self.fh, self.fw,
                    fx, fy, u0, v0, self.flip, self._blocks.data_ptr(), L.ptr(M), L.ptr(cxyz), L.ptr(self._cube32), status.data_ptr(), s)
@@ -314,10 +344,14 @@ class Predictor:
             # the tracked centres first (a lost slot's NaN seed finds nothing), the configured detector second, per slot whichever holds
             detect(D.SEED_GIVEN, self._track, self._tcenters, self._tstatus)
             detect(mode, None, self._dcenters, self._dstatus)
+            if self.palm:
+                palm(self._dcenters, self._dstatus)
             L.call("awr_centers_select", self._tcenters.data_ptr(), self._tstatus.data_ptr(), self._dcenters.data_ptr(), self._dstatus.data_ptr(),
                    nv, self._centers.data_ptr(), status.data_ptr(), None, s)
         else:
             detect(mode, seed, self._centers, status)
+            if self.palm and seed is None:
+                palm(self._centers, status)
         crop_and_predict()
         if self.recenter or self.track:
             codes = torch.zeros((self.recenter + 1, B), dtype=torch.int32, device=dev)

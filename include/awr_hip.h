@@ -903,6 +903,47 @@ int awr_detect_samples(const double* center_uvd, const double* cube, int cube_st
                        int fh, int fw, double fx, double fy, double u0, double v0, int flip, awr_nyu_sample* samples, float* M,
                        float* center_xyz, float* cube_out, int* status, void* stream);
 
+/* Forearm-robust palm centre (csrc/awr_palm.hip; the numpy statement is awr_amd/detect.py palm_center, results are
+ * bit-identical to it).  A centre of mass inside a cube is dragged up a forearm that lies at the hand's depth; the palm is the widest
+ * part of the hand-plus-arm silhouette, and the hand is at the end of its medial set beyond which more silhouette lies (the fingers).
+ * Per frame b, from a detector centre center_in[b] with status_in[b]:
+ *   1. frame[b] outside [0, n_frames): AWR_DET_BAD_FRAME, NaN centre, nothing is read.  Otherwise status_in[b] != AWR_DET_OK: centre and
+ *      status pass through unchanged.  Either way info = (-1, -1, 0, 0).
+ *   2. Window W = nyu_data.center2bounds(centre, (search * cube[0], search * cube[1], search * cube[2]), (fx, fy)) clipped to the frame,
+ *      as awr_detect clips it.  mask(v, u): the pixel is inside W, d != 0, zstart <= d <= zend of that call and zmin <= d <= zmax.  A
+ *      NaN or infinite centre or bound, an empty window or an empty mask: NaN centre, AWR_DET_EMPTY, info = (-1, -1, 0, 0).
+ *   3. D2, the exact squared Euclidean distance transform of the mask: everything outside W -- the one-pixel ring around it, and beyond
+ *      the frame too -- is background; D2(p) = min over background q of |p - q|^2, 0 on background.  As two passes: g(v, u) = the
+ *      distance along the column to the nearest background row (the ring rows v0 - 1 and v1 count), then
+ *      D2(v, u) = min over u' in [u0 - 1, u1] of (u - u')^2 + g(v, u')^2 with g = 0 on the ring columns.
+ *   4. m = max D2 (>= 1).  The medial set S = {p : tau_den * D2(p) >= tau_num * m}.
+ *   5. Every argmax takes the FIRST maximum in raster order (smallest v, then smallest u):
+ *      e0 = argmax_S D2;  e1 = argmax_S |p - e0|^2;  e2 = argmax_S |p - e1|^2;  a = e2 - e1;  L = |a|^2.
+ *   6. L == 0: p* = e0.  Otherwise t(p) = (p - e1) . a;  b1 = the mask pixels with t < 0;  b2 = the mask pixels with t > L;
+ *      s(p) = L - t(p) if b2 >= b1, else t(p);  N = {p in S : s <= 0 or s * s <= m * L} (within one palm radius of the chosen end along
+ *      the axis);  p* = argmax_N D2.
+ *   7. r2 = D2(p*).  The palm disc: the mask pixels with rho2_den * |p - p*|^2 <= rho2_num * r2.  n, sum of u, sum of v, sum of raw
+ *      depths over the disc as 64-bit integers; centre = (su / n, sv / n, sd / n) as three double divisions; AWR_DET_OK;
+ *      info = (p*.u, p*.v, r2, n) in frame pixels.
+ * Everything between the window (awr_detect's double arithmetic, the cube scaled by `search`) and the last three divisions is integer:
+ * with fh, fw <= 16384, D2 <= 2^28, L <= 2^29, |t|, |s| <= 2^30, so s * s <= 2^60, m * L <= 2^57 and, the four ratio terms being
+ * positive ints, tau * D2 and rho2 * |p - p*|^2 <= 2^60: every product stays below 2^62.  Larger frames are refused.  Integer sums and
+ * maxima packed with their raster index do not depend on launch geometry or arrival order: a frame is split by rows over several
+ * workgroups whose partial maxima and sums meet in 64-bit INTEGER atomics; there is no floating-point atomic and no floating-point
+ * reduction.
+ *   search > 0 and finite; 0 < tau_num <= tau_den; 0 < rho2_den <= rho2_num.  The defaults of the statement are 2.0, 1 / 3, 25 / 4.
+ *   cube: doubles on the device, 3 (cube_stride 0) or B x 3 (cube_stride 3).  Only uint16 frames (AWR_NYU_U16).
+ *   scratch: awr_detect_palm_scratch(B, fh, fw) bytes, 8-byte aligned (sixteen 64-bit accumulator words per frame, which the call
+ *   initialises, then one int32 word per pixel and frame: D2); nothing is written past it.
+ *   center_out (B, 3) doubles may be center_in; status_out (B) int32 may be status_in; info (B, 4) int32 may be NULL.
+ * Nine launches on `stream`, one per stage (the slots, the column scans, the row pass, e1, e2, the counts, p*, the disc, the outputs),
+ * ordered by the stream alone; only the last writes an output.  Nothing synchronises; nothing outside the frame store is read. */
+int64_t awr_detect_palm_scratch(int B, int fh, int fw);        /* bytes; -1 for a B outside [1, AWR_DET_MAX_BATCH] or a side outside [1, 16384] */
+int awr_detect_palm(const void* frames, int frame_type, int64_t n_frames, int fh, int fw, const int64_t* frame, int B,
+                    const double* center_in, const int* status_in, double zmin, double zmax, const double* cube, int cube_stride, double fx,
+                    double fy, double search, int tau_num, int tau_den, int rho2_num, int rho2_den, void* scratch, double* center_out,
+                    int* status_out, int* info, void* stream);
+
 /* Joints -> the next crop centre, per frame, with a gate (the numpy statement is awr_amd/detect.py joints_center,
  * results are bit-identical to it):
  *   xyz (B, J, 3) camera mm, as awr_joints_unproject writes xyz_out; center_uvd (B, 3) doubles, the centres this pass was cropped at;

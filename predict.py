@@ -14,6 +14,8 @@ awr_joints_center call: 1 = moved, 0 / 2 / 3 / 4 = kept, awr_amd.detect.RECENTER
 in-plane rotation (degrees), per cube scale and per centre shift (x:y:z camera millimetres) -- and fuses their joints with --fuse mean |
 conf | median; pred_uvd.txt / pred_xyz.txt then hold the fused joints, and pred_view_spread_mm.txt and pred_views_used.txt
 (J columns each) are written too.
+--palm sends the detector's centres through awr_detect_palm first: the centre of the palm disc of the silhouette's exact distance transform,
+which a forearm at the hand's depth does not drag up the arm (measured on procedural hands only).
 --ema predicts with the checkpoint's averaged weights ("model_ema", written by a run with config.ema_decay) instead of "model".
 `--set` overrides config entries as train.py does (img_size, kernel_size, cube, batch_size, jt_num, downsample, winograd ...)."""
 import argparse
@@ -35,6 +37,7 @@ def parse_args(argv=None):
     ap.add_argument("--track", action="store_true", help="the file is one sequence: start each crop at the previous frame's joint centre")
     ap.add_argument("--views", default=None, metavar="SPEC", help="test-time views, e.g. \"rot=-15,15;scale=0.9,1.1;shift=0:0:10\" (the identity view comes first by itself)")
     ap.add_argument("--fuse", default="mean", choices=("mean", "conf", "median"), help="how the views' joints are fused (with --views)")
+    ap.add_argument("--palm", action="store_true", help="move each detector centre to the palm disc of the silhouette's distance transform")
     ap.add_argument("--ema", action="store_true", help="load the checkpoint's \"model_ema\" (the EMA of the weights) instead of \"model\"")
     return ap.parse_args(argv)
 
@@ -67,7 +70,7 @@ def main(argv=None):
     views = None if args.views is None else detect.parse_views(args.views)
     pred = awr_amd.Predictor(net.cuda(), cfg.img_size, cfg.kernel_size, cube=cfg.cube, max_batch=bs, frame_shape=frames.shape[1:],
                              winograd=cfg.winograd, parity=cfg.parity_infer, confidence=args.confidence,
-                             recenter=args.recenter, track=args.track, views=views, fuse=args.fuse)
+                             recenter=args.recenter, track=args.track, views=views, fuse=args.fuse, palm=args.palm)
     stateful = bool(args.recenter or args.track)
     centers, codes = [], []
     uvd, xyz, extra = [], [], {"conf": [], "peak": [], "spread_mm": []}

@@ -1,7 +1,7 @@
 """Train on synthetic hand frames, then score every predictor option against ground truth, on one MI355X -> profiles/synth_accuracy.txt
 
     python tools/synth_accuracy.py [--train 32768] [--test 2048] [--epochs 4] [--workers 4] [--work DIR] [--parent HASH]
-                                   [--out profiles/synth_accuracy.txt]
+                                   [--out profiles/synth_accuracy.txt] [--append]
 
 THESE ARE PROCEDURAL HANDS (awr_amd/synth.py: capsules, uniform pose draws, no sensor model).  The numbers below say how the project's
 own pieces behave on a labelled input they can all consume; they say NOTHING about NYU or about any real camera.
@@ -14,7 +14,8 @@ at the first step that fails or times out.
   score: on the held-out frames, (1) the detector's centre against the label centre in mm, with the forearm and with the same poses
          rendered without it, (2) Predictor from RAW frames (its own detector, no label centre): plain, recenter=1, recenter=2, views
          (rot -15, +15) fused by mean and by conf, and the plain predictor over the EMA weights -- mean joint error in mm over the frames
-         whose status is OK, (3) Spearman's rank correlation of `conf` with the per-joint error (negative = confident joints are better).
+         whose status is OK, (3) Spearman's rank correlation of `conf` with the per-joint error (negative = confident joints are better),
+         (4) the same detector centres after awr_detect_palm, and Predictor(palm=True) plain, recenter=1 and recenter=2.
 No thresholds: the tool records.  There is no fall-back: without a GPU it fails."""
 import argparse
 import json
@@ -91,7 +92,21 @@ def step_score(a):
         d = uvd2xyz(c[ok], sf.paras, sf.flip).astype(np.float64) - sf.centers[ok]
         e = np.linalg.norm(d, axis=1)
         res["detector_" + tag] = dict(ok=int(ok.sum()), n=n, mean=float(e.mean()), median=float(np.median(e)), p90=float(np.percentile(e, 90)),
-                                      mean_offset=[float(v) for v in d.mean(0)])
+                                      mean_offset=[float(v) for v in d.mean(0)], over100=int((e > 100.0).sum()))
+        # the same centres after the palm pass, in batches: its scratch is one word per pixel and frame
+        pc, pst = [], []
+        for lo in range(0, n, B):
+            idx = np.arange(lo, min(n, lo + B))
+            c0, s0 = D.detect_device(sf.frame_store, idx)
+            c1, s1, _ = D.palm_device(sf.frame_store, idx, c0, s0)
+            pc.append(c1.cpu().numpy())
+            pst.append(s1.cpu().numpy())
+        c, st = np.concatenate(pc), np.concatenate(pst)
+        ok = st == 0
+        d = uvd2xyz(c[ok], sf.paras, sf.flip).astype(np.float64) - sf.centers[ok]
+        e = np.linalg.norm(d, axis=1)
+        res["palm_" + tag] = dict(ok=int(ok.sum()), n=n, mean=float(e.mean()), median=float(np.median(e)), p90=float(np.percentile(e, 90)),
+                                  mean_offset=[float(v) for v in d.mean(0)], over100=int((e > 100.0).sum()))
 
     def load(key):
         net = awr_amd.get_deconv_net(18, 14, 2)
@@ -126,6 +141,9 @@ def step_score(a):
     res["recenter=2"] = run(net, recenter=2)
     res["views mean"] = run(net, views=views, fuse="mean")
     res["views conf"] = run(net, views=views, fuse="conf")
+    res["palm, plain"] = run(net, palm=True)
+    res["palm, recenter=1"] = run(net, palm=True, recenter=1)
+    res["palm, recenter=2"] = run(net, palm=True, recenter=2)
     del net
     res["plain, EMA weights"] = run(load("model_ema"))
     json.dump(res, open(os.path.join(a.work, "score.json"), "w"))
@@ -140,6 +158,7 @@ def main():
     ap.add_argument("--work", default=os.path.join(REPO, "output", "synth_accuracy"))
     ap.add_argument("--parent", default=None)
     ap.add_argument("--out", default=os.path.join(REPO, "profiles", "synth_accuracy.txt"))
+    ap.add_argument("--append", action="store_true", help="write the new run below what --out already holds instead of replacing it")
     ap.add_argument("--step", choices=("train", "score"), default=None, help="(internal) run one GPU step in this process")
     a = ap.parse_args()
     if a.step:
@@ -195,9 +214,22 @@ def main():
     L.append("(4) conf against the per-joint error, plain predictor, %d joints: Spearman's rank correlation %+.3f" % (r["frames"] * 14, r["spearman_conf_error"]))
     L.append("  mean error of the most confident quarter of the joints %.3f mm, of the least confident quarter %.3f mm"
              % (r["mean_error_most_confident_quarter"], r["mean_error_least_confident_quarter"]))
+    L.append("")
+    L.append("(5) palm=True (awr_detect_palm after the detector; DESIGN.md 4.24): the centre against the label centre, mm, to be read against (2)")
+    for tag, name in (("forearm", "with the forearm"), ("no_forearm", "same poses, no forearm")):
+        for key, what in (("detector_", "detector"), ("palm_", "palm")):
+            d = sc[key + tag]
+            L.append("  %-24s %-9s mean %6.2f   median %6.2f   90th percentile %6.2f   %4d frames over 100 mm   %d of %d frames OK"
+                     % (name, what, d["mean"], d["median"], d["p90"], d["over100"], d["ok"], d["n"]))
+    L.append("  Predictor(palm=True) from RAW frames, mean / median joint error in mm over the frames with status OK, to be read against (3)")
+    for k in ("palm, plain", "palm, recenter=1", "palm, recenter=2"):
+        r = sc[k]
+        L.append("  %-22s mean %7.3f   median %7.3f   (%d frames, %d not OK)" % (k, r["mean"], r["median"], r["frames"], r["not_ok"]))
     text = "\n".join(L) + "\n"
     print(text)
     os.makedirs(os.path.dirname(os.path.abspath(a.out)), exist_ok=True)
+    if a.append and os.path.exists(a.out):          # keep the earlier runs: a new run goes below them, under its own parent-commit line
+        text = open(a.out).read() + "\n---- a later run of tools/synth_accuracy.py (--append): every row measured again, section (5) added ----\n\n" + text
     with open(a.out, "w") as f:
         f.write(text)
 
