@@ -29,6 +29,8 @@
 
 #include "awr_common.h"
 #include "awr_conv_modes.h"
+#include "awr_net_geometry.h"      // conv / weight-gradient problems, pack recipes, bucket planner (host logic, no HIP)
+#include "awr_net_layout.h"        // checkpoint layout (host logic, no HIP)
 
 extern "C" unsigned long long awr_dp_generation(const awr_dp* d);      // csrc/awr_dp.hip: generation of a communicator that has not been destroyed, else 0
 
@@ -39,10 +41,6 @@ using awr::set_error;
 
 constexpr float BN_EPS = 1e-5f;
 constexpr float BN_MOMENTUM = 0.1f;
-constexpr int N_ALIGN = 128;   // packed weight rows are padded to a multiple of the widest GEMM tile
-
-
-static inline int64_t round_up(int64_t x, int64_t m) { return (x + m - 1) / m * m; }
 
 #define NET_CHECK(call)                 \
     do {                                \
@@ -57,346 +55,6 @@ static inline int64_t round_up(int64_t x, int64_t m) { return (x + m - 1) / m * 
             return AWR_ERR_HIP;                                    \
         }                                                          \
     } while (0)
-
-// ------------------------------------------------------------------------------------------
-// checkpoint layout: ordered state_dict entries
-// ------------------------------------------------------------------------------------------
-enum Kind { CONV_W = 0, DECONV_W = 1, CONV_B = 2, BN_W = 3, BN_B = 4, BN_MEAN = 5, BN_VAR = 6, COUNTER = 7 };
-static inline bool is_param(int k) { return k <= BN_B; }
-
-struct Entry {
-    std::string key;
-    int ndim;
-    int64_t shape[4];
-    int kind;
-    int64_t off = 0;     // floats into the parameter arena (params) / buffer arena (running stats); index for counters
-    int64_t numel = 1;
-    bool unused = false;  // parameters that never receive a gradient (hourglass skip_layers with inp == out)
-};
-
-struct Layout {
-    std::vector<Entry> e;
-    int64_t n_params = 0, n_active = 0, n_buffers = 0;
-    int n_counters = 0;
-    std::map<std::string, int> index;
-
-    void add(const std::string& key, std::vector<int64_t> shape, int kind) {
-        Entry en;
-        en.key = key;
-        en.kind = kind;
-        en.ndim = (int)shape.size();
-        for (int i = 0; i < 4; ++i) en.shape[i] = i < en.ndim ? shape[i] : 1;
-        for (int i = 0; i < en.ndim; ++i) en.numel *= shape[i];
-        index[key] = (int)e.size();
-        e.push_back(en);
-    }
-    void bn(const std::string& p, int c) {
-        add(p + ".weight", {c}, BN_W);
-        add(p + ".bias", {c}, BN_B);
-        add(p + ".running_mean", {c}, BN_MEAN);
-        add(p + ".running_var", {c}, BN_VAR);
-        add(p + ".num_batches_tracked", {}, COUNTER);
-    }
-    const Entry& at(const std::string& key) const { return e[index.at(key)]; }
-    bool has(const std::string& key) const { return index.count(key) != 0; }
-
-    // arena offsets: live parameters first, never-trained ones at the tail (the optimiser / all-reduce cover [0, n_active)
-    // only -- exactly torch's `p.grad is None` skip); every view 16-byte aligned
-    void assign() {
-        int64_t off = 0;
-        for (int pass = 0; pass < 2; ++pass) {
-            for (auto& en : e) {
-                if (!is_param(en.kind) || en.unused != (pass == 1)) continue;
-                en.off = off;
-                off = round_up(off + en.numel, 4);
-            }
-            if (pass == 0) n_active = off;
-        }
-        n_params = off;
-        int64_t boff = 0;
-        int ci = 0;
-        for (auto& en : e) {
-            if (en.kind == BN_MEAN || en.kind == BN_VAR) {
-                en.off = boff;
-                boff += round_up(en.shape[0], 4);
-            } else if (en.kind == COUNTER) {
-                en.off = ci++;
-            }
-        }
-        n_buffers = boff;
-        n_counters = ci;
-    }
-};
-
-static std::string fmt(const char* f, ...) {
-    char buf[256];
-    va_list ap;
-    va_start(ap, f);
-    vsnprintf(buf, sizeof buf, f, ap);
-    va_end(ap);
-    return buf;
-}
-
-// get_deconv_net(depth, J, downsample).state_dict() (resnet_deconv.py:8-16, :31-53): BasicBlock [2,2,2,2] for depth 18, Bottleneck
-// (expansion 4) [3,4,6,3] / [3,4,23,3] / [3,8,36,3] for 50 / 101 / 152.  Registration order inside a block: conv1, bn1, conv2, bn2,
-// (conv3, bn3,) downsample (resnet_deconv.py:148-156, :182-195).
-static const int* resnet_blocks(int depth) {
-    static const int b18[4] = {2, 2, 2, 2}, b50[4] = {3, 4, 6, 3}, b101[4] = {3, 4, 23, 3}, b152[4] = {3, 8, 36, 3};
-    return depth == 50 ? b50 : depth == 101 ? b101 : depth == 152 ? b152 : b18;
-}
-
-static void resnet_layout(Layout& L, int depth, int J, int downsample) {
-    const bool bott = depth != 18;
-    const int exp = bott ? 4 : 1;
-    const int* nb = resnet_blocks(depth);
-    L.add("pre.0.weight", {64, 1, 5, 5}, CONV_W);
-    L.bn("pre.1", 64);
-    int cin = 64;
-    const int planes_[4] = {64, 128, 256, 512};
-    for (int li = 1; li <= 4; ++li) {
-        const int planes = planes_[li - 1];
-        for (int bi = 0; bi < nb[li - 1]; ++bi) {
-            const std::string p = fmt("layer%d.%d", li, bi);
-            if (!bott) {
-                L.add(p + ".conv1.weight", {planes, cin, 3, 3}, CONV_W);
-                L.bn(p + ".bn1", planes);
-                L.add(p + ".conv2.weight", {planes, planes, 3, 3}, CONV_W);
-                L.bn(p + ".bn2", planes);
-            } else {
-                L.add(p + ".conv1.weight", {planes, cin, 1, 1}, CONV_W);
-                L.bn(p + ".bn1", planes);
-                L.add(p + ".conv2.weight", {planes, planes, 3, 3}, CONV_W);
-                L.bn(p + ".bn2", planes);
-                L.add(p + ".conv3.weight", {planes * exp, planes, 1, 1}, CONV_W);
-                L.bn(p + ".bn3", planes * exp);
-            }
-            if (bi == 0 && (li > 1 || cin != planes * exp)) {      // _make_layer: stride != 1 or inplanes != planes * expansion
-                L.add(p + ".downsample.0.weight", {planes * exp, cin, 1, 1}, CONV_W);
-                L.bn(p + ".downsample.1", planes * exp);
-            }
-            cin = planes * exp;
-        }
-    }
-    int lg = 0;
-    while ((1 << lg) < downsample) ++lg;
-    for (int i = 0; i < 4 - lg; ++i) {
-        L.add(fmt("deconv_layers.%d.weight", 3 * i), {cin, 256, 4, 4}, DECONV_W);
-        L.bn(fmt("deconv_layers.%d", 3 * i + 1), 256);
-        cin = 256;
-    }
-    L.add("final1.weight", {3 * J, 256, 1, 1}, CONV_W);
-    L.add("final1.bias", {3 * J}, CONV_B);
-    L.add("final2.weight", {J, 256, 1, 1}, CONV_W);
-    L.add("final2.bias", {J}, CONV_B);
-}
-
-static void hgconv_keys(Layout& L, const std::string& p, int cin, int cout, int k, bool bn) {
-    L.add(p + ".conv.weight", {cout, cin, k, k}, CONV_W);
-    L.add(p + ".conv.bias", {cout}, CONV_B);
-    if (bn) L.bn(p + ".bn", cout);
-}
-
-// hourglass.py:28-42 -- registration order bn1, conv1, bn2, conv2, bn3, conv3, skip_layer (present even when unused)
-static void residual_keys(Layout& L, const std::string& p, int cin, int cout) {
-    const int h = cout / 2;
-    L.bn(p + ".bn1", cin);
-    hgconv_keys(L, p + ".conv1", cin, h, 1, false);
-    L.bn(p + ".bn2", h);
-    hgconv_keys(L, p + ".conv2", h, h, 3, false);
-    L.bn(p + ".bn3", h);
-    hgconv_keys(L, p + ".conv3", h, cout, 1, false);
-    hgconv_keys(L, p + ".skip_layer", cin, cout, 1, false);
-}
-
-static void hourglass_keys(Layout& L, const std::string& p, int depth, int f) {
-    residual_keys(L, p + ".up1", f, f);
-    residual_keys(L, p + ".low1", f, f);
-    if (depth > 1) hourglass_keys(L, p + ".low2", depth - 1, f);
-    else residual_keys(L, p + ".low2", f, f);
-    residual_keys(L, p + ".low3", f, f);
-}
-
-// PoseNet('hourglass_<nstack>', J).state_dict() (hourglass.py:105-142)
-static void hourglass_layout(Layout& L, int nstack, int J, int f) {
-    hgconv_keys(L, "pre.0", 1, 64, 5, true);
-    residual_keys(L, "pre.1", 64, 128);
-    residual_keys(L, "pre.3", 128, 256);
-    residual_keys(L, "pre.4", 256, f);
-    for (int i = 0; i < nstack; ++i) hourglass_keys(L, fmt("hgs.%d.0", i), 4, f);
-    for (int i = 0; i < nstack; ++i) {
-        residual_keys(L, fmt("features.%d.0", i), f, f);
-        hgconv_keys(L, fmt("features.%d.1", i), f, f, 1, true);
-    }
-    for (int i = 0; i < nstack; ++i) {
-        L.add(fmt("outs_1.%d.weight", i), {3 * J, f, 1, 1}, CONV_W);
-        L.add(fmt("outs_1.%d.bias", i), {3 * J}, CONV_B);
-    }
-    for (int i = 0; i < nstack; ++i) {
-        L.add(fmt("outs_2.%d.weight", i), {J, f, 1, 1}, CONV_W);
-        L.add(fmt("outs_2.%d.bias", i), {J}, CONV_B);
-    }
-    for (int i = 0; i < nstack - 1; ++i) hgconv_keys(L, fmt("merge_features.%d.conv", i), f, f, 1, false);
-    for (int i = 0; i < nstack - 1; ++i) hgconv_keys(L, fmt("merge_preds.%d.conv", i), 4 * J, f, 1, false);
-    // Residual.skip_layer exists in every block but only runs when inp_dim != out_dim (hourglass.py:38-47)
-    for (auto& en : L.e) {
-        const size_t pos = en.key.find(".skip_layer.");
-        if (pos == std::string::npos) continue;
-        const Entry& w = L.e[L.index.at(en.key.substr(0, pos) + ".skip_layer.conv.weight")];
-        if (w.shape[0] == w.shape[1]) en.unused = true;
-    }
-}
-
-// ------------------------------------------------------------------------------------------
-// conv geometry: the three GEMM problems of one nn.Conv2d / nn.ConvTranspose2d (k4 s2 p1)
-// ------------------------------------------------------------------------------------------
-struct Spec {
-    bool deconv = false;
-    int cin = 0, cout = 0, k = 1, stride = 1, pad = 0, cin_pad = 0, cout_pad = 0;
-    int T() const { return k * k; }
-    void out_hw(int h, int w, int& ho, int& wo) const {
-        if (!deconv) {
-            ho = (h + 2 * pad - k) / stride + 1;
-            wo = (w + 2 * pad - k) / stride + 1;
-        } else {
-            ho = (h - 1) * stride - 2 * pad + k;
-            wo = (w - 1) * stride - 2 * pad + k;
-        }
-    }
-};
-
-static Spec make_spec(bool deconv, int cin, int cout, int k, int stride, int pad, int cin_pad = 0, int cout_pad = 0) {
-    Spec s;
-    s.deconv = deconv;
-    s.cin = cin; s.cout = cout; s.k = k; s.stride = stride; s.pad = pad;
-    s.cin_pad = cin_pad ? cin_pad : cin;
-    s.cout_pad = cout_pad ? cout_pad : cout;
-    return s;
-}
-
-struct Tap { int dy, dx, wt; };
-struct PhaseT { int py, px; std::vector<Tap> taps; };
-struct Prob {
-    int Hin, Win, Cin, Hout, Wout, N, Hq, Wq, so, si;
-    std::vector<PhaseT> phases;
-    bool full;
-    int k_extent() const {      // terms one output element sums: taps x input channels of the longest phase
-        size_t taps = 0;
-        for (auto& ph : phases) taps = std::max(taps, ph.taps.size());
-        return (int)taps * Cin;
-    }
-};
-
-static std::vector<PhaseT> gather_taps(const Spec& s) {       // conv-type gather: one phase, taps (ky-p, kx-p, ky*k+kx)
-    PhaseT ph{0, 0, {}};
-    for (int ky = 0; ky < s.k; ++ky)
-        for (int kx = 0; kx < s.k; ++kx) ph.taps.push_back({ky - s.pad, kx - s.pad, ky * s.k + kx});
-    return {ph};
-}
-static std::vector<PhaseT> mirror_taps(const Spec& s) {       // stride-1 data gradient: dx[y] = sum_k dy[y + p - k] w[k]
-    PhaseT ph{0, 0, {}};
-    for (int ky = 0; ky < s.k; ++ky)
-        for (int kx = 0; kx < s.k; ++kx) ph.taps.push_back({s.pad - ky, s.pad - kx, ky * s.k + kx});
-    return {ph};
-}
-static int floordiv(int a, int b) { return (a >= 0) ? a / b : -((-a + b - 1) / b); }
-static int pymod(int a, int b) { return a - floordiv(a, b) * b; }
-static std::vector<PhaseT> scatter_phases(const Spec& sp) {   // transposed-type (output stride 2): phase (py,px) takes the taps with (py+p-ky) even
-    const int s = sp.stride, p = sp.pad, k = sp.k;
-    std::vector<PhaseT> out;
-    for (int py = 0; py < s; ++py)
-        for (int px = 0; px < s; ++px) {
-            PhaseT ph{py, px, {}};
-            for (int ky = 0; ky < k; ++ky) {
-                if (pymod(py + p - ky, s) != 0) continue;
-                for (int kx = 0; kx < k; ++kx) {
-                    if (pymod(px + p - kx, s) != 0) continue;
-                    ph.taps.push_back({floordiv(py + p - ky, s), floordiv(px + p - kx, s), ky * k + kx});
-                }
-            }
-            if (!ph.taps.empty()) out.push_back(ph);
-        }
-    return out;
-}
-
-static Prob fwd_problem(const Spec& s, int hin, int win) {
-    int ho, wo;
-    s.out_hw(hin, win, ho, wo);
-    if (!s.deconv) return Prob{hin, win, s.cin_pad, ho, wo, s.cout_pad, ho, wo, 1, s.stride, gather_taps(s), true};
-    auto ph = scatter_phases(s);
-    const bool full = ph.size() == 4;
-    return Prob{hin, win, s.cin_pad, ho, wo, s.cout_pad, ho / 2, wo / 2, 2, 1, ph, full};
-}
-
-// gradient w.r.t. the layer input: reads dY (B,Hout,Wout,cout_pad), writes dX (B,hin,win,cin_pad)
-static Prob dgrad_problem(const Spec& s, int hin, int win) {
-    int ho, wo;
-    s.out_hw(hin, win, ho, wo);
-    if (s.deconv) return Prob{ho, wo, s.cout_pad, hin, win, s.cin_pad, hin, win, 1, s.stride, gather_taps(s), true};   // adjoint of a transposed conv is a strided conv
-    if (s.stride == 1) return Prob{ho, wo, s.cout_pad, hin, win, s.cin_pad, hin, win, 1, 1, mirror_taps(s), true};
-    auto ph = scatter_phases(s);
-    const bool full = ph.size() == 4;
-    return Prob{ho, wo, s.cout_pad, hin, win, s.cin_pad, hin / 2, win / 2, 2, 1, ph, full};
-}
-
-// accum: the launch's accumulation order (0 / 1), resolved by the builder from the plan's modes (Builder::accum)
-static void fill_conv_args(awr_conv_args& a, const Prob& p, int B, const float* in, const float* w, const void* w_split, float* out, int T, int accum) {
-    memset(&a, 0, sizeof a);
-    a.in = in; a.w = w; a.out = out; a.w_split = w_split;
-    a.B = B; a.Hin = p.Hin; a.Win = p.Win; a.Cin = p.Cin;
-    a.Hq = p.Hq; a.Wq = p.Wq; a.Hout = p.Hout; a.Wout = p.Wout; a.N = p.N;
-    a.so = p.so; a.si = p.si; a.T = T;
-    a.nphase = (int)p.phases.size();
-    a.accum = accum;
-    for (int i = 0; i < a.nphase; ++i) {
-        a.ph[i].py = p.phases[i].py;
-        a.ph[i].px = p.phases[i].px;
-        a.ph[i].ntaps = (int)p.phases[i].taps.size();
-        for (int t = 0; t < a.ph[i].ntaps; ++t) {
-            const Tap& tp = p.phases[i].taps[t];
-            a.ph[i].tap[t] = (tp.dy & 0xff) | ((tp.dx & 0xff) << 8) | (tp.wt << 16);
-        }
-    }
-}
-
-// weight packing recipes for awr_pack_weight: (d0, d1, T, transpose, rows, ld)
-struct PackRecipe { int d0, d1, T, transpose, rows, ld; };
-static PackRecipe fwd_pack(const Spec& s) {
-    if (!s.deconv) return {s.cout, s.cin, s.T(), 0, (int)round_up(s.cout_pad, N_ALIGN), s.cin_pad};
-    return {s.cin, s.cout, s.T(), 1, (int)round_up(s.cout_pad, N_ALIGN), s.cin_pad};
-}
-static PackRecipe dgrad_pack(const Spec& s) {
-    if (!s.deconv) return {s.cout, s.cin, s.T(), 1, (int)round_up(s.cin_pad, N_ALIGN), s.cout_pad};
-    return {s.cin, s.cout, s.T(), 0, (int)round_up(s.cin_pad, N_ALIGN), s.cout_pad};
-}
-
-// R[d0][t][d1] in the weight's own (d0,d1) order.  conv: D = dY, G = X; deconv: D = X, G = dY.
-struct WProb { bool d_is_dy; int Hd, Wd, Cd, Hg, Wg, Cg, sg, ntaps, d0, d1; int8_t dy[16], dx[16]; };
-static WProb wgrad_problem(const Spec& s, int hin, int win) {
-    int ho, wo;
-    s.out_hw(hin, win, ho, wo);
-    WProb w;
-    memset(&w, 0, sizeof w);
-    w.ntaps = s.T();
-    for (int ky = 0; ky < s.k; ++ky)
-        for (int kx = 0; kx < s.k; ++kx) {
-            w.dy[ky * s.k + kx] = (int8_t)(ky - s.pad);
-            w.dx[ky * s.k + kx] = (int8_t)(kx - s.pad);
-        }
-    w.sg = s.stride;
-    if (!s.deconv) {
-        w.d_is_dy = true; w.Hd = ho; w.Wd = wo; w.Cd = s.cout_pad; w.Hg = hin; w.Wg = win; w.Cg = s.cin_pad; w.d0 = s.cout; w.d1 = s.cin;
-    } else {
-        w.d_is_dy = false; w.Hd = hin; w.Wd = win; w.Cd = s.cin_pad; w.Hg = ho; w.Wg = wo; w.Cg = s.cout_pad; w.d0 = s.cin; w.d1 = s.cout;
-    }
-    return w;
-}
-static void fill_wgrad_args(awr_wgrad_args& a, const WProb& w, int B, const float* D, const float* G, float* R, int ld) {
-    memset(&a, 0, sizeof a);
-    a.D = D; a.G = G; a.R = R;
-    a.B = B; a.Hd = w.Hd; a.Wd = w.Wd; a.Cd = w.Cd; a.Hg = w.Hg; a.Wg = w.Wg; a.Cg = w.Cg; a.sg = w.sg; a.T = w.ntaps; a.ld = ld;
-    memcpy(a.dy, w.dy, 16);
-    memcpy(a.dx, w.dx, 16);
-}
 
 // ------------------------------------------------------------------------------------------
 // layers bound to the arenas
@@ -651,6 +309,9 @@ struct Op {
                               // issuing chain wait for that record (NOT for the weight gradient queued behind it on the same side stream)
     bool gemm = false;        // conv / stem family (timed by run_timed)
     bool boundary = false;    // NCHW <-> NHWC bridge at the reference boundary: skipped while the plan's NHWC boundary is on
+    bool scatter = false;     // the batched gradient scatter (make_unpack_op): a plan with a comm stream hands it to that stream
+    bool joins = true;        // backward: not issued before the side and branch streams have joined -- it may read what they write (the weight-gradient
+                              // scratch, a bucket's gradients).  The safe default; the emitters of chain-only launches opt out (Builder::bc)
     double macs = 0.0;
 };
 
@@ -662,12 +323,6 @@ struct GemmRef {              // what autotune iterates over
     float us = 0.f;
     bool tuned = false;
 };
-
-struct UnpackJobH {           // host copy of awr_unpack_job + where its gradient lives in the arena
-    awr_unpack_job job;
-};
-
-struct GradWrite { int64_t lo, hi; int ready; int job; };
 
 }  // namespace awrnet
 
@@ -681,8 +336,7 @@ struct awr_plan {
     int bn_repeat = 1, n_buckets = 1;
     unsigned supervised = 0;
     std::vector<Op> fwd, bwd, pack_ops;
-    std::vector<std::function<int()>> nodes;       // backward emitters, in forward order
-    std::vector<ConvLayer*> layers;                // layers whose packed copies this plan refreshes
+    std::vector<ConvLayer*> layers;               // layers whose packed copies this plan refreshes
     int n_wino = 0;      // forward (and weight-gradient) launches that run as Winograd F(2x2, 3x3)
     std::vector<std::pair<ConvLayer*, float*>> wino_d;      // (layer, mirrored U[16][cout_pad][cin_pad])
     std::vector<std::pair<const awr_conv_args*, double>> wino_dg;      // candidate data-gradient launches (argument block, MACs): Winograd if the COMPLETED block is supported
@@ -704,16 +358,9 @@ struct awr_plan {
     bool nhwc_boundary = false;
     // wgrad split-K scratch arena
     float* scratch = nullptr;
-    int64_t scratch_used = 0, scratch_cap = 0;
-    std::vector<awr_unpack_job> unpack_jobs;
-    std::vector<GradWrite> grad_writes;
-    std::vector<void*> job_tables;
-    std::map<Tn*, std::vector<awr_conv_args*>> grad_writers;
-    std::map<Tn*, int> fork_results;
-    int fork_sid = 0;
+    int64_t scratch_cap = 0;
     std::vector<GemmRef> gemms;
-    struct Bucket { int64_t lo, hi; int ready; };
-    std::vector<Bucket> buckets;
+    std::vector<Range> buckets;
     bool built_bwd = false;
     // pack tables (device) for refresh_weights: [want_split][0 = forward layouts (+ dual layers), 1 = data-gradient layouts]
     void* pack_tab[2][2] = {{nullptr, nullptr}, {nullptr, nullptr}};
@@ -751,10 +398,37 @@ struct ConvOpt {
     bool relu_out = false, want_stats = false, use_bias = true;
 };
 
+// K steps (32-channel slices x taps) of a launch's shortest phase: what bounds its split-K depth
+static int min_k_steps(const awr_conv_args& a) {
+    int minsteps = 1 << 30;
+    for (int p = 0; p < a.nphase; ++p) minsteps = std::min(minsteps, a.ph[p].ntaps * (a.Cin / 32));
+    return minsteps;
+}
+
+// The split-K scratch rule: the largest number of raw output copies (a power of two, at most `cap`) a launch of `wgs` 64x64-tile workgroups
+// per phase and `nphase` phases gets scratch for -- workgroups x copies below 2048, at least 4 K slices per range at the deepest split and,
+// with a byte cap (max_bytes > 0), that many copies of `numel` floats within it.  1 = no scratch.
+static int split_k_copies(int64_t wgs, int nphase, int minsteps, int cap, int64_t numel = 0, int64_t max_bytes = 0) {
+    int smax = 1;
+    while (smax < cap && wgs * nphase * smax < 2048 && minsteps / (smax * 2) >= 4 && (max_bytes <= 0 || numel * 4 * (smax * 2) <= max_bytes)) smax *= 2;
+    return smax;
+}
+
+struct GradWrite { int64_t lo, hi; int ready; int job; };      // arena range a backward op finishes; job: its entry in the scatter table, or -1
+
+// Builds one plan.  Its members are what the build alone needs: they die with the builder (the backward emitters capture `this`), the plan
+// keeps only what a replay, the tuner or an awr_plan_* entry point reads.
 struct Builder {
     awr_plan& P;
     awr_net& N;
     int err = AWR_OK;
+    std::vector<std::function<int()>> nodes;       // backward emitters, in forward order
+    std::map<Tn*, std::vector<awr_conv_args*>> grad_writers;
+    std::map<Tn*, int> fork_results;
+    int fork_sid = 0;
+    std::vector<GradWrite> grad_writes;
+    std::vector<awr_unpack_job> unpack_jobs;
+    int64_t scratch_used = 0;                      // floats taken from the plan's weight-gradient scratch arena
     explicit Builder(awr_plan& p) : P(p), N(*p.net) {}
 
     template <typename Tp>
@@ -805,11 +479,8 @@ struct Builder {
         if (!P.training || !P.modes.train_split_k || awr_get_gemm_products() != 1 || a->in2 || a->w2 || a->in_bnb_y || a->partial) return;
         if (a->so != 1 && a->nphase != a->so * a->so) return;
         const int64_t numel = (int64_t)a->B * a->Hout * a->Wout * a->N;
-        const int64_t wgs = ((int64_t)a->B * a->Hq * a->Wq + 63) / 64 * ((a->N + 63) / 64) * (int64_t)a->nphase;
-        int minsteps = 1 << 30;
-        for (int p = 0; p < a->nphase; ++p) minsteps = std::min(minsteps, a->ph[p].ntaps * (a->Cin / 32));
-        int smax = 1;
-        while (smax < 8 && wgs * smax < 2048 && minsteps / (smax * 2) >= 4 && numel * 4 * (smax * 2) <= TRAIN_SPLIT_MAX_BYTES) smax *= 2;
+        const int64_t wgs = ((int64_t)a->B * a->Hq * a->Wq + 63) / 64 * ((a->N + 63) / 64);
+        const int smax = split_k_copies(wgs, a->nphase, min_k_steps(*a), 8, numel, TRAIN_SPLIT_MAX_BYTES);
         if (smax > 1) {
             a->partial = alloc<float>((int64_t)smax * numel);
             a->split_max = smax;
@@ -818,10 +489,10 @@ struct Builder {
 
     float* scratch(int64_t n) {        // slice of the split-K scratch arena (zeroed by ONE fill per step)
         n = round_up(n, 4);
-        const int64_t off = P.scratch_used;
-        P.scratch_used += n;
+        const int64_t off = scratch_used;
+        scratch_used += n;
         if (!P.scratch) P.scratch = alloc<float>(P.scratch_cap);
-        if (P.scratch_used > P.scratch_cap) {
+        if (scratch_used > P.scratch_cap) {
             set_error("plan: wgrad scratch arena too small");
             err = AWR_ERR_ARG;
             return nullptr;
@@ -844,16 +515,23 @@ struct Builder {
     }
     Op& f(const std::string& name, std::function<int(void*)> fn) { return push(P.fwd, name, std::move(fn)); }
     Op& b(const std::string& name, std::function<int(void*)> fn) { return push(P.bwd, name, std::move(fn)); }
+    // chain-only backward launch: reads and writes nothing a side or branch stream produces except through its own place in the issuing chain
+    // (data / stem / weight gradients, BatchNorm-backward passes, pooling / up-sampling backward, gradient adds) -- no join in front of it
+    Op& bc(const std::string& name, std::function<int(void*)> fn) {
+        Op& o = b(name, std::move(fn));
+        o.joins = false;
+        return o;
+    }
 
     void note_grad(const float* tensor, int64_t numel, int job = -1) {
         if (!N.grads || !tensor) return;
         const int64_t lo = tensor - N.grads;
-        P.grad_writes.push_back({lo, lo + numel, (int)P.bwd.size() - 1, job});
+        grad_writes.push_back({lo, lo + numel, (int)P.bwd.size() - 1, job});
     }
 
     // -> (gradient buffer, accumulate?) and marks the gradient as live
     std::pair<float*, bool> gtarget(Tn* t, bool dgrad_writer = false) {
-        if (!dgrad_writer) P.grad_writers[t].push_back(nullptr);
+        if (!dgrad_writer) grad_writers[t].push_back(nullptr);
         if (!t->grad) {
             t->grad = alloc<float>(t->numel());
             return {t->grad, false};
@@ -863,13 +541,13 @@ struct Builder {
     // grad(t) += src_grad where src_grad is a finished gradient buffer: alias when first
     void contribute_identity(Tn* t, float* src_grad) {
         if (!t->needs_grad) return;
-        P.grad_writers[t].push_back(nullptr);
+        grad_writers[t].push_back(nullptr);
         if (!t->grad) {
             t->grad = src_grad;
         } else {
             float* g = t->grad;
             const int64_t n = t->numel();
-            b("awr_add", [=](void* s) { return awr_add(g, src_grad, g, n, s); });
+            bc("awr_add", [=](void* s) { return awr_add(g, src_grad, g, n, s); });
         }
     }
     void use_layer(ConvLayer* l) {
@@ -890,7 +568,7 @@ struct Builder {
 
     // ---- forward branches that may run beside the main chain ----
     void fork(int sid) {
-        P.fork_sid = sid;
+        fork_sid = sid;
         Op& o = f("__fork__", nullptr);
         o.kind = OP_FORK;
         o.sid = sid;
@@ -898,13 +576,13 @@ struct Builder {
     void end_fork(Tn* result) {
         Op& o = f("__endfork__", nullptr);
         o.kind = OP_ENDFORK;
-        o.sid = P.fork_sid;
-        P.fork_results[result] = P.fork_sid;
+        o.sid = fork_sid;
+        fork_results[result] = fork_sid;
     }
     // Backward branches.  The emitters run in reverse node order, so a marker node pushed AFTER a group of nodes is emitted
     // BEFORE that group's backward ops.
     void bwd_marker_node(int kind, int sid) {
-        P.nodes.push_back([=]() {
+        nodes.push_back([=]() {
             Op& o = b(kind == OP_FORK ? "__fork__" : kind == OP_ENDFORK ? "__endfork__" : "__join__", nullptr);
             o.kind = kind;
             o.sid = sid;
@@ -913,12 +591,12 @@ struct Builder {
     }
     void join_if(Tn* t) {
         if (!t) return;
-        auto it = P.fork_results.find(t);
-        if (it == P.fork_results.end()) return;
+        auto it = fork_results.find(t);
+        if (it == fork_results.end()) return;
         Op& o = f("__join__", nullptr);
         o.kind = OP_JOIN;
         o.sid = it->second;
-        P.fork_results.erase(it);
+        fork_results.erase(it);
     }
 
     // ---- ops ----
@@ -992,7 +670,7 @@ struct Builder {
             P.wino_macs += op.macs;
             if (P.training) {
                 const bool has_bias = bias != nullptr;
-                P.nodes.push_back([=]() { return conv_bwd(x, y, layer, nullptr, has_bias); });
+                nodes.push_back([=]() { return conv_bwd(x, y, layer, nullptr, has_bias); });
             }
             return y;
         }
@@ -1010,11 +688,8 @@ struct Builder {
             // (awr_conv_gemm picks the depth from the workgroup count, the tuner refines it).  Not in a parity plan (blocked accumulation):
             // the split-K kernel and the fused pair below accumulate in their own order -- a plan built in that mode only contains launch
             // forms that honour it
-            const int64_t wgs = ((int64_t)B * prob.Hq * prob.Wq + 63) / 64 * ((prob.N + 63) / 64) * (int64_t)prob.phases.size();
-            int minsteps = 1 << 30;
-            for (auto& ph : prob.phases) minsteps = std::min(minsteps, (int)ph.taps.size() * (a->Cin / 32));
-            int smax = 1;
-            while (smax < 16 && wgs * smax < 2048 && minsteps / (smax * 2) >= 4) smax *= 2;
+            const int64_t wgs = ((int64_t)B * prob.Hq * prob.Wq + 63) / 64 * ((prob.N + 63) / 64);
+            const int smax = split_k_copies(wgs, a->nphase, min_k_steps(*a), 16);
             if (smax > 1) {
                 a->partial = alloc<float>((int64_t)smax * y->numel());
                 a->split_max = smax;
@@ -1030,7 +705,7 @@ struct Builder {
         if (P.training) {
             Tn* res = o.res;
             const bool has_bias = bias != nullptr;
-            P.nodes.push_back([=]() { return conv_bwd(x, y, layer, res, has_bias); });
+            nodes.push_back([=]() { return conv_bwd(x, y, layer, res, has_bias); });
         }
         return y;
     }
@@ -1144,7 +819,7 @@ struct Builder {
         note_pool_producer(y, ca);
         if (P.training) {
             ConvLayer *c3 = d->c3, *sk = d->sk;
-            P.nodes.push_back([=]() {
+            nodes.push_back([=]() {
                 NET_CHECK(conv_bwd(a, y, c3, nullptr, true));
                 return conv_bwd(x, y, sk, nullptr, true);
             });
@@ -1211,7 +886,7 @@ struct Builder {
             const float *g = y->lz_g, *yb = y->buf, *mean = y->lz_mean, *invstd = y->lz_invstd, *coef = y->lz_coef;
             const int64_t npix = y->npix();
             const int C = y->C;
-            Op& aop = b("awr_bn_bwd_apply", [=](void* s) { return awr_bn_bwd_apply_only(g, nullptr, yb, mean, invstd, nullptr, nullptr, coef, npix, C, dy, nullptr, nullptr, s); });
+            Op& aop = bc("awr_bn_bwd_apply", [=](void* s) { return awr_bn_bwd_apply_only(g, nullptr, yb, mean, invstd, nullptr, nullptr, coef, npix, C, dy, nullptr, nullptr, s); });
             aop.side_ok = (res == nullptr);
             aop.pair_next = true;
         }
@@ -1228,8 +903,8 @@ struct Builder {
         }
         const float *wx = x->buf, *wsc = x->lazy ? x->lz_scale : nullptr, *wsh = x->lazy ? x->lz_shift : nullptr;
         const int wrelu = x->lazy ? x->lz_relu : 0, wC = spec.cin_pad, wN = spec.cout_pad;
-        Op& wop = wino_w ? b(wname, [=](void* s) { return awr_wino_wgrad(wx, dy, wsc, wsh, wrelu, B, H, W, wC, wN, wscratch, R, ld, bsum, s); })
-                         : b(wname, [wa](void* s) { return awr_conv_wgrad(wa, s); });      // (reference into the op vector: do not use after the next push)
+        Op& wop = wino_w ? bc(wname, [=](void* s) { return awr_wino_wgrad(wx, dy, wsc, wsh, wrelu, B, H, W, wC, wN, wscratch, R, ld, bsum, s); })
+                         : bc(wname, [wa](void* s) { return awr_conv_wgrad(wa, s); });      // (reference into the op vector: do not use after the next push)
         wop.gemm = true;
         wop.macs = layer_macs;
         // safe to run beside the main chain when dY is written once before this node and nobody touches it again.  With a fused
@@ -1247,8 +922,8 @@ struct Builder {
             awr_unpack_job j;
             memset(&j, 0, sizeof j);
             j.packed = packed; j.grad = grad; j.d0 = d0; j.d1 = d1; j.T = T_; j.ld = ld_; j.slots = slots; j.slot_stride = stride;
-            P.unpack_jobs.push_back(j);
-            note_grad(grad, numel, (int)P.unpack_jobs.size() - 1);
+            unpack_jobs.push_back(j);
+            note_grad(grad, numel, (int)unpack_jobs.size() - 1);
         };
         if (!layer->head) {
             const int d0 = spec.deconv ? spec.cin : spec.cout, d1 = spec.deconv ? spec.cout : spec.cin;
@@ -1282,16 +957,16 @@ struct Builder {
             if (y->lz_g) { da->in_bnb_y = y->buf; da->in_bnb_coef = y->lz_lin4; }
             da->res = acc ? gx : nullptr;
             // remember who wrote d(x), in order: a full-coverage dgrad that is the LAST producer can host the fused BN-backward reduction
-            P.grad_writers[x].push_back(dp.full ? da : nullptr);
+            grad_writers[x].push_back(dp.full ? da : nullptr);
             const std::string dname = "awr_conv_dgrad:" + layer->name;
 #ifdef AWR_STUDY
             if (y->half_dy && res == nullptr) {      // d(y) arrives half by half (bn_bwd): part 0 now, part 1 behind the record of half B
-                Op& d0 = b(dname, [da](void* s) { return awr_conv_gemm_part(da, 2, 0, s); });
+                Op& d0 = bc(dname, [da](void* s) { return awr_conv_gemm_part(da, 2, 0, s); });
                 d0.gemm = true;
                 d0.macs = 0.5 * layer_macs;
                 Op& hw = b("__halfwait__", nullptr);
                 hw.kind = OP_HALFWAIT;
-                Op& d1 = b(dname + "/b", [da](void* s) { return awr_conv_gemm_part(da, 2, 1, s); });
+                Op& d1 = bc(dname + "/b", [da](void* s) { return awr_conv_gemm_part(da, 2, 1, s); });
                 d1.gemm = true;
                 d1.macs = 0.5 * layer_macs;
             } else
@@ -1315,7 +990,7 @@ struct Builder {
                     P.wino_dg.push_back({da, layer_macs});
                 }
                 if (!Ud) train_split_scratch(da);      // (in_bnb_y / partial-coverage launches are refused inside)
-                Op& dop = Ud ? b(dname, [da, Ud](void* s) { return awr_wino_dgrad_or_direct(da, Ud, s); }) : b(dname, [da](void* s) { return awr_conv_gemm(da, s); });
+                Op& dop = Ud ? bc(dname, [da, Ud](void* s) { return awr_wino_dgrad_or_direct(da, Ud, s); }) : bc(dname, [da](void* s) { return awr_conv_gemm(da, s); });
                 dop.gemm = true;
                 dop.macs = layer_macs;
             }
@@ -1383,7 +1058,7 @@ struct Builder {
             f("awr_bn_apply", [=](void* s) { return awr_bn_apply(xb, sc, sh, rb, relu ? 1 : 0, ob, npix, C, s); });
             if (!relu && !res) { a->bn_y = y->buf; a->bn_coef4 = coef4; }
         }
-        P.nodes.push_back([=]() { return bn_bwd(y, a, bn, relu, res, mean, invstd, sc, sh, coef4); });
+        nodes.push_back([=]() { return bn_bwd(y, a, bn, relu, res, mean, invstd, sc, sh, coef4); });
         return a;
     }
 
@@ -1402,7 +1077,7 @@ struct Builder {
         // With a residual added before the ReLU (ResNet block outputs: d(a) = the next block's skip gradient + its conv1 data gradient)
         // the LAST producer qualifies: it adds its tile onto the earlier contributions in place, takes the mask from the stored
         // activation, reduces, and leaves the MASKED gradient behind -- which is also d(res).
-        auto& writers = P.grad_writers[a];
+        auto& writers = grad_writers[a];
         awr_conv_args* ga = (!writers.empty() && relu) ? writers.back() : nullptr;
         if (ga && ga->res && (ga->res != ga->out || !res)) ga = nullptr;      // accumulating producers only for the residual form, in place
         if (ga && !ga->res && writers.size() != 1) ga = nullptr;
@@ -1438,7 +1113,7 @@ struct Builder {
         double* sp = sums.p;
         const int ns = sums.nslots;
         const bool pre_reduced = !fused && a->pre_sums.p && !relu && !res;
-        if (!fused && !pre_reduced) b("awr_bn_bwd_reduce", [=](void* s) { return awr_bn_bwd_reduce(da, act, yb, mean, invstd, msc, msh, npix, C, sp, ns, s); });
+        if (!fused && !pre_reduced) bc("awr_bn_bwd_reduce", [=](void* s) { return awr_bn_bwd_reduce(da, act, yb, mean, invstd, msc, msh, npix, C, sp, ns, s); });
         float* gy;
         bool acc = false;
         if (y->needs_grad) {
@@ -1450,7 +1125,7 @@ struct Builder {
         }
         float *g_out = nullptr, *post_add = nullptr;
         if (res && res->needs_grad && relu && !fused) {      // the masked gradient is d(res): written out by the apply kernel
-            P.grad_writers[res].push_back(nullptr);
+            grad_writers[res].push_back(nullptr);
             if (!res->grad) {
                 res->grad = alloc<float>(res->numel());
                 g_out = res->grad;
@@ -1477,7 +1152,7 @@ struct Builder {
             const float* dy_add = acc ? gy : nullptr;
             if (lazy_bnb) {
                 float* lin4 = alloc<float>(4 * (int64_t)C);
-                b("awr_bn_bwd_finalize", [=](void* s) { return awr_bn_bwd_finalize_lin(sp, C, npix, gam, mean, invstd, coef, lin4, gg, gb, 0, ns, s); });
+                bc("awr_bn_bwd_finalize", [=](void* s) { return awr_bn_bwd_finalize_lin(sp, C, npix, gam, mean, invstd, coef, lin4, gg, gb, 0, ns, s); });
                 y->lz_g = da; y->lz_lin4 = lin4; y->lz_mean = mean; y->lz_invstd = invstd; y->lz_coef = coef;
             } else if (y->half_ok && y->needs_grad) {
                 // Half-batch wavefront (round 5): the reduction needs the whole batch, the apply and the data gradient behind it do
@@ -1485,12 +1160,12 @@ struct Builder {
                 // (it waits for the chain, i.e. starts when half A is done, and the weight gradient queues behind it: it needs both halves anyway)
                 // -> conv_bwd issues dgrad(half A) beside it, waits for half B's record, then dgrad(half B).  The HBM-bound pass runs beside an
                 // MFMA-bound one instead of alone; no extra stream (the runtime's four hardware queues are taken).
-                b("awr_bn_bwd_finalize", [=](void* s) { return awr_bn_bwd_finalize(sp, C, npix, gam, invstd, coef, gg, gb, 0, ns, s); });
+                bc("awr_bn_bwd_finalize", [=](void* s) { return awr_bn_bwd_finalize(sp, C, npix, gam, invstd, coef, gg, gb, 0, ns, s); });
                 const int64_t hp = npix / 2, off = hp * C;
-                b("awr_bn_bwd_apply", [=](void* s) {
+                bc("awr_bn_bwd_apply", [=](void* s) {
                     return awr_bn_bwd_apply_only(da, act, yb, mean, invstd, msc, msh, coef, hp, C, gy, dy_add, g_out, s);
                 });
-                Op& hb = b("awr_bn_bwd_apply", [=](void* s) {
+                Op& hb = bc("awr_bn_bwd_apply", [=](void* s) {
                     return awr_bn_bwd_apply_only(da + off, act ? act + off : nullptr, yb + off, mean, invstd, msc, msh, coef, npix - hp, C, gy + off,
                                                  dy_add ? dy_add + off : nullptr, g_out ? g_out + off : nullptr, s);
                 });
@@ -1499,7 +1174,7 @@ struct Builder {
                 hb.half_sig = true;
                 y->half_dy = true;
             } else {
-                b("awr_bn_bwd_apply", [=](void* s) {
+                bc("awr_bn_bwd_apply", [=](void* s) {
                     return awr_bn_bwd_apply(da, act, yb, mean, invstd, gam, msc, msh, sp, coef, npix, C, gy, dy_add, g_out, gg, gb, 0, ns, s);
                 });
             }
@@ -1509,7 +1184,7 @@ struct Builder {
         if (post_add) {
             float* rg = res->grad;
             const int64_t n = res->numel();
-            b("awr_add", [=](void* s) { return awr_add(rg, post_add, rg, n, s); });
+            bc("awr_add", [=](void* s) { return awr_add(rg, post_add, rg, n, s); });
         }
         if (res && res->needs_grad && (!relu || fused)) contribute_identity(res, da);      // d(a) itself (already masked when fused) is d(res)
         return err;
@@ -1562,13 +1237,13 @@ struct Builder {
             }
         }
         if (P.training) {
-            P.nodes.push_back([=]() {
+            nodes.push_back([=]() {
                 if (!x->needs_grad) return (int)AWR_OK;
                 auto t = gtarget(x);
                 float* gx = t.first;
                 const int acc = t.second ? 1 : 0;
                 float* gyb = y->grad;
-                b("awr_maxpool_bwd", [=](void* s) { return awr_maxpool_bwd(gyb, arg, B, H, W, C, k, s_, p, gx, acc, s); });
+                bc("awr_maxpool_bwd", [=](void* s) { return awr_maxpool_bwd(gyb, arg, B, H, W, C, k, s_, p, gx, acc, s); });
                 return err;
             });
         }
@@ -1594,12 +1269,12 @@ struct Builder {
             });
         }
         if (P.training) {
-            P.nodes.push_back([=]() {
+            nodes.push_back([=]() {
                 auto t = gtarget(low);
                 float* gl = t.first;
                 const int acc = t.second ? 1 : 0;
                 float* gyb = y->grad;
-                b("awr_upsample2_bwd", [=](void* s) { return awr_upsample2_bwd(gyb, B, Hl, Wl, C, gl, acc, s); });
+                bc("awr_upsample2_bwd", [=](void* s) { return awr_upsample2_bwd(gyb, B, Hl, Wl, C, gl, acc, s); });
                 contribute_identity(up1, y->grad);
                 return err;
             });
@@ -1620,7 +1295,7 @@ struct Builder {
         P.head_preds.push_back(pred);
         P.head_grads.push_back(nullptr);
         if (P.training) {
-            P.nodes.push_back([=]() {
+            nodes.push_back([=]() {
                 if (!(P.supervised & (1u << stage))) return (int)AWR_OK;   // no loss on this stage (hourglass: only the last stage, train.py:116-121)
                 auto t = gtarget(pred);
                 float* g = t.first;
@@ -1628,7 +1303,7 @@ struct Builder {
                     float* tmp = alloc<float>(pred->numel());
                     const int64_t n = pred->numel();
                     b("awr_nchw_to_nhwc", [=](void* s) { return awr_nchw_to_nhwc(gout, B, F * F, Cp, 4 * J, tmp, s); });
-                    b("awr_add", [=](void* s) { return awr_add(g, tmp, g, n, s); });
+                    bc("awr_add", [=](void* s) { return awr_add(g, tmp, g, n, s); });
                 } else {
                     b("awr_nchw_to_nhwc", [=](void* s) { return awr_nchw_to_nhwc(gout, B, F * F, Cp, 4 * J, g, s); }).boundary = true;
                     P.head_grads[stage] = g;      // the only producer: a caller on the NHWC boundary writes d(pred) here itself
@@ -1677,7 +1352,7 @@ struct Builder {
             p.gemm = true;
             p.macs = (double)npix * 64 * 25;     // algorithmic work: the conv once forward, its weight gradient once backward
         }
-        P.nodes.push_back([=]() {
+        nodes.push_back([=]() {
             if (!y->grad) {
                 set_error("plan: no gradient reached the stem");
                 return (int)AWR_ERR_ARG;
@@ -1687,15 +1362,15 @@ struct Builder {
             float* slots = alloc<float>((int64_t)ns_dw * 64 * 26, true);
             float* dp = y->grad;
             double* sp = sums.p;
-            Op& r = b("awr_stem_bwd_reduce" + tag, [=](void* s) { return awr_stem_bwd_reduce(img, w, bias, coef4, dp, arg, B, H, W, sp, ns_stats, s); });
+            Op& r = bc("awr_stem_bwd_reduce" + tag, [=](void* s) { return awr_stem_bwd_reduce(img, w, bias, coef4, dp, arg, B, H, W, sp, ns_stats, s); });
             r.gemm = true;
             const float* gam = bn->gamma;
             float *gg = bn->ggamma, *gb = bn->gbeta;
-            b("awr_bn_bwd_finalize", [=](void* s) { return awr_bn_bwd_finalize(sp, 64, npix, gam, coef4 + 192, coef, gg, gb, 0, ns_stats, s); });
+            bc("awr_bn_bwd_finalize", [=](void* s) { return awr_bn_bwd_finalize(sp, 64, npix, gam, coef4 + 192, coef, gg, gb, 0, ns_stats, s); });
             note_grad(bn->ggamma, 64);
             note_grad(bn->gbeta, 64);
             float *gw = conv->gw, *gbias = bias ? conv->gbias : nullptr;
-            Op& wg = b("awr_stem_bwd_wgrad" + tag,
+            Op& wg = bc("awr_stem_bwd_wgrad" + tag,
                        [=](void* s) { return awr_stem_bwd_wgrad(img, w, bias, coef4, coef, dp, arg, B, H, W, slots, gw, gbias, ns_dw, s); });
             wg.gemm = true;
             wg.macs = (double)npix * 64 * 25;
@@ -1711,45 +1386,6 @@ struct Builder {
 
 namespace awrnet {
 
-// Group gradient tensors into contiguous arena ranges that become final in backward order: the ranges tile [0, n_active) from
-// the arena END downwards (the backward pass finishes the last layers first), ready_op non-decreasing, so bucket k can be
-// all-reduced while the backward of the earlier layers still runs.
-static std::vector<awr_plan::Bucket> plan_buckets(std::vector<GradWrite> ws, int64_t n_active, int n_buckets) {
-    std::vector<awr_plan::Bucket> out;
-    if (ws.empty()) return out;
-    std::stable_sort(ws.begin(), ws.end(), [](const GradWrite& a, const GradWrite& b) { return a.lo > b.lo; });
-    int64_t total = 0;
-    for (auto& w : ws) total += w.hi - w.lo;
-    // The LAST bucket (the arena's first layers: final only when the backward ends) has nothing left to hide its exchange behind, so it is
-    // kept small -- the leading tensors up to 1 % of the parameters (ResNet18: the stem and layer1, 0.6 MB of 61.5 MB) -- and the others
-    // share the rest equally.  (Equal quarters left 15 MB = a quarter of the all-reduce exposed after the last data-gradient GEMM.)
-    int64_t tail = 0;
-    if (n_buckets > 2)
-        for (size_t i = ws.size(); i-- > 0;) {
-            if (tail + (ws[i].hi - ws[i].lo) > total / 100) break;
-            tail += ws[i].hi - ws[i].lo;
-        }
-    const double target = (double)(total - tail) / (double)(n_buckets > 1 ? n_buckets - (tail > 0 ? 1 : 0) : 1);
-    int64_t acc = 0, hi_edge = n_active, left = total;
-    int ready = -1;
-    for (size_t i = 0; i < ws.size(); ++i) {
-        acc += ws[i].hi - ws[i].lo;
-        left -= ws[i].hi - ws[i].lo;
-        if (ws[i].ready > ready) ready = ws[i].ready;
-        const bool last = i + 1 == ws.size();
-        const bool cut_tail = tail > 0 && left == tail;      // everything below is the small last bucket
-        if (last || cut_tail || ((double)acc >= target && (int)out.size() < n_buckets - 1 - (tail > 0 ? 1 : 0))) {
-            const int64_t edge = last ? 0 : ws[i].lo;
-            out.push_back({edge, hi_edge, ready});
-            hi_edge = edge;
-            acc = 0;
-        }
-    }
-    for (size_t k = 1; k < out.size(); ++k)      // a later bucket is never launched before an earlier one
-        if (out[k].ready < out[k - 1].ready) out[k].ready = out[k - 1].ready;
-    return out;
-}
-
 static int upload_table(awr_plan& P, const void* host, size_t bytes, void** dev) {
     void* p = nullptr;
     NET_CHECK(dev_alloc(P.owned, bytes, false, &p));
@@ -1758,20 +1394,21 @@ static int upload_table(awr_plan& P, const void* host, size_t bytes, void** dev)
     return AWR_OK;
 }
 
-static int make_unpack_op(awr_plan& P, const std::vector<int>& job_ids, Op& out) {
+static int make_unpack_op(Builder& bld, const std::vector<int>& job_ids, Op& out) {
     std::vector<awr_unpack_job> jobs;
     int64_t total = 0;
     for (int id : job_ids) {
-        awr_unpack_job j = P.unpack_jobs[id];
+        awr_unpack_job j = bld.unpack_jobs[id];
         j.first = total;                 // one workgroup per gradient row
         total += j.d0;
         jobs.push_back(j);
     }
     void* tab = nullptr;
-    NET_CHECK(upload_table(P, jobs.data(), jobs.size() * sizeof(awr_unpack_job), &tab));
+    NET_CHECK(upload_table(bld.P, jobs.data(), jobs.size() * sizeof(awr_unpack_job), &tab));
     const int n = (int)jobs.size();
     out = Op();
     out.name = "awr_unpack_wgrads_batched";
+    out.scatter = true;
     out.fn = [=](void* s) { return awr_unpack_wgrads_batched((const awr_unpack_job*)tab, n, total, s); };
     return AWR_OK;
 }
@@ -1784,40 +1421,42 @@ static int build_backward(Builder& bld) {
         P.scratch_cap += round_up(!l->spec.deconv ? l->p_fwd.numel() : l->p_dgrad.numel(), 4) + AWR_STAT_SLOTS * round_up(l->spec.cout_pad, 4);
     const size_t first = P.bwd.size();
     bld.b("__zero__", nullptr).kind = OP_ZERO;       // placeholder for the scratch fill (kept in place so recorded op indices stay valid)
-    for (size_t i = P.nodes.size(); i-- > 0;) NET_CHECK(P.nodes[i]());
+    for (size_t i = bld.nodes.size(); i-- > 0;) NET_CHECK(bld.nodes[i]());
     if (bld.err) return bld.err;
     if (P.scratch) {
         P.bwd[first].p = P.scratch;
-        P.bwd[first].bytes = (size_t)P.scratch_used * 4;
+        P.bwd[first].bytes = (size_t)bld.scratch_used * 4;
     } else {
         P.bwd[first].p = bld.alloc<float>(4);
         P.bwd[first].bytes = 16;
     }
     const int64_t n_active = P.net->layout.n_active;
-    if (P.n_buckets <= 1 || P.grad_writes.empty()) {
-        if (!P.unpack_jobs.empty()) {       // ONE launch scatters every packed weight gradient back to checkpoint layout
-            std::vector<int> ids(P.unpack_jobs.size());
+    if (P.n_buckets <= 1 || bld.grad_writes.empty()) {
+        if (!bld.unpack_jobs.empty()) {       // ONE launch scatters every packed weight gradient back to checkpoint layout
+            std::vector<int> ids(bld.unpack_jobs.size());
             for (size_t i = 0; i < ids.size(); ++i) ids[i] = (int)i;
             Op op;
-            NET_CHECK(make_unpack_op(P, ids, op));
+            NET_CHECK(make_unpack_op(bld, ids, op));
             P.bwd.push_back(op);
         }
         P.buckets = {{0, n_active, (int)P.bwd.size() - 1}};
     } else {
         // data-parallel overlap: each bucket's weight gradients are scattered into the arena as soon as the backward has passed
         // its layers, then a marker lets the host start that bucket's all-reduce while the backward continues
-        P.buckets = plan_buckets(P.grad_writes, n_active, P.n_buckets);
+        std::vector<Range> writes;
+        for (auto& w : bld.grad_writes) writes.push_back({w.lo, w.hi, w.ready});
+        P.buckets = plan_buckets(writes, n_active, P.n_buckets);
         struct Ins { int pos; std::vector<Op> ops; };
         std::vector<Ins> inserts;
         for (auto& bk : P.buckets) {
             std::vector<int> ids;
-            for (auto& w : P.grad_writes)
+            for (auto& w : bld.grad_writes)
                 if (w.job >= 0 && bk.lo <= w.lo && w.lo < bk.hi) ids.push_back(w.job);
             Ins in;
             in.pos = bk.ready + 1;
             if (!ids.empty()) {
                 Op op;
-                NET_CHECK(make_unpack_op(P, ids, op));
+                NET_CHECK(make_unpack_op(bld, ids, op));
                 in.ops.push_back(op);
             }
             Op m;
@@ -1840,7 +1479,8 @@ struct NetBuilder {
     Builder& b;
     awr_plan& P;
     awr_net& N;
-    explicit NetBuilder(Builder& bb) : b(bb), P(bb.P), N(bb.N) {}
+    std::vector<std::function<int()>>& nodes;      // the builder's backward emitters: the block builders below reorder them
+    explicit NetBuilder(Builder& bb) : b(bb), P(bb.P), N(bb.N), nodes(bb.nodes) {}
     ConvLayer* C(const std::string& k) { return &N.convs.at(k); }
     BNLayer* BN(const std::string& k) { return &N.bns.at(k); }
 
@@ -1868,13 +1508,13 @@ struct NetBuilder {
             for (int bi = 0; bi < nb[li - 1]; ++bi) {
                 const std::string p = fmt("layer%d.%d", li, bi);
                 Tn* r;
-                const size_t n0 = P.nodes.size();
+                const size_t n0 = nodes.size();
                 size_t n1 = n0;
                 if (N.convs.count(p + ".downsample.0")) {   // 1x1 projection (+ stride) + its BatchNorm: independent of the main branch until the residual add
                     b.fork(0);
                     r = cbr(c, p + ".downsample.0", p + ".downsample.1", false);
                     b.end_fork(r);
-                    n1 = P.nodes.size();
+                    n1 = nodes.size();
                 } else {
                     r = c;
                 }
@@ -1882,7 +1522,7 @@ struct NetBuilder {
                 // cheaper than one write + read of the tensor -- the loader arithmetic costs 8-15 % of a GEMM whose K grows with the
                 // channel count, the tensor pass does not: beyond 128 channels the activation is written out
                 Tn* o = cbr(c, p + ".conv1", p + ".bn1", true, nullptr, C(p + ".conv1")->spec.cout <= 128);
-                const size_t n2 = P.nodes.size();
+                const size_t n2 = nodes.size();
                 if (!bott) {
                     c = cbr(o, p + ".conv2", p + ".bn2", true, r);
                 } else {
@@ -1901,7 +1541,7 @@ struct NetBuilder {
                 static const bool no_reorder = getenv("AWR_NO_DS_REORDER") != nullptr;      // same-box A/B hooks
                 static const bool no_branch = getenv("AWR_NO_DS_BRANCH") != nullptr;
                 if (P.training && n1 > n0 && !no_reorder) {
-                    std::vector<std::function<int()>> ds(P.nodes.begin() + n0, P.nodes.begin() + n1), mn(P.nodes.begin() + n1, P.nodes.end());
+                    std::vector<std::function<int()>> ds(nodes.begin() + n0, nodes.begin() + n1), mn(nodes.begin() + n1, nodes.end());
                     Builder* bp = &b;
                     auto marker = [bp](int kind) {
                         return std::function<int()>([bp, kind]() {
@@ -1919,8 +1559,8 @@ struct NetBuilder {
                     for (auto& f : ds) order.push_back(f);
                     if (!no_branch) order.push_back(marker(OP_FORK));
                     order.push_back(mn.back());                                    // the block output's BatchNorm
-                    P.nodes.erase(P.nodes.begin() + n0, P.nodes.end());
-                    for (auto& f : order) P.nodes.push_back(f);
+                    nodes.erase(nodes.begin() + n0, nodes.end());
+                    for (auto& f : order) nodes.push_back(f);
                 }
                 (void)n2;
             }
@@ -1990,11 +1630,11 @@ struct NetBuilder {
     Tn* hg(Tn* x, const std::string& p, int depth) {
         // the skip branch of a level only meets the low-resolution path again at the up-sampling add: issued on its own side
         // stream, its full-resolution GEMMs fill the chip while the main stream walks the small (<= 16x16) levels
-        const size_t n0 = P.nodes.size();
+        const size_t n0 = nodes.size();
         b.fork(depth);
         Tn* up1 = residual(x, p + ".up1");
         b.end_fork(up1);
-        const size_t n1 = P.nodes.size();
+        const size_t n1 = nodes.size();
         Tn* pooled = b.maxpool(x, 2, 2, 0);
         // backward branches for the two outer levels only (64x64 / 32x32 skip residuals): one stream each, no false dependencies
         // (measured: branches for the inner levels too change nothing, 25.7 ms either way vs 26.8-27.3 without any)
@@ -2010,12 +1650,12 @@ struct NetBuilder {
             // first writer of d(x) on a branch stream, the low path runs beside it on the main stream, and the join above orders
             // the max-pool backward's accumulation into d(x) after the branch.  (d(out) itself is read by the up-sampling backward
             // BEFORE the fork and may be accumulated into in place by the branch afterwards: the identity skip aliases it.)
-            std::rotate(P.nodes.begin() + n0, P.nodes.begin() + n1, P.nodes.end());
-            const size_t nlow = P.nodes.size() - (n1 - n0);       // up1's emitters now start here
-            P.nodes.insert(P.nodes.begin() + nlow, nullptr);      // placeholder: end-fork marker (emitted after up1's backward)
+            std::rotate(nodes.begin() + n0, nodes.begin() + n1, nodes.end());
+            const size_t nlow = nodes.size() - (n1 - n0);       // up1's emitters now start here
+            nodes.insert(nodes.begin() + nlow, nullptr);      // placeholder: end-fork marker (emitted after up1's backward)
             const int sid = depth;
             Builder* bp = &b;
-            P.nodes[nlow] = [bp, sid]() {
+            nodes[nlow] = [bp, sid]() {
                 Op& o = bp->b("__endfork__", nullptr);
                 o.kind = OP_ENDFORK;
                 o.sid = sid;
@@ -2129,14 +1769,22 @@ static int refresh_weights(awr_plan& P, void* stream) {
     return AWR_OK;
 }
 
-// waiter waits for everything enqueued on signaler so far (capturable: event record + stream wait)
-static int stream_wait(awr_plan& P, hipStream_t waiter, hipStream_t signaler) {
-    if (P.events.size() < 2048) {      // (large enough that an event is never re-recorded within one pass: hundreds of waits per Hourglass backward)
+// the next event of the plan's pool, which grows up to 2048 events (large enough that an event is never re-recorded within one pass: hundreds of
+// waits per Hourglass backward) and is cycled through from then on
+static int next_event(awr_plan& P, hipEvent_t* out) {
+    if (P.events.size() < 2048) {
         hipEvent_t e;
         HIP_TRY(hipEventCreateWithFlags(&e, hipEventDisableTiming));
         P.events.push_back(e);
     }
-    hipEvent_t e = P.events[P.ev_next++ % P.events.size()];
+    *out = P.events[P.ev_next++ % P.events.size()];
+    return AWR_OK;
+}
+
+// waiter waits for everything enqueued on signaler so far (capturable: event record + stream wait)
+static int stream_wait(awr_plan& P, hipStream_t waiter, hipStream_t signaler) {
+    hipEvent_t e;
+    NET_CHECK(next_event(P, &e));
     HIP_TRY(hipEventRecord(e, signaler));
     HIP_TRY(hipStreamWaitEvent(waiter, e, 0));
     return AWR_OK;
@@ -2168,7 +1816,7 @@ static int run_list(awr_plan& P, std::vector<Op>& ops, void* stream, bool is_bwd
     };
     for (auto& op : ops) {
         if (op.boundary && P.nhwc_boundary) continue;
-        if (comm && op.kind == OP_CALL && op.name == "awr_unpack_wgrads_batched") {
+        if (comm && op.kind == OP_CALL && op.scatter) {
             NET_CHECK(hand_off());
             handed = true;
             NET_CHECK(op.fn((void*)comm));
@@ -2180,17 +1828,12 @@ static int run_list(awr_plan& P, std::vector<Op>& ops, void* stream, bool is_bwd
             if (P.bucket_cb) P.bucket_cb(P.bucket_user, op.lo, op.hi, (void*)comm);
             continue;
         }
-        if (wside && pending && (op.kind == OP_CALL || op.kind == OP_BUCKET)) {
-            const std::string& n = op.name;
-            const bool no_join = op.kind == OP_CALL &&
-                                 (n.compare(0, 9, "awr_conv_") == 0 || n.compare(0, 9, "awr_stem_") == 0 || n == "awr_bn_bwd_reduce" || n == "awr_bn_bwd_apply" ||
-                                  n == "awr_bn_bwd_finalize" || n == "awr_maxpool_bwd" || n == "awr_upsample2_bwd" || n == "awr_add");
-            if (!no_join) {      // join before anything that consumes the weight-gradient scratch (scatter, buckets)
-                for (auto st : P.side) NET_CHECK(stream_wait(P, main, st));
-                for (auto st : P.branch) NET_CHECK(stream_wait(P, main, st));
-                pending = false;
-                after_join = true;      // ... and issue it on MAIN: inside an open fork region `cur` is a branch stream that did not wait
-            }
+        if (wside && pending && (op.kind == OP_CALL || op.kind == OP_BUCKET) && op.joins) {
+            // join before anything that consumes the weight-gradient scratch (scatter, buckets)
+            for (auto st : P.side) NET_CHECK(stream_wait(P, main, st));
+            for (auto st : P.branch) NET_CHECK(stream_wait(P, main, st));
+            pending = false;
+            after_join = true;      // ... and issue it on MAIN: inside an open fork region `cur` is a branch stream that did not wait
         }
         switch (op.kind) {
             case OP_ZERO:      // (on the issuing chain: a zero fill inside a branch belongs to the branch's data gradient)
@@ -2235,12 +1878,7 @@ static int run_list(awr_plan& P, std::vector<Op>& ops, void* stream, bool is_bwd
             rc = op.fn((void*)st);
             pending = true;
             if (op.half_sig && rc == AWR_OK) {
-                if (P.events.size() < 2048) {
-                    hipEvent_t e;
-                    HIP_TRY(hipEventCreateWithFlags(&e, hipEventDisableTiming));
-                    P.events.push_back(e);
-                }
-                half_ev = P.events[P.ev_next++ % P.events.size()];
+                NET_CHECK(next_event(P, &half_ev));
                 HIP_TRY(hipEventRecord(half_ev, st));
             }
         } else {
@@ -2340,8 +1978,7 @@ static int autotune(awr_plan& P, int reps, void* stream) {
                 cands.erase(std::remove_if(cands.begin(), cands.end(), [&](const Cand& c) { return g.ca->Wq % (32 * c.tm) != 0; }), cands.end());
             if (g.ca->partial && g.ca->split_max > 1 && awr_get_gemm_products() == 1) {      // (tile, split-K depth) pairs; tb = depth
                 std::vector<Cand> withk;
-                int minsteps = 1 << 30;
-                for (int p = 0; p < g.ca->nphase; ++p) minsteps = std::min(minsteps, g.ca->ph[p].ntaps * (g.ca->Cin / 32));
+                const int minsteps = min_k_steps(*g.ca);
                 for (auto& c : cands)
                     for (int sk = 1; sk <= g.ca->split_max; sk *= 2) {
                         // blocked accumulation: only depths the accumulation rule admits (a whole 128-k block per K range, awr_hip.h)
@@ -2625,7 +2262,7 @@ int awr_plan_op(const awr_plan* p, int list, int i, const char** name, double* m
     AWR_REQUIRE(i >= 0 && i < (int)v.size(), "plan_op: index out of range");
     if (name) *name = v[i].name.c_str();
     if (macs) *macs = v[i].macs;
-    if (flags) *flags = (v[i].side_ok ? 1 : 0) | (v[i].gemm ? 2 : 0);
+    if (flags) *flags = (v[i].side_ok ? 1 : 0) | (v[i].gemm ? 2 : 0) | (v[i].scatter ? 4 : 0) | (v[i].joins ? 8 : 0);
     return AWR_OK;
 }
 

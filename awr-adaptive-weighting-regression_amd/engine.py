@@ -19,7 +19,8 @@ _KIND_NAMES = ("conv_w", "deconv_w", "conv_b", "bn_w", "bn_b", "bn_mean", "bn_va
 
 
 def plan_buckets(writes, n_active, n_buckets):
-    """Reference statement of the native bucket planner (csrc/awr_net.hip: plan_buckets), kept for the CPU unit test.
+    """The reference the native bucket planner (csrc/awr_net_geometry.h: plan_buckets, what every plan runs) is compared against:
+    tests/test_host_cpu.py runs both on the same write lists and requires equal buckets.  No plan is built from this function.
 
     writes: list of (arena_lo, arena_hi, ready_op) -- the gradient occupying [lo,hi) floats is final once backward op number
     `ready_op` has been enqueued.  Returns [(lo, hi, ready_op)] with the ranges tiling [0, n_active) from the arena END downwards

@@ -620,7 +620,9 @@ int awr_plan_info(const awr_plan* plan, int64_t* bytes, int* deterministic, int*
 int awr_plan_winograd(const awr_plan* plan, int* n, double* macs);
 int awr_plan_bucket(const awr_plan* plan, int i, int64_t* lo, int64_t* hi, int* ready_op);
 /* op i of the forward (list 0) / backward (list 1) launch list: name, algorithmic MACs (GEMM-family launches),
- * flags bit 0 = weight gradient that may run on a side stream, bit 1 = conv / stem family (the launches a roofline is quoted for) */
+ * flags bit 0 = weight gradient that may run on a side stream, bit 1 = conv / stem family (the launches a roofline is quoted for),
+ * bit 2 = the batched gradient scatter (a plan with a comm stream hands it to that stream), bit 3 = a backward replay joins the side and
+ * branch streams before it issues this op (set unless the op's emitter declared it chain-only; forward replays ignore it) */
 int awr_plan_op(const awr_plan* plan, int list, int i, const char** name, double* macs, int* flags);
 /* parity / debugging introspection: activation tensor i of the plan in build order (i past the end returns AWR_ERR_ARG): name
  * ("<layer>.out" = a conv's raw output, "<bn>.act" = a materialised BatchNorm(+ReLU) output, "<bn>.act(lazy)" = one that is never

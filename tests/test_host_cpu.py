@@ -145,11 +145,24 @@ def test_reference_init_distributions(amd):
     assert float(w.abs().max()) <= 1.0 / (w.shape[1] * 9) ** 0.5 + 1e-7                       # kaiming_uniform(a=sqrt(5))
 
 
+# 6 tensors laid out in forward order; backward finalises them in reverse, with a local swap (offset 300 before 400)
+BUCKET_WRITES_SWAPPED = [(0, 100, 50), (100, 300, 40), (300, 400, 25), (400, 700, 30), (700, 900, 10), (900, 1000, 5)]
+
+
+def resnet_like_bucket_writes():
+    """-> (writes, n_active): ten contiguous tensors of ResNet18-like sizes, final in reverse order."""
+    sizes = [1728, 74000, 74000, 520000, 2100000, 8400000, 2100000, 1050000, 1050000, 14000]
+    w2, lo = [], 0
+    for i, n in enumerate(sizes):
+        w2.append((lo, lo + n, 100 - 10 * i))
+        lo += n
+    return w2, lo
+
+
 def test_gradient_bucket_planner(amd):
     """Data-parallel overlap: buckets tile the arena from its end downwards, in backward (ready) order."""
     from awr_amd.engine import plan_buckets
-    # 6 tensors laid out in forward order; backward finalises them in reverse, with a local swap (offset 300 before 400)
-    writes = [(0, 100, 50), (100, 300, 40), (300, 400, 25), (400, 700, 30), (700, 900, 10), (900, 1000, 5)]
+    writes = BUCKET_WRITES_SWAPPED
     b = plan_buckets(writes, 1000, 3)
     assert b[0][1] == 1000 and b[-1][0] == 0
     assert all(x[0] == y[1] for x, y in zip(b, b[1:]))                 # contiguous, descending
@@ -159,11 +172,7 @@ def test_gradient_bucket_planner(amd):
     assert plan_buckets(writes, 1000, 1) == [(0, 1000, 50)]
     assert len(plan_buckets(writes, 1000, 16)) <= 6
     # the last bucket -- final only when the backward ends -- is the small one: ResNet18-like sizes (stem + layer1 = 1 % of the arena)
-    sizes = [1728, 74000, 74000, 520000, 2100000, 8400000, 2100000, 1050000, 1050000, 14000]
-    w2, lo = [], 0
-    for i, n in enumerate(sizes):
-        w2.append((lo, lo + n, 100 - 10 * i))
-        lo += n
+    w2, lo = resnet_like_bucket_writes()
     b4 = plan_buckets(w2, lo, 4)
     assert 3 <= len(b4) <= 4 and b4[-1] == (0, 1728 + 74000 + 74000, 100) and b4[0][1] == lo
     assert all(x[0] == y[1] for x, y in zip(b4, b4[1:])) and [r for _, _, r in b4] == sorted(r for _, _, r in b4)
@@ -278,3 +287,127 @@ def test_bench_dump_outputs_helpers(tmp_path):
     with pytest.raises(SystemExit):
         bench._dump_outputs(big, {"z": torch.zeros(bench.DUMP_LIMIT_BYTES // 4 + 1)})
     assert not os.path.exists(big)
+
+
+# ---- the plan engine's native host logic (csrc/awr_net_layout.h, csrc/awr_net_geometry.h) against the Python statements -------------------
+def _hipcc_clangxx():
+    """The clang++ of the hipcc the library is built with (its InstalledDir)."""
+    import subprocess
+    from awr_amd import build
+    hipcc = build._hipcc()
+    for line in subprocess.run([hipcc, "--version"], stdout=subprocess.PIPE, stderr=subprocess.STDOUT, text=True, check=True).stdout.splitlines():
+        if line.startswith("InstalledDir:"):
+            cxx = os.path.join(line.split(":", 1)[1].strip(), "clang++")
+            if os.path.exists(cxx):
+                return cxx
+    cxx = os.path.join(os.path.dirname(os.path.dirname(os.path.realpath(hipcc))), "lib", "llvm", "bin", "clang++")
+    assert os.path.exists(cxx), "no clang++ beside %s" % hipcc
+    return cxx
+
+
+# the layer specs of tests/native/plan_host_main.cpp, in its order: (kind, cin, cout, k, stride, pad, cin_pad)
+HOST_SPECS = [("conv", 64, 128, 1, 1, 0, None), ("conv", 64, 64, 3, 1, 1, None), ("conv", 64, 128, 3, 2, 1, None), ("conv", 3, 64, 7, 2, 3, 32),
+              ("conv", 64, 128, 1, 2, 0, None), ("deconv", 128, 64, 4, 2, 1, None)]
+HOST_NETS = {"resnet_18": (0, 18, 14, 2), "hourglass_1": (1, 1, 14, 2), "hourglass_2": (1, 2, 21, 2)}      # NetHandle arguments
+MAX_TAPS = 16       # awr_phase.tap[16], awr_wgrad_args.dy[16] / dx[16]
+
+
+def _bucket_cases(handles):
+    """[(writes, n_active, n_buckets)]: the two hand-written lists, one write per live parameter tensor of two layouts, 200 random lists."""
+    cases = [(BUCKET_WRITES_SWAPPED, 1000, nb) for nb in (3, 1, 16)]
+    w2, lo = resnet_like_bucket_writes()
+    cases.append((w2, lo, 4))
+    for name in ("resnet_18", "hourglass_2"):
+        h = handles[name]
+        live = sorted((off, int(np.prod(shape, dtype=np.int64))) for _, shape, kind, off, unused in h.layout
+                      if kind in ("conv_w", "deconv_w", "conv_b", "bn_w", "bn_b") and not unused)
+        writes = [(off, off + n, len(live) - i) for i, (off, n) in enumerate(live)]       # ready falls as the arena offset rises
+        cases += [(writes, h.n_active, nb) for nb in (1, 2, 3, 4, 8, 16)]
+    rng = np.random.default_rng(0)
+    for _ in range(200):
+        n = int(rng.integers(1, 41))
+        sizes = np.clip(np.floor(10.0 ** rng.uniform(np.log10(4.0), 7.0, n)), 4, 10 ** 7).astype(np.int64)      # 4 .. 10^7 floats, every magnitude
+        ready = rng.permutation(n * 3)[:n]          # distinct, in shuffled order
+        edges = np.concatenate([[0], np.cumsum(sizes)])
+        writes = [(int(edges[i]), int(edges[i + 1]), int(ready[i])) for i in range(n)]
+        cases.append((writes, int(edges[-1]), int(rng.integers(1, 9))))
+    return cases
+
+
+def _args_fields(a, names):
+    return {k: int(getattr(a, k)) for k in names}
+
+
+def test_native_plan_host_logic_equals_the_python_statements(amd, tmp_path):
+    """tests/native/plan_host_main.cpp, built with the address and undefined-behaviour sanitizers and run as a plain child process, prints
+    what the plan engine's host logic computes; every figure must equal the Python statement of the same rule: (a) the checkpoint layouts
+    = NetHandle.layout, (b) the launch geometry = ops.ConvSpec with make_conv_args / make_wgrad_args, (c) the gradient buckets =
+    engine.plan_buckets.  A phase of more than 16 taps (the 7x7 forward) and a weight gradient of more than 16 taps have no argument block in
+    either statement (awr_phase.tap[16], awr_wgrad_args.dy[16]): those are compared as problems, not as packed words."""
+    import subprocess
+    from awr_amd import ops
+    from awr_amd.engine import NetHandle, plan_buckets, _KIND_NAMES
+    repo = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+    exe = str(tmp_path / "plan_host_main")
+    # a host-only program compiled by clang++ as plain C++: the sanitizers instrument host code and nothing else (-fno-gpu-sanitize says so)
+    flags = ["-std=c++17", "-O1", "-g", "-fsanitize=address,undefined", "-fno-gpu-sanitize", "-fno-sanitize-recover=all", "-Wno-unused-command-line-argument"]
+    subprocess.run([_hipcc_clangxx()] + flags + [os.path.join(repo, "tests", "native", "plan_host_main.cpp"), "-o", exe], check=True)
+    handles = {name: NetHandle(*args) for name, args in HOST_NETS.items()}
+    cases = _bucket_cases(handles)
+    assert len(cases) == 4 + 12 + 200
+    inp = tmp_path / "buckets.txt"
+    with open(inp, "w") as f:
+        f.write("%d\n" % len(cases))
+        for writes, n_active, nb in cases:
+            f.write("%d %d %d\n" % (n_active, nb, len(writes)) + "".join("%d %d %d\n" % w for w in writes))
+    run = subprocess.run([exe, str(inp)], stdout=subprocess.PIPE, stderr=subprocess.PIPE, text=True)
+    assert run.returncode == 0 and run.stderr == "", run.stderr[-4000:]
+    got = json.loads(run.stdout)
+
+    # (a) layouts
+    assert sorted(got["layouts"]) == sorted(HOST_NETS)
+    for name, h in handles.items():
+        g = got["layouts"][name]
+        assert (g["n_params"], g["n_active"], g["n_buffers"], g["n_counters"]) == (h.n_params, h.n_active, h.n_buffers, h.n_counters), name
+        assert [(k, tuple(s), _KIND_NAMES[kind], off, bool(un)) for k, s, kind, off, un in g["entries"]] == h.layout, name
+
+    # (b) geometry
+    conv_names = ("B", "Hin", "Win", "Cin", "Hq", "Wq", "Hout", "Wout", "N", "so", "si", "T", "nphase", "accum")
+    wgrad_names = ("B", "Hd", "Wd", "Cd", "Hg", "Wg", "Cg", "sg", "T", "ld")
+    assert [(g["spec"], g["h"]) for g in got["geometry"]] == [(i, h) for i in range(len(HOST_SPECS)) for h in (8, 32)]
+    n_blocks = 0
+    for g in got["geometry"]:
+        kind, cin, cout, k, stride, pad, cin_pad = HOST_SPECS[g["spec"]]
+        spec, h, B = ops.ConvSpec(kind, cin, cout, k, stride, pad, cin_pad=cin_pad), g["h"], 2
+        assert tuple(g["out_hw"]) == spec.out_hw(h, h)
+        assert tuple(g["fwd_pack"]) == spec.fwd_pack() and tuple(g["dgrad_pack"]) == spec.dgrad_pack()
+        for which, prob in (("fwd", spec.fwd_problem(h, h)), ("dgrad", spec.dgrad_problem(h, h))):
+            n = g[which]
+            for key in ("Hin", "Win", "Cin", "Hout", "Wout", "N", "Hq", "Wq", "so", "si"):
+                assert n[key] == prob[key], (g["spec"], h, which, key)
+            assert bool(n["full"]) == prob["full"]
+            assert [(py, px, [tuple(t) for t in taps]) for py, px, taps in n["phases"]] == prob["phases"], (g["spec"], h, which)
+            assert n["k_extent"] == max(len(taps) for _, _, taps in prob["phases"]) * prob["Cin"]
+            fits = all(len(taps) <= MAX_TAPS for _, _, taps in prob["phases"])
+            assert (n["args"] is not None) == fits
+            if fits:
+                a = ops.make_conv_args(prob, B, None, None, None, T=spec.T)
+                assert {key: n["args"][key] for key in conv_names} == _args_fields(a, conv_names), (g["spec"], h, which)
+                assert n["args"]["ph"] == [[a.ph[i].py, a.ph[i].px, a.ph[i].ntaps, [int(a.ph[i].tap[t]) for t in range(a.ph[i].ntaps)]]
+                                           for i in range(a.nphase)], (g["spec"], h, which)
+                n_blocks += 1
+        wp = spec.wgrad_problem(h, h)
+        assert (g["wgrad"] is not None) == (spec.T <= MAX_TAPS)
+        if g["wgrad"] is not None:
+            n = g["wgrad"]
+            assert bool(n["d_is_dy"]) == (wp["D"] == "dy") and (n["d0"], n["d1"]) == (wp["d0"], wp["d1"])
+            a = ops.make_wgrad_args(wp, B, None, None, None, wp["Cg"])
+            assert {key: n[key] for key in wgrad_names} == _args_fields(a, wgrad_names), (g["spec"], h)
+            assert (n["dy"], n["dx"]) == ([int(a.dy[t]) for t in range(a.T)], [int(a.dx[t]) for t in range(a.T)]) and len(n["dy"]) == spec.T
+            n_blocks += 1
+    assert n_blocks == 12 * 3 - 2 * 2       # every block but the 7x7 layer's forward and weight gradient, at both sizes
+
+    # (c) buckets
+    assert len(got["buckets"]) == len(cases)
+    for i, (writes, n_active, nb) in enumerate(cases):
+        assert [tuple(b) for b in got["buckets"][i]] == plan_buckets(writes, n_active, nb), (i, writes, n_active, nb)
