@@ -9,6 +9,7 @@
     Predictor(..., track=True)              # start each call's crop at the previous call's joint centre of the same batch slot
     Predictor(..., views=make_views(rot=(-15, 15)), fuse="mean")      # the same hand under several views in ONE pass, fused
     Predictor(..., palm=True)               # move the detector's centre to the palm disc, away from the forearm
+    Predictor(..., smooth=True)             # filter the joints over time: One-Euro per joint, gate, coasting, look-ahead
 
 Everything between the frames and the joints runs on the device, on the current stream, without a synchronisation: awr_detect (hand
 centre by iterated centre of mass) -> awr_detect_samples (crop blocks, crop matrices) -> awr_nyu_batch (crop + normalise) -> the
@@ -42,6 +43,15 @@ window of palm_search cubes, its medial set, the end of it with the fingers beyo
 awr_detect_samples.  With track=True only the detector branch is refined, before awr_centers_select: a tracked centre is the joints' own.
 With centers_uvd handed to predict() it does not apply.  Measured on procedural hands only (profiles/synth_accuracy.txt); behaviour on real
 depth frames -- sleeves, a body within the search depth, NYU -- is UNMEASURED.
+
+Temporal filter (opt-in; smooth=None issues the launches and gives the bits it always did).  smooth=True | dict | track.OneEuro puts ONE
+awr_joints_filter launch behind the final pass (with views: behind awr_views_fuse): per batch slot, joint and axis a One-Euro low-pass
+in camera millimetres whose state (six doubles and two ints per joint) lives on the device from call to call; a measurement outside
+gate_mm, a frame that is not OK or a non-finite joint is answered with the held joint for up to max_coast calls, then the track restarts
+at the measurement or is dropped.  predict() returns the filtered joints; raw_xyz / raw_uvd / ahead_xyz / filter_codes hold the rest.
+lead=True hands the tracker the look-ahead joints x + d dt for the next call's crop.  The statement is awr_amd.track.filter_step; the
+kernel equals it bit for bit.  Measured on procedural sequences only (profiles/track_accuracy.txt, profiles/predict_smooth.txt); the
+defaults are engineering choices and accuracy on real frames is UNMEASURED.
 """
 import collections
 import types
@@ -52,6 +62,7 @@ import torch
 from . import _lib as L
 from . import detect as D
 from . import nyu_data as ND
+from . import track as T
 
 Prediction = collections.namedtuple("Prediction", "xyz uvd center_xyz M status")
 ConfidentPrediction = collections.namedtuple("ConfidentPrediction", Prediction._fields + ("conf", "peak", "spread_mm"))
@@ -63,10 +74,12 @@ MAX_VIEWS = D.MAX_VIEWS
 
 class Predictor:
     views, fuse, V = None, "mean", 1          # a predictor without views: one identity view, no view table, no per-view buffers
+    smooth = None                             # a predictor without a temporal filter: no filter state, no launch, no extra attributes
 
     def __init__(self, net, img_size, kernel_size, cube=(300, 300, 300), paras=ND.PARAS, flip=-1, max_batch=1, frame_shape=(480, 640),
                  seed="nearest", depth_range=D.DEPTH_RANGE, slab=D.SLAB, refine_iters=D.REFINE_ITERS, winograd=None, parity=False, confidence=False,
-                 recenter=0, track=False, center_joints=None, max_shift=1.0, views=None, fuse="mean", palm=False, palm_search=D.PALM_SEARCH):
+                 recenter=0, track=False, center_joints=None, max_shift=1.0, views=None, fuse="mean", palm=False, palm_search=D.PALM_SEARCH,
+                 smooth=None):
         """net: an awr_amd network on the GPU with its weights loaded.  cube: the crop cube in mm.  paras = (fx, fy, u0, v0), flip: the camera.
         max_batch: the static batch of the inference plan; smaller batches are padded, larger ones refused.  seed / depth_range / slab /
         refine_iters: the detector (awr_amd.detect); with `centers_uvd` handed to predict() the seed is the given centre and refine_iters
@@ -97,7 +110,18 @@ class Predictor:
         the fused joints and view 0's centre and cube are what awr_joints_center reads, and each pass expands its views anew.
         palm: True -- the configured detector's centres go through awr_detect_palm (awr_amd.detect.palm_center) before the
         crop; not applied to centers_uvd handed to predict() nor to a tracked centre.  palm_search: the side of its window in cubes.  After
-        such a predict(), palm_info (nb, 4) int32 holds awr_detect_palm's info rows (palm point u, v, its squared radius, pixels of the disc)."""
+        such a predict(), palm_info (nb, 4) int32 holds awr_detect_palm's info rows (palm point u, v, its squared radius, pixels of the disc).
+        smooth: None | True (the defaults) | a dict of awr_amd.track.OneEuro's fields | a OneEuro -- one awr_joints_filter launch (DESIGN.md
+        4.25; statement: awr_amd.track.filter_step) behind the final pass (with views: behind awr_views_fuse): a One-Euro low-pass per batch
+        slot, joint and axis with a gate (gate_mm), coasting (max_coast) and a constant-velocity look-ahead.  predict() then returns the
+        FILTERED joints in xyz / uvd of the same named tuples; status, center_xyz, M and the confidence fields remain the measurement's.  A
+        frame that is not OK yields the held joints instead of NaN rows while its track lives (check() still reports the frame).  After
+        such a predict(): raw_xyz, raw_uvd (nb, J, 3) the unfiltered joints, ahead_xyz (nb, J, 3) the joints one dt ahead at the filtered
+        velocity, filter_codes (nb, J) int32 awr_amd.track's NONE ... LOST -- device tensors, nothing synchronised.  Slot b of the filter is
+        batch slot b, as the tracker's is; slots >= n_valid keep their state; reset_smooth() clears it.  weight="conf" scales each step by
+        the joint's conf (view 0's) and switches the engine's confidence pass on whether or not confidence=True asks for the fields.
+        lead=True needs track=True: the tracker's centre for the next call is the joint centre of ahead_xyz, not of the raw joints (the
+        re-centring passes inside a call are unaffected).  The defaults are engineering choices; accuracy on real frames is UNMEASURED."""
         if not isinstance(palm, bool):
             raise TypeError("palm is True or False, not %r" % (palm,))
         self.palm, self.palm_search = palm, D.check_palm(palm_search)[0]
@@ -128,6 +152,10 @@ class Predictor:
             self.views, self.fuse = D.check_views(views, fuse), fuse
             self.V = len(self.views)
         self.view_outputs = None
+        if smooth is not None:
+            self.smooth = T.check_filter(smooth)
+            if self.smooth.lead and not track:
+                raise ValueError("smooth lead=True moves the TRACKER's next centre to the look-ahead joints: it needs track=True")
         self.recenter, self.track, self.max_shift = recenter, track, float(max_shift)
         self.centers_uvd = self.next_centers_uvd = self.recenter_codes = None
         if not torch.cuda.is_available():
@@ -150,7 +178,7 @@ class Predictor:
         V = self.V
         P = B * V                                # rows of the plan: view-major, view 0 first
         self.engine = InferEngine(net, P, self.S, kernel_size, winograd=winograd, parity=parity,
-                                  confidence=confidence or (V > 1 and fuse == "conf"))
+                                  confidence=confidence or (V > 1 and fuse == "conf") or (smooth is not None and self.smooth.weight == "conf"))
         self.J = self.engine.J
         # the predictor's own small frame store: the FrameStore layout, one row per image of a batch
         self._frames = torch.empty((B, self.fh, self.fw), dtype=torch.uint16, device=dev)
@@ -182,6 +210,10 @@ class Predictor:
                 raise L.AwrError(L.last_error())
             self._palm_scratch = torch.empty(nbytes // 4, dtype=torch.int32, device=dev)
             self._palm_info = torch.empty((B, 4), dtype=torch.int32, device=dev)
+        if smooth is not None:
+            self._filter_state = torch.zeros((B, self.J, 6), dtype=torch.float64, device=dev)          # x0 x1 x2 d0 d1 d2 per slot and joint
+            self._filter_count = torch.zeros((B, self.J, 2), dtype=torch.int32, device=dev)            # age, coast
+            self.raw_xyz = self.raw_uvd = self.ahead_xyz = self.filter_codes = None
         if track:
             self._track = torch.full((B, 3), float("nan"), dtype=torch.float64, device=dev)
             self._tcenters = torch.empty((B, 3), dtype=torch.float64, device=dev)
@@ -223,11 +255,36 @@ class Predictor:
         else:
             self._track.index_fill_(0, idx, float("nan"))
 
+    def reset_smooth(self, slots=None):
+        """Drop the temporal filter's tracks of batch slots (default: all of them): their next usable frame starts a track.  Does not block."""
+        if self.smooth is None:
+            raise L.AwrError("reset_smooth needs a Predictor built with smooth=...")
+        idx = self._slots(slots)
+        if idx is None:
+            self._filter_state.zero_()
+            self._filter_count.zero_()
+        else:
+            self._filter_state.index_fill_(0, idx, 0.0)
+            self._filter_count.index_fill_(0, idx, 0)
+
     def _joints_center(self, xyz, cxyz, status, ustatus, nv, center_out, next_out, code):
         fx, fy, u0, v0 = self.paras
         L.call("awr_joints_center", L.ptr(xyz), self._centers.data_ptr(), L.ptr(cxyz), L.ptr(self._cube32), status.data_ptr(), ustatus.data_ptr(),
                self.B, self.J, nv, L.ptr(self._joints), 0 if self._joints is None else int(self._joints.numel()), fx, fy, u0, v0, self.flip,
                self.depth_range[0], self.depth_range[1], self.max_shift, center_out.data_ptr(), L.ptr(next_out), code.data_ptr(), L.stream())
+
+    def _smooth_step(self, xyz, status, ustatus, conf, nv, dt):
+        """one awr_joints_filter launch over the call's output joints -> (xyz_f, uvd_f, ahead (B, J, 3), code (B, J)), fresh tensors"""
+        cfg, B, J, dev = self.smooth, self.B, self.J, self.device
+        fx, fy, u0, v0 = self.paras
+        if cfg.weight == "conf" and conf is None:
+            conf = self.engine.conf[:B, :, 0].contiguous()          # (B, J): view 0's rows come first
+        out = [torch.empty((B, J, 3), dtype=torch.float32, device=dev) for _ in range(3)] + [torch.empty((B, J), dtype=torch.int32, device=dev)]
+        L.call("awr_joints_filter", self._filter_state.data_ptr(), self._filter_count.data_ptr(), L.ptr(xyz), status.data_ptr(), ustatus.data_ptr(),
+               L.ptr(conf) if cfg.weight == "conf" else None, B, J, nv, dt, cfg.min_cutoff, cfg.beta, cfg.d_cutoff,
+               -1.0 if cfg.gate_mm is None else cfg.gate_mm, cfg.max_coast, T.WEIGHTS[cfg.weight], cfg.conf_floor, fx, fy, u0, v0, self.flip,
+               L.ptr(out[0]), L.ptr(out[1]), L.ptr(out[2]), L.ptr(out[3]), L.stream())
+        return out
 
     def _upload(self, frames):
         """(nb, fh, fw) uint16 -> rows [0, nb) of the frame store, without blocking"""
@@ -259,13 +316,19 @@ class Predictor:
             self._frames[:nb].copy_(frames, non_blocking=True)
         return nb
 
-    def predict(self, frames, centers_uvd=None, n_valid=None):
+    def predict(self, frames, centers_uvd=None, n_valid=None, dt=None):
         """-> Prediction(xyz (nb, J, 3), uvd (nb, J, 3), center_xyz (nb, 3), M (nb, 3, 3), status (nb,) int32), device tensors, nothing
         synchronised; with confidence=True a ConfidentPrediction: these and conf, peak, spread_mm (nb, J).  centers_uvd (nb, 3): hand centres in original-image uvd (numpy or tensor) instead of the detector's seed.  n_valid:
         frames of the batch that count (default: all of them); rows past it hold unspecified values.  status: awr_amd.detect's codes; a frame that is
         not OK has NaN rows (of conf / peak / spread_mm too).  With recenter > 0 every field is the FINAL pass's; with track=True a call
         without centers_uvd starts from the tracked centres (see __init__), an explicit centers_uvd overrides them for this call, and either
-        way slots [0, n_valid) of the tracker take this call's next_centers_uvd."""
+        way slots [0, n_valid) of the tracker take this call's next_centers_uvd.  dt: seconds since the previous call, for a predictor with
+        smooth (default 1 / its fps); xyz and uvd are then the filtered joints (see __init__)."""
+        if self.smooth is None:
+            if dt is not None:
+                raise L.AwrError("predict(dt=...) is the temporal filter's time step: it needs a Predictor built with smooth=...")
+        else:
+            dt = T.check_dt(1.0 / self.smooth.fps if dt is None else dt)
         nb = self._upload(frames)
         nv = nb if n_valid is None else int(n_valid)
         if not 0 < nv <= nb:
@@ -336,6 +399,7 @@ class Predictor:
             L.call("awr_views_fuse", L.ptr(xyz), vstatus.data_ptr(), ustatus.data_ptr(), L.ptr(weights[0]), D.FUSE_MODES[self.fuse], V, B, J, nv,
                    fx, fy, u0, v0, self.flip, L.ptr(fxyz), L.ptr(fuvd), L.ptr(vspread), L.ptr(vused), s)
 
+        smoothed = None
         if V > 1:
             crop_and_predict, out_xyz, out_uvd, out_status = views_and_predict, fxyz, fuvd, vstatus
         else:
@@ -360,11 +424,23 @@ class Predictor:
                 self._joints_center(out_xyz, cxyz, out_status, ustatus, nv, self._centers, None, codes[k])
                 crop_and_predict()
             nxt = torch.full((B, 3), float("nan"), dtype=torch.float64, device=dev)
-            self._joints_center(out_xyz, cxyz, out_status, ustatus, nv, self._moved, nxt, codes[self.recenter])
+            next_from = out_xyz
+            if self.smooth is not None and self.smooth.lead:
+                # the next call's crop starts where constant velocity says the hand will be: filter first, centre the look-ahead joints
+                smoothed = self._smooth_step(out_xyz, out_status, ustatus, weights[0] if V > 1 else None, nv, dt)
+                next_from = smoothed[2]
+            self._joints_center(next_from, cxyz, out_status, ustatus, nv, self._moved, nxt, codes[self.recenter])
             self.centers_uvd, self.next_centers_uvd, self.recenter_codes = self._centers[:nb].clone(), nxt[:nb], codes[:, :nb]
             if self.track:
                 self._track[:nv].copy_(nxt[:nv])
         self._last = (out_status, ustatus, nv)
+        if self.smooth is not None:
+            fxyz_t, fuvd_t, ahead, fcodes = smoothed or self._smooth_step(out_xyz, out_status, ustatus, weights[0] if V > 1 else None, nv, dt)
+            self.raw_xyz, self.raw_uvd, self.ahead_xyz, self.filter_codes = out_xyz[:nb], out_uvd[:nb], ahead[:nb], fcodes[:nb]
+            if V > 1:
+                fxyz, fuvd = fxyz_t, fuvd_t
+            else:
+                xyz, uvd = fxyz_t, fuvd_t
         if self.confidence:
             # (with views: view 0's rows are the first B of every per-row buffer)
             fields = torch.empty((3, B, J), dtype=torch.float32, device=dev)

@@ -4,7 +4,8 @@ include/awr_hip.h "Synthetic hand frames").
 These are procedural hands.  They give every layer of the project one labelled input that needs no download; they say nothing about NYU.
 
   * `HandModel`, `sample_poses`, `forward_kinematics`, `labels`: the model and its kinematics, numpy float64 on the host.  All
-    trigonometry happens here, once; the renderer only sees a table of capsules.
+    trigonometry happens here, once; the renderer only sees a table of capsules.  `sample_sequences` eases between key poses drawn by
+    `sample_poses`: temporally coherent sequences for the tracker and the temporal joint filter.
   * `render`: the statement of the renderer, vectorised numpy over one frame.  `render_device` runs the same sequence of float64
     operations in one kernel launch per chunk of frames (awr_synth_render) and writes into an HBM-resident frame store.
   * `SyntheticFrames`: poses -> kinematics -> frames -> a dataset (`DeviceNYU` over a `FrameStore`, or with device=None the host `NYU`).
@@ -144,6 +145,32 @@ def sample_poses(n, seed, model=None, z_range=(500.0, 900.0), scale_range=(0.85,
     target = np.stack([(cu - u0) * z / fx, flip * (cv - v0) * z / fy, z], -1)
     poses["position"] = target - mid
     return poses
+
+
+def sample_sequences(n_seq, length, seed, key_every=15, model=None, rot_range=(50.0, 50.0, 60.0), **pose_options):
+    """n_seq temporally coherent sequences of `length` frames each: a pose dict with sample_poses' keys and n_seq * length rows,
+    SEQUENCE-MAJOR (frame t of sequence s is row s * length + t).  One sample_poses(n_seq * K, seed, ...) call draws K =
+    (length - 2) // key_every + 2 key poses per sequence (key k of sequence s is its row s * K + k; a key every key_every frames, and one
+    past the last frame); frame t lies between keys k = t // key_every and k + 1 at f = (t % key_every) / key_every, eased by the
+    smoothstep s = f f (3 - 2 f), and EVERY field is a + s (b - a): a frame on a key equals that key bit for bit.  The default rot_range
+    keeps the in-plane rotation of two neighbouring keys within a hand's reach (angles are interpolated as numbers, not on the circle).
+    forward_kinematics, labels, render and render_device take the result unchanged."""
+    n_seq, length, key_every = int(n_seq), int(length), int(key_every)
+    if n_seq < 1 or length < 1 or key_every < 1:
+        raise ValueError("sample_sequences needs n_seq, length and key_every >= 1, got %d, %d, %d" % (n_seq, length, key_every))
+    K = (length - 2) // key_every + 2
+    keys = sample_poses(n_seq * K, seed, model, rot_range=rot_range, **pose_options)
+    t = np.arange(length)
+    k = t // key_every
+    f = (t % key_every) / np.float64(key_every)
+    s = f * f * (3.0 - 2.0 * f)
+    out = {}
+    for name, v in keys.items():
+        v = v.reshape((n_seq, K) + v.shape[1:])
+        a, b = v[:, k], v[:, np.minimum(k + 1, K - 1)]          # (a last frame ON the last key has s = 0: the clamp only names a row)
+        w = s.reshape((1, length) + (1,) * (v.ndim - 2))
+        out[name] = np.ascontiguousarray((a + w * (b - a)).reshape((n_seq * length,) + v.shape[2:]))
+    return out
 
 
 def _global_rotation(poses):
@@ -405,10 +432,11 @@ class SyntheticFrames:
     the numpy statement into host memory (`.frames`) and `.dataset` is the host nyu_data.NYU: for small n on a machine without a GPU.
     `.labels_xyz` (n, jt_num, 3), `.centers` (n, 3), `.joints21` (n, 21, 3), `.prims`, `.bbox` are numpy arrays; `.status` (n,) int32 holds
     the renderer's code per frame (a device tensor with a device).  The dataset's test cube is the same for every frame: the NYU rule that
-    shrinks it for frames >= 2440 describes that dataset's second subject and does not apply here."""
+    shrinks it for frames >= 2440 describes that dataset's second subject and does not apply here.
+    poses: a pose dict of n rows (sample_poses' keys, e.g. sample_sequences' output) used INSTEAD of the class's own sample_poses call."""
 
     def __init__(self, n, seed, phase, jt_num=14, img_size=128, cube=(300, 300, 300), aug_para=None, frame_shape=(480, 640), paras=ND.PARAS,
-                 flip=-1, device="cuda", chunk=256, forearm=True, background_mm=0, noise_mm=0, center_jitter_mm=0.0, **pose_options):
+                 flip=-1, device="cuda", chunk=256, forearm=True, background_mm=0, noise_mm=0, center_jitter_mm=0.0, poses=None, **pose_options):
         self.n, self.seed, self.phase = int(n), int(seed), phase
         self.frame_shape, self.paras, self.flip = (int(frame_shape[0]), int(frame_shape[1])), tuple(float(p) for p in paras), int(flip)
         fh, fw = self.frame_shape
@@ -424,8 +452,14 @@ class SyntheticFrames:
             if need > free:           # before anything is drawn or allocated
                 raise L.AwrError("%d frames of %d x %d need %.1f GB of device memory and %.1f GB are free" % (self.n, fh, fw, need / 1e9, free / 1e9))
         self.model = HandModel(forearm=forearm)
-        self.poses = sample_poses(self.n, self.seed, self.model, cube=cube, frame_shape=self.frame_shape, paras=self.paras, flip=self.flip,
-                                  **pose_options)
+        if poses is None:
+            poses = sample_poses(self.n, self.seed, self.model, cube=cube, frame_shape=self.frame_shape, paras=self.paras, flip=self.flip,
+                                 **pose_options)
+        elif pose_options:
+            raise ValueError("poses= replaces the sample_poses call: its options %s have nothing to act on" % sorted(pose_options))
+        elif any(len(v) != self.n for v in poses.values()):
+            raise ValueError("poses holds %s rows, not n = %d" % (sorted({len(v) for v in poses.values()}), self.n))
+        self.poses = poses
         self.joints21, self.prims, self.bbox = forward_kinematics(self.poses, self.model, self.frame_shape, self.paras, self.flip)
         self.labels_xyz, self.centers = labels(self.joints21, jt_num, center_jitter_mm, self.seed)
         kw = dict(paras=self.paras, flip=self.flip, background_mm=background_mm, noise_mm=noise_mm, seed=self.seed)

@@ -1069,6 +1069,53 @@ int awr_synth_render(const double* prims, const int* bbox, int n, int K, int fh,
                      int background_mm, int noise_mm, unsigned int seed, int64_t frame0, uint16_t* out, int64_t row, int64_t capacity,
                      int* status, void* stream);
 
+/* ------------------------------------------------------------------------------------------
+ * Temporal joint filter (csrc/awr_track.hip; statement: awr_amd/track.py filter_step, results are bit-identical to it)
+ *
+ * awr_joints_filter runs one step of a One-Euro low-pass per (batch slot, joint, axis) over camera-space joints, with a measurement gate,
+ * an optional confidence weight, coasting over frames without a usable measurement and a constant-velocity look-ahead.
+ *   state (B, J, 6) doubles `x0 x1 x2 d0 d1 d2`: the filtered position in camera mm and the filtered velocity in mm/s; count (B, J, 2)
+ *     int32 `age coast`; age == 0: no track.  Both zeroed make an empty filter; both are updated in place and stay on the device.
+ *   xyz (B, J, 3) float32 camera mm as awr_joints_unproject / awr_views_fuse write it; status, ustatus (B) the frame's codes;
+ *   conf (B, J) float32, read only with weight = 1 (may be NULL otherwise).
+ * Constants of a call, computed by the entry point on the host in double, in this order:
+ *   w = (2.0 * M_PI) * dt;  alpha_d = 1.0 / (1.0 + 1.0 / (w * d_cutoff));  gate2 = gate_mm * gate_mm, +infinity for gate_mm < 0 (no gate)
+ * Per b < n_valid and j, z[a] = (double)xyz[b][j][a], everything in IEEE double without contraction, in the order written:
+ *   ok = status[b] == 0 && ustatus[b] == 0 && z[0], z[1], z[2] are finite
+ *   age == 0:  ok -> x = z, d = 0, age = 1, coast = 0: AWR_FILTER_INIT;  otherwise AWR_FILTER_NONE: NaN outputs, state untouched
+ *   age != 0 and ok:  y[a] = z[a] - x[a];  g2 = (y0 * y0 + y1 * y1) + y2 * y2;  the measurement is accepted iff g2 <= gate2
+ *   accepted:  wgt = 1.0; with weight = 1 and c = (double)conf[b][j]:  wgt = conf_floor; if (c > conf_floor) wgt = c; if (c > 1.0) wgt = 1.0
+ *     (a NaN gives the floor); then per axis
+ *       dx = y[a] / dt;  d[a] = d[a] + alpha_d * (dx - d[a]);  cut = min_cutoff + beta * fabs(d[a]);  al = 1.0 / (1.0 + 1.0 / (w * cut));
+ *       x[a] = x[a] + (al * wgt) * y[a]
+ *     age += 1 (saturating at INT_MAX), coast = 0: AWR_FILTER_UPDATED
+ *   not accepted (gated, or not ok):  coast += 1;
+ *     coast > max_coast and ok      -> the state is set as by INIT: AWR_FILTER_REINIT
+ *     coast > max_coast and not ok  -> age = coast = 0, the six state words are zeroed, NaN outputs: AWR_FILTER_LOST
+ *     otherwise x and d stay and the outputs are the held ones: AWR_FILTER_GATED if ok, else AWR_FILTER_HELD
+ *   outputs where age != 0 after the step:  xyz_out[a] = (float)x[a];  ahead_out[a] = (float)(x[a] + d[a] * dt);
+ *     uvd_out = (float) of (x0 * fx / x2 + u0, (x1 * flip) * fy / x2 + v0, x2), awr_joints_center's step 6
+ *   xyz_out, uvd_out, ahead_out (B, J, 3) float32; code (B, J) int32.  Rows >= n_valid are neither read nor written.
+ * The device evaluates + - * /, fabs, comparisons and the float conversions only: no square root, no transcendental.  One thread per
+ * (b, j), 256 per workgroup, one launch on `stream`; each thread owns its state words: no atomics, no LDS, nothing synchronises.
+ * A NULL pointer (conf with weight = 0 excepted), J outside [1, AWR_FILTER_MAX_JOINTS], B outside [1, AWR_FILTER_MAX_BATCH], n_valid
+ * outside [0, B], dt not finite or <= 0, min_cutoff <= 0, beta < 0, d_cutoff <= 0, gate_mm zero or NaN, max_coast < 0, conf_floor
+ * outside (0, 1], weight not 0 / 1, flip not +-1 or a zero focal length return AWR_ERR_ARG with a message, before any launch;
+ * n_valid = 0 returns AWR_OK without one.  A NaN or Inf anywhere in xyz or conf is a code, never a fault. */
+#define AWR_FILTER_NONE 0
+#define AWR_FILTER_INIT 1
+#define AWR_FILTER_UPDATED 2
+#define AWR_FILTER_GATED 3
+#define AWR_FILTER_HELD 4
+#define AWR_FILTER_REINIT 5
+#define AWR_FILTER_LOST 6
+#define AWR_FILTER_MAX_JOINTS 256
+#define AWR_FILTER_MAX_BATCH (1 << 20)
+int awr_joints_filter(double* state, int* count, const float* xyz, const int* status, const int* ustatus, const float* conf, int B, int J,
+                      int n_valid, double dt, double min_cutoff, double beta, double d_cutoff, double gate_mm, int max_coast, int weight,
+                      double conf_floor, double fx, double fy, double u0, double v0, int flip, float* xyz_out, float* uvd_out,
+                      float* ahead_out, int* code, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

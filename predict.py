@@ -16,6 +16,11 @@ conf | median; pred_uvd.txt / pred_xyz.txt then hold the fused 
 (J columns each) are written too.
 --palm sends the detector's centres through awr_detect_palm first: the centre of the palm disc of the silhouette's exact distance transform,
 which a forearm at the hand's depth does not drag up the arm (measured on procedural hands only).
+--smooth [MIN_CUTOFF,BETA,D_CUTOFF] puts the temporal joint filter behind the joints (a One-Euro low-pass per joint with coasting over lost
+frames; defaults 1.0,0.02,1.0 in Hz, 1/mm, Hz): like --track it treats the file as ONE sequence (batch size 1) at --fps F
+(default 30); --gate-mm G ignores a measurement further than G mm from the filtered joint; --lead (with --track) starts the next frame's crop
+at the constant-velocity look-ahead of the joints.  pred_uvd.txt / pred_xyz.txt then hold the FILTERED joints, and pred_raw_uvd.txt,
+pred_raw_xyz.txt (the network's own) and pred_filter_code.txt (J columns, awr_amd.track.FILTER_NAMES) are written too.
 --ema predicts with the checkpoint's averaged weights ("model_ema", written by a run with config.ema_decay) instead of "model".
 `--set` overrides config entries as train.py does (img_size, kernel_size, cube, batch_size, jt_num, downsample, winograd ...)."""
 import argparse
@@ -38,12 +43,42 @@ def parse_args(argv=None):
     ap.add_argument("--views", default=None, metavar="SPEC", help="test-time views, e.g. \"rot=-15,15;scale=0.9,1.1;shift=0:0:10\" (the identity view comes first by itself)")
     ap.add_argument("--fuse", default="mean", choices=("mean", "conf", "median"), help="how the views' joints are fused (with --views)")
     ap.add_argument("--palm", action="store_true", help="move each detector centre to the palm disc of the silhouette's distance transform")
+    ap.add_argument("--smooth", nargs="?", const="", default=None, metavar="MIN_CUTOFF,BETA,D_CUTOFF",
+                    help="filter the joints over time (the file is one sequence); optionally the One-Euro constants in Hz, 1/mm, Hz")
+    ap.add_argument("--fps", type=float, default=None, metavar="F", help="frame rate of the sequence (with --smooth; default 30)")
+    ap.add_argument("--gate-mm", type=float, default=None, metavar="G", help="with --smooth: ignore a measurement further than G mm from the filtered joint")
+    ap.add_argument("--lead", action="store_true", help="with --smooth and --track: crop the next frame at the look-ahead joints")
     ap.add_argument("--ema", action="store_true", help="load the checkpoint's \"model_ema\" (the EMA of the weights) instead of \"model\"")
     return ap.parse_args(argv)
 
 
+def smooth_config(args):
+    """--smooth / --fps / --gate-mm / --lead -> the dict Predictor(smooth=...) takes, or None"""
+    if args.smooth is None:
+        if args.fps is not None or args.gate_mm is not None or args.lead:
+            raise SystemExit("--fps, --gate-mm and --lead belong to --smooth")
+        return None
+    cfg = {}
+    if args.smooth:
+        try:
+            vals = [float(v) for v in args.smooth.split(",")]
+        except ValueError:
+            vals = []
+        if len(vals) != 3:
+            raise SystemExit("--smooth takes MIN_CUTOFF,BETA,D_CUTOFF (three numbers), not %r" % args.smooth)
+        cfg.update(min_cutoff=vals[0], beta=vals[1], d_cutoff=vals[2])
+    if args.fps is not None:
+        cfg["fps"] = args.fps
+    if args.gate_mm is not None:
+        cfg["gate_mm"] = args.gate_mm
+    if args.lead:
+        cfg["lead"] = True
+    return cfg
+
+
 def main(argv=None):
     args = parse_args(argv)
+    smooth = smooth_config(args)
 
     import numpy as np
     import torch
@@ -66,15 +101,17 @@ def main(argv=None):
     if key not in pth:
         raise awr_amd._lib.AwrError("{} holds no \"{}\" entry{}".format(cfg.load_model, key, " (--ema needs a checkpoint written with ema_decay)" if args.ema else ""))
     net.load_state_dict(pth[key])
-    bs = 1 if args.track else min(cfg.batch_size, len(frames))
+    bs = 1 if args.track or smooth is not None else min(cfg.batch_size, len(frames))
     views = None if args.views is None else detect.parse_views(args.views)
     pred = awr_amd.Predictor(net.cuda(), cfg.img_size, cfg.kernel_size, cube=cfg.cube, max_batch=bs, frame_shape=frames.shape[1:],
                              winograd=cfg.winograd, parity=cfg.parity_infer, confidence=args.confidence,
-                             recenter=args.recenter, track=args.track, views=views, fuse=args.fuse, palm=args.palm)
+                             recenter=args.recenter, track=args.track, views=views, fuse=args.fuse, palm=args.palm,
+                             smooth=smooth)
     stateful = bool(args.recenter or args.track)
     centers, codes = [], []
     uvd, xyz, extra = [], [], {"conf": [], "peak": [], "spread_mm": []}
     fused = {"view_spread_mm": [], "views_used": []}
+    raw = {"raw_uvd": [], "raw_xyz": [], "filter_code": []}
     for lo in range(0, len(frames), bs):
         out = pred.predict(np.array(frames[lo:lo + bs]))
         uvd.append(out.uvd.cpu().numpy())
@@ -85,6 +122,9 @@ def main(argv=None):
         if views is not None:
             for k in fused:
                 fused[k].append(getattr(out, k).cpu().numpy())
+        if smooth is not None:
+            for k, t in (("raw_uvd", pred.raw_uvd), ("raw_xyz", pred.raw_xyz), ("filter_code", pred.filter_codes)):
+                raw[k].append(t.cpu().numpy())
         if stateful:
             centers.append(pred.centers_uvd.cpu().numpy())
             codes.append(pred.recenter_codes.cpu().numpy().T)
@@ -101,6 +141,10 @@ def main(argv=None):
     if views is not None:
         np.savetxt(os.path.join(args.out, "pred_view_spread_mm.txt"), np.concatenate(fused["view_spread_mm"], 0), fmt="%.6g")
         np.savetxt(os.path.join(args.out, "pred_views_used.txt"), np.concatenate(fused["views_used"], 0), fmt="%d")
+    if smooth is not None:
+        for k in ("raw_uvd", "raw_xyz"):
+            np.savetxt(os.path.join(args.out, "pred_%s.txt" % k), np.concatenate(raw[k], 0).reshape(len(frames), cfg.jt_num * 3), fmt="%.3f")
+        np.savetxt(os.path.join(args.out, "pred_filter_code.txt"), np.concatenate(raw["filter_code"], 0), fmt="%d")
     if stateful:
         np.savetxt(os.path.join(args.out, "pred_center_uvd.txt"), np.concatenate(centers, 0), fmt="%.6f")
         np.savetxt(os.path.join(args.out, "pred_recenter_code.txt"), np.concatenate(codes, 0), fmt="%d")
