@@ -254,6 +254,9 @@ _SIGS = {
     # palm centre from an exact distance transform (csrc/awr_palm.hip)
     "awr_detect_palm_scratch": ([_I, _I, _I], C.c_int64),
     "awr_detect_palm": ([_P, _I, _L, _I, _I, _P, _I, _P, _P, _D, _D, _P, _I, _D, _D, _D, _I, _I, _I, _I, _P, _P, _P, _P, _P], C.c_int),
+    # several hands per frame from connected components (csrc/awr_hands.hip)
+    "awr_detect_hands_scratch": ([_I, _I, _I], C.c_int64),
+    "awr_detect_hands": ([_P, _I, _L, _I, _I, _P, _I, _I, _D, _D, _D, _D, _I, _P, _P, _P, _P, _P, _P, _P], C.c_int),
     # test-time views (csrc/awr_detect.hip)
     "awr_view_centers": ([_P, _P, _P, _I, _P, _I, _I, _I, _D, _D, _D, _D, _I, _P, _P, _P, _P, _P], C.c_int),
     "awr_view_rotate": ([_P, _P, _P, _P, _I, _I, _I, _P], C.c_int),

@@ -34,6 +34,7 @@ SOURCES = {
     "awr_eval.hip": ["-ffp-contract=off"],    # joint scoring: the host evaluator's numpy arithmetic
     "awr_detect.hip": ["-ffp-contract=off"],  # hand detection: center2bounds / set_crop in numpy's double arithmetic
     "awr_palm.hip": ["-ffp-contract=off"],    # palm centre: integer distance transform; center2bounds' double arithmetic for the window
+    "awr_hands.hip": ["-ffp-contract=off"],   # several hands: integer connected components; the depth limits are single double additions
     "awr_synth.hip": ["-ffp-contract=off"],   # synthetic hand frames: the ray / capsule arithmetic of synth.render, operation by operation
     "awr_track.hip": ["-ffp-contract=off"],   # temporal joint filter: track.filter_step's double arithmetic, operation by operation
 }

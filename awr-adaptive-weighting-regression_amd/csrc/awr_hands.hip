@@ -1,0 +1,463 @@
+// Several hands per frame: the near foreground of a depth frame split into its 4-connected components, the K nearest
+// large ones seeded with a centre of mass each -- a restatement of awr_amd/detect.py components and hand_seeds, bit for bit.
+//
+// Everything up to the last three divisions per slot is INTEGER arithmetic.  A component's label is the smallest raster index v * fw + u
+// of its pixels, which is canonical: any correct labelling, in any order, gives these integers.  The labelling is a union-find forest
+// over the pixels of the frame, one int32 pointer per pixel, joined by smaller index: to join a and b, find both roots, order them
+// a > b, old = atomicMin(&L[a], b); old == a means a was still a root and now hangs under b, otherwise go on from old.  Every pointer
+// only ever DECREASES, so every find and every retry ends, and the root that survives is the component's minimum whatever the order in
+// which the joins arrive.  Counts and minimum depths per component, the candidates' count and the slab sums are integer atomics and
+// integer reductions; the K nearest are K minima of (zc << 32 | root), unique words.  There is no floating-point atomic and no
+// floating-point reduction in this file, no kernel waits for another workgroup, and only the stream orders the stages.
+//
+// Shape, as awr_palm.hip's: a frame is split over several workgroups, a stage is a launch, and the stages meet in the frame's slots
+// (64-bit words at the head of the caller's scratch) and in three int32 words per pixel behind them -- L the forest, CNT and ZC the
+// pixels and the smallest raw depth of the component whose root the word belongs to.
+//   1. hands_init_kernel: the slots.  hands_dmin_kernel: dmin of the foreground, a block minimum and one atomicMin per workgroup;
+//   2. hands_tile_kernel: a 64 x 16 tile per workgroup: the mask (foreground with d <= min(dmin + reach, zmax)), a union-find over the
+//      tile in LDS (left and upper neighbour), L = the global raster index of the local root, CNT = 0, ZC = INT_MAX;
+//   3. hands_border_kernel: joins across the tiles' upper and left borders in global memory;
+//   4. hands_flatten_kernel: L = find(L) (and labels_out); CNT and ZC of the root by atomicAdd / atomicMin, the lanes of a wave that
+//      share a root summed first;
+//   5. hands_roots_kernel: every workgroup's K smallest keys among its roots with CNT >= min_pixels (a sorted list per thread, then K
+//      block minima) and the candidates' count; hands_pick_kernel: one workgroup per frame merges them -- at most 64 x 4 words, no pass
+//      over the frame (ONE workgroup per frame over the whole frame is what awr_palm.hip's header measured at 12 GB/s);
+//   6. hands_sums_kernel: n, su, sv, sd of the chosen components' pixels with d <= min(zc + slab, zmax), a block sum and one 64-bit
+//      atomicAdd per workgroup, slot and word;
+//   7. hands_finalize_kernel: a thread per frame and slot writes centre, status, info and count, hand-major (row k * B + b).
+// The depth tests are the statement's float64 comparisons: for an integer d, d <= x  <=>  d <= floor(x) (compiled with
+// -ffp-contract=off; the sums base + span are single double additions).
+#include <limits.h>
+#include <math.h>
+
+#include "awr_common.h"
+
+namespace awr {
+namespace {
+
+constexpr int HANDS_THREADS = 256;
+constexpr int HANDS_WAVES = HANDS_THREADS / 64;
+constexpr int HANDS_TILE_W = 64, HANDS_TILE_H = 16;   // a wave per tile row, four rows per thread
+constexpr int HANDS_MAX_K = 4;
+constexpr int HANDS_MAX_PARTS = 64;                   // workgroups per frame of the streaming stages
+constexpr int HANDS_MAX_SIDE = 16384;                 // pixel indices stay inside int32, sums of columns below 2^42
+
+typedef unsigned long long u64;
+typedef long long i64;
+
+// a frame's slots: 64-bit words
+enum { HS_DMIN = 0, HS_COUNT = 1, HS_KEY = 2, HS_SUM = HS_KEY + HANDS_MAX_K, HS_PART = HS_SUM + 4 * HANDS_MAX_K };
+constexpr int HANDS_SLOTS = HS_PART + HANDS_MAX_PARTS * HANDS_MAX_K;
+constexpr u64 HANDS_NONE = ~0ull;
+
+struct HandsArgs {
+    const uint16_t* frames; int64_t n_frames; int fh, fw;
+    const int64_t* frame; int B, K;
+    int dlo, dhi;                 // zmin <= d <= zmax and d != 0  <=>  dlo <= d <= dhi
+    double zmax, reach, slab; int min_pixels;
+    u64* slots; int* L; int* CNT; int* ZC;
+    int* labels_out;
+};
+
+struct HandsFrame {
+    const uint16_t* F; u64* S; int* L; int* CNT; int* ZC;
+    bool bad;                     // the frame index is outside the store: nothing of it is read
+};
+
+__device__ __forceinline__ HandsFrame hands_frame(const HandsArgs& a, int b) {
+    HandsFrame hf;
+    const int64_t f = a.frame[b], np = (int64_t)a.fh * a.fw;
+    hf.bad = f < 0 || f >= a.n_frames;
+    hf.F = a.frames + (hf.bad ? 0 : f) * np;
+    hf.S = a.slots + (int64_t)b * HANDS_SLOTS;
+    hf.L = a.L + b * np; hf.CNT = a.CNT + b * np; hf.ZC = a.ZC + b * np;
+    return hf;
+}
+
+// the largest integer d in [-1, 65535] with (double)d <= min(base + span, zmax)
+__device__ __forceinline__ int hands_limit(int base, double span, double zmax) {
+    const double lim = fmin((double)base + span, zmax);
+    return (int)fmin(fmax(floor(lim), -1.0), 65535.0);
+}
+
+// pixels [p0, p1) of workgroup blockIdx.x of gridDim.x: whole rows
+__device__ __forceinline__ void hands_share(const HandsArgs& a, int& p0, int& p1) {
+    const int per = (a.fh + (int)gridDim.x - 1) / (int)gridDim.x;
+    const int r0 = min((int)blockIdx.x * per, a.fh), r1 = min(r0 + per, a.fh);
+    p0 = r0 * a.fw; p1 = r1 * a.fw;
+}
+
+__device__ __forceinline__ u64 block_min(u64 v, u64* red) {
+#pragma unroll
+    for (int o = 32; o > 0; o >>= 1) {
+        const u64 t = (u64)__shfl_xor((i64)v, o, 64);
+        v = t < v ? t : v;
+    }
+    if ((threadIdx.x & 63) == 0) red[threadIdx.x >> 6] = v;
+    __syncthreads();
+    u64 r = red[0];
+#pragma unroll
+    for (int i = 1; i < HANDS_WAVES; ++i) r = red[i] < r ? red[i] : r;
+    __syncthreads();
+    return r;
+}
+
+__device__ __forceinline__ u64 block_sum(u64 v, u64* red) {
+#pragma unroll
+    for (int o = 32; o > 0; o >>= 1) v += (u64)__shfl_xor((i64)v, o, 64);
+    if ((threadIdx.x & 63) == 0) red[threadIdx.x >> 6] = v;
+    __syncthreads();
+    u64 r = 0;
+#pragma unroll
+    for (int i = 0; i < HANDS_WAVES; ++i) r += red[i];
+    __syncthreads();
+    return r;
+}
+
+// ---- the forest -------------------------------------------------------------------------------------------------------------------
+// (other lanes and workgroups lower these words while they are read: every load is an atomic one, never a cached copy)
+__device__ __forceinline__ int uf_load(const int* p) { return __hip_atomic_load(p, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT); }
+
+// the root above x at the time of the walk; the path walked is then pointed at it (a root is never above its descendants' indices, so
+// atomicMin keeps every pointer decreasing and inside the component)
+__device__ __forceinline__ int uf_find(int* L, int x) {
+    int r = x, n;
+    while ((n = uf_load(L + r)) != r) r = n;
+    while (x > r) {
+        n = uf_load(L + x);
+        if (n > r) atomicMin(L + x, r);
+        x = n;
+    }
+    return r;
+}
+
+__device__ __forceinline__ void uf_union(int* L, int a, int b) {
+    a = uf_find(L, a); b = uf_find(L, b);
+    while (a != b) {
+        if (a < b) { const int t = a; a = b; b = t; }
+        const int old = atomicMin(L + a, b);
+        if (old == a) break;            // a was a root and hangs under b now
+        a = old;                        // a had a parent already: that parent and b are what remains to be joined
+    }
+}
+
+// the K smallest of the words offered to it, ascending; HANDS_NONE where there are fewer
+struct SmallestK {
+    u64 k[HANDS_MAX_K];
+    __device__ __forceinline__ void clear() {
+#pragma unroll
+        for (int i = 0; i < HANDS_MAX_K; ++i) k[i] = HANDS_NONE;
+    }
+    __device__ __forceinline__ void offer(u64 v) {
+#pragma unroll
+        for (int i = 0; i < HANDS_MAX_K; ++i)
+            if (v < k[i]) { const u64 t = k[i]; k[i] = v; v = t; }
+    }
+    __device__ __forceinline__ void pop() {
+#pragma unroll
+        for (int i = 0; i + 1 < HANDS_MAX_K; ++i) k[i] = k[i + 1];
+        k[HANDS_MAX_K - 1] = HANDS_NONE;
+    }
+};
+
+}  // namespace
+
+__global__ __launch_bounds__(HANDS_THREADS) void hands_init_kernel(u64* __restrict__ slots, int64_t n) {
+    const int64_t i = (int64_t)blockIdx.x * HANDS_THREADS + threadIdx.x;
+    if (i >= n) return;
+    const int w = (int)(i % HANDS_SLOTS);
+    slots[i] = (w == HS_DMIN || (w >= HS_KEY && w < HS_SUM) || w >= HS_PART) ? HANDS_NONE : 0ull;
+}
+
+// 1. dmin: the smallest foreground depth of the frame
+__global__ __launch_bounds__(HANDS_THREADS) void hands_dmin_kernel(HandsArgs a) {
+    __shared__ u64 red[HANDS_WAVES];
+    const HandsFrame hf = hands_frame(a, blockIdx.y);
+    if (hf.bad) return;
+    int p0, p1;
+    hands_share(a, p0, p1);
+    const unsigned dlo = (unsigned)a.dlo;
+    const int dhi = a.dhi;
+    u64 best = HANDS_NONE;
+    for (int p = p0 + (int)threadIdx.x; p < p1; p += HANDS_THREADS) {
+        const unsigned d = hf.F[p];
+        if (d >= dlo && (int)d <= dhi && (u64)d < best) best = d;
+    }
+    best = block_min(best, red);
+    if (threadIdx.x == 0 && best != HANDS_NONE) atomicMin(hf.S + HS_DMIN, best);
+}
+
+// 2. a tile: the mask, the tile's own forest in LDS, L = the global raster index of the local root (-1 on background); CNT and ZC of
+// every pixel start at "none"
+__global__ __launch_bounds__(HANDS_THREADS) void hands_tile_kernel(HandsArgs a) {
+    __shared__ int lab[HANDS_TILE_W * HANDS_TILE_H];
+    const HandsFrame hf = hands_frame(a, blockIdx.y);
+    const int fw = a.fw, fh = a.fh;
+    const int tiles_x = (fw + HANDS_TILE_W - 1) / HANDS_TILE_W;
+    const int tu = ((int)blockIdx.x % tiles_x) * HANDS_TILE_W, tv = ((int)blockIdx.x / tiles_x) * HANDS_TILE_H;
+    const int col = threadIdx.x & 63, row0 = threadIdx.x >> 6;
+    const int u = tu + col;
+    const u64 dmin = hf.S[HS_DMIN];
+    const int dlo = a.dlo;
+    const int dhi = (hf.bad || dmin == HANDS_NONE) ? -1 : min(a.dhi, hands_limit((int)dmin, a.reach, a.zmax));
+    bool m[4];
+#pragma unroll
+    for (int q = 0; q < 4; ++q) {
+        const int row = row0 + HANDS_WAVES * q, v = tv + row, i = row * HANDS_TILE_W + col;
+        const bool inside = u < fw && v < fh;
+        m[q] = false;
+        if (inside && dhi >= dlo) {
+            const int d = hf.F[v * fw + u];
+            m[q] = d >= dlo && d <= dhi;
+        }
+        lab[i] = m[q] ? i : -1;
+        if (inside) { hf.CNT[v * fw + u] = 0; hf.ZC[v * fw + u] = INT_MAX; }
+    }
+    __syncthreads();
+#pragma unroll
+    for (int q = 0; q < 4; ++q) {
+        const int row = row0 + HANDS_WAVES * q, i = row * HANDS_TILE_W + col;
+        if (!m[q]) continue;
+        if (col > 0 && uf_load(lab + i - 1) >= 0) uf_union(lab, i, i - 1);
+        if (row > 0 && uf_load(lab + i - HANDS_TILE_W) >= 0) uf_union(lab, i, i - HANDS_TILE_W);
+    }
+    __syncthreads();
+#pragma unroll
+    for (int q = 0; q < 4; ++q) {
+        const int row = row0 + HANDS_WAVES * q, v = tv + row, i = row * HANDS_TILE_W + col;
+        if (!(u < fw && v < fh)) continue;
+        int label = -1;
+        if (m[q]) {
+            int r = i, n;
+            while ((n = lab[r]) != r) r = n;            // (nothing writes lab any more)
+            label = (tv + r / HANDS_TILE_W) * fw + tu + r % HANDS_TILE_W;
+        }
+        hf.L[v * fw + u] = label;
+    }
+}
+
+// 3. joins across the tiles' borders: threads 0 ... 63 the tile's first row with the row above it, 64 ... 79 its first column with the
+// column left of it
+__global__ __launch_bounds__(128) void hands_border_kernel(HandsArgs a) {
+    const HandsFrame hf = hands_frame(a, blockIdx.y);
+    const int fw = a.fw, fh = a.fh;
+    const int tiles_x = (fw + HANDS_TILE_W - 1) / HANDS_TILE_W;
+    const int tu = ((int)blockIdx.x % tiles_x) * HANDS_TILE_W, tv = ((int)blockIdx.x / tiles_x) * HANDS_TILE_H;
+    const int t = threadIdx.x;
+    int p = -1, q = -1;
+    if (t < HANDS_TILE_W) {
+        if (tv > 0 && tu + t < fw) { p = tv * fw + tu + t; q = p - fw; }
+    } else if (t < HANDS_TILE_W + HANDS_TILE_H) {
+        const int v = tv + t - HANDS_TILE_W;
+        if (tu > 0 && v < fh) { p = v * fw + tu; q = p - 1; }
+    }
+    if (p >= 0 && uf_load(hf.L + p) >= 0 && uf_load(hf.L + q) >= 0) uf_union(hf.L, p, q);
+}
+
+// 4. L = find(L); pixels and smallest depth of every component at its root's words
+__global__ __launch_bounds__(HANDS_THREADS) void hands_flatten_kernel(HandsArgs a) {
+    const HandsFrame hf = hands_frame(a, blockIdx.y);
+    int p0, p1;
+    hands_share(a, p0, p1);
+    int* out = a.labels_out ? a.labels_out + (int64_t)blockIdx.y * a.fh * a.fw : nullptr;
+    const int lane = threadIdx.x & 63;
+    for (int base = p0; base < p1; base += HANDS_THREADS) {            // (uniform over the workgroup: the shuffles below see whole waves)
+        const int p = base + (int)threadIdx.x;
+        int r = -1, d = INT_MAX;
+        if (p < p1) {
+            if (uf_load(hf.L + p) >= 0) {
+                r = uf_find(hf.L, p);
+                __hip_atomic_store(hf.L + p, r, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+                d = hf.F[p];
+            }
+            if (out) out[p] = r;
+        }
+        u64 left = __ballot(r >= 0);
+        while (left) {
+            const int leader = __ffsll((i64)left) - 1;
+            const int lr = __shfl(r, leader, 64);
+            const bool mine = r == lr;
+            const u64 same = __ballot(mine);
+            int dm = mine ? d : INT_MAX;
+#pragma unroll
+            for (int o = 32; o > 0; o >>= 1) dm = min(dm, __shfl_xor(dm, o, 64));
+            if (lane == leader) {
+                atomicAdd(hf.CNT + lr, __popcll(same));
+                atomicMin(hf.ZC + lr, dm);
+            }
+            left &= ~same;
+        }
+    }
+}
+
+// 5a. per workgroup: its K smallest (zc << 32 | root) among the roots with CNT >= min_pixels, and how many such roots it holds
+__global__ __launch_bounds__(HANDS_THREADS) void hands_roots_kernel(HandsArgs a) {
+    __shared__ u64 red[HANDS_WAVES];
+    const HandsFrame hf = hands_frame(a, blockIdx.y);
+    int p0, p1;
+    hands_share(a, p0, p1);
+    SmallestK mine;
+    mine.clear();
+    u64 n = 0;
+    for (int p = p0 + (int)threadIdx.x; p < p1; p += HANDS_THREADS) {
+        if (hf.L[p] == p && hf.CNT[p] >= a.min_pixels) {
+            n += 1;
+            mine.offer(((u64)(unsigned)hf.ZC[p] << 32) | (u64)(unsigned)p);
+        }
+    }
+    n = block_sum(n, red);
+    if (n == 0) return;                                                  // (uniform; the workgroup's words stay "none")
+    if (threadIdx.x == 0) atomicAdd(hf.S + HS_COUNT, n);
+    for (int i = 0; i < a.K; ++i) {
+        const u64 best = block_min(mine.k[0], red);
+        if (best == HANDS_NONE) break;
+        if (mine.k[0] == best) mine.pop();                               // (the words are unique: one thread holds it)
+        if (threadIdx.x == 0) hf.S[HS_PART + (int)blockIdx.x * HANDS_MAX_K + i] = best;
+    }
+}
+
+// 5b. per frame: the K smallest of the workgroups' words, ascending
+__global__ __launch_bounds__(HANDS_THREADS) void hands_pick_kernel(HandsArgs a) {
+    __shared__ u64 red[HANDS_WAVES];
+    static_assert(HANDS_MAX_PARTS * HANDS_MAX_K == HANDS_THREADS, "a word per thread");
+    u64* S = a.slots + (int64_t)blockIdx.x * HANDS_SLOTS;
+    u64 mine = S[HS_PART + threadIdx.x];
+    for (int i = 0; i < a.K; ++i) {
+        const u64 best = block_min(mine, red);
+        if (best == HANDS_NONE) break;
+        if (mine == best) mine = HANDS_NONE;
+        if (threadIdx.x == 0) S[HS_KEY + i] = best;
+    }
+}
+
+// 6. the slab sums of the chosen components
+__global__ __launch_bounds__(HANDS_THREADS) void hands_sums_kernel(HandsArgs a) {
+    __shared__ u64 red[HANDS_WAVES];
+    const HandsFrame hf = hands_frame(a, blockIdx.y);
+    if (hf.S[HS_KEY] == HANDS_NONE) return;                             // no candidate at all
+    int p0, p1;
+    hands_share(a, p0, p1);
+    int root[HANDS_MAX_K], lim[HANDS_MAX_K];
+    u64 acc[HANDS_MAX_K][4];
+#pragma unroll
+    for (int k = 0; k < HANDS_MAX_K; ++k) {
+        const u64 key = k < a.K ? hf.S[HS_KEY + k] : HANDS_NONE;
+        root[k] = key == HANDS_NONE ? -2 : (int)(key & 0xFFFFFFFFull);
+        lim[k] = key == HANDS_NONE ? -1 : min(a.dhi, hands_limit((int)(key >> 32), a.slab, a.zmax));
+        acc[k][0] = acc[k][1] = acc[k][2] = acc[k][3] = 0;
+    }
+    const int fw = a.fw;
+    for (int p = p0 + (int)threadIdx.x; p < p1; p += HANDS_THREADS) {
+        const int l = hf.L[p];
+        if (l < 0) continue;
+        const int d = hf.F[p];
+#pragma unroll
+        for (int k = 0; k < HANDS_MAX_K; ++k)
+            if (l == root[k] && d <= lim[k]) {
+                acc[k][0] += 1; acc[k][1] += (u64)(p % fw); acc[k][2] += (u64)(p / fw); acc[k][3] += (u64)d;
+            }
+    }
+#pragma unroll
+    for (int k = 0; k < HANDS_MAX_K; ++k) {
+        if (root[k] < 0) continue;                                       // (uniform)
+        u64 s[4];
+#pragma unroll
+        for (int j = 0; j < 4; ++j) s[j] = block_sum(acc[k][j], red);
+        if (threadIdx.x == 0 && s[0]) {
+#pragma unroll
+            for (int j = 0; j < 4; ++j) atomicAdd(hf.S + HS_SUM + 4 * k + j, s[j]);
+        }
+    }
+}
+
+// 7. a thread per frame and slot: centre, status, info and count, hand-major
+__global__ void hands_finalize_kernel(HandsArgs a, double* __restrict__ centers, int* __restrict__ status, int* __restrict__ info,
+                                      int* __restrict__ count) {
+    const int b = blockIdx.x, k = threadIdx.x;
+    if (k >= a.K) return;
+    const HandsFrame hf = hands_frame(a, b);
+    const double nan = __builtin_nan("");
+    double c[3] = {nan, nan, nan};
+    int st = hf.bad ? AWR_DET_BAD_FRAME : AWR_DET_EMPTY, in[4] = {-1, -1, 0, 0};
+    const u64 key = hf.bad ? HANDS_NONE : hf.S[HS_KEY + k];
+    if (key != HANDS_NONE) {
+        const int root = (int)(key & 0xFFFFFFFFull);
+        const u64* s = hf.S + HS_SUM + 4 * k;
+        const double dn = (double)s[0];                                  // (the component's nearest pixel is in its slab: n >= 1)
+        c[0] = (double)s[1] / dn; c[1] = (double)s[2] / dn; c[2] = (double)s[3] / dn;
+        st = AWR_DET_OK;
+        in[0] = root % a.fw; in[1] = root / a.fw; in[2] = hf.CNT[root]; in[3] = (int)(key >> 32);
+    }
+    const int64_t r = (int64_t)k * a.B + b;
+    centers[3 * r] = c[0]; centers[3 * r + 1] = c[1]; centers[3 * r + 2] = c[2];
+    status[r] = st;
+    info[4 * r] = in[0]; info[4 * r + 1] = in[1]; info[4 * r + 2] = in[2]; info[4 * r + 3] = in[3];
+    if (k == 0) count[b] = hf.bad ? 0 : (int)hf.S[HS_COUNT];
+}
+
+static int hands_parts(int B, int fh) {
+    // about four workgroups per CU over the batch, at most 64 per frame and never more than one per row of the frame
+    int p = (1024 + B - 1) / B;
+    p = p < fh ? p : fh;
+    return p < 1 ? 1 : (p > HANDS_MAX_PARTS ? HANDS_MAX_PARTS : p);
+}
+
+}  // namespace awr
+
+using namespace awr;
+
+extern "C" {
+
+int64_t awr_detect_hands_scratch(int B, int fh, int fw) {
+    if (B <= 0 || B > AWR_DET_MAX_BATCH || fh <= 0 || fw <= 0 || fh > HANDS_MAX_SIDE || fw > HANDS_MAX_SIDE) {
+        set_error("awr_detect_hands_scratch: B = %d is outside [1, %d] or the frame of %d x %d is outside [1, %d]^2", B, AWR_DET_MAX_BATCH, fh,
+                  fw, HANDS_MAX_SIDE);
+        return -1;
+    }
+    const int64_t words = 3 * (int64_t)B * fh * fw;                       // (a whole number of 64-bit words: callers allocate those)
+    return (int64_t)B * HANDS_SLOTS * (int64_t)sizeof(u64) + (words + (words & 1)) * (int64_t)sizeof(int);
+}
+
+int awr_detect_hands(const void* frames, int frame_type, int64_t n_frames, int fh, int fw, const int64_t* frame, int B, int K, double zmin,
+                     double zmax, double reach, double slab, int min_pixels, void* scratch, int* labels_out, double* centers, int* status,
+                     int* info, int* count, void* stream) {
+    AWR_REQUIRE(frame_type == AWR_NYU_U16, "awr_detect_hands: the frame store must be uint16 millimetres (AWR_NYU_U16), as for awr_detect "
+                "(got frame_type %d)", frame_type);
+    AWR_REQUIRE(K >= 1 && K <= AWR_DET_MAX_HANDS, "awr_detect_hands: K = %d hands is outside [1, %d]", K, AWR_DET_MAX_HANDS);
+    AWR_REQUIRE(B > 0 && B <= AWR_DET_MAX_BATCH, "awr_detect_hands: B = %d is outside [1, %d]", B, AWR_DET_MAX_BATCH);
+    AWR_REQUIRE(n_frames > 0, "awr_detect_hands: n_frames = %lld must be positive", (long long)n_frames);
+    AWR_REQUIRE(fh > 0 && fw > 0 && fh <= HANDS_MAX_SIDE && fw <= HANDS_MAX_SIDE, "awr_detect_hands: frame of %d x %d is outside [1, %d]^2", fh,
+                fw, HANDS_MAX_SIDE);
+    AWR_REQUIRE(min_pixels >= 1, "awr_detect_hands: min_pixels = %d must be at least 1", min_pixels);
+    AWR_REQUIRE(zmin <= zmax, "awr_detect_hands: depth range needs zmin <= zmax (got %g, %g)", zmin, zmax);
+    AWR_REQUIRE(reach >= 0.0, "awr_detect_hands: reach = %g must be >= 0", reach);
+    AWR_REQUIRE(slab >= 0.0, "awr_detect_hands: slab = %g must be >= 0", slab);
+    AWR_REQUIRE(frames && frame && scratch && centers && status && info && count, "awr_detect_hands: NULL pointer");
+    AWR_REQUIRE(((uintptr_t)frames & 1) == 0 && ((uintptr_t)scratch & 7) == 0, "awr_detect_hands: misaligned frame store / scratch");
+    static_assert(AWR_DET_MAX_HANDS == HANDS_MAX_K, "the slots hold AWR_DET_MAX_HANDS hands");
+    hipStream_t s = as_stream(stream);
+    const int64_t np = (int64_t)B * fh * fw;
+    HandsArgs a;
+    a.frames = (const uint16_t*)frames; a.n_frames = n_frames; a.fh = fh; a.fw = fw; a.frame = frame; a.B = B; a.K = K;
+    a.dlo = (int)fmin(fmax(ceil(zmin), 1.0), 65536.0);
+    a.dhi = (int)fmin(fmax(floor(zmax), -1.0), 65535.0);
+    a.zmax = zmax; a.reach = reach; a.slab = slab; a.min_pixels = min_pixels;
+    a.slots = (u64*)scratch;
+    a.L = (int*)(a.slots + (int64_t)B * HANDS_SLOTS); a.CNT = a.L + np; a.ZC = a.CNT + np;
+    a.labels_out = labels_out;
+    const int64_t nw = (int64_t)B * HANDS_SLOTS;
+    const int tiles = ((fw + HANDS_TILE_W - 1) / HANDS_TILE_W) * ((fh + HANDS_TILE_H - 1) / HANDS_TILE_H);
+    const dim3 share(hands_parts(B, fh), B), tile(tiles, B);
+    hands_init_kernel<<<(unsigned)((nw + HANDS_THREADS - 1) / HANDS_THREADS), HANDS_THREADS, 0, s>>>(a.slots, nw);
+    hands_dmin_kernel<<<share, HANDS_THREADS, 0, s>>>(a);
+    hands_tile_kernel<<<tile, HANDS_THREADS, 0, s>>>(a);
+    hands_border_kernel<<<tile, 128, 0, s>>>(a);
+    hands_flatten_kernel<<<share, HANDS_THREADS, 0, s>>>(a);
+    hands_roots_kernel<<<share, HANDS_THREADS, 0, s>>>(a);
+    hands_pick_kernel<<<B, HANDS_THREADS, 0, s>>>(a);
+    hands_sums_kernel<<<share, HANDS_THREADS, 0, s>>>(a);
+    hands_finalize_kernel<<<B, HANDS_MAX_K, 0, s>>>(a, centers, status, info, count);
+    return check_launch("awr_detect_hands");
+}
+
+}  // extern "C"

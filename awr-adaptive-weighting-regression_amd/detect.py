@@ -10,6 +10,8 @@ Two things live here:
     awr_centers_select (a tracked centre where it is usable, the detector's otherwise); DESIGN.md 4.19.
   * `palm_center` and `distance_transform`: the statement of awr_detect_palm (csrc/awr_palm.hip) -- a detector centre ->
     the centre of the palm disc of an exact integer distance transform, which a forearm does not drag up the arm; `palm_device` wraps it.
+  * `components` and `hand_seeds`: the statements of awr_detect_hands (csrc/awr_hands.hip) -- the near foreground split
+    into 4-connected components with canonical labels, the K nearest large ones seeded per component; `hands_device` wraps it.
   * `make_views`, `check_views`, `view_table`, `view_centers`, `view_rotate` and `fuse_views`: test-time views -- the host
     table of the views' rotations and the statements of awr_view_centers, awr_view_rotate and awr_views_fuse.
 
@@ -324,6 +326,108 @@ def palm_center(frame, center, status=OK, cube=(300, 300, 300), paras=ND.PARAS, 
     return (float(su) / float(n), float(sv) / float(n), float(sd) / float(n)), OK, (pu + u0, pv + v0, r2, n)
 
 
+# ---- several hands per frame from connected components (include/awr_hip.h awr_detect_hands) ---------------------------
+# Engineering defaults, not measured on real frames (none are available where this was written): at most four hands, a mask as deep as an
+# arm's reach behind the nearest pixel, and a component of fewer than 400 pixels (a 20 x 20 patch; a hand at 1.5 m covers some 2000) is
+# debris, not a hand.
+MAX_HANDS, REACH, MIN_PIXELS = 4, 300.0, 400
+
+
+def _check_hands(hands, reach, slab, min_pixels):
+    if isinstance(hands, bool) or not isinstance(hands, (int, np.integer)):
+        raise TypeError("hands is an int in [1, %d], not %r" % (MAX_HANDS, hands))
+    if not 1 <= int(hands) <= MAX_HANDS:
+        raise ValueError("hands = %d is outside [1, %d]" % (hands, MAX_HANDS))
+    if isinstance(min_pixels, bool) or not isinstance(min_pixels, (int, np.integer)):
+        raise TypeError("min_pixels is an int >= 1, not %r" % (min_pixels,))
+    if int(min_pixels) < 1:
+        raise ValueError("min_pixels = %d must be at least 1" % min_pixels)
+    for x, what in ((reach, "reach"), (slab, "slab")):
+        if isinstance(x, (bool, str, bytes)) or not isinstance(x, (int, float, np.integer, np.floating)):
+            raise TypeError("%s is a number of millimetres >= 0, not %r" % (what, x))
+        if not float(x) >= 0.0:
+            raise ValueError("%s = %r must be >= 0" % (what, x))
+    return int(hands), float(reach), float(slab), int(min_pixels)
+
+
+def components(frame, depth_range=DEPTH_RANGE, reach=REACH):
+    """-> labels (fh, fw) int32.  Foreground: zmin <= d <= zmax and d != 0; dmin its smallest depth; the mask is the foreground with
+    d <= min(dmin + reach, zmax) (float64 comparisons, as in `detect`).  Two mask pixels are connected when they are 4-neighbours -- no
+    depth test.  A pixel's label is the smallest raster index v * fw + u of its component, -1 on background: canonical, so any correct
+    algorithm gives these integers.  Here: the rows' runs, joined where the runs of two neighbouring rows share a column."""
+    frame = _u16(frame)
+    fh, fw = frame.shape
+    zmin, zmax = float(depth_range[0]), float(depth_range[1])
+    if not zmin <= zmax:
+        raise ValueError("depth_range needs zmin <= zmax")
+    if not float(reach) >= 0.0:
+        raise ValueError("reach = %r must be >= 0" % (reach,))
+    labels = np.full((fh, fw), -1, np.int32)
+    fg = (frame >= zmin) & (frame <= zmax) & (frame != 0)
+    if not fg.any():
+        return labels
+    dmin = float(frame[fg].min())
+    mask = fg & (frame <= min(dmin + float(reach), zmax))
+    # a run starts where a mask pixel has no mask pixel to its left; runs are numbered in raster order, so a smaller number is a smaller
+    # first index, and the smallest run of a component starts at the component's smallest index
+    start = mask.copy()
+    start[:, 1:] &= ~mask[:, :-1]
+    run = np.cumsum(start.ravel()).reshape(fh, fw) - 1          # on a mask pixel: the number of its own run
+    first = np.flatnonzero(start.ravel())
+    parent = np.arange(first.size)
+    both = mask[:-1] & mask[1:]
+    pairs = np.unique(run[:-1][both].astype(np.int64) * first.size + run[1:][both])
+    p = parent.tolist()
+    for a, b in zip((pairs // first.size).tolist(), (pairs % first.size).tolist()):
+        while p[a] != a:
+            p[a] = p[p[a]]
+            a = p[a]
+        while p[b] != b:
+            p[b] = p[p[b]]
+            b = p[b]
+        if a < b:
+            p[b] = a
+        elif b < a:
+            p[a] = b
+    parent = np.asarray(p, np.int64)
+    while True:
+        up = parent[parent]
+        if np.array_equal(up, parent):
+            break
+        parent = up
+    labels[mask] = first[parent[run[mask]]]
+    return labels
+
+
+def hand_seeds(frame, hands, depth_range=DEPTH_RANGE, reach=REACH, slab=SLAB, min_pixels=MIN_PIXELS):
+    """The statement of awr_detect_hands for one frame: -> (centers (K, 3) float64, status (K,) int32, info (K, 4) int32, count).
+    Candidates: the components of `components` with n >= min_pixels pixels; a candidate's key is (zc, root), zc its smallest raw depth
+    and root its label; the K = hands smallest keys fill the slots in ascending order (slot 0: the nearest hand; a tie in depth goes to
+    the smaller root).  A slot's seed is the centre of mass of its component's pixels with d <= min(zc + slab, zmax) -- the "nearest"
+    rule per component, int64 sums and three double divisions as center_of_mass does; status OK; info = (root % fw, root // fw, n, zc).
+    Slots past the candidates: NaN, EMPTY, (-1, -1, 0, 0).  count: the number of candidates, which may exceed K.  A seed is then refined
+    by detect(seed="given", center=...), unchanged."""
+    K, reach, slab, min_pixels = _check_hands(hands, reach, slab, min_pixels)
+    frame = _u16(frame)
+    fw = frame.shape[1]
+    zmax = float(depth_range[1])
+    labels = components(frame, depth_range, reach)
+    centers, status, info = np.full((K, 3), np.nan), np.full(K, EMPTY, np.int32), np.tile(np.array(_NO_INFO, np.int32), (K, 1))
+    on = labels >= 0
+    if not on.any():
+        return centers, status, info, 0
+    roots, inv, n = np.unique(labels[on], return_inverse=True, return_counts=True)
+    zc = np.full(roots.size, 65536, np.int64)
+    np.minimum.at(zc, inv.ravel(), frame[on].astype(np.int64))
+    cand = np.flatnonzero(n >= min_pixels)
+    cand = cand[np.lexsort((roots[cand], zc[cand]))]
+    for k, i in enumerate(cand[:K].tolist()):
+        root = int(roots[i])
+        c, _ = center_of_mass(np.where(labels == root, frame, np.uint16(0)), None, -np.inf, min(float(zc[i]) + slab, zmax))
+        centers[k], status[k], info[k] = c, OK, (root % fw, root // fw, int(n[i]), int(zc[i]))
+    return centers, status, info, int(cand.size)
+
+
 # ---- test-time views: the same hand under rotations, cube scales and centre shifts (DESIGN.md 4.22) ----------------------------------
 def _number(x, what):
     if isinstance(x, (bool, str, bytes)) or not isinstance(x, (int, float, np.integer, np.floating)):
@@ -569,6 +673,35 @@ def palm_device(store, frame_idx, centers, status, cube=(300, 300, 300), paras=N
            L.ptr(status), float(depth_range[0]), float(depth_range[1]), cb.data_ptr(), 3 if cb.dim() == 2 else 0, float(paras[0]),
            float(paras[1]), search, tau0, tau1, rho0, rho1, scratch.data_ptr(), L.ptr(center_out), L.ptr(status_out), L.ptr(info), L.stream())
     return center_out, status_out, info
+
+
+def hands_device(store, frame_idx, hands, depth_range=DEPTH_RANGE, reach=REACH, slab=SLAB, min_pixels=MIN_PIXELS, labels=False, scratch=None):
+    """awr_detect_hands on a FrameStore-like object: -> (centres (K, B, 3) float64, status (K, B) int32, info (K, B, 4) int32, count (B,)
+    int32, labels (B, fh, fw) int32 or None) on the device, hand-major, nothing synchronised.  labels: True (allocated), False (NULL) or
+    a tensor; scratch: an int64 tensor of at least awr_detect_hands_scratch(B, fh, fw) bytes."""
+    import torch
+    from . import _lib as L
+    dev = store.data.device
+    idx = torch.as_tensor(np.asarray(frame_idx, np.int64)).to(dev) if not isinstance(frame_idx, torch.Tensor) else frame_idx
+    B, K = int(idx.shape[0]), int(hands)
+    if scratch is None:
+        nbytes = int(L.lib.awr_detect_hands_scratch(B, store.fh, store.fw))
+        if nbytes < 0:
+            raise L.AwrError(L.last_error())
+        scratch = torch.empty(nbytes // 8, dtype=torch.int64, device=dev)
+    rows = max(K, 1)                                         # (a K the entry point refuses still gets its message from there)
+    centers = torch.empty((rows, B, 3), dtype=torch.float64, device=dev)
+    status = torch.empty((rows, B), dtype=torch.int32, device=dev)
+    info = torch.empty((rows, B, 4), dtype=torch.int32, device=dev)
+    count = torch.empty(B, dtype=torch.int32, device=dev)
+    if labels is True:
+        labels = torch.empty((B, store.fh, store.fw), dtype=torch.int32, device=dev)
+    elif labels is False:
+        labels = None
+    L.call("awr_detect_hands", store.data.data_ptr(), store.ftype, int(store.data.shape[0]), store.fh, store.fw, idx.data_ptr(), B, K,
+           float(depth_range[0]), float(depth_range[1]), float(reach), float(slab), int(min_pixels), scratch.data_ptr(), L.ptr(labels),
+           centers.data_ptr(), status.data_ptr(), info.data_ptr(), count.data_ptr(), L.stream())
+    return centers, status, info, count, labels
 
 
 def samples_device(centers, cube, dsize, frame_idx, n_frames, frame_shape, paras=ND.PARAS, flip=-1, status=None):

@@ -10,6 +10,7 @@
     Predictor(..., views=make_views(rot=(-15, 15)), fuse="mean")      # the same hand under several views in ONE pass, fused
     Predictor(..., palm=True)               # move the detector's centre to the palm disc, away from the forearm
     Predictor(..., smooth=True)             # filter the joints over time: One-Euro per joint, gate, coasting, look-ahead
+    Predictor(..., hands=2)                 # up to K hands per frame from connected components; the outputs gain a hand axis
 
 Everything between the frames and the joints runs on the device, on the current stream, without a synchronisation: awr_detect (hand
 centre by iterated centre of mass) -> awr_detect_samples (crop blocks, crop matrices) -> awr_nyu_batch (crop + normalise) -> the
@@ -52,6 +53,16 @@ at the measurement or is dropped.  predict() returns the filtered joints; raw_xy
 lead=True hands the tracker the look-ahead joints x + d dt for the next call's crop.  The statement is awr_amd.track.filter_step; the
 kernel equals it bit for bit.  Measured on procedural sequences only (profiles/track_accuracy.txt, profiles/predict_smooth.txt); the
 defaults are engineering choices and accuracy on real frames is UNMEASURED.
+
+Several hands (opt-in; hands=1 issues the launches and gives the bits it always did).  The "nearest" seed is the centre of mass of every
+pixel within the slab of the nearest one: with two hands in view it lies between them, and one hand at most is reported.  hands=K >= 2
+puts awr_detect_hands (nine small launches: the near foreground's 4-connected components by a union-find forest with integer atomicMin,
+canonical labels, the K nearest components of at least min_pixels pixels seeded with their own slab's centre of mass) in front of the
+unchanged awr_detect, which refines all K * max_batch hand-major seeds as given centres; the crop, the network, the un-projection, the
+re-centring passes, the confidence fields and the palm pass then run per row, as the views' rows do.  Touching or overlapping hands are
+ONE component and count as one hand; which hand of one call is which hand of the next is not decided here, so views, track and smooth
+are refused with hands >= 2.  Measured on procedural two-hand composites only (profiles/detect_hands.txt); reach and min_pixels are
+engineering defaults, UNMEASURED on real frames.
 """
 import collections
 import types
@@ -68,6 +79,8 @@ Prediction = collections.namedtuple("Prediction", "xyz uvd center_xyz M status")
 ConfidentPrediction = collections.namedtuple("ConfidentPrediction", Prediction._fields + ("conf", "peak", "spread_mm"))
 ViewPrediction = collections.namedtuple("ViewPrediction", Prediction._fields + ("view_spread_mm", "views_used"))
 ConfidentViewPrediction = collections.namedtuple("ConfidentViewPrediction", ConfidentPrediction._fields + ("view_spread_mm", "views_used"))
+HandsPrediction = collections.namedtuple("HandsPrediction", Prediction._fields + ("n_hands",))
+ConfidentHandsPrediction = collections.namedtuple("ConfidentHandsPrediction", HandsPrediction._fields + ("conf", "peak", "spread_mm"))
 MAX_RECENTER = 4
 MAX_VIEWS = D.MAX_VIEWS
 
@@ -79,7 +92,7 @@ class Predictor:
     def __init__(self, net, img_size, kernel_size, cube=(300, 300, 300), paras=ND.PARAS, flip=-1, max_batch=1, frame_shape=(480, 640),
                  seed="nearest", depth_range=D.DEPTH_RANGE, slab=D.SLAB, refine_iters=D.REFINE_ITERS, winograd=None, parity=False, confidence=False,
                  recenter=0, track=False, center_joints=None, max_shift=1.0, views=None, fuse="mean", palm=False, palm_search=D.PALM_SEARCH,
-                 smooth=None):
+                 smooth=None, hands=1, reach=D.REACH, min_pixels=D.MIN_PIXELS):
         """net: an awr_amd network on the GPU with its weights loaded.  cube: the crop cube in mm.  paras = (fx, fy, u0, v0), flip: the camera.
         max_batch: the static batch of the inference plan; smaller batches are padded, larger ones refused.  seed / depth_range / slab /
         refine_iters: the detector (awr_amd.detect); with `centers_uvd` handed to predict() the seed is the given centre and refine_iters
@@ -121,7 +134,27 @@ class Predictor:
         batch slot b, as the tracker's is; slots >= n_valid keep their state; reset_smooth() clears it.  weight="conf" scales each step by
         the joint's conf (view 0's) and switches the engine's confidence pass on whether or not confidence=True asks for the fields.
         lead=True needs track=True: the tracker's centre for the next call is the joint centre of ahead_xyz, not of the raw joints (the
-        re-centring passes inside a call are unaffected).  The defaults are engineering choices; accuracy on real frames is UNMEASURED."""
+        re-centring passes inside a call are unaffected).  The defaults are engineering choices; accuracy on real frames is UNMEASURED.
+        hands: 1 | 2 ... 4 -- the hands looked for in every frame.  With K >= 2 the plan holds max_batch * K images,
+        hand-major (slot k of batch slot b is row k * max_batch + b), awr_detect_hands seeds the K nearest connected components of the
+        near foreground (reach: the depth of that foreground behind the nearest pixel, in millimetres; min_pixels: the smallest component
+        that counts) and the configured refinement, the optional palm pass, the crop, the network and the re-centring passes run per row.
+        predict() then returns a HandsPrediction / ConfidentHandsPrediction whose fields carry a hand axis behind the batch axis -- xyz, uvd
+        (nb, K, J, 3), center_xyz (nb, K, 3), M (nb, K, 3, 3), status (nb, K), conf / peak / spread_mm (nb, K, J) -- and n_hands (nb,)
+        int32; slot 0 is the nearest hand, an absent hand has status EMPTY and NaN rows.  hand_info (nb, K, 4) int32 holds
+        awr_detect_hands' info rows (the component's first pixel u, v, its pixels, its nearest depth) after a call.  Not combined with
+        views, track or smooth yet; touching or overlapping hands are ONE component and count as one hand; reach and min_pixels are
+        engineering defaults, UNMEASURED on real frames."""
+        if isinstance(hands, bool) or not isinstance(hands, int):
+            raise TypeError("hands is an int in [1, %d], not %r" % (D.MAX_HANDS, hands))
+        K, self.reach, _, self.min_pixels = D._check_hands(hands, reach, 0.0, min_pixels)
+        self.hands, self.hand_info = K, None
+        if K > 1:
+            D._check_hands(K, reach, slab, min_pixels)
+            for name, on in (("views", views is not None), ("track", track is not False), ("smooth", smooth is not None)):
+                if on:
+                    raise ValueError("hands = %d and %s are not combined yet: which hand of one call is which hand of the next is not decided "
+                                     "here (hands=1 takes %s)" % (K, name, name))
         if not isinstance(palm, bool):
             raise TypeError("palm is True or False, not %r" % (palm,))
         self.palm, self.palm_search = palm, D.check_palm(palm_search)[0]
@@ -176,7 +209,7 @@ class Predictor:
         dev = self.device = net.device
         B = self.B
         V = self.V
-        P = B * V                                # rows of the plan: view-major, view 0 first
+        P = B * V * K                            # rows of the plan: view-major, view 0 first; with hands hand-major, the nearest hand first
         self.engine = InferEngine(net, P, self.S, kernel_size, winograd=winograd, parity=parity,
                                   confidence=confidence or (V > 1 and fuse == "conf") or (smooth is not None and self.smooth.weight == "conf"))
         self.J = self.engine.J
@@ -187,11 +220,11 @@ class Predictor:
         self._stage_free = None                  # event: the last upload from the staging buffer has been issued and has finished
         self._store = types.SimpleNamespace(data=self._frames, ftype=0, fh=self.fh, fw=self.fw, n=B)
         self._render = DV.Renderer(self._store, self.S, P)
-        self._idx = torch.arange(B, dtype=torch.int64, device=dev)
+        self._idx = torch.arange(B, dtype=torch.int64, device=dev).repeat(K)          # (K > 1: the frame of every hand-major row)
         self._cube = torch.tensor([float(c) for c in cube], dtype=torch.float64, device=dev)
-        self._scratch = torch.empty(int(L.lib.awr_detect_scratch(B)) // 8, dtype=torch.int64, device=dev)
-        self._centers = torch.empty((B, 3), dtype=torch.float64, device=dev)
-        self._seed = torch.empty((B, 3), dtype=torch.float64, device=dev)
+        self._scratch = torch.empty(int(L.lib.awr_detect_scratch(B * K)) // 8, dtype=torch.int64, device=dev)
+        self._centers = torch.empty((B * K, 3), dtype=torch.float64, device=dev)
+        self._seed = torch.empty((B * K, 3), dtype=torch.float64, device=dev)
         self._blocks = torch.empty((P, DV.BLOCK_BYTES), dtype=torch.uint8, device=dev)
         self._cube32 = torch.empty((P, 3), dtype=torch.float32, device=dev)
         self._img = torch.zeros((P, 1, self.S, self.S), dtype=torch.float32, device=dev)
@@ -203,13 +236,21 @@ class Predictor:
             self._vframe = torch.zeros(P, dtype=torch.int64, device=dev)
         if recenter or track:
             self._joints = None if center_joints is None else torch.tensor(center_joints, dtype=torch.int32, device=dev)
-            self._moved = torch.empty((B, 3), dtype=torch.float64, device=dev)          # center_out of the call that only asks for `next`
+            self._moved = torch.empty((B * K, 3), dtype=torch.float64, device=dev)      # center_out of the call that only asks for `next`
         if palm:
-            nbytes = int(L.lib.awr_detect_palm_scratch(B, self.fh, self.fw))
+            nbytes = int(L.lib.awr_detect_palm_scratch(B * K, self.fh, self.fw))
             if nbytes < 0:
                 raise L.AwrError(L.last_error())
             self._palm_scratch = torch.empty(nbytes // 4, dtype=torch.int32, device=dev)
-            self._palm_info = torch.empty((B, 4), dtype=torch.int32, device=dev)
+            self._palm_info = torch.empty((B * K, 4), dtype=torch.int32, device=dev)
+        if K > 1:
+            nbytes = int(L.lib.awr_detect_hands_scratch(B, self.fh, self.fw))
+            if nbytes < 0:
+                raise L.AwrError(L.last_error())
+            self._hands_scratch = torch.empty(nbytes // 8, dtype=torch.int64, device=dev)
+            self._hands_status = torch.empty((K, B), dtype=torch.int32, device=dev)
+            self._hands_info = torch.empty((K, B, 4), dtype=torch.int32, device=dev)
+            self._hands_count = torch.empty(B, dtype=torch.int32, device=dev)
         if smooth is not None:
             self._filter_state = torch.zeros((B, self.J, 6), dtype=torch.float64, device=dev)          # x0 x1 x2 d0 d1 d2 per slot and joint
             self._filter_count = torch.zeros((B, self.J, 2), dtype=torch.int32, device=dev)            # age, coast
@@ -324,6 +365,10 @@ class Predictor:
         without centers_uvd starts from the tracked centres (see __init__), an explicit centers_uvd overrides them for this call, and either
         way slots [0, n_valid) of the tracker take this call's next_centers_uvd.  dt: seconds since the previous call, for a predictor with
         smooth (default 1 / its fps); xyz and uvd are then the filtered joints (see __init__)."""
+        if self.hands > 1:
+            if dt is not None:
+                raise L.AwrError("predict(dt=...) is the temporal filter's time step: it needs a Predictor built with smooth=...")
+            return self._predict_hands(frames, centers_uvd, n_valid)
         if self.smooth is None:
             if dt is not None:
                 raise L.AwrError("predict(dt=...) is the temporal filter's time step: it needs a Predictor built with smooth=...")
@@ -461,11 +506,105 @@ class Predictor:
             return ConfidentPrediction(xyz[:nb], uvd[:nb], cxyz[:nb], M[:nb], status[:nb], fields[0, :nb], fields[1, :nb], fields[2, :nb])
         return Prediction(xyz[:nb], uvd[:nb], cxyz[:nb], M[:nb], status[:nb])
 
+    def _predict_hands(self, frames, centers_uvd, n_valid):
+        """predict() of a predictor with hands = K >= 2: every stage over the K * max_batch hand-major rows, row k * max_batch + b"""
+        nb = self._upload(frames)
+        nv = nb if n_valid is None else int(n_valid)
+        if not 0 < nv <= nb:
+            raise L.AwrError("n_valid = %d is outside [1, %d]" % (nv, nb))
+        dev, B, K, J, s = self.device, self.B, self.hands, self.J, L.stream()
+        P = B * K
+        fx, fy, u0, v0 = self.paras
+        nan = float("nan")
+        seeds = self._seed.view(K, B, 3)
+        if centers_uvd is not None:
+            c = centers_uvd if isinstance(centers_uvd, torch.Tensor) else torch.from_numpy(np.ascontiguousarray(centers_uvd, dtype=np.float64))
+            if tuple(c.shape) != (nb, K, 3):
+                raise L.AwrError("centers_uvd must be (%d, %d, 3): a centre per frame and hand, NaN rows for an absent hand, got %s" % (nb, K, tuple(c.shape)))
+            seeds[:, :nb].copy_(c.transpose(0, 1), non_blocking=True)          # (converts to float64 on the way)
+            self.hand_info = None
+        else:
+            L.call("awr_detect_hands", self._frames.data_ptr(), 0, B, self.fh, self.fw, self._idx.data_ptr(), B, K, self.depth_range[0],
+                   self.depth_range[1], self.reach, self.slab, self.min_pixels, self._hands_scratch.data_ptr(), None, self._seed.data_ptr(),
+                   self._hands_status.data_ptr(), self._hands_info.data_ptr(), self._hands_count.data_ptr(), s)
+            self.hand_info = self._hands_info[:, :nb].transpose(0, 1)
+        if nv < B:
+            seeds[:, nv:].fill_(nan)                 # rows past n_valid of every block: NaN seeds, blocks without pixels
+        M = torch.empty((P, 3, 3), dtype=torch.float32, device=dev)
+        cxyz = torch.empty((P, 3), dtype=torch.float32, device=dev)
+        status = torch.empty(P, dtype=torch.int32, device=dev)
+        ustatus = torch.zeros(P, dtype=torch.int32, device=dev)
+        uvd = torch.empty((P, J, 3), dtype=torch.float32, device=dev)
+        xyz = torch.empty((P, J, 3), dtype=torch.float32, device=dev)
+        # the unchanged detector refines every seed: a NaN seed (an absent hand) finds nothing and ends EMPTY
+        L.call("awr_detect", self._frames.data_ptr(), 0, B, self.fh, self.fw, self._idx.data_ptr(), P, D.SEED_GIVEN, self._seed.data_ptr(),
+               self.depth_range[0], self.depth_range[1], self.slab, self._cube.data_ptr(), 0, fx, fy, self.iters, 0, self._scratch.data_ptr(),
+               self._centers.data_ptr(), status.data_ptr(), s)
+        if self.palm and centers_uvd is None:
+            L.call("awr_detect_palm", self._frames.data_ptr(), 0, B, self.fh, self.fw, self._idx.data_ptr(), P, self._centers.data_ptr(),
+                   status.data_ptr(), self.depth_range[0], self.depth_range[1], self._cube.data_ptr(), 0, fx, fy, self.palm_search,
+                   D.PALM_TAU[0], D.PALM_TAU[1], D.PALM_RHO2[0], D.PALM_RHO2[1], self._palm_scratch.data_ptr(), self._centers.data_ptr(),
+                   status.data_ptr(), self._palm_info.data_ptr(), s)
+            self.palm_info = self._palm_info.view(K, B, 4)[:, :nb].transpose(0, 1)
+
+        def crop_and_predict():
+            L.call("awr_detect_samples", self._centers.data_ptr(), self._cube.data_ptr(), 0, B, self._idx.data_ptr(), P, self.S, self.fh, self.fw,
+                   fx, fy, u0, v0, self.flip, self._blocks.data_ptr(), L.ptr(M), L.ptr(cxyz), L.ptr(self._cube32), status.data_ptr(), s)
+            self._render(self._blocks, out=self._img)
+            jt = self.engine(self._img)
+            L.call("awr_joints_unproject", L.ptr(jt), L.ptr(cxyz), L.ptr(M), L.ptr(self._cube32), P, J, P, float(self.S), fx, fy, u0, v0, self.flip,
+                   L.ptr(uvd), L.ptr(xyz), ustatus.data_ptr(), s)
+
+        def joints_center(center_out, next_out, code):
+            L.call("awr_joints_center", L.ptr(xyz), self._centers.data_ptr(), L.ptr(cxyz), L.ptr(self._cube32), status.data_ptr(), ustatus.data_ptr(),
+                   P, J, P, L.ptr(self._joints), 0 if self._joints is None else int(self._joints.numel()), fx, fy, u0, v0, self.flip,
+                   self.depth_range[0], self.depth_range[1], self.max_shift, center_out.data_ptr(), L.ptr(next_out), code.data_ptr(), s)
+
+        crop_and_predict()
+        if self.recenter:
+            codes = torch.zeros((self.recenter + 1, P), dtype=torch.int32, device=dev)
+            for k in range(self.recenter):
+                joints_center(self._centers, None, codes[k])
+                crop_and_predict()
+            nxt = torch.full((P, 3), nan, dtype=torch.float64, device=dev)
+            joints_center(self._moved, nxt, codes[self.recenter])
+            self.centers_uvd = self._centers.clone().view(K, B, 3)[:, :nb].transpose(0, 1)
+            self.next_centers_uvd = nxt.view(K, B, 3)[:, :nb].transpose(0, 1)
+            self.recenter_codes = codes.view(self.recenter + 1, K, B)[:, :, :nb].transpose(1, 2)
+        self._last = (status.view(K, B), ustatus.view(K, B), nv)
+        if centers_uvd is None:
+            n_hands = self._hands_count[:nb].clamp(max=K)
+        else:
+            n_hands = (status.view(K, B)[:, :nb] == D.OK).sum(0, dtype=torch.int32)
+
+        def rows(t):          # hand-major (K * B, ...) -> a (nb, K, ...) view
+            return t.view((K, B) + tuple(t.shape[1:]))[:, :nb].transpose(0, 1)
+        fields = (rows(xyz), rows(uvd), rows(cxyz), rows(M), rows(status), n_hands)
+        if self.confidence:
+            conf = torch.empty((3, P, J), dtype=torch.float32, device=dev)
+            L.call("awr_confidence_fields", L.ptr(self.engine.conf), L.ptr(self.engine.stat), L.ptr(self._cube32), status.data_ptr(),
+                   ustatus.data_ptr(), P, J, P, L.ptr(conf[0]), L.ptr(conf[1]), L.ptr(conf[2]), s)
+            return ConfidentHandsPrediction(*fields, rows(conf[0]), rows(conf[1]), rows(conf[2]))
+        return HandsPrediction(*fields)
+
     def check(self):
-        """Synchronising: raise AwrError naming the first frame of the last batch that could not be predicted, and its status code."""
+        """Synchronising: raise AwrError naming the first frame of the last batch that could not be predicted, and its status code.  With
+        hands >= 2: the first frame whose slot 0 (the nearest hand) is not OK, or a found hand whose un-projection failed; an absent
+        second hand is not an error."""
         if self._last is None:
             return
         status, ustatus, nv = self._last
+        if self.hands > 1:
+            st, ust = status[:, :nv].tolist(), ustatus[:, :nv].tolist()
+            for b in range(nv):
+                if st[0][b] != D.OK:
+                    raise L.AwrError("predict: frame %d of the batch, hand slot 0: %s (status %d); no hand was found and its joints are NaN"
+                                     % (b, D.STATUS_NAMES.get(st[0][b], "invalid"), st[0][b]))
+                for k in range(self.hands):
+                    if st[k][b] == D.OK and ust[k][b] != 0:
+                        raise L.AwrError("predict: frame %d of the batch, hand slot %d: its crop matrix is %s (un-projection status %d); its "
+                                         "joints are NaN" % (b, k, {1: "singular", 2: "not finite"}.get(ust[k][b], "invalid"), ust[k][b]))
+            return
         st, ust = status[:nv].tolist(), ustatus[:nv].tolist()
         for b in range(nv):
             if st[b] != D.OK:

@@ -147,6 +147,44 @@ def sample_poses(n, seed, model=None, z_range=(500.0, 900.0), scale_range=(0.85,
     return poses
 
 
+def place_poses(poses, u, v, z, model=None, paras=ND.PARAS, flip=-1):
+    """-> a copy of the pose dict whose palm point (the point sample_poses places: 0.6 middle metacarpals up the palm from the wrist)
+    projects to pixel (u, v) at depth z millimetres; u, v, z are numbers or (n,) arrays.  sample_poses' own last lines, for a caller that
+    decides where each hand goes -- two hands side by side, say (`compose`)."""
+    model = model or HandModel()
+    out = {k: np.array(a, dtype=np.float64) for k, a in poses.items()}
+    n = len(out["scale"])
+    fx, fy, u0, v0 = (float(p) for p in paras)
+    u, v, z = (np.broadcast_to(np.asarray(x, np.float64), (n,)) for x in (u, v, z))
+    out["position"] = np.zeros((n, 3))
+    mid = _palm_point(out, model)
+    target = np.stack([(u - u0) * z / fx, flip * (v - v0) * z / fy, z], -1)
+    out["position"] = target - mid
+    return out
+
+
+def compose(*frames):
+    """The per-pixel NEAREST NON-ZERO depth of equally shaped uint16 frames (0: no frame has a return there): what one camera sees of
+    scenes rendered apart.  numpy arrays -> a numpy array, device (or host) tensors -> a tensor of the same kind."""
+    if not frames:
+        raise ValueError("compose needs at least one frame")
+    if all(isinstance(f, np.ndarray) for f in frames):
+        if any(f.dtype != np.uint16 or f.shape != frames[0].shape for f in frames):
+            raise ValueError("compose takes equally shaped uint16 frames")
+        out = frames[0].copy()
+        for f in frames[1:]:
+            out = np.where(out == 0, f, np.where(f == 0, out, np.minimum(out, f)))
+        return out
+    import torch
+    if any(not isinstance(f, torch.Tensor) or f.dtype != torch.uint16 or f.shape != frames[0].shape or f.device != frames[0].device for f in frames):
+        raise ValueError("compose takes equally shaped uint16 frames, all numpy arrays or all tensors of one device")
+    wide = [f.contiguous().view(torch.int16).to(torch.int32) & 0xFFFF for f in frames]          # (uint16 tensors have no arithmetic)
+    out = wide[0]
+    for f in wide[1:]:
+        out = torch.where(out == 0, f, torch.where(f == 0, out, torch.minimum(out, f)))
+    return torch.where(out >= 32768, out - 65536, out).to(torch.int16).view(torch.uint16)
+
+
 def sample_sequences(n_seq, length, seed, key_every=15, model=None, rot_range=(50.0, 50.0, 60.0), **pose_options):
     """n_seq temporally coherent sequences of `length` frames each: a pose dict with sample_poses' keys and n_seq * length rows,
     SEQUENCE-MAJOR (frame t of sequence s is row s * length + t).  One sample_poses(n_seq * K, seed, ...) call draws K =

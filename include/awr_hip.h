@@ -946,6 +946,43 @@ int awr_detect_palm(const void* frames, int frame_type, int64_t n_frames, int fh
                     double fy, double search, int tau_num, int tau_den, int rho2_num, int rho2_den, void* scratch, double* center_out,
                     int* status_out, int* info, void* stream);
 
+/* Several hands per frame (csrc/awr_hands.hip; the numpy statements are awr_amd/detect.py components and hand_seeds,
+ * results are bit-identical to them).  awr_detect's "nearest" seed is the centre of mass of EVERY pixel of the frame within `slab` of the
+ * nearest one: with two hands in view it lies between them, and at most one hand is ever reported.  This entry splits the near
+ * foreground into connected components and seeds the K nearest large ones; each seed is then refined by the unchanged awr_detect with
+ * AWR_DET_SEED_GIVEN.  Per frame b:
+ *   1. frame[b] outside [0, n_frames): AWR_DET_BAD_FRAME and a NaN centre in every slot, info = (-1, -1, 0, 0), count = 0, labels -1;
+ *      nothing is read.
+ *   2. Foreground: zmin <= d <= zmax and d != 0 (awr_detect's rule).  dmin = the smallest foreground depth.  The mask is the foreground
+ *      with d <= min(dmin + reach, zmax), compared in double.
+ *   3. Two mask pixels are connected when they are 4-neighbours; there is no depth test.  A pixel's label is the smallest raster index
+ *      v * fw + u of its component, -1 on background: canonical integers, whatever the algorithm and the order.
+ *   4. Candidates: the components with n >= min_pixels pixels; count[b] = their number (it may exceed K).  A candidate's key is
+ *      (zc, root): zc its smallest raw depth, root its label.  The K smallest keys fill slots 0 ... K - 1 in ascending order: slot 0 is
+ *      the nearest hand, and a tie in depth goes to the smaller root.
+ *   5. A slot's seed: n, sum of u, sum of v, sum of raw depths over the component's pixels with d <= min(zc + slab, zmax) as 64-bit
+ *      integers, centre = (su / n, sv / n, sd / n) as three double divisions -- the "nearest" rule per component; AWR_DET_OK;
+ *      info = (root % fw, root / fw, n of the component, zc).  A slot past the candidates: NaN centre, AWR_DET_EMPTY, (-1, -1, 0, 0).
+ * Outputs are HAND-MAJOR: slot k of frame b is row k * B + b of centers (K, B, 3) doubles, status (K, B) and info (K, B, 4) int32 -- the
+ * layout of the test-time views, so awr_detect, awr_detect_palm, awr_detect_samples and what follows take K * B rows as they are.
+ * count (B) int32.  labels_out (B, fh, fw) int32 may be NULL.
+ *   K in [1, AWR_DET_MAX_HANDS], B in [1, AWR_DET_MAX_BATCH], fh, fw in [1, 16384], min_pixels >= 1, zmin <= zmax, reach >= 0 and
+ *   slab >= 0 (infinity allowed, NaN not): anything else returns AWR_ERR_ARG with a message, before any launch.  Only uint16 frames.
+ *   scratch: awr_detect_hands_scratch(B, fh, fw) bytes, 8-byte aligned: per batch row 278 64-bit words, which the call initialises, then
+ *   three int32 words per pixel and batch row (the forest, and pixels and smallest depth per root); nothing is written past it.  The same
+ *   frame twice in a batch uses two independent regions.
+ * The labelling is a union-find forest joined by smaller index with integer atomicMin -- every pointer only ever decreases, so the root
+ * that survives is the component's smallest index in any order; sums, counts and minima are integer atomics.  There is no floating-point
+ * atomic and no floating-point reduction.  Nine launches on `stream`, one per stage (the slots, dmin, the tiles, the tile borders, the
+ * flattening, the roots, the pick, the slab sums, the outputs); only the stream orders them, no workgroup waits for another, nothing
+ * synchronises, nothing outside the frame store is read. */
+#define AWR_DET_MAX_HANDS 4
+int64_t awr_detect_hands_scratch(int B, int fh, int fw);       /* bytes; -1 for a B outside [1, AWR_DET_MAX_BATCH] or a side outside [1, 16384] */
+int awr_detect_hands(const void* frames, int frame_type, int64_t n_frames, int fh, int fw, const int64_t* frame, int B, int K,
+                     double zmin, double zmax, double reach, double slab, int min_pixels, void* scratch,
+                     int* labels_out /* B*fh*fw, may be NULL */, double* centers /* K,B,3 */, int* status /* K,B */,
+                     int* info /* K,B,4 */, int* count /* B */, void* stream);
+
 /* Joints -> the next crop centre, per frame, with a gate (the numpy statement is awr_amd/detect.py joints_center,
  * results are bit-identical to it):
  *   xyz (B, J, 3) camera mm, as awr_joints_unproject writes xyz_out; center_uvd (B, 3) doubles, the centres this pass was cropped at;

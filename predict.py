@@ -21,6 +21,12 @@ frames; defaults 1.0,0.02,1.0 in Hz, 1/mm, Hz): like --track it 
 (default 30); --gate-mm G ignores a measurement further than G mm from the filtered joint; --lead (with --track) starts the next frame's crop
 at the constant-velocity look-ahead of the joints.  pred_uvd.txt / pred_xyz.txt then hold the FILTERED joints, and pred_raw_uvd.txt,
 pred_raw_xyz.txt (the network's own) and pred_filter_code.txt (J columns, awr_amd.track.FILTER_NAMES) are written too.
+--hands K (2 ... 4) looks for up to K hands per frame: awr_detect_hands splits the near foreground into connected components and seeds the K
+nearest large ones (--reach MM: how far behind the nearest pixel that foreground goes, default 300; --min-pixels N: the smallest component
+that counts, default 400; DESIGN.md 4.26 -- both UNMEASURED on real frames; touching hands are one hand).  The saved arrays gain the hand
+axis: pred_uvd.txt / pred_xyz.txt hold n * K rows (frame-major, the nearest hand first; an absent hand's row is nan), and pred_n_hands.txt
+(one count per frame), pred_hand_status.txt (K columns, awr_amd.detect's codes) and pred_hand_info.txt (n * K rows: the component's first
+pixel u, v, its pixels, its nearest depth) are written too.  Not combined with --views, --track or --smooth yet.
 --ema predicts with the checkpoint's averaged weights ("model_ema", written by a run with config.ema_decay) instead of "model".
 `--set` overrides config entries as train.py does (img_size, kernel_size, cube, batch_size, jt_num, downsample, winograd ...)."""
 import argparse
@@ -48,6 +54,9 @@ def parse_args(argv=None):
     ap.add_argument("--fps", type=float, default=None, metavar="F", help="frame rate of the sequence (with --smooth; default 30)")
     ap.add_argument("--gate-mm", type=float, default=None, metavar="G", help="with --smooth: ignore a measurement further than G mm from the filtered joint")
     ap.add_argument("--lead", action="store_true", help="with --smooth and --track: crop the next frame at the look-ahead joints")
+    ap.add_argument("--hands", type=int, default=1, metavar="K", help="look for up to K hands per frame (1 ... 4); the outputs gain a hand axis")
+    ap.add_argument("--reach", type=float, default=None, metavar="MM", help="with --hands: depth of the foreground behind the nearest pixel (default 300)")
+    ap.add_argument("--min-pixels", type=int, default=None, metavar="N", help="with --hands: the smallest component that counts as a hand (default 400)")
     ap.add_argument("--ema", action="store_true", help="load the checkpoint's \"model_ema\" (the EMA of the weights) instead of \"model\"")
     return ap.parse_args(argv)
 
@@ -103,10 +112,16 @@ def main(argv=None):
     net.load_state_dict(pth[key])
     bs = 1 if args.track or smooth is not None else min(cfg.batch_size, len(frames))
     views = None if args.views is None else detect.parse_views(args.views)
+    if args.hands == 1 and (args.reach is not None or args.min_pixels is not None):
+        raise SystemExit("--reach and --min-pixels belong to --hands K with K >= 2")
+    hands_kw = {} if args.hands == 1 else dict(hands=args.hands, reach=detect.REACH if args.reach is None else args.reach,
+                                               min_pixels=detect.MIN_PIXELS if args.min_pixels is None else args.min_pixels)
+    K = args.hands
     pred = awr_amd.Predictor(net.cuda(), cfg.img_size, cfg.kernel_size, cube=cfg.cube, max_batch=bs, frame_shape=frames.shape[1:],
                              winograd=cfg.winograd, parity=cfg.parity_infer, confidence=args.confidence,
                              recenter=args.recenter, track=args.track, views=views, fuse=args.fuse, palm=args.palm,
-                             smooth=smooth)
+                             smooth=smooth, **hands_kw)
+    hands = {"n_hands": [], "hand_status": [], "hand_info": []}
     stateful = bool(args.recenter or args.track)
     centers, codes = [], []
     uvd, xyz, extra = [], [], {"conf": [], "peak": [], "spread_mm": []}
@@ -125,19 +140,26 @@ def main(argv=None):
         if smooth is not None:
             for k, t in (("raw_uvd", pred.raw_uvd), ("raw_xyz", pred.raw_xyz), ("filter_code", pred.filter_codes)):
                 raw[k].append(t.cpu().numpy())
+        if K > 1:
+            hands["n_hands"].append(out.n_hands.cpu().numpy())
+            hands["hand_status"].append(out.status.cpu().numpy())
+            hands["hand_info"].append(pred.hand_info.cpu().numpy().reshape(-1, 4))
         if stateful:
-            centers.append(pred.centers_uvd.cpu().numpy())
-            codes.append(pred.recenter_codes.cpu().numpy().T)
+            centers.append(pred.centers_uvd.cpu().numpy().reshape(-1, 3))
+            codes.append(pred.recenter_codes.cpu().numpy().reshape(args.recenter + 1, -1).T)
         try:
             pred.check()
         except awr_amd._lib.AwrError as e:
             print("frames %d...: %s" % (lo, e), file=sys.stderr)
     os.makedirs(args.out, exist_ok=True)
     for name, rows in (("pred_uvd.txt", uvd), ("pred_xyz.txt", xyz)):
-        np.savetxt(os.path.join(args.out, name), np.concatenate(rows, 0).reshape(len(frames), cfg.jt_num * 3), fmt="%.3f")
+        np.savetxt(os.path.join(args.out, name), np.concatenate(rows, 0).reshape(len(frames) * K, cfg.jt_num * 3), fmt="%.3f")
     if args.confidence:
         for k, rows in extra.items():
-            np.savetxt(os.path.join(args.out, "pred_%s.txt" % k), np.concatenate(rows, 0).reshape(len(frames), cfg.jt_num), fmt="%.6g")
+            np.savetxt(os.path.join(args.out, "pred_%s.txt" % k), np.concatenate(rows, 0).reshape(len(frames) * K, cfg.jt_num), fmt="%.6g")
+    if K > 1:
+        for k, rows in hands.items():
+            np.savetxt(os.path.join(args.out, "pred_%s.txt" % k), np.concatenate(rows, 0), fmt="%d")
     if views is not None:
         np.savetxt(os.path.join(args.out, "pred_view_spread_mm.txt"), np.concatenate(fused["view_spread_mm"], 0), fmt="%.6g")
         np.savetxt(os.path.join(args.out, "pred_views_used.txt"), np.concatenate(fused["views_used"], 0), fmt="%d")
