@@ -265,6 +265,8 @@ _SIGS = {
     "awr_synth_render": ([_P, _P, _I, _I, _I, _I, _D, _D, _D, _D, _I, _I, _I, C.c_uint, _L, _P, _L, _L, _P, _P], C.c_int),
     # temporal joint filter (csrc/awr_track.hip)
     "awr_joints_filter": ([_P, _P, _P, _P, _P, _P, _I, _I, _I, _D, _D, _D, _D, _D, _I, _I, _D, _D, _D, _D, _D, _I, _P, _P, _P, _P, _P], C.c_int),
+    # hand identities across calls (csrc/awr_assign.hip)
+    "awr_hands_assign": ([_P, _P, _P, _P, _P, _P, _P, _P, _I, _I, _I, _D, _D, _I, _D, _D, _D, _D, _I, _P, _P, _I, _P, _P, _P, _P, _P, _P, _P], C.c_int),
 }
 
 # entry points of study builds only (hipcc -DAWR_STUDY, AWR_BUILD_STUDY=1 for awr_amd.build): measured-and-rejected forms that the default

@@ -11,6 +11,7 @@
     Predictor(..., palm=True)               # move the detector's centre to the palm disc, away from the forearm
     Predictor(..., smooth=True)             # filter the joints over time: One-Euro per joint, gate, coasting, look-ahead
     Predictor(..., hands=2)                 # up to K hands per frame from connected components; the outputs gain a hand axis
+    Predictor(..., hands=2, identity=True)  # slot k is the same hand from call to call; track, smooth and lead work per hand
 
 Everything between the frames and the joints runs on the device, on the current stream, without a synchronisation: awr_detect (hand
 centre by iterated centre of mass) -> awr_detect_samples (crop blocks, crop matrices) -> awr_nyu_batch (crop + normalise) -> the
@@ -61,8 +62,20 @@ canonical labels, the K nearest components of at least min_pixels pixels seeded 
 unchanged awr_detect, which refines all K * max_batch hand-major seeds as given centres; the crop, the network, the un-projection, the
 re-centring passes, the confidence fields and the palm pass then run per row, as the views' rows do.  Touching or overlapping hands are
 ONE component and count as one hand; which hand of one call is which hand of the next is not decided here, so views, track and smooth
-are refused with hands >= 2.  Measured on procedural two-hand composites only (profiles/detect_hands.txt); reach and min_pixels are
+are refused with hands >= 2 (identity=..., below, decides it and lifts the refusal for track and smooth).  Measured on procedural two-hand composites only (profiles/detect_hands.txt); reach and min_pixels are
 engineering defaults, UNMEASURED on real frames.
+
+Hand identities (opt-in; identity=None issues the launches, gives the bits and raises the errors it always did).  With hands=K >= 2 and
+identity=True | dict | track.Identity, ONE awr_hands_assign launch between the detector and the crop decides which of this call's
+detected hands (the candidates) is which identity of the previous call: an exact assignment over the K! permutations in camera
+millimetres, gated by gate_mm, per batch slot, with state (last centre, id, misses, next id) that stays on the device.  Slot k then is
+the same hand from call to call -- a hand without a candidate waits for max_miss calls (status EMPTY, NaN rows) before its slot is given
+up, a new hand takes the lowest free slot and a fresh id -- and so track=True (a second awr_detect seeded with every slot's last centre;
+two trackers that end on one hand are merged), smooth=... (K launches of the unchanged awr_joints_filter over the hand-major filter
+state, whose rows awr_hands_assign zeroes where an identity starts or ends) and lead=True are accepted.  predict() returns a
+TrackedHandsPrediction with ids (nb, K).  The statement is awr_amd.track.assign_step; the kernel equals it bit for bit.  Measured on
+procedural two-hand sequences only (profiles/hands_identity.txt); gate_mm, merge_mm and max_miss are engineering defaults, UNMEASURED on
+real frames.
 """
 import collections
 import types
@@ -81,6 +94,8 @@ ViewPrediction = collections.namedtuple("ViewPrediction", Prediction._fields + (
 ConfidentViewPrediction = collections.namedtuple("ConfidentViewPrediction", ConfidentPrediction._fields + ("view_spread_mm", "views_used"))
 HandsPrediction = collections.namedtuple("HandsPrediction", Prediction._fields + ("n_hands",))
 ConfidentHandsPrediction = collections.namedtuple("ConfidentHandsPrediction", HandsPrediction._fields + ("conf", "peak", "spread_mm"))
+TrackedHandsPrediction = collections.namedtuple("TrackedHandsPrediction", HandsPrediction._fields + ("ids",))
+ConfidentTrackedHandsPrediction = collections.namedtuple("ConfidentTrackedHandsPrediction", TrackedHandsPrediction._fields + ("conf", "peak", "spread_mm"))
 MAX_RECENTER = 4
 MAX_VIEWS = D.MAX_VIEWS
 
@@ -88,11 +103,12 @@ MAX_VIEWS = D.MAX_VIEWS
 class Predictor:
     views, fuse, V = None, "mean", 1          # a predictor without views: one identity view, no view table, no per-view buffers
     smooth = None                             # a predictor without a temporal filter: no filter state, no launch, no extra attributes
+    identity = None                           # a predictor without hand identities: no assignment state, no launch, no extra attributes
 
     def __init__(self, net, img_size, kernel_size, cube=(300, 300, 300), paras=ND.PARAS, flip=-1, max_batch=1, frame_shape=(480, 640),
                  seed="nearest", depth_range=D.DEPTH_RANGE, slab=D.SLAB, refine_iters=D.REFINE_ITERS, winograd=None, parity=False, confidence=False,
                  recenter=0, track=False, center_joints=None, max_shift=1.0, views=None, fuse="mean", palm=False, palm_search=D.PALM_SEARCH,
-                 smooth=None, hands=1, reach=D.REACH, min_pixels=D.MIN_PIXELS):
+                 smooth=None, hands=1, reach=D.REACH, min_pixels=D.MIN_PIXELS, identity=None):
         """net: an awr_amd network on the GPU with its weights loaded.  cube: the crop cube in mm.  paras = (fx, fy, u0, v0), flip: the camera.
         max_batch: the static batch of the inference plan; smaller batches are padded, larger ones refused.  seed / depth_range / slab /
         refine_iters: the detector (awr_amd.detect); with `centers_uvd` handed to predict() the seed is the given centre and refine_iters
@@ -143,16 +159,33 @@ class Predictor:
         (nb, K, J, 3), center_xyz (nb, K, 3), M (nb, K, 3, 3), status (nb, K), conf / peak / spread_mm (nb, K, J) -- and n_hands (nb,)
         int32; slot 0 is the nearest hand, an absent hand has status EMPTY and NaN rows.  hand_info (nb, K, 4) int32 holds
         awr_detect_hands' info rows (the component's first pixel u, v, its pixels, its nearest depth) after a call.  Not combined with
-        views, track or smooth yet; touching or overlapping hands are ONE component and count as one hand; reach and min_pixels are
-        engineering defaults, UNMEASURED on real frames."""
+        views, track or smooth (track and smooth: unless identity is set, below); touching or overlapping hands are ONE component and count as one hand; reach and min_pixels are
+        engineering defaults, UNMEASURED on real frames.
+        identity: None | True (the defaults) | a dict of awr_amd.track.Identity's fields | an Identity -- with hands >= 2, keep every hand in
+        ITS slot from call to call (statement: awr_amd.track.assign_step): one awr_hands_assign launch assigns this call's
+        detected hands to the identities of the previous call of the same batch slot, exactly, within gate_mm camera millimetres; a hand
+        that is not seen waits for max_miss calls (status EMPTY, NaN rows), a new hand takes the lowest free slot and the next id.  track,
+        smooth (with lead) and predict(dt=...) are then accepted: the tracker seeds a second detector run with every slot's last centre and
+        two tracked centres within merge_mm of each other are one hand; the filter state is (K * max_batch, J, ...) and a slot's rows are
+        zeroed where an identity starts or ends.  predict() returns a TrackedHandsPrediction / ConfidentTrackedHandsPrediction:
+        HandsPrediction's fields, where slot k is an identity and NOT the k-th nearest hand, n_hands the slots with status OK, and ids
+        (nb, K) int32 (0: a free slot).  After such a call: hand_codes, hand_source (nb, K) int32 awr_amd.track's FREE ... MERGED and the
+        candidate each slot took (-1 none, -2 its tracked centre), hands_dropped (nb,) int32 candidates that found no slot; hand_info and
+        palm_info stay in CANDIDATE order (the nearest first); raw_xyz, raw_uvd, ahead_xyz, filter_codes carry the hand axis.  Explicit
+        centers_uvd (nb, K, 3) are the candidates.  reset_identity() forgets the identities.  views stays refused.  The defaults are
+        engineering choices, UNMEASURED on real frames."""
         if isinstance(hands, bool) or not isinstance(hands, int):
             raise TypeError("hands is an int in [1, %d], not %r" % (D.MAX_HANDS, hands))
         K, self.reach, _, self.min_pixels = D._check_hands(hands, reach, 0.0, min_pixels)
         self.hands, self.hand_info = K, None
+        if identity is not None:
+            self.identity = T.check_identity(identity)
+            if K == 1:
+                raise ValueError("identity decides which of SEVERAL hands is which: it needs hands >= 2 (hands=1 has one slot, and track=True follows it)")
         if K > 1:
             D._check_hands(K, reach, slab, min_pixels)
             for name, on in (("views", views is not None), ("track", track is not False), ("smooth", smooth is not None)):
-                if on:
+                if on and (identity is None or name == "views"):
                     raise ValueError("hands = %d and %s are not combined yet: which hand of one call is which hand of the next is not decided "
                                      "here (hands=1 takes %s)" % (K, name, name))
         if not isinstance(palm, bool):
@@ -252,14 +285,28 @@ class Predictor:
             self._hands_info = torch.empty((K, B, 4), dtype=torch.int32, device=dev)
             self._hands_count = torch.empty(B, dtype=torch.int32, device=dev)
         if smooth is not None:
-            self._filter_state = torch.zeros((B, self.J, 6), dtype=torch.float64, device=dev)          # x0 x1 x2 d0 d1 d2 per slot and joint
-            self._filter_count = torch.zeros((B, self.J, 2), dtype=torch.int32, device=dev)            # age, coast
+            self._filter_state = torch.zeros((B * K, self.J, 6), dtype=torch.float64, device=dev)      # x0 x1 x2 d0 d1 d2 per slot (and hand) and joint
+            self._filter_count = torch.zeros((B * K, self.J, 2), dtype=torch.int32, device=dev)        # age, coast
             self.raw_xyz = self.raw_uvd = self.ahead_xyz = self.filter_codes = None
+        if self.identity is not None:
+            # the assignment's state, hand-major (track.identity_state), and the candidates it chooses among
+            self._id_last = torch.full((K, B, 3), float("nan"), dtype=torch.float64, device=dev)
+            self._id_ids = torch.zeros((K, B), dtype=torch.int32, device=dev)
+            self._id_miss = torch.zeros((K, B), dtype=torch.int32, device=dev)
+            self._id_next = torch.ones(B, dtype=torch.int32, device=dev)
+            self._cand = torch.empty((B * K, 3), dtype=torch.float64, device=dev)
+            self._cand_status = torch.empty(B * K, dtype=torch.int32, device=dev)
+            self.hand_codes = self.hand_source = self.hands_dropped = None
+            if recenter or track:
+                self._zero_status = torch.zeros(B * K, dtype=torch.int32, device=dev)
+                self._sel = torch.empty((B * K, 3), dtype=torch.float64, device=dev)
+                self._sel_status = torch.empty(B * K, dtype=torch.int32, device=dev)
         if track:
-            self._track = torch.full((B, 3), float("nan"), dtype=torch.float64, device=dev)
-            self._tcenters = torch.empty((B, 3), dtype=torch.float64, device=dev)
+            # (with identities the tracked centres ARE the assignment's last centres, one per slot and hand)
+            self._track = torch.full((B, 3), float("nan"), dtype=torch.float64, device=dev) if K == 1 else self._id_last.view(B * K, 3)
+            self._tcenters = torch.empty((B * K, 3), dtype=torch.float64, device=dev)
             self._dcenters = torch.empty((B, 3), dtype=torch.float64, device=dev)
-            self._tstatus = torch.empty(B, dtype=torch.int32, device=dev)
+            self._tstatus = torch.empty(B * K, dtype=torch.int32, device=dev)
             self._dstatus = torch.empty(B, dtype=torch.int32, device=dev)
 
     def _slots(self, slots, n=None):
@@ -274,9 +321,11 @@ class Predictor:
 
     def set_track(self, centers_uvd, slots=None):
         """Set the tracked centres from outside: centers_uvd (n, 3), numpy or tensor, host or device, for batch slots `slots` (default:
-        slots [0, n)).  A NaN row marks its slot as lost.  Does not block."""
+        slots [0, n)).  A NaN row marks its slot as lost.  With identity: (n, K, 3), a centre per hand slot (see _set_track_hands).  Does not block."""
         if not self.track:
             raise L.AwrError("set_track needs a Predictor built with track=True")
+        if self.identity is not None:
+            return self._set_track_hands(centers_uvd, slots)
         c = centers_uvd if isinstance(centers_uvd, torch.Tensor) else torch.from_numpy(np.ascontiguousarray(centers_uvd, dtype=np.float64))
         if c.dim() != 2 or c.shape[1] != 3 or not 0 < c.shape[0] <= self.B:
             raise L.AwrError("centers_uvd must be (n, 3) with n in [1, max_batch = %d], got %s" % (self.B, tuple(c.shape)))
@@ -287,9 +336,12 @@ class Predictor:
             self._track.index_copy_(0, idx, c.to(device=self.device, dtype=torch.float64, non_blocking=True))
 
     def reset_track(self, slots=None):
-        """Mark batch slots (default: all of them) as lost: their next call starts from the detector.  Does not block."""
+        """Mark batch slots (default: all of them) as lost: their next call starts from the detector.  With identity this is reset_identity.
+        Does not block."""
         if not self.track:
             raise L.AwrError("reset_track needs a Predictor built with track=True")
+        if self.identity is not None:
+            return self.reset_identity(slots)          # (a tracked centre is its identity's last centre: without one the identity ends)
         idx = self._slots(slots)
         if idx is None:
             self._track.fill_(float("nan"))
@@ -297,16 +349,63 @@ class Predictor:
             self._track.index_fill_(0, idx, float("nan"))
 
     def reset_smooth(self, slots=None):
-        """Drop the temporal filter's tracks of batch slots (default: all of them): their next usable frame starts a track.  Does not block."""
+        """Drop the temporal filter's tracks of batch slots (default: all of them; with hands >= 2 every hand of each): their next usable
+        frame starts a track.  Does not block."""
         if self.smooth is None:
             raise L.AwrError("reset_smooth needs a Predictor built with smooth=...")
         idx = self._slots(slots)
         if idx is None:
             self._filter_state.zero_()
             self._filter_count.zero_()
+        elif self.hands > 1:                     # hand-major rows: batch slot b is row k * max_batch + b of every hand k
+            self._filter_state.view(self.hands, self.B, self.J, 6).index_fill_(1, idx, 0.0)
+            self._filter_count.view(self.hands, self.B, self.J, 2).index_fill_(1, idx, 0)
         else:
             self._filter_state.index_fill_(0, idx, 0.0)
             self._filter_count.index_fill_(0, idx, 0)
+
+    def reset_identity(self, slots=None):
+        """Forget the hand identities of batch slots (default: all of them), every hand of each: their next call starts new identities (ids are
+        never used again) and, with smooth, new filter tracks.  Does not block."""
+        if self.identity is None:
+            raise L.AwrError("reset_identity needs a Predictor built with identity=...")
+        idx = self._slots(slots)
+        if idx is None:
+            self._id_last.fill_(float("nan"))
+            self._id_ids.zero_()
+            self._id_miss.zero_()
+        else:
+            self._id_last.index_fill_(1, idx, float("nan"))
+            self._id_ids.index_fill_(1, idx, 0)
+            self._id_miss.index_fill_(1, idx, 0)
+        if self.smooth is not None:
+            self.reset_smooth(slots)
+
+    def _set_track_hands(self, centers_uvd, slots):
+        """set_track with identities: centers_uvd (n, K, 3); a finite row puts slot k of its batch slot there -- it keeps the identity it has, a
+        free slot gets the next one -- and a NaN row ends the slot's identity.  Device arithmetic only; does not block."""
+        K, B, nan = self.hands, self.B, float("nan")
+        c = centers_uvd if isinstance(centers_uvd, torch.Tensor) else torch.from_numpy(np.ascontiguousarray(centers_uvd, dtype=np.float64))
+        if c.dim() != 3 or tuple(c.shape[1:]) != (K, 3) or not 0 < c.shape[0] <= B:
+            raise L.AwrError("centers_uvd must be (n, %d, 3) with n in [1, max_batch = %d], got %s" % (K, B, tuple(c.shape)))
+        n = int(c.shape[0])
+        idx = self._slots(slots, n)
+        if idx is None:
+            idx = torch.arange(n, dtype=torch.int64, device=self.device)
+        c = c.to(device=self.device, dtype=torch.float64, non_blocking=True).transpose(0, 1)          # (K, n, 3)
+        ids, nxt = self._id_ids.index_select(1, idx), self._id_next.index_select(0, idx)
+        finite = torch.isfinite(c).all(-1)
+        new = finite & (ids == 0)
+        fresh = (nxt[None] + new.cumsum(0) - 1).to(torch.int32)
+        ended = ~finite & (ids > 0)
+        self._id_ids.index_copy_(1, idx, torch.where(new, fresh, torch.where(finite, ids, torch.zeros_like(ids))))
+        self._id_miss.index_fill_(1, idx, 0)
+        self._id_next.index_copy_(0, idx, (nxt + new.sum(0)).to(torch.int32))
+        self._id_last.index_copy_(1, idx, torch.where(finite[..., None], c, torch.full_like(c, nan)))
+        if self.smooth is not None:
+            fs, fc = self._filter_state.view(K, B, self.J, 6), self._filter_count.view(K, B, self.J, 2)
+            fs.index_copy_(1, idx, torch.where(ended[..., None, None], torch.zeros_like(fs[:, :n]), fs.index_select(1, idx)))
+            fc.index_copy_(1, idx, torch.where(ended[..., None, None], torch.zeros_like(fc[:, :n]), fc.index_select(1, idx)))
 
     def _joints_center(self, xyz, cxyz, status, ustatus, nv, center_out, next_out, code):
         fx, fy, u0, v0 = self.paras
@@ -366,8 +465,12 @@ class Predictor:
         way slots [0, n_valid) of the tracker take this call's next_centers_uvd.  dt: seconds since the previous call, for a predictor with
         smooth (default 1 / its fps); xyz and uvd are then the filtered joints (see __init__)."""
         if self.hands > 1:
+            if self.identity is not None and self.smooth is not None:
+                return self._predict_identity(frames, centers_uvd, n_valid, T.check_dt(1.0 / self.smooth.fps if dt is None else dt))
             if dt is not None:
                 raise L.AwrError("predict(dt=...) is the temporal filter's time step: it needs a Predictor built with smooth=...")
+            if self.identity is not None:
+                return self._predict_identity(frames, centers_uvd, n_valid, None)
             return self._predict_hands(frames, centers_uvd, n_valid)
         if self.smooth is None:
             if dt is not None:
@@ -587,17 +690,146 @@ class Predictor:
             return ConfidentHandsPrediction(*fields, rows(conf[0]), rows(conf[1]), rows(conf[2]))
         return HandsPrediction(*fields)
 
+    def _predict_identity(self, frames, centers_uvd, n_valid, dt):
+        """predict() of a predictor with hands = K >= 2 and identity: _predict_hands with awr_hands_assign between the detector and the crop,
+        the optional tracker in front of it and the optional temporal filter behind the final pass"""
+        nb = self._upload(frames)
+        nv = nb if n_valid is None else int(n_valid)
+        if not 0 < nv <= nb:
+            raise L.AwrError("n_valid = %d is outside [1, %d]" % (nv, nb))
+        dev, B, K, J, s = self.device, self.B, self.hands, self.J, L.stream()
+        P = B * K
+        fx, fy, u0, v0 = self.paras
+        nan, cfg = float("nan"), self.identity
+        seeds = self._seed.view(K, B, 3)
+        if centers_uvd is not None:
+            c = centers_uvd if isinstance(centers_uvd, torch.Tensor) else torch.from_numpy(np.ascontiguousarray(centers_uvd, dtype=np.float64))
+            if tuple(c.shape) != (nb, K, 3):
+                raise L.AwrError("centers_uvd must be (%d, %d, 3): a centre per frame and hand, NaN rows for an absent hand, got %s" % (nb, K, tuple(c.shape)))
+            seeds[:, :nb].copy_(c.transpose(0, 1), non_blocking=True)          # (converts to float64 on the way)
+            self.hand_info = None
+        else:
+            L.call("awr_detect_hands", self._frames.data_ptr(), 0, B, self.fh, self.fw, self._idx.data_ptr(), B, K, self.depth_range[0],
+                   self.depth_range[1], self.reach, self.slab, self.min_pixels, self._hands_scratch.data_ptr(), None, self._seed.data_ptr(),
+                   self._hands_status.data_ptr(), self._hands_info.data_ptr(), self._hands_count.data_ptr(), s)
+            self.hand_info = self._hands_info[:, :nb].transpose(0, 1)
+        if nv < B:
+            seeds[:, nv:].fill_(nan)                 # rows past n_valid of every block: NaN seeds, candidates that are EMPTY
+        M = torch.empty((P, 3, 3), dtype=torch.float32, device=dev)
+        cxyz = torch.empty((P, 3), dtype=torch.float32, device=dev)
+        status = torch.empty(P, dtype=torch.int32, device=dev)
+        ustatus = torch.zeros(P, dtype=torch.int32, device=dev)
+        uvd = torch.empty((P, J, 3), dtype=torch.float32, device=dev)
+        xyz = torch.empty((P, J, 3), dtype=torch.float32, device=dev)
+        assigned = torch.empty((3, K, B), dtype=torch.int32, device=dev)          # code, reset, source
+        dropped = torch.empty(B, dtype=torch.int32, device=dev)
+
+        def detect(seed, centers, dstatus):
+            L.call("awr_detect", self._frames.data_ptr(), 0, B, self.fh, self.fw, self._idx.data_ptr(), P, D.SEED_GIVEN, seed.data_ptr(),
+                   self.depth_range[0], self.depth_range[1], self.slab, self._cube.data_ptr(), 0, fx, fy, self.iters, 0, self._scratch.data_ptr(),
+                   centers.data_ptr(), dstatus.data_ptr(), s)
+
+        # the candidates: the detector over the K nearest components' seeds, in depth order
+        detect(self._seed, self._cand, self._cand_status)
+        if self.palm and centers_uvd is None:
+            L.call("awr_detect_palm", self._frames.data_ptr(), 0, B, self.fh, self.fw, self._idx.data_ptr(), P, self._cand.data_ptr(),
+                   self._cand_status.data_ptr(), self.depth_range[0], self.depth_range[1], self._cube.data_ptr(), 0, fx, fy, self.palm_search,
+                   D.PALM_TAU[0], D.PALM_TAU[1], D.PALM_RHO2[0], D.PALM_RHO2[1], self._palm_scratch.data_ptr(), self._cand.data_ptr(),
+                   self._cand_status.data_ptr(), self._palm_info.data_ptr(), s)
+            self.palm_info = self._palm_info.view(K, B, 4)[:, :nb].transpose(0, 1)
+        if self.track:
+            # every slot's last centre as a given seed (a free slot's NaN seed finds nothing): where it still finds the hand the slot is held
+            detect(self._track, self._tcenters, self._tstatus)
+        smooth = self.smooth is not None
+        L.call("awr_hands_assign", self._id_last.data_ptr(), self._id_ids.data_ptr(), self._id_miss.data_ptr(), self._id_next.data_ptr(),
+               self._cand.data_ptr(), self._cand_status.data_ptr(), self._tcenters.data_ptr() if self.track else None,
+               self._tstatus.data_ptr() if self.track else None, K, B, nv, cfg.gate_mm, cfg.merge_mm, cfg.max_miss, fx, fy, u0, v0, self.flip,
+               self._filter_state.data_ptr() if smooth else None, self._filter_count.data_ptr() if smooth else None, J if smooth else 0,
+               self._centers.data_ptr(), status.data_ptr(), L.ptr(assigned[0]), L.ptr(assigned[1]), L.ptr(assigned[2]), dropped.data_ptr(), s)
+
+        def crop_and_predict():
+            L.call("awr_detect_samples", self._centers.data_ptr(), self._cube.data_ptr(), 0, B, self._idx.data_ptr(), P, self.S, self.fh, self.fw,
+                   fx, fy, u0, v0, self.flip, self._blocks.data_ptr(), L.ptr(M), L.ptr(cxyz), L.ptr(self._cube32), status.data_ptr(), s)
+            self._render(self._blocks, out=self._img)
+            jt = self.engine(self._img)
+            L.call("awr_joints_unproject", L.ptr(jt), L.ptr(cxyz), L.ptr(M), L.ptr(self._cube32), P, J, P, float(self.S), fx, fy, u0, v0, self.flip,
+                   L.ptr(uvd), L.ptr(xyz), ustatus.data_ptr(), s)
+
+        def joints_center(joints, center_out, next_out, code):
+            L.call("awr_joints_center", L.ptr(joints), self._centers.data_ptr(), L.ptr(cxyz), L.ptr(self._cube32), status.data_ptr(), ustatus.data_ptr(),
+                   P, J, P, L.ptr(self._joints), 0 if self._joints is None else int(self._joints.numel()), fx, fy, u0, v0, self.flip,
+                   self.depth_range[0], self.depth_range[1], self.max_shift, center_out.data_ptr(), L.ptr(next_out), code.data_ptr(), s)
+
+        def smooth_step():
+            """K launches of awr_joints_filter, one per hand block: the rows past n_valid of EVERY block keep their state"""
+            scfg = self.smooth
+            weighted = scfg.weight == "conf"
+            conf = self.engine.conf[..., 0].contiguous() if weighted else None          # (P, J)
+            out = [torch.empty((P, J, 3), dtype=torch.float32, device=dev) for _ in range(3)] + [torch.empty((P, J), dtype=torch.int32, device=dev)]
+            for k in range(K):
+                o = k * B
+                L.call("awr_joints_filter", self._filter_state[o:].data_ptr(), self._filter_count[o:].data_ptr(), xyz[o:].data_ptr(),
+                       status[o:].data_ptr(), ustatus[o:].data_ptr(), conf[o:].data_ptr() if weighted else None, B, J, nv, dt, scfg.min_cutoff,
+                       scfg.beta, scfg.d_cutoff, -1.0 if scfg.gate_mm is None else scfg.gate_mm, scfg.max_coast, T.WEIGHTS[scfg.weight],
+                       scfg.conf_floor, fx, fy, u0, v0, self.flip, out[0][o:].data_ptr(), out[1][o:].data_ptr(), out[2][o:].data_ptr(),
+                       out[3][o:].data_ptr(), s)
+            return out
+
+        def rows(t):          # hand-major (K * B, ...) -> a (nb, K, ...) view
+            return t.view((K, B) + tuple(t.shape[1:]))[:, :nb].transpose(0, 1)
+
+        crop_and_predict()
+        smoothed = None
+        if self.recenter or self.track:
+            codes = torch.zeros((self.recenter + 1, P), dtype=torch.int32, device=dev)
+            for k in range(self.recenter):
+                joints_center(xyz, self._centers, None, codes[k])
+                crop_and_predict()
+            nxt = torch.full((P, 3), nan, dtype=torch.float64, device=dev)
+            next_from = xyz
+            if smooth and self.smooth.lead:
+                # the next call's crop starts where constant velocity says the hand will be: filter first, centre the look-ahead joints
+                smoothed = smooth_step()
+                next_from = smoothed[2]
+            joints_center(next_from, self._moved, nxt, codes[self.recenter])
+            # every slot's last centre becomes its joints' centre where there is one: `nxt` where finite, else what it was
+            L.call("awr_centers_select", nxt.data_ptr(), self._zero_status.data_ptr(), self._id_last.data_ptr(), self._cand_status.data_ptr(), P,
+                   self._sel.data_ptr(), self._sel_status.data_ptr(), None, s)
+            self._id_last.view(P, 3).copy_(self._sel)
+            self.centers_uvd = rows(self._centers.clone())
+            self.next_centers_uvd = rows(nxt)
+            self.recenter_codes = codes.view(self.recenter + 1, K, B)[:, :, :nb].transpose(1, 2)
+        self._last = (status.view(K, B), ustatus.view(K, B), nv)
+        n_hands = (status.view(K, B)[:, :nb] == D.OK).sum(0, dtype=torch.int32)
+        self.hand_codes, self.hand_source, self.hands_dropped = rows(assigned[0].reshape(P)), rows(assigned[2].reshape(P)), dropped[:nb]
+        out_xyz, out_uvd = xyz, uvd
+        if smooth:
+            out_xyz, out_uvd, ahead, fcodes = smoothed or smooth_step()
+            self.raw_xyz, self.raw_uvd, self.ahead_xyz, self.filter_codes = rows(xyz), rows(uvd), rows(ahead), rows(fcodes)
+        ids = self._id_ids[:, :nb].transpose(0, 1).clone()          # (the state moves on with the next call)
+        fields = (rows(out_xyz), rows(out_uvd), rows(cxyz), rows(M), rows(status), n_hands, ids)
+        if self.confidence:
+            conf = torch.empty((3, P, J), dtype=torch.float32, device=dev)
+            L.call("awr_confidence_fields", L.ptr(self.engine.conf), L.ptr(self.engine.stat), L.ptr(self._cube32), status.data_ptr(),
+                   ustatus.data_ptr(), P, J, P, L.ptr(conf[0]), L.ptr(conf[1]), L.ptr(conf[2]), s)
+            return ConfidentTrackedHandsPrediction(*fields, rows(conf[0]), rows(conf[1]), rows(conf[2]))
+        return TrackedHandsPrediction(*fields)
+
     def check(self):
         """Synchronising: raise AwrError naming the first frame of the last batch that could not be predicted, and its status code.  With
         hands >= 2: the first frame whose slot 0 (the nearest hand) is not OK, or a found hand whose un-projection failed; an absent
-        second hand is not an error."""
+        second hand is not an error.  With identity: the first frame without ANY slot that is OK; an EMPTY slot 0 is not an error."""
         if self._last is None:
             return
         status, ustatus, nv = self._last
         if self.hands > 1:
             st, ust = status[:, :nv].tolist(), ustatus[:, :nv].tolist()
             for b in range(nv):
-                if st[0][b] != D.OK:
+                if self.identity is not None:      # a slot is an identity, not a depth rank: slot 0 may well be the one that is away
+                    if all(st[k][b] != D.OK for k in range(self.hands)):
+                        raise L.AwrError("predict: frame %d of the batch: no hand slot is OK (slot 0: %s, status %d); no hand was found and its "
+                                         "joints are NaN" % (b, D.STATUS_NAMES.get(st[0][b], "invalid"), st[0][b]))
+                elif st[0][b] != D.OK:
                     raise L.AwrError("predict: frame %d of the batch, hand slot 0: %s (status %d); no hand was found and its joints are NaN"
                                      % (b, D.STATUS_NAMES.get(st[0][b], "invalid"), st[0][b]))
                 for k in range(self.hands):

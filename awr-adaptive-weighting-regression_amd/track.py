@@ -1,5 +1,6 @@
 """Temporal joint filter: the numpy statement of awr_joints_filter (csrc/awr_track.hip; include/awr_hip.h "Temporal joint filter";
-DESIGN.md 4.25) and its thin device wrapper.
+DESIGN.md 4.25) and its thin device wrapper; further down, hand identities across calls: the numpy statement of awr_hands_assign
+(csrc/awr_assign.hip; include/awr_hip.h "Hand identities across calls"), `assign_step`, and its wrapper.
 
 A One-Euro filter (Casiez, Roussel, Vogel 2012) per batch slot, joint and axis over camera-space joints: a first-order low-pass whose
 cut-off rises with the filtered speed, so a still hand is smoothed hard and a fast one lags little.  Around it sit the three answers a
@@ -248,4 +249,268 @@ def filter_step_device(state, count, xyz, status, ustatus, conf, cfg, dt=None, n
            B if n_valid is None else int(n_valid), dt, cfg.min_cutoff, cfg.beta, cfg.d_cutoff, -1.0 if cfg.gate_mm is None else cfg.gate_mm,
            cfg.max_coast, WEIGHTS[cfg.weight], cfg.conf_floor, float(paras[0]), float(paras[1]), float(paras[2]), float(paras[3]), int(flip),
            L.ptr(out[0]), L.ptr(out[1]), L.ptr(out[2]), L.ptr(out[3]), L.stream())
+    return out
+
+
+# ---- hand identities across calls (include/awr_hip.h awr_hands_assign; csrc/awr_assign.hip) --------------------------------
+# Predictor(hands=K) reports "the k-th nearest component of this frame" in slot k.  assign_step decides which of this call's detected hands
+# is which identity of the previous call: an exact assignment over all K! permutations (K <= 4: at most 24), largest number of pairs inside
+# the gate first, smallest summed squared distance second, first permutation third.  Positions are compared in camera millimetres; the
+# arithmetic is IEEE double + - * / and comparisons only, no square root: squared distances against gate_mm^2 and merge_mm^2.
+# awr_hands_assign's codes (include/awr_hip.h AWR_ASSIGN_*)
+FREE, BORN, MATCHED, TRACKED, COASTING, ID_LOST, MERGED = 0, 1, 2, 3, 4, 5, 6
+ASSIGN_NAMES = {FREE: "no identity in this slot", BORN: "a new identity started at a candidate", MATCHED: "the identity took a candidate inside the gate",
+                TRACKED: "the identity's tracked centre found the hand", COASTING: "no candidate inside the gate: the identity waits",
+                ID_LOST: "waited too long: the identity was released", MERGED: "two tracked centres on one hand: the younger identity was released"}
+SOURCE_NONE, SOURCE_TRACKED = -1, -2
+MAX_HANDS = 4
+_OK, _EMPTY = 0, 1                      # awr_amd.detect's status codes (AWR_DET_OK, AWR_DET_EMPTY)
+
+# gate_mm: the furthest a hand's centre may move between two calls and keep its identity; merge_mm: two TRACKED centres closer than this are
+# one hand; max_miss: calls an identity waits without a candidate before it is released.  ENGINEERING CHOICES -- half a crop cube, a palm's
+# width, a sixth of a second at 30 fps -- and unmeasured on real frames: none are available where this was written.
+_Identity = collections.namedtuple("Identity", "gate_mm merge_mm max_miss")
+
+
+class Identity(_Identity):
+    """The identity assignment's configuration, an immutable record.  gate_mm (> 0): a candidate further than this from an identity's last
+    centre (camera mm) is not that identity; merge_mm (>= 0): two tracked centres within this distance are one hand and the younger identity
+    is released; max_miss (int >= 0): calls an identity survives without a candidate.  The defaults are unmeasured engineering choices."""
+    __slots__ = ()
+
+    def __new__(cls, gate_mm=150.0, merge_mm=60.0, max_miss=5):
+        return super().__new__(cls, gate_mm, merge_mm, max_miss)
+
+
+def check_identity(cfg):
+    """True (the defaults) | a dict of Identity's fields | an Identity -> a validated Identity with plain Python values (the rules are
+    awr_hands_assign's argument rules)."""
+    if cfg is True:
+        cfg = Identity()
+    elif isinstance(cfg, dict):
+        unknown = sorted(set(cfg) - set(Identity._fields))
+        if unknown:
+            raise ValueError("unknown identity option(s) %s: the options are %s" % (unknown, list(Identity._fields)))
+        cfg = Identity(**cfg)
+    elif not isinstance(cfg, Identity):
+        raise TypeError("identity is None, True, a dict or a track.Identity, not %r" % (cfg,))
+    gate_mm, merge_mm = _number("gate_mm", cfg.gate_mm), _number("merge_mm", cfg.merge_mm)
+    if not (gate_mm > 0.0 and math.isfinite(gate_mm)):
+        raise ValueError("gate_mm = %r must be finite and positive (mm)" % (cfg.gate_mm,))
+    if not (merge_mm >= 0.0 and math.isfinite(merge_mm)):
+        raise ValueError("merge_mm = %r must be finite and >= 0 (mm)" % (cfg.merge_mm,))
+    if isinstance(cfg.max_miss, bool) or not isinstance(cfg.max_miss, (int, np.integer)):
+        raise TypeError("max_miss is an int >= 0, not %r" % (cfg.max_miss,))
+    if not 0 <= int(cfg.max_miss) <= INT32_MAX - 1:
+        raise ValueError("max_miss = %r is outside [0, %d]" % (cfg.max_miss, INT32_MAX - 1))
+    return Identity(gate_mm, merge_mm, int(cfg.max_miss))
+
+
+def identity_state(K, B):
+    """-> (last_uvd (K, B, 3) float64 NaN, ids (K, B) int32 0, miss (K, B) int32 0, next_id (B,) int32 1): no identity anywhere.  Hand-major,
+    like every buffer of Predictor(hands=K); an identity is a positive int, unique within its batch slot and never used again."""
+    K, B = int(K), int(B)
+    if not (1 <= K <= MAX_HANDS and 1 <= B <= MAX_BATCH):
+        raise ValueError("identity_state: K in [1, %d] and B in [1, %d] are required, got %d and %d" % (MAX_HANDS, MAX_BATCH, K, B))
+    return np.full((K, B, 3), np.nan, np.float64), np.zeros((K, B), np.int32), np.zeros((K, B), np.int32), np.ones(B, np.int32)
+
+
+def permutation(p, K):
+    """the p-th permutation of range(K) in lexicographic order, decoded in the factorial number system (as the kernel's lanes do)"""
+    left, out = list(range(K)), []
+    for i in range(K):
+        f = math.factorial(K - 1 - i)
+        out.append(left.pop(p // f))
+        p %= f
+    return out
+
+
+def _finite3(row):
+    return bool(np.isfinite(row[0]) and np.isfinite(row[1]) and np.isfinite(row[2]))
+
+
+def _state_arrays(last_uvd, ids, miss, next_id):
+    if not (isinstance(last_uvd, np.ndarray) and last_uvd.dtype == np.float64 and last_uvd.ndim == 3 and last_uvd.shape[2] == 3 and last_uvd.flags.c_contiguous):
+        raise ValueError("last_uvd is a contiguous (K, B, 3) float64 array (identity_state)")
+    K, B = last_uvd.shape[0], last_uvd.shape[1]
+    for a, name, shape in ((ids, "ids", (K, B)), (miss, "miss", (K, B)), (next_id, "next_id", (B,))):
+        if not (isinstance(a, np.ndarray) and a.dtype == np.int32 and a.shape == shape and a.flags.c_contiguous):
+            raise ValueError("%s is a contiguous %s int32 array (identity_state)" % (name, shape))
+    return K, B
+
+
+def assign_step(last_uvd, ids, miss, next_id, cand_uvd, cand_status, trk_uvd=None, trk_status=None, cfg=True, n_valid=None, paras=ND.PARAS, flip=-1,
+                filter_state=None, filter_count=None):
+    """The statement of awr_hands_assign (include/awr_hip.h): one step of the identity assignment.  last_uvd (K, B, 3) float64, ids, miss
+    (K, B) int32 and next_id (B,) int32 (identity_state) are updated IN PLACE.  cand_uvd (K, B, 3) float64 / cand_status (K, B): this call's
+    detected hands, awr_detect's outputs over awr_detect_hands' seeds; trk_uvd / trk_status: awr_detect's outputs over last_uvd as given
+    seeds, or None without a tracker.  filter_state ((K * B, J, 6) float64) / filter_count ((K * B, J, 2) int32): the temporal filter's state,
+    whose rows of every slot that starts or loses an identity are zeroed in place; None without one.  Rows >= n_valid keep their state.
+    -> (centers (K, B, 3) float64, status (K, B) int32, code (K, B) int32, reset (K, B) int32, source (K, B) int32, dropped (B,) int32).
+    An explicit loop in IEEE double, in the header's order."""
+    cfg = check_identity(cfg)
+    K, B = _state_arrays(last_uvd, ids, miss, next_id)
+    cand_uvd, cand_status = np.asarray(cand_uvd, np.float64), np.asarray(cand_status)
+    if cand_uvd.shape != (K, B, 3) or cand_status.shape != (K, B):
+        raise ValueError("cand_uvd is (%d, %d, 3) and cand_status (%d, %d), got %s and %s" % (K, B, K, B, cand_uvd.shape, cand_status.shape))
+    tracked = trk_uvd is not None
+    if tracked:
+        trk_uvd, trk_status = np.asarray(trk_uvd, np.float64), np.asarray(trk_status)
+        if trk_uvd.shape != (K, B, 3) or trk_status.shape != (K, B):
+            raise ValueError("trk_uvd is (%d, %d, 3) and trk_status (%d, %d), got %s and %s" % (K, B, K, B, trk_uvd.shape, trk_status.shape))
+    nv = B if n_valid is None else int(n_valid)
+    fx, fy, u0, v0 = (np.float64(p) for p in paras)
+    if not (1 <= K <= MAX_HANDS and 1 <= B <= MAX_BATCH and 0 <= nv <= B and int(flip) in (1, -1) and fx != 0 and fy != 0):
+        raise ValueError("assign_step: K in [1, %d], n_valid in [0, B], flip = +-1 and non-zero focal lengths are required" % MAX_HANDS)
+    if (filter_state is None) != (filter_count is None):
+        raise ValueError("filter_state and filter_count come together")
+    if filter_state is not None:
+        J = filter_state.shape[1] if filter_state.ndim == 3 else 0
+        if not (filter_state.dtype == np.float64 and filter_state.shape == (K * B, J, 6) and filter_count.dtype == np.int32
+                and filter_count.shape == (K * B, J, 2) and 1 <= J <= MAX_JOINTS):
+            raise ValueError("filter_state is (K * B, J, 6) float64 and filter_count (K * B, J, 2) int32")
+    fl = np.float64(flip)
+    gate2, merge2, max_miss = np.float64(cfg.gate_mm) * np.float64(cfg.gate_mm), np.float64(cfg.merge_mm) * np.float64(cfg.merge_mm), int(cfg.max_miss)
+    nan = np.float64(np.nan)
+
+    def xyz(c):                                                   # evaluator.uvd2xyz in its operation order, kept in double
+        return ((c[0] - u0) * c[2] / fx, (c[1] - v0) * c[2] / fy * fl, c[2])
+
+    def dist2(a, b):
+        d = [a[0] - b[0], a[1] - b[1], a[2] - b[2]]
+        return (d[0] * d[0] + d[1] * d[1]) + d[2] * d[2]
+
+    centers = np.full((K, B, 3), np.nan, np.float64)
+    status = np.full((K, B), _EMPTY, np.int32)
+    code, reset, dropped = np.zeros((K, B), np.int32), np.zeros((K, B), np.int32), np.zeros(B, np.int32)
+    source = np.full((K, B), SOURCE_NONE, np.int32)
+    with np.errstate(all="ignore"):
+        for b in range(nv):
+            ident = [int(ids[i, b]) for i in range(K)]
+            ms = [int(miss[i, b]) for i in range(K)]
+            cd, released = [FREE] * K, [False] * K
+            # 1. held slots; two tracked centres on one hand: the younger identity goes
+            held = [bool(tracked and ident[i] > 0 and trk_status[i, b] == _OK and _finite3(trk_uvd[i, b])) for i in range(K)]
+            r = [xyz(trk_uvd[i, b]) if held[i] else xyz(last_uvd[i, b]) for i in range(K)]
+            for i in range(K):
+                for j in range(i + 1, K):
+                    if held[i] and held[j] and dist2(r[i], r[j]) <= merge2:
+                        g = j if ident[j] > ident[i] else i
+                        held[g], ident[g], ms[g], cd[g], released[g] = False, 0, 0, MERGED, True
+            # 2. usable candidates, admissible pairs
+            usable = [bool(cand_status[j, b] == _OK and _finite3(cand_uvd[j, b])) for j in range(K)]
+            q = [xyz(cand_uvd[j, b]) for j in range(K)]
+            c = [[dist2(r[i], q[j]) for j in range(K)] for i in range(K)]
+            adm = [[bool(ident[i] > 0 and usable[j] and c[i][j] <= gate2) for j in range(K)] for i in range(K)]
+            # 3. the permutation: most pairs, then the smallest sum, then the first
+            best = None
+            for p in range(math.factorial(K)):
+                perm = permutation(p, K)
+                m, s = 0, np.float64(0.0)
+                for i in range(K):
+                    if adm[i][perm[i]]:
+                        m, s = m + 1, s + c[i][perm[i]]
+                if best is None or m > best[0] or (m == best[0] and s < best[1]):
+                    best = (m, s, perm)
+            perm = best[2]
+            # 4. every live slot
+            consumed = [False] * K
+            out = [None] * K                                      # the candidate index, SOURCE_TRACKED, or None
+            for i in range(K):
+                if ident[i] <= 0:
+                    continue
+                j = perm[i] if adm[i][perm[i]] else -1
+                if held[i]:
+                    out[i], ms[i], cd[i] = SOURCE_TRACKED, 0, TRACKED
+                    if j >= 0:
+                        consumed[j] = True                        # the same hand, seen twice
+                elif j >= 0:
+                    out[i], ms[i], cd[i], consumed[j] = j, 0, MATCHED, True
+                else:
+                    ms[i] += 1
+                    if ms[i] <= max_miss:
+                        cd[i] = COASTING
+                    else:
+                        ident[i], ms[i], cd[i], released[i] = 0, 0, ID_LOST, True
+            # 5. births: the lowest free slot, else the slot that has coasted longest
+            nid = int(next_id[b])
+            for j in range(K):
+                if not usable[j] or consumed[j]:
+                    continue
+                slot = -1
+                for i in range(K):
+                    if ident[i] == 0:
+                        slot = i
+                        break
+                if slot < 0:
+                    for i in range(K):
+                        if cd[i] == COASTING and (slot < 0 or ms[i] > ms[slot]):
+                            slot = i
+                if slot < 0:
+                    dropped[b] += 1
+                    continue
+                ident[slot], ms[slot], cd[slot], out[slot], reset[slot, b] = nid, 0, BORN, j, 1
+                nid = min(nid + 1, INT32_MAX)
+            next_id[b] = nid
+            # 6. outputs and state
+            for i in range(K):
+                if out[i] is not None:
+                    centers[i, b] = trk_uvd[i, b] if out[i] == SOURCE_TRACKED else cand_uvd[out[i], b]
+                    status[i, b], source[i, b] = _OK, out[i]
+                    last_uvd[i, b] = centers[i, b]
+                elif ident[i] == 0:
+                    last_uvd[i, b] = nan
+                ids[i, b], miss[i, b], code[i, b] = ident[i], ms[i], cd[i]
+                if filter_state is not None and (reset[i, b] or released[i]):
+                    filter_state[i * B + b], filter_count[i * B + b] = 0.0, 0
+    return centers, status, code, reset, source, dropped
+
+
+def identity_state_device(K, B, device="cuda"):
+    """identity_state as device tensors"""
+    import torch
+    return tuple(torch.from_numpy(a).to(device) for a in identity_state(K, B))
+
+
+def assign_step_device(last_uvd, ids, miss, next_id, cand_uvd, cand_status, trk_uvd=None, trk_status=None, cfg=True, n_valid=None, paras=ND.PARAS,
+                       flip=-1, filter_state=None, filter_count=None, out=None):
+    """awr_hands_assign on device tensors: the state (identity_state_device) stays on the device and is updated in place, as are the rows of
+    filter_state / filter_count that start or lose an identity; -> (centers (K, B, 3) float64, status, code, reset, source (K, B) int32,
+    dropped (B,) int32) device tensors (`out`: these six, to write into).  Nothing synchronises.  There is no host fall-back: assign_step is
+    the statement for a machine without a GPU."""
+    import torch
+    from . import _lib as L
+    cfg = check_identity(cfg)
+    if last_uvd.dtype != torch.float64 or last_uvd.dim() != 3 or last_uvd.shape[2] != 3:
+        raise L.AwrError("last_uvd is a (K, B, 3) float64 device tensor")
+    K, B = int(last_uvd.shape[0]), int(last_uvd.shape[1])
+    for t, name, shape in ((ids, "ids", (K, B)), (miss, "miss", (K, B)), (next_id, "next_id", (B,)), (cand_status, "cand_status", (K, B))):
+        if t.dtype != torch.int32 or tuple(t.shape) != shape:
+            raise L.AwrError("%s is a %s int32 device tensor" % (name, shape))
+    if cand_uvd.dtype != torch.float64 or tuple(cand_uvd.shape) != (K, B, 3):
+        raise L.AwrError("cand_uvd is a (%d, %d, 3) float64 device tensor" % (K, B))
+    if (trk_uvd is None) != (trk_status is None):
+        raise L.AwrError("trk_uvd and trk_status come together")
+    if trk_uvd is not None and (trk_uvd.dtype != torch.float64 or tuple(trk_uvd.shape) != (K, B, 3) or trk_status.dtype != torch.int32
+                                or tuple(trk_status.shape) != (K, B)):
+        raise L.AwrError("trk_uvd is a (%d, %d, 3) float64 and trk_status a (%d, %d) int32 device tensor" % (K, B, K, B))
+    J = 0
+    if (filter_state is None) != (filter_count is None):
+        raise L.AwrError("filter_state and filter_count come together")
+    if filter_state is not None:
+        J = int(filter_state.shape[1]) if filter_state.dim() == 3 else 0
+        if (filter_state.dtype != torch.float64 or tuple(filter_state.shape) != (K * B, J, 6) or filter_count.dtype != torch.int32
+                or tuple(filter_count.shape) != (K * B, J, 2)):
+            raise L.AwrError("filter_state is a (K * B, J, 6) float64 and filter_count a (K * B, J, 2) int32 device tensor")
+    dev = last_uvd.device
+    if out is None:
+        out = ((torch.empty((K, B, 3), dtype=torch.float64, device=dev),) + tuple(torch.empty((K, B), dtype=torch.int32, device=dev) for _ in range(4))
+               + (torch.empty(B, dtype=torch.int32, device=dev),))
+    for t, shape, dtype in zip(out, ((K, B, 3),) + ((K, B),) * 4 + ((B,),), (torch.float64,) + (torch.int32,) * 5):
+        if tuple(t.shape) != shape or t.dtype != dtype:
+            raise L.AwrError("out is (centers (K, B, 3) float64, status, code, reset, source (K, B) int32, dropped (B,) int32)")
+    L.call("awr_hands_assign", L.ptr(last_uvd), L.ptr(ids), L.ptr(miss), L.ptr(next_id), L.ptr(cand_uvd), L.ptr(cand_status), L.ptr(trk_uvd),
+           L.ptr(trk_status), K, B, B if n_valid is None else int(n_valid), cfg.gate_mm, cfg.merge_mm, cfg.max_miss, float(paras[0]), float(paras[1]),
+           float(paras[2]), float(paras[3]), int(flip), L.ptr(filter_state), L.ptr(filter_count), J, L.ptr(out[0]), L.ptr(out[1]), L.ptr(out[2]),
+           L.ptr(out[3]), L.ptr(out[4]), L.ptr(out[5]), L.stream())
     return out

@@ -1153,6 +1153,58 @@ int awr_joints_filter(double* state, int* count, const float* xyz, const int* st
                       double conf_floor, double fx, double fy, double u0, double v0, int flip, float* xyz_out, float* uvd_out,
                       float* ahead_out, int* code, void* stream);
 
+/* ------------------------------------------------------------------------------------------
+ * Hand identities across calls (csrc/awr_assign.hip; statement: awr_amd/track.py assign_step, results are bit-identical to it)
+ *
+ * awr_hands_assign decides, per frame, which of this call's K detected hands is which identity of the previous call.  Every (K, B, ...)
+ * array is HAND-MAJOR: slot or candidate k of frame b is row k * B + b.
+ *   state, updated in place:  last_uvd (K, B, 3) doubles, the uvd centre an identity was last seen at (NaN: a free slot);  ids (K, B)
+ *     int32, > 0 an identity, 0 a free slot;  miss (K, B) int32, calls without a candidate;  next_id (B) int32, the next identity of
+ *     the frame's batch slot (start: 1; identities are never used again; it saturates at INT_MAX).
+ *   cand_uvd (K, B, 3) doubles, cand_status (K, B): this call's hands, awr_detect's outputs over awr_detect_hands' seeds.
+ *   trk_uvd, trk_status: awr_detect's outputs over last_uvd as given seeds -- the tracker -- or both NULL.
+ * Constants of a call, on the host in double: gate2 = gate_mm * gate_mm, merge2 = merge_mm * merge_mm.  Positions are compared in camera
+ * millimetres: xyz(c) = ((c.u - u0) * c.d / fx, (c.v - v0) * c.d / fy * flip, c.d), evaluator.uvd2xyz's order;
+ * |a - b|^2 = (dx * dx + dy * dy) + dz * dz.  IEEE double without contraction, + - * / and comparisons only: no square root.
+ * Per frame b < n_valid:
+ *   1. slot i is live iff ids > 0; with trk_*, a live slot is HELD iff its trk_status is AWR_DET_OK and its trk_uvd row is finite.
+ *      r_i = xyz(trk_uvd) if held, else xyz(last_uvd).  For the pairs i < j in lexicographic order, both still held and
+ *      |r_i - r_j|^2 <= merge2: the one with the larger id is released (id 0, miss 0, last_uvd NaN, AWR_ASSIGN_MERGED) and takes no further part.
+ *   2. candidate j is usable iff its status is AWR_DET_OK and its row is finite; c_ij = |r_i - xyz(cand_j)|^2; (i, j) is admissible iff
+ *      slot i is live, candidate j usable and c_ij <= gate2 (a NaN is not).
+ *   3. over the K! permutations p of 0 .. K - 1 in lexicographic order: m(p) = the admissible (i, p[i]), s(p) = the sum of their c from
+ *      0.0 in ascending i.  The largest m, then the smallest s, then the first p wins; its admissible pairs are the matches.
+ *   4. a live slot that is held: centre = trk_uvd, AWR_ASSIGN_TRACKED, miss = 0, source AWR_ASSIGN_SOURCE_TRACKED; its match, if any, is
+ *      consumed (the same hand seen twice).  Not held but matched: the candidate's centre, AWR_ASSIGN_MATCHED, miss = 0, source j.
+ *      Neither: miss += 1, no centre; AWR_ASSIGN_COASTING while miss <= max_miss, beyond it released as in 1. with AWR_ASSIGN_LOST.
+ *   5. births: the usable candidates not consumed, in ascending j, each take the lowest free slot; if none is free, the COASTING slot of
+ *      this step with the largest miss (the lowest index on ties), whose identity ends; if there is neither, dropped[b] += 1.  A birth:
+ *      id = next_id++, miss = 0, AWR_ASSIGN_BORN, reset = 1, source j.
+ *   6. centers (K, B, 3) doubles: the slot's centre bit for bit, NaN without one;  status (K, B): AWR_DET_OK with a centre, else
+ *      AWR_DET_EMPTY;  code (K, B): AWR_ASSIGN_*;  reset (K, B): 1 for a birth;  source (K, B);  dropped (B).  last_uvd takes the centre
+ *      where the status is AWR_DET_OK.  With filter_state ((K * B, J, 6) doubles) and filter_count ((K * B, J, 2) int32), awr_joints_filter's
+ *      state over the same rows (both NULL: none), the rows of every slot with reset = 1 or a released identity are zeroed: no track.
+ * Frames >= n_valid keep their state; their outputs are NaN / AWR_DET_EMPTY / AWR_ASSIGN_FREE / 0 / AWR_ASSIGN_SOURCE_NONE / 0.
+ * One wave per frame, four frames per 256-thread workgroup: lane p < K! evaluates permutation p, an xor-shuffle reduction over the total
+ * order of 3. picks the winner; no atomics, no LDS, nothing synchronises, one launch on `stream`.  A NULL pointer (trk_* and filter_*
+ * excepted, each pair NULL together), K outside [1, AWR_ASSIGN_MAX_HANDS], B outside [1, AWR_FILTER_MAX_BATCH], n_valid outside [0, B],
+ * gate_mm not finite or <= 0, merge_mm not finite or < 0, max_miss outside [0, INT_MAX), flip not +-1, a zero focal length or, with
+ * filter_state, J outside [1, AWR_FILTER_MAX_JOINTS] return AWR_ERR_ARG with a message, before any launch.  K = 1 is legal. */
+#define AWR_ASSIGN_FREE 0
+#define AWR_ASSIGN_BORN 1
+#define AWR_ASSIGN_MATCHED 2
+#define AWR_ASSIGN_TRACKED 3
+#define AWR_ASSIGN_COASTING 4
+#define AWR_ASSIGN_LOST 5
+#define AWR_ASSIGN_MERGED 6
+#define AWR_ASSIGN_SOURCE_NONE (-1)
+#define AWR_ASSIGN_SOURCE_TRACKED (-2)
+#define AWR_ASSIGN_MAX_HANDS 4
+int awr_hands_assign(double* last_uvd, int* ids, int* miss, int* next_id, const double* cand_uvd, const int* cand_status, const double* trk_uvd,
+                     const int* trk_status, int K, int B, int n_valid, double gate_mm, double merge_mm, int max_miss, double fx, double fy,
+                     double u0, double v0, int flip, double* filter_state, int* filter_count, int J, double* centers, int* status, int* code,
+                     int* reset, int* source, int* dropped, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

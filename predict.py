@@ -26,7 +26,11 @@ nearest large ones (--reach MM: how far behind the nearest pixel that foreground
 that counts, default 400; DESIGN.md 4.26 -- both UNMEASURED on real frames; touching hands are one hand).  The saved arrays gain the hand
 axis: pred_uvd.txt / pred_xyz.txt hold n * K rows (frame-major, the nearest hand first; an absent hand's row is nan), and pred_n_hands.txt
 (one count per frame), pred_hand_status.txt (K columns, awr_amd.detect's codes) and pred_hand_info.txt (n * K rows: the component's first
-pixel u, v, its pixels, its nearest depth) are written too.  Not combined with --views, --track or --smooth yet.
+pixel u, v, its pixels, its nearest depth) are written too.  Not combined with --views, --track or --smooth yet -- unless:
+--identity [GATE_MM,MERGE_MM,MAX_MISS] (with --hands K) keeps every hand in ITS slot from frame to frame (awr_hands_assign, an exact
+assignment of each frame's detected hands to the previous frame's; defaults 150,60,5, UNMEASURED on real frames): the file
+is ONE sequence (batch size 1), --track and --smooth then work per hand, and pred_hand_id.txt (K columns, 0: a free slot) and
+pred_hand_code.txt (K columns, awr_amd.track.ASSIGN_NAMES) are written too; pred_hand_info.txt stays in detection order.
 --ema predicts with the checkpoint's averaged weights ("model_ema", written by a run with config.ema_decay) instead of "model".
 `--set` overrides config entries as train.py does (img_size, kernel_size, cube, batch_size, jt_num, downsample, winograd ...)."""
 import argparse
@@ -57,6 +61,8 @@ def parse_args(argv=None):
     ap.add_argument("--hands", type=int, default=1, metavar="K", help="look for up to K hands per frame (1 ... 4); the outputs gain a hand axis")
     ap.add_argument("--reach", type=float, default=None, metavar="MM", help="with --hands: depth of the foreground behind the nearest pixel (default 300)")
     ap.add_argument("--min-pixels", type=int, default=None, metavar="N", help="with --hands: the smallest component that counts as a hand (default 400)")
+    ap.add_argument("--identity", nargs="?", const="", default=None, metavar="GATE_MM,MERGE_MM,MAX_MISS",
+                    help="with --hands: keep each hand in its slot across frames (the file is one sequence); optionally the gate, the merge distance and the misses allowed")
     ap.add_argument("--ema", action="store_true", help="load the checkpoint's \"model_ema\" (the EMA of the weights) instead of \"model\"")
     return ap.parse_args(argv)
 
@@ -85,9 +91,27 @@ def smooth_config(args):
     return cfg
 
 
+def identity_config(args):
+    """--identity -> what Predictor(identity=...) takes, or None"""
+    if args.identity is None:
+        return None
+    if args.hands < 2:
+        raise SystemExit("--identity belongs to --hands K with K >= 2")
+    if not args.identity:
+        return True
+    vals = args.identity.split(",")
+    try:
+        return dict(gate_mm=float(vals[0]), merge_mm=float(vals[1]), max_miss=int(vals[2])) if len(vals) == 3 else None
+    except ValueError:
+        return None
+
+
 def main(argv=None):
     args = parse_args(argv)
     smooth = smooth_config(args)
+    identity = identity_config(args)
+    if args.identity and identity is None:
+        raise SystemExit("--identity takes GATE_MM,MERGE_MM,MAX_MISS (two numbers and an int), not %r" % args.identity)
 
     import numpy as np
     import torch
@@ -110,7 +134,7 @@ def main(argv=None):
     if key not in pth:
         raise awr_amd._lib.AwrError("{} holds no \"{}\" entry{}".format(cfg.load_model, key, " (--ema needs a checkpoint written with ema_decay)" if args.ema else ""))
     net.load_state_dict(pth[key])
-    bs = 1 if args.track or smooth is not None else min(cfg.batch_size, len(frames))
+    bs = 1 if args.track or smooth is not None or identity is not None else min(cfg.batch_size, len(frames))
     views = None if args.views is None else detect.parse_views(args.views)
     if args.hands == 1 and (args.reach is not None or args.min_pixels is not None):
         raise SystemExit("--reach and --min-pixels belong to --hands K with K >= 2")
@@ -120,8 +144,10 @@ def main(argv=None):
     pred = awr_amd.Predictor(net.cuda(), cfg.img_size, cfg.kernel_size, cube=cfg.cube, max_batch=bs, frame_shape=frames.shape[1:],
                              winograd=cfg.winograd, parity=cfg.parity_infer, confidence=args.confidence,
                              recenter=args.recenter, track=args.track, views=views, fuse=args.fuse, palm=args.palm,
-                             smooth=smooth, **hands_kw)
+                             smooth=smooth, identity=identity, **hands_kw)
     hands = {"n_hands": [], "hand_status": [], "hand_info": []}
+    if identity is not None:
+        hands.update(hand_id=[], hand_code=[])
     stateful = bool(args.recenter or args.track)
     centers, codes = [], []
     uvd, xyz, extra = [], [], {"conf": [], "peak": [], "spread_mm": []}
@@ -144,6 +170,9 @@ def main(argv=None):
             hands["n_hands"].append(out.n_hands.cpu().numpy())
             hands["hand_status"].append(out.status.cpu().numpy())
             hands["hand_info"].append(pred.hand_info.cpu().numpy().reshape(-1, 4))
+            if identity is not None:
+                hands["hand_id"].append(out.ids.cpu().numpy())
+                hands["hand_code"].append(pred.hand_codes.cpu().numpy())
         if stateful:
             centers.append(pred.centers_uvd.cpu().numpy().reshape(-1, 3))
             codes.append(pred.recenter_codes.cpu().numpy().reshape(args.recenter + 1, -1).T)
@@ -165,8 +194,8 @@ def main(argv=None):
         np.savetxt(os.path.join(args.out, "pred_views_used.txt"), np.concatenate(fused["views_used"], 0), fmt="%d")
     if smooth is not None:
         for k in ("raw_uvd", "raw_xyz"):
-            np.savetxt(os.path.join(args.out, "pred_%s.txt" % k), np.concatenate(raw[k], 0).reshape(len(frames), cfg.jt_num * 3), fmt="%.3f")
-        np.savetxt(os.path.join(args.out, "pred_filter_code.txt"), np.concatenate(raw["filter_code"], 0), fmt="%d")
+            np.savetxt(os.path.join(args.out, "pred_%s.txt" % k), np.concatenate(raw[k], 0).reshape(len(frames) * K, cfg.jt_num * 3), fmt="%.3f")
+        np.savetxt(os.path.join(args.out, "pred_filter_code.txt"), np.concatenate(raw["filter_code"], 0).reshape(len(frames) * K, cfg.jt_num), fmt="%d")
     if stateful:
         np.savetxt(os.path.join(args.out, "pred_center_uvd.txt"), np.concatenate(centers, 0), fmt="%.6f")
         np.savetxt(os.path.join(args.out, "pred_recenter_code.txt"), np.concatenate(codes, 0), fmt="%d")
