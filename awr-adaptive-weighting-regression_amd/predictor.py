@@ -4,78 +4,31 @@
     out = pred.predict(frames)              # (B, 480, 640) uint16 millimetres: numpy, host tensor or device tensor
     out.xyz, out.uvd                        # (B, J, 3) camera millimetres / original-image uvd, on the device
     pred.check()                            # synchronises; raises AwrError naming the first frame that could not be predicted
-    Predictor(..., confidence=True)         # out additionally carries conf, peak, spread_mm (B, J): how sure each joint is
-    Predictor(..., recenter=1)              # crop again around the predicted joints and predict again
-    Predictor(..., track=True)              # start each call's crop at the previous call's joint centre of the same batch slot
-    Predictor(..., views=make_views(rot=(-15, 15)), fuse="mean")      # the same hand under several views in ONE pass, fused
-    Predictor(..., palm=True)               # move the detector's centre to the palm disc, away from the forearm
-    Predictor(..., smooth=True)             # filter the joints over time: One-Euro per joint, gate, coasting, look-ahead
-    Predictor(..., hands=2)                 # up to K hands per frame from connected components; the outputs gain a hand axis
-    Predictor(..., hands=2, identity=True)  # slot k is the same hand from call to call; track, smooth and lead work per hand
 
-Everything between the frames and the joints runs on the device, on the current stream, without a synchronisation: awr_detect (hand
-centre by iterated centre of mass) -> awr_detect_samples (crop blocks, crop matrices) -> awr_nyu_batch (crop + normalise) -> the
-inference plan and the single-pass head (InferEngine) -> awr_joints_unproject.  The host only issues launches.  There is no host
-fallback in this class: without a GPU it raises; `awr_amd.detect.detect` is the numpy statement of the detector for such a machine.
+Everything between the frames and the joints runs on the device, on the current stream, without a synchronisation; the host only issues
+launches.  There is no host fallback in this class: without a GPU it raises; `awr_amd.detect.detect` is the numpy statement of the
+detector for such a machine.  Every option is opt-in, and a predictor without it issues the launches and gives the bits it always did
+(tests/test_predictor_trace_gpu.py holds every configuration's launches to the recorded ones).  The options, described in __init__:
 
-Re-centring and tracking (both opt-in; with the defaults the launches and the bits are what they were).  The detector's centre is a centre
-of mass of depth pixels, biased towards the forearm and whatever else lies in the slab, while the network was trained on refined centres.
-The network's own joints are the better centre, and awr_joints_center turns them into one on the device: the float64 mean of the (selected)
-joints, projected back to uvd, accepted only where the frame has no status code, the mean is finite, its depth lies in the detector's
-depth_range and it is within max_shift half cubes of the present centre on every axis.  recenter=N appends N passes of awr_joints_center ->
-awr_detect_samples -> render -> engine -> awr_joints_unproject on the same engine and buffers; a frame that is not moved keeps its centre
-and so repeats its previous pass bit for bit.  track=True keeps one float64 centre per batch slot (NaN: lost) and runs the detector twice,
-seeded with the tracked centres and as configured, and awr_centers_select takes the tracked result where it found the hand.  Nothing of this
-synchronises.  Whether either improves accuracy on real frames is UNMEASURED: no NYU frames and no trained checkpoint exist where this was
-written.
+    confidence=True                         conf, peak, spread_mm per joint                               DESIGN.md 4.18
+    recenter=N, track=True                  crop again around the predicted joints; follow them from call to call      4.19
+    views=make_views(...), fuse=            the same hand under several views in ONE batched pass, fused               4.22
+    palm=True                               the detector's centre moved to the palm disc, away from the forearm        4.24
+    smooth=True | dict | track.OneEuro      One-Euro filter per joint, gate, coasting, look-ahead (lead)               4.25
+    hands=K                                 up to K hands per frame from connected components; a hand axis             4.26
+    hands=K, identity=True | dict           slot k is the same hand from call to call; track, smooth, lead per hand    4.27
 
-Views (opt-in; views=None issues the launches and gives the bits it always did).  Test-time ensembling over the three augmentations the
-network was trained with (loader.py:75-86): in-plane rotations, cube scales and shifts of the crop centre.  The plan holds max_batch x V
-images, view-major (view v of batch slot b is row v * max_batch + b, so view 0 sits where a plain predictor's rows do).  awr_view_centers
-expands the centres, the unchanged awr_detect_samples builds V * max_batch blocks with a cube per row, awr_view_rotate turns the rotating
-views' blocks into AWR_NYU_AFFINE ones and their crop matrices into M_v = R . M; the renderer, the engine and awr_joints_unproject then run
-once over all rows -- un-projection inverts whatever matrix it is given, so a rotated view needs no arithmetic of its own -- and
-awr_views_fuse fuses the views' camera-space joints per frame and joint.  Whether fusing views lowers the joint error on real frames is
-UNMEASURED too, for the same reason.
+predict() is ONE pipeline over one stage method per entry point, and it reads top to bottom: upload the frames ->
+the seeds (given centres | awr_detect_hands | the configured seed mode) -> the candidate centres (awr_detect, awr_detect_palm) -> the
+tracked detector (a second awr_detect) -> combine (awr_centers_select | awr_hands_assign | nothing) -> crop and predict
+(awr_detect_samples -> awr_nyu_batch -> the inference plan and the single-pass head -> awr_joints_unproject; with views awr_view_centers
+and awr_view_rotate around the crop and awr_views_fuse behind it) -> the recenter passes (awr_joints_center, crop and predict) -> the next
+centre, from the look-ahead joints with lead -> the tracker's state -> awr_joints_filter -> awr_confidence_fields -> the named tuple.
+The plan's rows are group-major: G = V views or K hands, each a group of max_batch rows, group 0 first (_rows).
 
-Palm centre (opt-in; palm=False issues the launches and gives the bits it always did).  The detector's centre of mass is dragged up a
-forearm that lies at the hand's depth, and no later pass repairs a first crop that misses the hand.  palm=True sends the configured
-detector's centres through awr_detect_palm (nine small launches, a frame split over several workgroups: the exact integer distance transform of the silhouette in a
-window of palm_search cubes, its medial set, the end of it with the fingers beyond, the palm disc's centre of mass) before
-awr_detect_samples.  With track=True only the detector branch is refined, before awr_centers_select: a tracked centre is the joints' own.
-With centers_uvd handed to predict() it does not apply.  Measured on procedural hands only (profiles/synth_accuracy.txt); behaviour on real
-depth frames -- sleeves, a body within the search depth, NYU -- is UNMEASURED.
-
-Temporal filter (opt-in; smooth=None issues the launches and gives the bits it always did).  smooth=True | dict | track.OneEuro puts ONE
-awr_joints_filter launch behind the final pass (with views: behind awr_views_fuse): per batch slot, joint and axis a One-Euro low-pass
-in camera millimetres whose state (six doubles and two ints per joint) lives on the device from call to call; a measurement outside
-gate_mm, a frame that is not OK or a non-finite joint is answered with the held joint for up to max_coast calls, then the track restarts
-at the measurement or is dropped.  predict() returns the filtered joints; raw_xyz / raw_uvd / ahead_xyz / filter_codes hold the rest.
-lead=True hands the tracker the look-ahead joints x + d dt for the next call's crop.  The statement is awr_amd.track.filter_step; the
-kernel equals it bit for bit.  Measured on procedural sequences only (profiles/track_accuracy.txt, profiles/predict_smooth.txt); the
-defaults are engineering choices and accuracy on real frames is UNMEASURED.
-
-Several hands (opt-in; hands=1 issues the launches and gives the bits it always did).  The "nearest" seed is the centre of mass of every
-pixel within the slab of the nearest one: with two hands in view it lies between them, and one hand at most is reported.  hands=K >= 2
-puts awr_detect_hands (nine small launches: the near foreground's 4-connected components by a union-find forest with integer atomicMin,
-canonical labels, the K nearest components of at least min_pixels pixels seeded with their own slab's centre of mass) in front of the
-unchanged awr_detect, which refines all K * max_batch hand-major seeds as given centres; the crop, the network, the un-projection, the
-re-centring passes, the confidence fields and the palm pass then run per row, as the views' rows do.  Touching or overlapping hands are
-ONE component and count as one hand; which hand of one call is which hand of the next is not decided here, so views, track and smooth
-are refused with hands >= 2 (identity=..., below, decides it and lifts the refusal for track and smooth).  Measured on procedural two-hand composites only (profiles/detect_hands.txt); reach and min_pixels are
-engineering defaults, UNMEASURED on real frames.
-
-Hand identities (opt-in; identity=None issues the launches, gives the bits and raises the errors it always did).  With hands=K >= 2 and
-identity=True | dict | track.Identity, ONE awr_hands_assign launch between the detector and the crop decides which of this call's
-detected hands (the candidates) is which identity of the previous call: an exact assignment over the K! permutations in camera
-millimetres, gated by gate_mm, per batch slot, with state (last centre, id, misses, next id) that stays on the device.  Slot k then is
-the same hand from call to call -- a hand without a candidate waits for max_miss calls (status EMPTY, NaN rows) before its slot is given
-up, a new hand takes the lowest free slot and a fresh id -- and so track=True (a second awr_detect seeded with every slot's last centre;
-two trackers that end on one hand are merged), smooth=... (K launches of the unchanged awr_joints_filter over the hand-major filter
-state, whose rows awr_hands_assign zeroes where an identity starts or ends) and lead=True are accepted.  predict() returns a
-TrackedHandsPrediction with ids (nb, K).  The statement is awr_amd.track.assign_step; the kernel equals it bit for bit.  Measured on
-procedural two-hand sequences only (profiles/hands_identity.txt); gate_mm, merge_mm and max_miss are engineering defaults, UNMEASURED on
-real frames.
+What is measured and what is not stands with each option in DESIGN.md: accuracy on real frames is UNMEASURED throughout (no NYU frames
+and no trained checkpoint exist where this was written); the detector, the palm pass, the filter, the hands and the identities are
+measured on procedural hands only (profiles/).
 """
 import collections
 import types
@@ -96,6 +49,8 @@ HandsPrediction = collections.namedtuple("HandsPrediction", Prediction._fields +
 ConfidentHandsPrediction = collections.namedtuple("ConfidentHandsPrediction", HandsPrediction._fields + ("conf", "peak", "spread_mm"))
 TrackedHandsPrediction = collections.namedtuple("TrackedHandsPrediction", HandsPrediction._fields + ("ids",))
 ConfidentTrackedHandsPrediction = collections.namedtuple("ConfidentTrackedHandsPrediction", TrackedHandsPrediction._fields + ("conf", "peak", "spread_mm"))
+_CONFIDENT = {Prediction: ConfidentPrediction, ViewPrediction: ConfidentViewPrediction, HandsPrediction: ConfidentHandsPrediction,
+              TrackedHandsPrediction: ConfidentTrackedHandsPrediction}
 MAX_RECENTER = 4
 MAX_VIEWS = D.MAX_VIEWS
 
@@ -407,24 +362,158 @@ class Predictor:
             fs.index_copy_(1, idx, torch.where(ended[..., None, None], torch.zeros_like(fs[:, :n]), fs.index_select(1, idx)))
             fc.index_copy_(1, idx, torch.where(ended[..., None, None], torch.zeros_like(fc[:, :n]), fc.index_select(1, idx)))
 
-    def _joints_center(self, xyz, cxyz, status, ustatus, nv, center_out, next_out, code):
-        fx, fy, u0, v0 = self.paras
-        L.call("awr_joints_center", L.ptr(xyz), self._centers.data_ptr(), L.ptr(cxyz), L.ptr(self._cube32), status.data_ptr(), ustatus.data_ptr(),
-               self.B, self.J, nv, L.ptr(self._joints), 0 if self._joints is None else int(self._joints.numel()), fx, fy, u0, v0, self.flip,
-               self.depth_range[0], self.depth_range[1], self.max_shift, center_out.data_ptr(), L.ptr(next_out), code.data_ptr(), L.stream())
+    # ---- one call: the row layout, the call's tensors, one stage per entry point, predict() -------------------------------
+    # The plan has R = max_batch * V * K rows, group-major: G = V views or K hands, each a group of max_batch rows, group 0 first.  The
+    # detector's buffers have F = max_batch * K rows (F == R unless there are views).  A stage takes the rows it is launched over, how many
+    # of them are valid and the tensors it reads and writes; the camera, the depth range, the cube, the frame store and the stream are self's.
 
-    def _smooth_step(self, xyz, status, ustatus, conf, nv, dt):
-        """one awr_joints_filter launch over the call's output joints -> (xyz_f, uvd_f, ahead (B, J, 3), code (B, J)), fresh tensors"""
+    def _rows(self, t, nb, axis=0, group_first=False):
+        """What a result carries of a group-major (G * max_batch, ...) buffer whose rows lie along `axis`: with hands its (nb, K, ...) view,
+        else the nb rows of group 0 (the only group, or view 0).  group_first: the (G, nb, ...) view."""
+        if self.hands == 1 and not group_first:
+            return t.narrow(axis, 0, nb)
+        t = t.view(tuple(t.shape[:axis]) + (-1, self.B) + tuple(t.shape[axis + 1:])).narrow(axis + 1, 0, nb)
+        return t if group_first else t.transpose(axis, axis + 1)
+
+    def _tensors(self, nb, nv):
+        """Everything one call allocates, and its row counts.  F, fv: the detector's rows and how many of them are valid -- hands = 1 launches
+        over (max_batch, n_valid) and needs a zeroed status, hands >= 2 over (F, F): its rows past n_valid have NaN seeds and end EMPTY by
+        themselves.  R, rv: the same for the plan's rows, (R, R) unless the plan is one group.  xyz_j / uvd_j / status_j are the joints and
+        codes the stages behind the crop read: the fused ones with views."""
+        dev, B, K, J = self.device, self.B, self.hands, self.J
+        F, R = B * K, B * K * self.V
+        c = types.SimpleNamespace(nb=nb, nv=nv, F=F, R=R, fv=nv if K == 1 else F, rv=nv if R == B else R, weights=None, filtered=None)
+        c.M = torch.empty((R, 3, 3), dtype=torch.float32, device=dev)
+        c.cxyz = torch.empty((R, 3), dtype=torch.float32, device=dev)
+        c.status = torch.zeros(B, dtype=torch.int32, device=dev) if K == 1 else torch.empty(F, dtype=torch.int32, device=dev)
+        c.ustatus = torch.zeros(R, dtype=torch.int32, device=dev)
+        c.uvd = torch.empty((R, J, 3), dtype=torch.float32, device=dev)
+        c.xyz = torch.empty((R, J, 3), dtype=torch.float32, device=dev)
+        c.xyz_j, c.uvd_j, c.status_j = c.xyz, c.uvd, c.status
+        if self.V > 1:
+            # status: the frames' (the detector's); vstatus: one per row, view 0's first -- what every later stage and check() read
+            c.vstatus = torch.zeros(R, dtype=torch.int32, device=dev)
+            c.fxyz = torch.empty((B, J, 3), dtype=torch.float32, device=dev)
+            c.fuvd = torch.empty((B, J, 3), dtype=torch.float32, device=dev)
+            c.vspread = torch.empty((B, J), dtype=torch.float32, device=dev)
+            c.vused = torch.empty((B, J), dtype=torch.int32, device=dev)
+            c.xyz_j, c.uvd_j, c.status_j = c.fxyz, c.fuvd, c.vstatus
+        if self.identity is not None:
+            c.assigned = torch.empty((3, F), dtype=torch.int32, device=dev)          # code, reset, source
+            c.dropped = torch.empty(B, dtype=torch.int32, device=dev)
+        if self.recenter or self.track:
+            c.codes = torch.zeros((self.recenter + 1, F), dtype=torch.int32, device=dev)
+            c.nxt = torch.full((F, 3), float("nan"), dtype=torch.float64, device=dev)
+        if self.confidence:
+            c.fields = torch.empty((3, F, J), dtype=torch.float32, device=dev)
+        return c
+
+    def _detect(self, n, mode, seed, centers, status):
+        L.call("awr_detect", self._frames.data_ptr(), 0, self.B, self.fh, self.fw, self._idx.data_ptr(), n, mode, L.ptr(seed), self.depth_range[0],
+               self.depth_range[1], self.slab, self._cube.data_ptr(), 0, self.paras[0], self.paras[1], self.iters, 0, self._scratch.data_ptr(),
+               centers.data_ptr(), status.data_ptr(), L.stream())
+
+    def _detect_palm(self, n, nb, centers, status):
+        """in place: a frame that is not OK keeps its centre and status"""
+        L.call("awr_detect_palm", self._frames.data_ptr(), 0, self.B, self.fh, self.fw, self._idx.data_ptr(), n, centers.data_ptr(),
+               status.data_ptr(), self.depth_range[0], self.depth_range[1], self._cube.data_ptr(), 0, self.paras[0], self.paras[1], self.palm_search,
+               D.PALM_TAU[0], D.PALM_TAU[1], D.PALM_RHO2[0], D.PALM_RHO2[1], self._palm_scratch.data_ptr(), centers.data_ptr(),
+               status.data_ptr(), self._palm_info.data_ptr(), L.stream())
+        self.palm_info = self._rows(self._palm_info, nb)
+
+    def _detect_hands(self, nb):
+        """the K nearest components' seeds of every frame -> self._seed, hand-major"""
+        L.call("awr_detect_hands", self._frames.data_ptr(), 0, self.B, self.fh, self.fw, self._idx.data_ptr(), self.B, self.hands, self.depth_range[0],
+               self.depth_range[1], self.reach, self.slab, self.min_pixels, self._hands_scratch.data_ptr(), None, self._seed.data_ptr(),
+               self._hands_status.data_ptr(), self._hands_info.data_ptr(), self._hands_count.data_ptr(), L.stream())
+        self.hand_info = self._hands_info[:, :nb].transpose(0, 1)
+
+    def _centers_select(self, n, first, first_status, second, second_status, out, out_status):
+        """per row `first` where its status is OK, else `second`"""
+        L.call("awr_centers_select", first.data_ptr(), first_status.data_ptr(), second.data_ptr(), second_status.data_ptr(), n, out.data_ptr(),
+               out_status.data_ptr(), None, L.stream())
+
+    def _hands_assign(self, c):
+        """the candidates (and the tracked centres) -> every slot's centre and status, in self._centers / c.status; the state moves on"""
+        cfg, smooth = self.identity, self.smooth is not None
+        L.call("awr_hands_assign", self._id_last.data_ptr(), self._id_ids.data_ptr(), self._id_miss.data_ptr(), self._id_next.data_ptr(),
+               self._cand.data_ptr(), self._cand_status.data_ptr(), self._tcenters.data_ptr() if self.track else None,
+               self._tstatus.data_ptr() if self.track else None, self.hands, self.B, c.nv, cfg.gate_mm, cfg.merge_mm, cfg.max_miss, *self.paras,
+               self.flip, self._filter_state.data_ptr() if smooth else None, self._filter_count.data_ptr() if smooth else None,
+               self.J if smooth else 0, self._centers.data_ptr(), c.status.data_ptr(), L.ptr(c.assigned[0]), L.ptr(c.assigned[1]),
+               L.ptr(c.assigned[2]), c.dropped.data_ptr(), L.stream())
+
+    def _detect_samples(self, n, c, centers, cubes, cube_stride, frame, status):
+        """centres -> crop blocks, crop matrices, centres in camera space, float cubes"""
+        L.call("awr_detect_samples", centers.data_ptr(), cubes.data_ptr(), cube_stride, self.B, frame.data_ptr(), n, self.S, self.fh, self.fw,
+               *self.paras, self.flip, self._blocks.data_ptr(), L.ptr(c.M), L.ptr(c.cxyz), L.ptr(self._cube32), status.data_ptr(), L.stream())
+
+    def _joints_unproject(self, n, nv, jt, c):
+        L.call("awr_joints_unproject", L.ptr(jt), L.ptr(c.cxyz), L.ptr(c.M), L.ptr(self._cube32), n, self.J, nv, float(self.S), *self.paras, self.flip,
+               L.ptr(c.uvd), L.ptr(c.xyz), c.ustatus.data_ptr(), L.stream())
+
+    def _view_centers(self, c):
+        """the centres -> one centre, cube and frame row per view, and the rows' status"""
+        L.call("awr_view_centers", self._centers.data_ptr(), c.status.data_ptr(), self._cube.data_ptr(), 0, self._vtable.data_ptr(), self.V, self.B,
+               c.nv, *self.paras, self.flip, self._vcenters.data_ptr(), self._vcubes.data_ptr(), self._vframe.data_ptr(), c.vstatus.data_ptr(),
+               L.stream())
+
+    def _view_rotate(self, c):
+        L.call("awr_view_rotate", self._blocks.data_ptr(), L.ptr(c.M), c.vstatus.data_ptr(), self._vtable.data_ptr(), self.V, self.B, c.nv, L.stream())
+
+    def _views_fuse(self, c):
+        L.call("awr_views_fuse", L.ptr(c.xyz), c.vstatus.data_ptr(), c.ustatus.data_ptr(), L.ptr(c.weights), D.FUSE_MODES[self.fuse], self.V, self.B,
+               self.J, c.nv, *self.paras, self.flip, L.ptr(c.fxyz), L.ptr(c.fuvd), L.ptr(c.vspread), L.ptr(c.vused), L.stream())
+
+    def _joints_center(self, c, joints, center_out, next_out, code):
+        """the joints' centre per frame row, gated (see __init__): moved rows into center_out, every row's into next_out (NaN: not moved)"""
+        L.call("awr_joints_center", L.ptr(joints), self._centers.data_ptr(), L.ptr(c.cxyz), L.ptr(self._cube32), c.status_j.data_ptr(),
+               c.ustatus.data_ptr(), c.F, self.J, c.fv, L.ptr(self._joints), 0 if self._joints is None else int(self._joints.numel()), *self.paras,
+               self.flip, self.depth_range[0], self.depth_range[1], self.max_shift, center_out.data_ptr(), L.ptr(next_out), code.data_ptr(),
+               L.stream())
+
+    def _joints_filter(self, c, dt):
+        """awr_joints_filter over the call's joints, one launch per group of max_batch rows (the rows past n_valid of EVERY group keep their
+        state) -> c.filtered = (xyz, uvd, ahead (F, J, 3), code (F, J)), fresh tensors"""
         cfg, B, J, dev = self.smooth, self.B, self.J, self.device
-        fx, fy, u0, v0 = self.paras
-        if cfg.weight == "conf" and conf is None:
-            conf = self.engine.conf[:B, :, 0].contiguous()          # (B, J): view 0's rows come first
-        out = [torch.empty((B, J, 3), dtype=torch.float32, device=dev) for _ in range(3)] + [torch.empty((B, J), dtype=torch.int32, device=dev)]
-        L.call("awr_joints_filter", self._filter_state.data_ptr(), self._filter_count.data_ptr(), L.ptr(xyz), status.data_ptr(), ustatus.data_ptr(),
-               L.ptr(conf) if cfg.weight == "conf" else None, B, J, nv, dt, cfg.min_cutoff, cfg.beta, cfg.d_cutoff,
-               -1.0 if cfg.gate_mm is None else cfg.gate_mm, cfg.max_coast, T.WEIGHTS[cfg.weight], cfg.conf_floor, fx, fy, u0, v0, self.flip,
-               L.ptr(out[0]), L.ptr(out[1]), L.ptr(out[2]), L.ptr(out[3]), L.stream())
-        return out
+        conf = None
+        if cfg.weight == "conf":          # (F, J): the views' weights where there are some, else the head's conf; view 0's rows come first
+            conf = c.weights if c.weights is not None else self.engine.conf[:c.F, :, 0].contiguous()
+        out = [torch.empty((c.F, J, 3), dtype=torch.float32, device=dev) for _ in range(3)] + [torch.empty((c.F, J), dtype=torch.int32, device=dev)]
+        for o in range(0, c.F, B):
+            L.call("awr_joints_filter", self._filter_state[o:].data_ptr(), self._filter_count[o:].data_ptr(), c.xyz_j[o:].data_ptr(),
+                   c.status_j[o:].data_ptr(), c.ustatus[o:].data_ptr(), None if conf is None else conf[o:].data_ptr(), B, J, c.nv, dt, cfg.min_cutoff,
+                   cfg.beta, cfg.d_cutoff, -1.0 if cfg.gate_mm is None else cfg.gate_mm, cfg.max_coast, T.WEIGHTS[cfg.weight], cfg.conf_floor,
+                   *self.paras, self.flip, out[0][o:].data_ptr(), out[1][o:].data_ptr(), out[2][o:].data_ptr(), out[3][o:].data_ptr(), L.stream())
+        c.filtered = out
+
+    def _confidence_fields(self, c):
+        """conf, peak, spread_mm of every frame row (with views: view 0's rows are the first of every per-row buffer) -> c.fields"""
+        L.call("awr_confidence_fields", L.ptr(self.engine.conf), L.ptr(self.engine.stat), L.ptr(self._cube32), c.status_j.data_ptr(),
+               c.ustatus.data_ptr(), c.F, self.J, c.fv, L.ptr(c.fields[0]), L.ptr(c.fields[1]), L.ptr(c.fields[2]), L.stream())
+
+    def _crop_and_predict(self, c):
+        """self._centers -> c.xyz / c.uvd (with views: and the fused c.fxyz / c.fuvd): crop, render, the network, un-projection"""
+        if self.V > 1:
+            # one centre, cube and frame row per view; the rows past n_valid of each view hold NaN centres: blocks without pixels
+            if c.nv < self.B:
+                self._vcenters.fill_(float("nan"))
+            self._view_centers(c)
+            self._detect_samples(c.R, c, self._vcenters, self._vcubes, 3, self._vframe, c.vstatus)
+            self._view_rotate(c)
+        else:
+            self._detect_samples(c.fv, c, self._centers, self._cube, 0, self._idx, c.status)
+        if c.R == self.B:
+            self._render(self._blocks[:c.nv], out=self._img[:c.nv])
+            if c.nv < self.B:
+                self._img[c.nv:].zero_()          # padding rows of the static plan: constant input, and no later stage reads their output
+        else:
+            self._render(self._blocks, out=self._img)
+        self._joints_unproject(c.R, c.rv, self.engine(self._img), c)
+        if self.V > 1:
+            if self.fuse == "conf":
+                c.weights = self.engine.conf[..., 0].contiguous()          # (R, J): the head's conf of every row, packed
+            self._views_fuse(c)
 
     def _upload(self, frames):
         """(nb, fh, fw) uint16 -> rows [0, nb) of the frame store, without blocking"""
@@ -439,381 +528,136 @@ class Predictor:
         nb = int(frames.shape[0])
         if not 0 < nb <= self.B:
             raise L.AwrError("a batch of %d frames does not fit the predictor's max_batch %d" % (nb, self.B))
-        if frames.is_cuda:
-            self._frames[:nb].copy_(frames, non_blocking=True)
-            return nb
-        if not frames.is_pinned():
+        staged = not frames.is_cuda and not frames.is_pinned()
+        if staged:
             # pageable memory -> the pinned staging buffer -> HBM.  The buffer is reused: wait for the previous upload FROM IT (a copy, not
             # the pipeline: the launches behind it stay queued)
             if self._stage_free is not None:
                 self._stage_free.synchronize()
             self._stage[:nb].copy_(frames)
             frames = self._stage[:nb]
-            self._frames[:nb].copy_(frames, non_blocking=True)
+        self._frames[:nb].copy_(frames, non_blocking=True)
+        if staged:
             self._stage_free = torch.cuda.Event()
             self._stage_free.record()
-        else:
-            self._frames[:nb].copy_(frames, non_blocking=True)
         return nb
+
+    def _given_centers(self, centers_uvd, nb):
+        """centers_uvd (nb, 3), with hands (nb, K, 3) -> rows [0, nb) of every group of self._seed (converts to float64 on the way)"""
+        K = self.hands
+        c = centers_uvd if isinstance(centers_uvd, torch.Tensor) else torch.from_numpy(np.ascontiguousarray(centers_uvd, dtype=np.float64))
+        if K == 1 and tuple(c.shape) != (nb, 3):
+            raise L.AwrError("centers_uvd must be (%d, 3), got %s" % (nb, tuple(c.shape)))
+        if K > 1 and tuple(c.shape) != (nb, K, 3):
+            raise L.AwrError("centers_uvd must be (%d, %d, 3): a centre per frame and hand, NaN rows for an absent hand, got %s" % (nb, K, tuple(c.shape)))
+        self._rows(self._seed, nb, group_first=True).copy_(c if K == 1 else c.transpose(0, 1), non_blocking=True)
 
     def predict(self, frames, centers_uvd=None, n_valid=None, dt=None):
         """-> Prediction(xyz (nb, J, 3), uvd (nb, J, 3), center_xyz (nb, 3), M (nb, 3, 3), status (nb,) int32), device tensors, nothing
-        synchronised; with confidence=True a ConfidentPrediction: these and conf, peak, spread_mm (nb, J).  centers_uvd (nb, 3): hand centres in original-image uvd (numpy or tensor) instead of the detector's seed.  n_valid:
-        frames of the batch that count (default: all of them); rows past it hold unspecified values.  status: awr_amd.detect's codes; a frame that is
-        not OK has NaN rows (of conf / peak / spread_mm too).  With recenter > 0 every field is the FINAL pass's; with track=True a call
-        without centers_uvd starts from the tracked centres (see __init__), an explicit centers_uvd overrides them for this call, and either
-        way slots [0, n_valid) of the tracker take this call's next_centers_uvd.  dt: seconds since the previous call, for a predictor with
-        smooth (default 1 / its fps); xyz and uvd are then the filtered joints (see __init__)."""
-        if self.hands > 1:
-            if self.identity is not None and self.smooth is not None:
-                return self._predict_identity(frames, centers_uvd, n_valid, T.check_dt(1.0 / self.smooth.fps if dt is None else dt))
-            if dt is not None:
-                raise L.AwrError("predict(dt=...) is the temporal filter's time step: it needs a Predictor built with smooth=...")
-            if self.identity is not None:
-                return self._predict_identity(frames, centers_uvd, n_valid, None)
-            return self._predict_hands(frames, centers_uvd, n_valid)
-        if self.smooth is None:
-            if dt is not None:
-                raise L.AwrError("predict(dt=...) is the temporal filter's time step: it needs a Predictor built with smooth=...")
-        else:
+        synchronised; with confidence=True a ConfidentPrediction: these and conf, peak, spread_mm (nb, J); with views, hands or identity the
+        named tuples __init__ describes.  centers_uvd (nb, 3), with hands (nb, K, 3): hand centres in original-image uvd (numpy or tensor)
+        instead of the detector's seed.  n_valid: frames of the batch that count (default: all of them); rows past it hold unspecified values.
+        status: awr_amd.detect's codes; a frame that is not OK has NaN rows (of conf / peak / spread_mm too).  With recenter > 0 every field
+        is the FINAL pass's; with track=True a call without centers_uvd starts from the tracked centres (see __init__), an explicit
+        centers_uvd overrides them for this call (with identity: it is the candidates), and either way slots [0, n_valid) of the tracker take
+        this call's next_centers_uvd.  dt: seconds since the previous call, for a predictor with smooth (default 1 / its fps); xyz and uvd are
+        then the filtered joints (see __init__)."""
+        K, B, nan = self.hands, self.B, float("nan")
+        if self.smooth is not None:
             dt = T.check_dt(1.0 / self.smooth.fps if dt is None else dt)
+        elif dt is not None:
+            raise L.AwrError("predict(dt=...) is the temporal filter's time step: it needs a Predictor built with smooth=...")
         nb = self._upload(frames)
         nv = nb if n_valid is None else int(n_valid)
         if not 0 < nv <= nb:
             raise L.AwrError("n_valid = %d is outside [1, %d]" % (nv, nb))
-        dev, B, J, s = self.device, self.B, self.J, L.stream()
-        fx, fy, u0, v0 = self.paras
-        mode, seed = D.SEEDS[self.seed], None
-        if centers_uvd is not None:
-            c = centers_uvd if isinstance(centers_uvd, torch.Tensor) else torch.from_numpy(np.ascontiguousarray(centers_uvd, dtype=np.float64))
-            if tuple(c.shape) != (nb, 3):
-                raise L.AwrError("centers_uvd must be (%d, 3), got %s" % (nb, tuple(c.shape)))
-            self._seed[:nb].copy_(c, non_blocking=True)          # (converts to float64 on the way)
-            mode, seed = D.SEED_GIVEN, self._seed
-        V, P = self.V, self.B * self.V
-        M = torch.empty((P, 3, 3), dtype=torch.float32, device=dev)
-        cxyz = torch.empty((P, 3), dtype=torch.float32, device=dev)
-        status = torch.zeros(B, dtype=torch.int32, device=dev)
-        ustatus = torch.zeros(P, dtype=torch.int32, device=dev)
-        uvd = torch.empty((P, J, 3), dtype=torch.float32, device=dev)
-        xyz = torch.empty((P, J, 3), dtype=torch.float32, device=dev)
-        if V > 1:
-            # status: the frames' (the detector's); vstatus: one per row, view 0's first -- what every later stage and check() read
-            vstatus = torch.zeros(P, dtype=torch.int32, device=dev)
-            fxyz = torch.empty((B, J, 3), dtype=torch.float32, device=dev)
-            fuvd = torch.empty((B, J, 3), dtype=torch.float32, device=dev)
-            vspread = torch.empty((B, J), dtype=torch.float32, device=dev)
-            vused = torch.empty((B, J), dtype=torch.int32, device=dev)
-            weights = [None]
-
-        def detect(mode, seed, centers, status):
-            L.call("awr_detect", self._frames.data_ptr(), 0, B, self.fh, self.fw, self._idx.data_ptr(), nv, mode, L.ptr(seed), self.depth_range[0],
-                   self.depth_range[1], self.slab, self._cube.data_ptr(), 0, fx, fy, self.iters, 0, self._scratch.data_ptr(),
-                   centers.data_ptr(), status.data_ptr(), s)
-
-        def palm(centers, status):
-            # in place: a frame that is not OK keeps its centre and status
-            L.call("awr_detect_palm", self._frames.data_ptr(), 0, B, self.fh, self.fw, self._idx.data_ptr(), nv, centers.data_ptr(),
-                   status.data_ptr(), self.depth_range[0], self.depth_range[1], self._cube.data_ptr(), 0, fx, fy, self.palm_search,
-                   D.PALM_TAU[0], D.PALM_TAU[1], D.PALM_RHO2[0], D.PALM_RHO2[1], self._palm_scratch.data_ptr(), centers.data_ptr(),
-                   status.data_ptr(), self._palm_info.data_ptr(), s)
-            self.palm_info = self._palm_info[:nb]
-
-        def crop_and_predict():
-            L.call("awr_detect_samples", self._centers.data_ptr(), self._cube.data_ptr(), 0, B, self._idx.data_ptr(), nv, self.S, self.fh, self.fw,
-                   fx, fy, u0, v0, self.flip, self._blocks.data_ptr(), L.ptr(M), L.ptr(cxyz), L.ptr(self._cube32), status.data_ptr(), s)
-            self._render(self._blocks[:nv], out=self._img[:nv])
-            if nv < B:
-                self._img[nv:].zero_()          # padding rows of the static plan: constant input, and no later stage reads their output
-            jt = self.engine(self._img)
-            L.call("awr_joints_unproject", L.ptr(jt), L.ptr(cxyz), L.ptr(M), L.ptr(self._cube32), B, J, nv, float(self.S), fx, fy, u0, v0, self.flip,
-                   L.ptr(uvd), L.ptr(xyz), ustatus.data_ptr(), s)
-
-        def views_and_predict():
-            # centres -> one centre, cube and frame row per view; the rows past n_valid of each view hold NaN centres: blocks without pixels
-            if nv < B:
-                self._vcenters.fill_(float("nan"))
-            L.call("awr_view_centers", self._centers.data_ptr(), status.data_ptr(), self._cube.data_ptr(), 0, self._vtable.data_ptr(), V, B, nv,
-                   fx, fy, u0, v0, self.flip, self._vcenters.data_ptr(), self._vcubes.data_ptr(), self._vframe.data_ptr(), vstatus.data_ptr(), s)
-            L.call("awr_detect_samples", self._vcenters.data_ptr(), self._vcubes.data_ptr(), 3, B, self._vframe.data_ptr(), P, self.S, self.fh,
-                   self.fw, fx, fy, u0, v0, self.flip, self._blocks.data_ptr(), L.ptr(M), L.ptr(cxyz), L.ptr(self._cube32), vstatus.data_ptr(), s)
-            L.call("awr_view_rotate", self._blocks.data_ptr(), L.ptr(M), vstatus.data_ptr(), self._vtable.data_ptr(), V, B, nv, s)
-            self._render(self._blocks, out=self._img)
-            jt = self.engine(self._img)
-            L.call("awr_joints_unproject", L.ptr(jt), L.ptr(cxyz), L.ptr(M), L.ptr(self._cube32), P, J, P, float(self.S), fx, fy, u0, v0, self.flip,
-                   L.ptr(uvd), L.ptr(xyz), ustatus.data_ptr(), s)
-            if self.fuse == "conf":
-                weights[0] = self.engine.conf[..., 0].contiguous()          # (P, J): the head's conf of every row, packed
-            L.call("awr_views_fuse", L.ptr(xyz), vstatus.data_ptr(), ustatus.data_ptr(), L.ptr(weights[0]), D.FUSE_MODES[self.fuse], V, B, J, nv,
-                   fx, fy, u0, v0, self.flip, L.ptr(fxyz), L.ptr(fuvd), L.ptr(vspread), L.ptr(vused), s)
-
-        smoothed = None
-        if V > 1:
-            crop_and_predict, out_xyz, out_uvd, out_status = views_and_predict, fxyz, fuvd, vstatus
-        else:
-            out_xyz, out_uvd, out_status = xyz, uvd, status
-        if self.track and seed is None:
-            # the tracked centres first (a lost slot's NaN seed finds nothing), the configured detector second, per slot whichever holds
-            detect(D.SEED_GIVEN, self._track, self._tcenters, self._tstatus)
-            detect(mode, None, self._dcenters, self._dstatus)
-            if self.palm:
-                palm(self._dcenters, self._dstatus)
-            L.call("awr_centers_select", self._tcenters.data_ptr(), self._tstatus.data_ptr(), self._dcenters.data_ptr(), self._dstatus.data_ptr(),
-                   nv, self._centers.data_ptr(), status.data_ptr(), None, s)
-        else:
-            detect(mode, seed, self._centers, status)
-            if self.palm and seed is None:
-                palm(self._centers, status)
-        crop_and_predict()
+        # the seeds: given centres, the K nearest components, or the configured seed mode
+        given = centers_uvd is not None
+        mode, seed = (D.SEED_GIVEN, self._seed) if given or K > 1 else (D.SEEDS[self.seed], None)
+        if given:
+            self._given_centers(centers_uvd, nb)
+            self.hand_info = None
+        elif K > 1:
+            self._detect_hands(nb)
+        if K > 1 and nv < B:
+            self._seed.view(K, B, 3)[:, nv:].fill_(nan)          # rows past n_valid of every group: NaN seeds, blocks without pixels
+        c = self._tensors(nb, nv)
+        # the candidate centres, where configured through the palm pass, and the tracked detector: seeded with the centres the previous
+        # call left (a lost slot's NaN seed finds nothing).  Hands without identities have nothing to combine: the candidates are the centres
+        tracked = self.track and (K > 1 or not given)
+        cand, cand_status = self._centers, c.status
+        if tracked and K == 1:
+            cand, cand_status = self._dcenters, self._dstatus
+            self._detect(c.fv, D.SEED_GIVEN, self._track, self._tcenters, self._tstatus)          # (one slot: the tracker goes first)
+        elif self.identity is not None:
+            cand, cand_status = self._cand, self._cand_status
+        self._detect(c.fv, mode, seed, cand, cand_status)
+        if self.palm and not given:
+            self._detect_palm(c.fv, nb, cand, cand_status)
+        if tracked and K > 1:
+            self._detect(c.fv, D.SEED_GIVEN, self._track, self._tcenters, self._tstatus)
+        # combine them: per slot the tracked centre where it holds, else the detector's; with identities the assignment
+        if tracked and K == 1:
+            self._centers_select(nv, self._tcenters, self._tstatus, cand, cand_status, self._centers, c.status)
+        elif self.identity is not None:
+            self._hands_assign(c)
+        self._crop_and_predict(c)
         if self.recenter or self.track:
-            codes = torch.zeros((self.recenter + 1, B), dtype=torch.int32, device=dev)
             for k in range(self.recenter):
                 # moved frames get their new centre in place, the others keep theirs: their next pass repeats this one bit for bit
-                self._joints_center(out_xyz, cxyz, out_status, ustatus, nv, self._centers, None, codes[k])
-                crop_and_predict()
-            nxt = torch.full((B, 3), float("nan"), dtype=torch.float64, device=dev)
-            next_from = out_xyz
+                self._joints_center(c, c.xyz_j, self._centers, None, c.codes[k])
+                self._crop_and_predict(c)
+            next_from = c.xyz_j
             if self.smooth is not None and self.smooth.lead:
                 # the next call's crop starts where constant velocity says the hand will be: filter first, centre the look-ahead joints
-                smoothed = self._smooth_step(out_xyz, out_status, ustatus, weights[0] if V > 1 else None, nv, dt)
-                next_from = smoothed[2]
-            self._joints_center(next_from, cxyz, out_status, ustatus, nv, self._moved, nxt, codes[self.recenter])
-            self.centers_uvd, self.next_centers_uvd, self.recenter_codes = self._centers[:nb].clone(), nxt[:nb], codes[:, :nb]
-            if self.track:
-                self._track[:nv].copy_(nxt[:nv])
-        self._last = (out_status, ustatus, nv)
+                self._joints_filter(c, dt)
+                next_from = c.filtered[2]
+            self._joints_center(c, next_from, self._moved, c.nxt, c.codes[self.recenter])
+            if self.identity is not None:
+                # every slot's last centre becomes its joints' centre where there is one: `nxt` where finite, else what it was
+                self._centers_select(c.F, c.nxt, self._zero_status, self._id_last, self._cand_status, self._sel, self._sel_status)
+                self._id_last.view(c.F, 3).copy_(self._sel)
+            self.centers_uvd = self._rows(self._centers.clone(), nb)
+            self.next_centers_uvd, self.recenter_codes = self._rows(c.nxt, nb), self._rows(c.codes, nb, axis=1)
+            if self.track and K == 1:
+                self._track[:nv].copy_(c.nxt[:nv])
+        self._last = (c.status_j, c.ustatus, nv) if K == 1 else (c.status.view(K, B), c.ustatus.view(K, B), nv)
+        if self.smooth is not None and c.filtered is None:
+            self._joints_filter(c, dt)
+        if self.confidence:
+            self._confidence_fields(c)
+        return self._result(c, given)
+
+    def _result(self, c, given):
+        """the call's named tuple, picked by (views, hands, identity, confidence), and the after-call attributes"""
+        K, nb = self.hands, c.nb
+        xyz, uvd = c.xyz_j, c.uvd_j
         if self.smooth is not None:
-            fxyz_t, fuvd_t, ahead, fcodes = smoothed or self._smooth_step(out_xyz, out_status, ustatus, weights[0] if V > 1 else None, nv, dt)
-            self.raw_xyz, self.raw_uvd, self.ahead_xyz, self.filter_codes = out_xyz[:nb], out_uvd[:nb], ahead[:nb], fcodes[:nb]
-            if V > 1:
-                fxyz, fuvd = fxyz_t, fuvd_t
+            xyz, uvd, ahead, codes = c.filtered
+            self.raw_xyz, self.raw_uvd = self._rows(c.xyz_j, nb), self._rows(c.uvd_j, nb)
+            self.ahead_xyz, self.filter_codes = self._rows(ahead, nb), self._rows(codes, nb)
+        fields = [self._rows(t, nb) for t in (xyz, uvd, c.cxyz, c.M, c.status_j)]
+        kind = Prediction
+        if K > 1:
+            kind = HandsPrediction
+            if given or self.identity is not None:
+                fields.append((self._rows(c.status, nb, group_first=True) == D.OK).sum(0, dtype=torch.int32))
             else:
-                xyz, uvd = fxyz_t, fuvd_t
+                fields.append(self._hands_count[:nb].clamp(max=K))
+        if self.identity is not None:
+            kind = TrackedHandsPrediction
+            self.hand_codes, self.hand_source, self.hands_dropped = self._rows(c.assigned[0], nb), self._rows(c.assigned[2], nb), c.dropped[:nb]
+            fields.append(self._id_ids[:, :nb].transpose(0, 1).clone())          # (the state moves on with the next call)
         if self.confidence:
-            # (with views: view 0's rows are the first B of every per-row buffer)
-            fields = torch.empty((3, B, J), dtype=torch.float32, device=dev)
-            L.call("awr_confidence_fields", L.ptr(self.engine.conf), L.ptr(self.engine.stat), L.ptr(self._cube32), out_status.data_ptr(),
-                   ustatus.data_ptr(), B, J, nv, L.ptr(fields[0]), L.ptr(fields[1]), L.ptr(fields[2]), s)
-        if V > 1:
-            per_view = dict(xyz=xyz.view(V, B, J, 3)[:, :nb], uvd=uvd.view(V, B, J, 3)[:, :nb], M=M.view(V, B, 3, 3)[:, :nb],
-                            center_xyz=cxyz.view(V, B, 3)[:, :nb], cube=self._cube32.view(V, B, 3)[:, :nb], status=vstatus.view(V, B)[:, :nb],
-                            ustatus=ustatus.view(V, B)[:, :nb])
+            fields += [self._rows(f, nb) for f in c.fields]
+        if self.V > 1:
+            kind = ViewPrediction
+            per_view = dict(xyz=c.xyz, uvd=c.uvd, M=c.M, center_xyz=c.cxyz, cube=self._cube32, status=c.vstatus, ustatus=c.ustatus)
             if self.engine.conf is not None:
-                per_view["conf"] = (self.engine.conf[..., 0] if weights[0] is None else weights[0]).view(V, B, J)[:, :nb]
-            self.view_outputs = types.SimpleNamespace(**per_view)
-            if self.confidence:
-                return ConfidentViewPrediction(fxyz[:nb], fuvd[:nb], cxyz[:nb], M[:nb], vstatus[:nb], fields[0, :nb], fields[1, :nb], fields[2, :nb],
-                                               vspread[:nb], vused[:nb])
-            return ViewPrediction(fxyz[:nb], fuvd[:nb], cxyz[:nb], M[:nb], vstatus[:nb], vspread[:nb], vused[:nb])
-        if self.confidence:
-            return ConfidentPrediction(xyz[:nb], uvd[:nb], cxyz[:nb], M[:nb], status[:nb], fields[0, :nb], fields[1, :nb], fields[2, :nb])
-        return Prediction(xyz[:nb], uvd[:nb], cxyz[:nb], M[:nb], status[:nb])
-
-    def _predict_hands(self, frames, centers_uvd, n_valid):
-        """predict() of a predictor with hands = K >= 2: every stage over the K * max_batch hand-major rows, row k * max_batch + b"""
-        nb = self._upload(frames)
-        nv = nb if n_valid is None else int(n_valid)
-        if not 0 < nv <= nb:
-            raise L.AwrError("n_valid = %d is outside [1, %d]" % (nv, nb))
-        dev, B, K, J, s = self.device, self.B, self.hands, self.J, L.stream()
-        P = B * K
-        fx, fy, u0, v0 = self.paras
-        nan = float("nan")
-        seeds = self._seed.view(K, B, 3)
-        if centers_uvd is not None:
-            c = centers_uvd if isinstance(centers_uvd, torch.Tensor) else torch.from_numpy(np.ascontiguousarray(centers_uvd, dtype=np.float64))
-            if tuple(c.shape) != (nb, K, 3):
-                raise L.AwrError("centers_uvd must be (%d, %d, 3): a centre per frame and hand, NaN rows for an absent hand, got %s" % (nb, K, tuple(c.shape)))
-            seeds[:, :nb].copy_(c.transpose(0, 1), non_blocking=True)          # (converts to float64 on the way)
-            self.hand_info = None
-        else:
-            L.call("awr_detect_hands", self._frames.data_ptr(), 0, B, self.fh, self.fw, self._idx.data_ptr(), B, K, self.depth_range[0],
-                   self.depth_range[1], self.reach, self.slab, self.min_pixels, self._hands_scratch.data_ptr(), None, self._seed.data_ptr(),
-                   self._hands_status.data_ptr(), self._hands_info.data_ptr(), self._hands_count.data_ptr(), s)
-            self.hand_info = self._hands_info[:, :nb].transpose(0, 1)
-        if nv < B:
-            seeds[:, nv:].fill_(nan)                 # rows past n_valid of every block: NaN seeds, blocks without pixels
-        M = torch.empty((P, 3, 3), dtype=torch.float32, device=dev)
-        cxyz = torch.empty((P, 3), dtype=torch.float32, device=dev)
-        status = torch.empty(P, dtype=torch.int32, device=dev)
-        ustatus = torch.zeros(P, dtype=torch.int32, device=dev)
-        uvd = torch.empty((P, J, 3), dtype=torch.float32, device=dev)
-        xyz = torch.empty((P, J, 3), dtype=torch.float32, device=dev)
-        # the unchanged detector refines every seed: a NaN seed (an absent hand) finds nothing and ends EMPTY
-        L.call("awr_detect", self._frames.data_ptr(), 0, B, self.fh, self.fw, self._idx.data_ptr(), P, D.SEED_GIVEN, self._seed.data_ptr(),
-               self.depth_range[0], self.depth_range[1], self.slab, self._cube.data_ptr(), 0, fx, fy, self.iters, 0, self._scratch.data_ptr(),
-               self._centers.data_ptr(), status.data_ptr(), s)
-        if self.palm and centers_uvd is None:
-            L.call("awr_detect_palm", self._frames.data_ptr(), 0, B, self.fh, self.fw, self._idx.data_ptr(), P, self._centers.data_ptr(),
-                   status.data_ptr(), self.depth_range[0], self.depth_range[1], self._cube.data_ptr(), 0, fx, fy, self.palm_search,
-                   D.PALM_TAU[0], D.PALM_TAU[1], D.PALM_RHO2[0], D.PALM_RHO2[1], self._palm_scratch.data_ptr(), self._centers.data_ptr(),
-                   status.data_ptr(), self._palm_info.data_ptr(), s)
-            self.palm_info = self._palm_info.view(K, B, 4)[:, :nb].transpose(0, 1)
-
-        def crop_and_predict():
-            L.call("awr_detect_samples", self._centers.data_ptr(), self._cube.data_ptr(), 0, B, self._idx.data_ptr(), P, self.S, self.fh, self.fw,
-                   fx, fy, u0, v0, self.flip, self._blocks.data_ptr(), L.ptr(M), L.ptr(cxyz), L.ptr(self._cube32), status.data_ptr(), s)
-            self._render(self._blocks, out=self._img)
-            jt = self.engine(self._img)
-            L.call("awr_joints_unproject", L.ptr(jt), L.ptr(cxyz), L.ptr(M), L.ptr(self._cube32), P, J, P, float(self.S), fx, fy, u0, v0, self.flip,
-                   L.ptr(uvd), L.ptr(xyz), ustatus.data_ptr(), s)
-
-        def joints_center(center_out, next_out, code):
-            L.call("awr_joints_center", L.ptr(xyz), self._centers.data_ptr(), L.ptr(cxyz), L.ptr(self._cube32), status.data_ptr(), ustatus.data_ptr(),
-                   P, J, P, L.ptr(self._joints), 0 if self._joints is None else int(self._joints.numel()), fx, fy, u0, v0, self.flip,
-                   self.depth_range[0], self.depth_range[1], self.max_shift, center_out.data_ptr(), L.ptr(next_out), code.data_ptr(), s)
-
-        crop_and_predict()
-        if self.recenter:
-            codes = torch.zeros((self.recenter + 1, P), dtype=torch.int32, device=dev)
-            for k in range(self.recenter):
-                joints_center(self._centers, None, codes[k])
-                crop_and_predict()
-            nxt = torch.full((P, 3), nan, dtype=torch.float64, device=dev)
-            joints_center(self._moved, nxt, codes[self.recenter])
-            self.centers_uvd = self._centers.clone().view(K, B, 3)[:, :nb].transpose(0, 1)
-            self.next_centers_uvd = nxt.view(K, B, 3)[:, :nb].transpose(0, 1)
-            self.recenter_codes = codes.view(self.recenter + 1, K, B)[:, :, :nb].transpose(1, 2)
-        self._last = (status.view(K, B), ustatus.view(K, B), nv)
-        if centers_uvd is None:
-            n_hands = self._hands_count[:nb].clamp(max=K)
-        else:
-            n_hands = (status.view(K, B)[:, :nb] == D.OK).sum(0, dtype=torch.int32)
-
-        def rows(t):          # hand-major (K * B, ...) -> a (nb, K, ...) view
-            return t.view((K, B) + tuple(t.shape[1:]))[:, :nb].transpose(0, 1)
-        fields = (rows(xyz), rows(uvd), rows(cxyz), rows(M), rows(status), n_hands)
-        if self.confidence:
-            conf = torch.empty((3, P, J), dtype=torch.float32, device=dev)
-            L.call("awr_confidence_fields", L.ptr(self.engine.conf), L.ptr(self.engine.stat), L.ptr(self._cube32), status.data_ptr(),
-                   ustatus.data_ptr(), P, J, P, L.ptr(conf[0]), L.ptr(conf[1]), L.ptr(conf[2]), s)
-            return ConfidentHandsPrediction(*fields, rows(conf[0]), rows(conf[1]), rows(conf[2]))
-        return HandsPrediction(*fields)
-
-    def _predict_identity(self, frames, centers_uvd, n_valid, dt):
-        """predict() of a predictor with hands = K >= 2 and identity: _predict_hands with awr_hands_assign between the detector and the crop,
-        the optional tracker in front of it and the optional temporal filter behind the final pass"""
-        nb = self._upload(frames)
-        nv = nb if n_valid is None else int(n_valid)
-        if not 0 < nv <= nb:
-            raise L.AwrError("n_valid = %d is outside [1, %d]" % (nv, nb))
-        dev, B, K, J, s = self.device, self.B, self.hands, self.J, L.stream()
-        P = B * K
-        fx, fy, u0, v0 = self.paras
-        nan, cfg = float("nan"), self.identity
-        seeds = self._seed.view(K, B, 3)
-        if centers_uvd is not None:
-            c = centers_uvd if isinstance(centers_uvd, torch.Tensor) else torch.from_numpy(np.ascontiguousarray(centers_uvd, dtype=np.float64))
-            if tuple(c.shape) != (nb, K, 3):
-                raise L.AwrError("centers_uvd must be (%d, %d, 3): a centre per frame and hand, NaN rows for an absent hand, got %s" % (nb, K, tuple(c.shape)))
-            seeds[:, :nb].copy_(c.transpose(0, 1), non_blocking=True)          # (converts to float64 on the way)
-            self.hand_info = None
-        else:
-            L.call("awr_detect_hands", self._frames.data_ptr(), 0, B, self.fh, self.fw, self._idx.data_ptr(), B, K, self.depth_range[0],
-                   self.depth_range[1], self.reach, self.slab, self.min_pixels, self._hands_scratch.data_ptr(), None, self._seed.data_ptr(),
-                   self._hands_status.data_ptr(), self._hands_info.data_ptr(), self._hands_count.data_ptr(), s)
-            self.hand_info = self._hands_info[:, :nb].transpose(0, 1)
-        if nv < B:
-            seeds[:, nv:].fill_(nan)                 # rows past n_valid of every block: NaN seeds, candidates that are EMPTY
-        M = torch.empty((P, 3, 3), dtype=torch.float32, device=dev)
-        cxyz = torch.empty((P, 3), dtype=torch.float32, device=dev)
-        status = torch.empty(P, dtype=torch.int32, device=dev)
-        ustatus = torch.zeros(P, dtype=torch.int32, device=dev)
-        uvd = torch.empty((P, J, 3), dtype=torch.float32, device=dev)
-        xyz = torch.empty((P, J, 3), dtype=torch.float32, device=dev)
-        assigned = torch.empty((3, K, B), dtype=torch.int32, device=dev)          # code, reset, source
-        dropped = torch.empty(B, dtype=torch.int32, device=dev)
-
-        def detect(seed, centers, dstatus):
-            L.call("awr_detect", self._frames.data_ptr(), 0, B, self.fh, self.fw, self._idx.data_ptr(), P, D.SEED_GIVEN, seed.data_ptr(),
-                   self.depth_range[0], self.depth_range[1], self.slab, self._cube.data_ptr(), 0, fx, fy, self.iters, 0, self._scratch.data_ptr(),
-                   centers.data_ptr(), dstatus.data_ptr(), s)
-
-        # the candidates: the detector over the K nearest components' seeds, in depth order
-        detect(self._seed, self._cand, self._cand_status)
-        if self.palm and centers_uvd is None:
-            L.call("awr_detect_palm", self._frames.data_ptr(), 0, B, self.fh, self.fw, self._idx.data_ptr(), P, self._cand.data_ptr(),
-                   self._cand_status.data_ptr(), self.depth_range[0], self.depth_range[1], self._cube.data_ptr(), 0, fx, fy, self.palm_search,
-                   D.PALM_TAU[0], D.PALM_TAU[1], D.PALM_RHO2[0], D.PALM_RHO2[1], self._palm_scratch.data_ptr(), self._cand.data_ptr(),
-                   self._cand_status.data_ptr(), self._palm_info.data_ptr(), s)
-            self.palm_info = self._palm_info.view(K, B, 4)[:, :nb].transpose(0, 1)
-        if self.track:
-            # every slot's last centre as a given seed (a free slot's NaN seed finds nothing): where it still finds the hand the slot is held
-            detect(self._track, self._tcenters, self._tstatus)
-        smooth = self.smooth is not None
-        L.call("awr_hands_assign", self._id_last.data_ptr(), self._id_ids.data_ptr(), self._id_miss.data_ptr(), self._id_next.data_ptr(),
-               self._cand.data_ptr(), self._cand_status.data_ptr(), self._tcenters.data_ptr() if self.track else None,
-               self._tstatus.data_ptr() if self.track else None, K, B, nv, cfg.gate_mm, cfg.merge_mm, cfg.max_miss, fx, fy, u0, v0, self.flip,
-               self._filter_state.data_ptr() if smooth else None, self._filter_count.data_ptr() if smooth else None, J if smooth else 0,
-               self._centers.data_ptr(), status.data_ptr(), L.ptr(assigned[0]), L.ptr(assigned[1]), L.ptr(assigned[2]), dropped.data_ptr(), s)
-
-        def crop_and_predict():
-            L.call("awr_detect_samples", self._centers.data_ptr(), self._cube.data_ptr(), 0, B, self._idx.data_ptr(), P, self.S, self.fh, self.fw,
-                   fx, fy, u0, v0, self.flip, self._blocks.data_ptr(), L.ptr(M), L.ptr(cxyz), L.ptr(self._cube32), status.data_ptr(), s)
-            self._render(self._blocks, out=self._img)
-            jt = self.engine(self._img)
-            L.call("awr_joints_unproject", L.ptr(jt), L.ptr(cxyz), L.ptr(M), L.ptr(self._cube32), P, J, P, float(self.S), fx, fy, u0, v0, self.flip,
-                   L.ptr(uvd), L.ptr(xyz), ustatus.data_ptr(), s)
-
-        def joints_center(joints, center_out, next_out, code):
-            L.call("awr_joints_center", L.ptr(joints), self._centers.data_ptr(), L.ptr(cxyz), L.ptr(self._cube32), status.data_ptr(), ustatus.data_ptr(),
-                   P, J, P, L.ptr(self._joints), 0 if self._joints is None else int(self._joints.numel()), fx, fy, u0, v0, self.flip,
-                   self.depth_range[0], self.depth_range[1], self.max_shift, center_out.data_ptr(), L.ptr(next_out), code.data_ptr(), s)
-
-        def smooth_step():
-            """K launches of awr_joints_filter, one per hand block: the rows past n_valid of EVERY block keep their state"""
-            scfg = self.smooth
-            weighted = scfg.weight == "conf"
-            conf = self.engine.conf[..., 0].contiguous() if weighted else None          # (P, J)
-            out = [torch.empty((P, J, 3), dtype=torch.float32, device=dev) for _ in range(3)] + [torch.empty((P, J), dtype=torch.int32, device=dev)]
-            for k in range(K):
-                o = k * B
-                L.call("awr_joints_filter", self._filter_state[o:].data_ptr(), self._filter_count[o:].data_ptr(), xyz[o:].data_ptr(),
-                       status[o:].data_ptr(), ustatus[o:].data_ptr(), conf[o:].data_ptr() if weighted else None, B, J, nv, dt, scfg.min_cutoff,
-                       scfg.beta, scfg.d_cutoff, -1.0 if scfg.gate_mm is None else scfg.gate_mm, scfg.max_coast, T.WEIGHTS[scfg.weight],
-                       scfg.conf_floor, fx, fy, u0, v0, self.flip, out[0][o:].data_ptr(), out[1][o:].data_ptr(), out[2][o:].data_ptr(),
-                       out[3][o:].data_ptr(), s)
-            return out
-
-        def rows(t):          # hand-major (K * B, ...) -> a (nb, K, ...) view
-            return t.view((K, B) + tuple(t.shape[1:]))[:, :nb].transpose(0, 1)
-
-        crop_and_predict()
-        smoothed = None
-        if self.recenter or self.track:
-            codes = torch.zeros((self.recenter + 1, P), dtype=torch.int32, device=dev)
-            for k in range(self.recenter):
-                joints_center(xyz, self._centers, None, codes[k])
-                crop_and_predict()
-            nxt = torch.full((P, 3), nan, dtype=torch.float64, device=dev)
-            next_from = xyz
-            if smooth and self.smooth.lead:
-                # the next call's crop starts where constant velocity says the hand will be: filter first, centre the look-ahead joints
-                smoothed = smooth_step()
-                next_from = smoothed[2]
-            joints_center(next_from, self._moved, nxt, codes[self.recenter])
-            # every slot's last centre becomes its joints' centre where there is one: `nxt` where finite, else what it was
-            L.call("awr_centers_select", nxt.data_ptr(), self._zero_status.data_ptr(), self._id_last.data_ptr(), self._cand_status.data_ptr(), P,
-                   self._sel.data_ptr(), self._sel_status.data_ptr(), None, s)
-            self._id_last.view(P, 3).copy_(self._sel)
-            self.centers_uvd = rows(self._centers.clone())
-            self.next_centers_uvd = rows(nxt)
-            self.recenter_codes = codes.view(self.recenter + 1, K, B)[:, :, :nb].transpose(1, 2)
-        self._last = (status.view(K, B), ustatus.view(K, B), nv)
-        n_hands = (status.view(K, B)[:, :nb] == D.OK).sum(0, dtype=torch.int32)
-        self.hand_codes, self.hand_source, self.hands_dropped = rows(assigned[0].reshape(P)), rows(assigned[2].reshape(P)), dropped[:nb]
-        out_xyz, out_uvd = xyz, uvd
-        if smooth:
-            out_xyz, out_uvd, ahead, fcodes = smoothed or smooth_step()
-            self.raw_xyz, self.raw_uvd, self.ahead_xyz, self.filter_codes = rows(xyz), rows(uvd), rows(ahead), rows(fcodes)
-        ids = self._id_ids[:, :nb].transpose(0, 1).clone()          # (the state moves on with the next call)
-        fields = (rows(out_xyz), rows(out_uvd), rows(cxyz), rows(M), rows(status), n_hands, ids)
-        if self.confidence:
-            conf = torch.empty((3, P, J), dtype=torch.float32, device=dev)
-            L.call("awr_confidence_fields", L.ptr(self.engine.conf), L.ptr(self.engine.stat), L.ptr(self._cube32), status.data_ptr(),
-                   ustatus.data_ptr(), P, J, P, L.ptr(conf[0]), L.ptr(conf[1]), L.ptr(conf[2]), s)
-            return ConfidentTrackedHandsPrediction(*fields, rows(conf[0]), rows(conf[1]), rows(conf[2]))
-        return TrackedHandsPrediction(*fields)
+                per_view["conf"] = self.engine.conf[..., 0] if c.weights is None else c.weights
+            self.view_outputs = types.SimpleNamespace(**{name: self._rows(t, nb, group_first=True) for name, t in per_view.items()})
+            fields += [c.vspread[:nb], c.vused[:nb]]
+        return (_CONFIDENT[kind] if self.confidence else kind)(*fields)
 
     def check(self):
         """Synchronising: raise AwrError naming the first frame of the last batch that could not be predicted, and its status code.  With
@@ -822,25 +666,18 @@ class Predictor:
         if self._last is None:
             return
         status, ustatus, nv = self._last
-        if self.hands > 1:
-            st, ust = status[:, :nv].tolist(), ustatus[:, :nv].tolist()
-            for b in range(nv):
-                if self.identity is not None:      # a slot is an identity, not a depth rank: slot 0 may well be the one that is away
-                    if all(st[k][b] != D.OK for k in range(self.hands)):
-                        raise L.AwrError("predict: frame %d of the batch: no hand slot is OK (slot 0: %s, status %d); no hand was found and its "
-                                         "joints are NaN" % (b, D.STATUS_NAMES.get(st[0][b], "invalid"), st[0][b]))
-                elif st[0][b] != D.OK:
-                    raise L.AwrError("predict: frame %d of the batch, hand slot 0: %s (status %d); no hand was found and its joints are NaN"
-                                     % (b, D.STATUS_NAMES.get(st[0][b], "invalid"), st[0][b]))
-                for k in range(self.hands):
-                    if st[k][b] == D.OK and ust[k][b] != 0:
-                        raise L.AwrError("predict: frame %d of the batch, hand slot %d: its crop matrix is %s (un-projection status %d); its "
-                                         "joints are NaN" % (b, k, {1: "singular", 2: "not finite"}.get(ust[k][b], "invalid"), ust[k][b]))
-            return
-        st, ust = status[:nv].tolist(), ustatus[:nv].tolist()
+        K = self.hands
+        st, ust = (t.view(-1, self.B)[:K, :nv].tolist() for t in (status, ustatus))          # (G, nv); with views only view 0's rows are read
+        slot0, absent = (", hand slot 0", "no hand was found and ") if K > 1 else ("", "")
         for b in range(nv):
-            if st[b] != D.OK:
-                raise L.AwrError("predict: frame %d of the batch: %s (status %d); its joints are NaN" % (b, D.STATUS_NAMES.get(st[b], "invalid"), st[b]))
-            if ust[b] != 0:
-                raise L.AwrError("predict: frame %d of the batch: its crop matrix is %s (un-projection status %d); its joints are NaN"
-                                 % (b, {1: "singular", 2: "not finite"}.get(ust[b], "invalid"), ust[b]))
+            if self.identity is not None:      # a slot is an identity, not a depth rank: slot 0 may well be the one that is away
+                if all(st[k][b] != D.OK for k in range(K)):
+                    raise L.AwrError("predict: frame %d of the batch: no hand slot is OK (slot 0: %s, status %d); no hand was found and its "
+                                     "joints are NaN" % (b, D.STATUS_NAMES.get(st[0][b], "invalid"), st[0][b]))
+            elif st[0][b] != D.OK:
+                raise L.AwrError("predict: frame %d of the batch%s: %s (status %d); %sits joints are NaN"
+                                 % (b, slot0, D.STATUS_NAMES.get(st[0][b], "invalid"), st[0][b], absent))
+            for k in range(K):
+                if st[k][b] == D.OK and ust[k][b] != 0:
+                    raise L.AwrError("predict: frame %d of the batch%s: its crop matrix is %s (un-projection status %d); its joints are NaN"
+                                     % (b, ", hand slot %d" % k if K > 1 else "", {1: "singular", 2: "not finite"}.get(ust[k][b], "invalid"), ust[k][b]))
