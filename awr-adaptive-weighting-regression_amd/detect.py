@@ -428,6 +428,26 @@ def hand_seeds(frame, hands, depth_range=DEPTH_RANGE, reach=REACH, slab=SLAB, mi
     return centers, status, info, int(cand.size)
 
 
+def isolate(frame, labels, roots):
+    """The statement of awr_hands_isolate for one frame: -> (K, fh, fw) uint16, a frame per hand slot that holds only the slot's own
+    component.  labels: `components`' (fh, fw) int32; roots: (K,) ints, slot k's root = info[1] * fw + info[0] of the info
+    row hand_seeds returns, negative for an EMPTY slot.  Output k equals the frame with every pixel set to 0 where labels >= 0 and
+    labels != roots[k]; when roots[k] < 0, output k is the unchanged frame.  Unlabelled pixels stay: background, depth 0, and foreground
+    beyond dmin + reach.  Debris components below min_pixels are labelled, so they are removed from EVERY hand's frame."""
+    frame = _u16(frame)
+    labels = np.asarray(labels)
+    roots = np.asarray(roots)
+    if labels.shape != frame.shape or labels.dtype.kind != "i":
+        raise ValueError("labels must be integers of the frame's shape %s, got %s %s" % (frame.shape, labels.dtype, labels.shape))
+    if roots.ndim != 1 or roots.dtype.kind != "i" or not 1 <= roots.size <= MAX_HANDS:
+        raise ValueError("roots must be 1 ... %d integers, got %s %s" % (MAX_HANDS, roots.dtype, roots.shape))
+    out = np.repeat(frame[None], roots.size, 0)
+    for k, root in enumerate(roots.tolist()):
+        if root >= 0:
+            out[k][(labels >= 0) & (labels != root)] = 0
+    return out
+
+
 # ---- test-time views: the same hand under rotations, cube scales and centre shifts (DESIGN.md 4.22) ----------------------------------
 def _number(x, what):
     if isinstance(x, (bool, str, bytes)) or not isinstance(x, (int, float, np.integer, np.floating)):
@@ -702,6 +722,34 @@ def hands_device(store, frame_idx, hands, depth_range=DEPTH_RANGE, reach=REACH, 
            float(depth_range[0]), float(depth_range[1]), float(reach), float(slab), int(min_pixels), scratch.data_ptr(), L.ptr(labels),
            centers.data_ptr(), status.data_ptr(), info.data_ptr(), count.data_ptr(), L.stream())
     return centers, status, info, count, labels
+
+
+def isolate_device(store, frame_idx, labels, roots=None, info=None, out=None):
+    """awr_hands_isolate on a FrameStore-like object: labels (B, fh, fw) int32 and either info (K, B, 4) int32 (hands_device's) or roots
+    (K, B) ints (negative: an EMPTY slot), on the device or numpy -> (out (K * B, fh, fw) uint16, row k * B + b, status (B,) int32) on the
+    device, nothing synchronised.  out: a tensor to write into."""
+    import torch
+    from . import _lib as L
+    dev = store.data.device
+    idx = torch.as_tensor(np.asarray(frame_idx, np.int64)).to(dev) if not isinstance(frame_idx, torch.Tensor) else frame_idx
+    B = int(idx.shape[0])
+    if (roots is None) == (info is None):
+        raise ValueError("isolate_device takes either roots or info")
+    if info is None:
+        r = torch.as_tensor(np.asarray(roots, np.int64)).to(dev) if not isinstance(roots, torch.Tensor) else roots.to(torch.int64)
+        fw = max(int(store.fw), 1)
+        none = r < 0
+        info = torch.stack([torch.where(none, -1, r % fw), torch.where(none, -1, r // fw), torch.zeros_like(r), torch.zeros_like(r)], -1).to(torch.int32)
+    if not isinstance(labels, torch.Tensor):
+        labels = torch.from_numpy(np.ascontiguousarray(labels, dtype=np.int32)).to(dev)
+    info = (info if isinstance(info, torch.Tensor) else torch.from_numpy(np.ascontiguousarray(info, dtype=np.int32)).to(dev)).contiguous()
+    K = int(info.shape[0]) if info.dim() == 3 else 0          # (a K the entry point refuses still gets its message from there)
+    if out is None:
+        out = torch.empty((max(K, 1) * B, store.fh, store.fw), dtype=torch.uint16, device=dev)
+    status = torch.empty(B, dtype=torch.int32, device=dev)
+    L.call("awr_hands_isolate", store.data.data_ptr(), store.ftype, int(store.data.shape[0]), store.fh, store.fw, idx.data_ptr(), B, K,
+           L.ptr(labels), L.ptr(info), L.ptr(out), status.data_ptr(), L.stream())
+    return out, status
 
 
 def samples_device(centers, cube, dsize, frame_idx, n_frames, frame_shape, paras=ND.PARAS, flip=-1, status=None):

@@ -17,10 +17,12 @@ detector for such a machine.  Every option is opt-in, and a predictor without it
     smooth=True | dict | track.OneEuro      One-Euro filter per joint, gate, coasting, look-ahead (lead)               4.25
     hands=K                                 up to K hands per frame from connected components; a hand axis             4.26
     hands=K, identity=True | dict           slot k is the same hand from call to call; track, smooth, lead per hand    4.27
+    hands=K, isolate=True                   every hand refined and cropped on a frame that holds only its component    4.28
 
 predict() is ONE pipeline over one stage method per entry point, and it reads top to bottom: upload the frames ->
-the seeds (given centres | awr_detect_hands | the configured seed mode) -> the candidate centres (awr_detect, awr_detect_palm) -> the
-tracked detector (a second awr_detect) -> combine (awr_centers_select | awr_hands_assign | nothing) -> crop and predict
+the seeds (given centres | awr_detect_hands | the configured seed mode) -> with isolate a frame per hand (awr_hands_isolate) -> the
+candidate centres (awr_detect, awr_detect_palm) -> the tracked detector (a second awr_detect) -> combine (awr_centers_select |
+awr_hands_assign | nothing) -> crop and predict
 (awr_detect_samples -> awr_nyu_batch -> the inference plan and the single-pass head -> awr_joints_unproject; with views awr_view_centers
 and awr_view_rotate around the crop and awr_views_fuse behind it) -> the recenter passes (awr_joints_center, crop and predict) -> the next
 centre, from the look-ahead joints with lead -> the tracker's state -> awr_joints_filter -> awr_confidence_fields -> the named tuple.
@@ -63,7 +65,7 @@ class Predictor:
     def __init__(self, net, img_size, kernel_size, cube=(300, 300, 300), paras=ND.PARAS, flip=-1, max_batch=1, frame_shape=(480, 640),
                  seed="nearest", depth_range=D.DEPTH_RANGE, slab=D.SLAB, refine_iters=D.REFINE_ITERS, winograd=None, parity=False, confidence=False,
                  recenter=0, track=False, center_joints=None, max_shift=1.0, views=None, fuse="mean", palm=False, palm_search=D.PALM_SEARCH,
-                 smooth=None, hands=1, reach=D.REACH, min_pixels=D.MIN_PIXELS, identity=None):
+                 smooth=None, hands=1, reach=D.REACH, min_pixels=D.MIN_PIXELS, identity=None, isolate=False):
         """net: an awr_amd network on the GPU with its weights loaded.  cube: the crop cube in mm.  paras = (fx, fy, u0, v0), flip: the camera.
         max_batch: the static batch of the inference plan; smaller batches are padded, larger ones refused.  seed / depth_range / slab /
         refine_iters: the detector (awr_amd.detect); with `centers_uvd` handed to predict() the seed is the given centre and refine_iters
@@ -128,7 +130,16 @@ class Predictor:
         candidate each slot took (-1 none, -2 its tracked centre), hands_dropped (nb,) int32 candidates that found no slot; hand_info and
         palm_info stay in CANDIDATE order (the nearest first); raw_xyz, raw_uvd, ahead_xyz, filter_codes carry the hand axis.  Explicit
         centers_uvd (nb, K, 3) are the candidates.  reset_identity() forgets the identities.  views stays refused.  The defaults are
-        engineering choices, UNMEASURED on real frames."""
+        engineering choices, UNMEASURED on real frames.
+        isolate: True -- with hands >= 2, every hand gets a frame that holds only ITS component (statement:
+        awr_amd.detect.isolate): awr_detect_hands writes its labels, one awr_hands_isolate launch writes K frames per frame behind the raw
+        ones (the frame store grows to max_batch + K * max_batch rows), and the refinement, the palm pass, the crop and every recenter pass
+        of slot k read row max_batch + k * max_batch + b instead of b -- two hands nearer than half a crop cube no longer stand in each
+        other's window and crop.  With identity the candidates are refined on their isolated rows and a slot crops from the row of the
+        candidate it took; a slot that follows its tracked centre, the tracker's own detector run and predict(centers_uvd=...) (which
+        computes no labels) read the raw frames.  After a call `isolated` (nb, K) int32: 1 where the slot's row was an isolated frame, 0
+        for a raw one and for a slot without a hand.  Refused with hands=1 and with views.  Touching hands remain ONE component and ONE
+        hand; UNMEASURED on real frames."""
         if isinstance(hands, bool) or not isinstance(hands, int):
             raise TypeError("hands is an int in [1, %d], not %r" % (D.MAX_HANDS, hands))
         K, self.reach, _, self.min_pixels = D._check_hands(hands, reach, 0.0, min_pixels)
@@ -143,6 +154,11 @@ class Predictor:
                 if on and (identity is None or name == "views"):
                     raise ValueError("hands = %d and %s are not combined yet: which hand of one call is which hand of the next is not decided "
                                      "here (hands=1 takes %s)" % (K, name, name))
+        if not isinstance(isolate, bool):
+            raise TypeError("isolate is True or False, not %r" % (isolate,))
+        if isolate and (K == 1 or views is not None):
+            raise ValueError("isolate gives each of SEVERAL hands a frame of its own component: it needs hands >= 2, and views are not combined with it")
+        self.isolate, self.isolated = isolate, None
         if not isinstance(palm, bool):
             raise TypeError("palm is True or False, not %r" % (palm,))
         self.palm, self.palm_search = palm, D.check_palm(palm_search)[0]
@@ -202,11 +218,14 @@ class Predictor:
                                   confidence=confidence or (V > 1 and fuse == "conf") or (smooth is not None and self.smooth.weight == "conf"))
         self.J = self.engine.J
         # the predictor's own small frame store: the FrameStore layout, one row per image of a batch
-        self._frames = torch.empty((B, self.fh, self.fw), dtype=torch.uint16, device=dev)
-        self._frames.view(torch.int16).zero_()
+        # (isolate: one buffer of B + K * B rows -- the raw frames, then every hand's isolated frames, hand-major)
+        self._nframes = B + K * B if isolate else B
+        self._all_frames = torch.empty((self._nframes, self.fh, self.fw), dtype=torch.uint16, device=dev)
+        self._all_frames.view(torch.int16).zero_()
+        self._frames = self._all_frames[:B]
         self._stage = torch.empty((B, self.fh, self.fw), dtype=torch.uint16).pin_memory()
         self._stage_free = None                  # event: the last upload from the staging buffer has been issued and has finished
-        self._store = types.SimpleNamespace(data=self._frames, ftype=0, fh=self.fh, fw=self.fw, n=B)
+        self._store = types.SimpleNamespace(data=self._all_frames, ftype=0, fh=self.fh, fw=self.fw, n=self._nframes)
         self._render = DV.Renderer(self._store, self.S, P)
         self._idx = torch.arange(B, dtype=torch.int64, device=dev).repeat(K)          # (K > 1: the frame of every hand-major row)
         self._cube = torch.tensor([float(c) for c in cube], dtype=torch.float64, device=dev)
@@ -239,6 +258,10 @@ class Predictor:
             self._hands_status = torch.empty((K, B), dtype=torch.int32, device=dev)
             self._hands_info = torch.empty((K, B, 4), dtype=torch.int32, device=dev)
             self._hands_count = torch.empty(B, dtype=torch.int32, device=dev)
+        if isolate:
+            self._labels = torch.empty((B, self.fh, self.fw), dtype=torch.int32, device=dev)
+            self._iso_status = torch.empty(B, dtype=torch.int32, device=dev)
+            self._iso_idx = torch.arange(B, B + K * B, dtype=torch.int64, device=dev)          # the isolated frame of every hand-major row
         if smooth is not None:
             self._filter_state = torch.zeros((B * K, self.J, 6), dtype=torch.float64, device=dev)      # x0 x1 x2 d0 d1 d2 per slot (and hand) and joint
             self._filter_count = torch.zeros((B * K, self.J, 2), dtype=torch.int32, device=dev)        # age, coast
@@ -408,14 +431,14 @@ class Predictor:
             c.fields = torch.empty((3, F, J), dtype=torch.float32, device=dev)
         return c
 
-    def _detect(self, n, mode, seed, centers, status):
-        L.call("awr_detect", self._frames.data_ptr(), 0, self.B, self.fh, self.fw, self._idx.data_ptr(), n, mode, L.ptr(seed), self.depth_range[0],
+    def _detect(self, n, mode, seed, centers, status, frame):
+        L.call("awr_detect", self._frames.data_ptr(), 0, self._nframes, self.fh, self.fw, frame.data_ptr(), n, mode, L.ptr(seed), self.depth_range[0],
                self.depth_range[1], self.slab, self._cube.data_ptr(), 0, self.paras[0], self.paras[1], self.iters, 0, self._scratch.data_ptr(),
                centers.data_ptr(), status.data_ptr(), L.stream())
 
-    def _detect_palm(self, n, nb, centers, status):
+    def _detect_palm(self, n, nb, centers, status, frame):
         """in place: a frame that is not OK keeps its centre and status"""
-        L.call("awr_detect_palm", self._frames.data_ptr(), 0, self.B, self.fh, self.fw, self._idx.data_ptr(), n, centers.data_ptr(),
+        L.call("awr_detect_palm", self._frames.data_ptr(), 0, self._nframes, self.fh, self.fw, frame.data_ptr(), n, centers.data_ptr(),
                status.data_ptr(), self.depth_range[0], self.depth_range[1], self._cube.data_ptr(), 0, self.paras[0], self.paras[1], self.palm_search,
                D.PALM_TAU[0], D.PALM_TAU[1], D.PALM_RHO2[0], D.PALM_RHO2[1], self._palm_scratch.data_ptr(), centers.data_ptr(),
                status.data_ptr(), self._palm_info.data_ptr(), L.stream())
@@ -424,9 +447,15 @@ class Predictor:
     def _detect_hands(self, nb):
         """the K nearest components' seeds of every frame -> self._seed, hand-major"""
         L.call("awr_detect_hands", self._frames.data_ptr(), 0, self.B, self.fh, self.fw, self._idx.data_ptr(), self.B, self.hands, self.depth_range[0],
-               self.depth_range[1], self.reach, self.slab, self.min_pixels, self._hands_scratch.data_ptr(), None, self._seed.data_ptr(),
+               self.depth_range[1], self.reach, self.slab, self.min_pixels, self._hands_scratch.data_ptr(),
+               self._labels.data_ptr() if self.isolate else None, self._seed.data_ptr(),
                self._hands_status.data_ptr(), self._hands_info.data_ptr(), self._hands_count.data_ptr(), L.stream())
         self.hand_info = self._hands_info[:, :nb].transpose(0, 1)
+
+    def _hands_isolate(self):
+        """the raw frames, their labels and the slots' info rows -> rows [B, B + K * B) of the frame store: a frame per hand, hand-major"""
+        L.call("awr_hands_isolate", self._frames.data_ptr(), 0, self.B, self.fh, self.fw, self._idx.data_ptr(), self.B, self.hands,
+               self._labels.data_ptr(), self._hands_info.data_ptr(), self._all_frames[self.B:].data_ptr(), self._iso_status.data_ptr(), L.stream())
 
     def _centers_select(self, n, first, first_status, second, second_status, out, out_status):
         """per row `first` where its status is OK, else `second`"""
@@ -445,7 +474,7 @@ class Predictor:
 
     def _detect_samples(self, n, c, centers, cubes, cube_stride, frame, status):
         """centres -> crop blocks, crop matrices, centres in camera space, float cubes"""
-        L.call("awr_detect_samples", centers.data_ptr(), cubes.data_ptr(), cube_stride, self.B, frame.data_ptr(), n, self.S, self.fh, self.fw,
+        L.call("awr_detect_samples", centers.data_ptr(), cubes.data_ptr(), cube_stride, self._nframes, frame.data_ptr(), n, self.S, self.fh, self.fw,
                *self.paras, self.flip, self._blocks.data_ptr(), L.ptr(c.M), L.ptr(c.cxyz), L.ptr(self._cube32), status.data_ptr(), L.stream())
 
     def _joints_unproject(self, n, nv, jt, c):
@@ -502,7 +531,7 @@ class Predictor:
             self._detect_samples(c.R, c, self._vcenters, self._vcubes, 3, self._vframe, c.vstatus)
             self._view_rotate(c)
         else:
-            self._detect_samples(c.fv, c, self._centers, self._cube, 0, self._idx, c.status)
+            self._detect_samples(c.fv, c, self._centers, self._cube, 0, c.frame, c.status)
         if c.R == self.B:
             self._render(self._blocks[:c.nv], out=self._img[:c.nv])
             if c.nv < self.B:
@@ -579,28 +608,40 @@ class Predictor:
             self.hand_info = None
         elif K > 1:
             self._detect_hands(nb)
+        # the frame of every detector row: the raw one, or with isolate the hand's own (given centres come without labels: raw frames)
+        isolated = self.isolate and not given
+        frame = self._idx
+        if isolated:
+            self._hands_isolate()
+            frame = self._iso_idx
         if K > 1 and nv < B:
             self._seed.view(K, B, 3)[:, nv:].fill_(nan)          # rows past n_valid of every group: NaN seeds, blocks without pixels
         c = self._tensors(nb, nv)
+        c.frame = frame
         # the candidate centres, where configured through the palm pass, and the tracked detector: seeded with the centres the previous
         # call left (a lost slot's NaN seed finds nothing).  Hands without identities have nothing to combine: the candidates are the centres
         tracked = self.track and (K > 1 or not given)
         cand, cand_status = self._centers, c.status
         if tracked and K == 1:
             cand, cand_status = self._dcenters, self._dstatus
-            self._detect(c.fv, D.SEED_GIVEN, self._track, self._tcenters, self._tstatus)          # (one slot: the tracker goes first)
+            self._detect(c.fv, D.SEED_GIVEN, self._track, self._tcenters, self._tstatus, self._idx)          # (one slot: the tracker goes first)
         elif self.identity is not None:
             cand, cand_status = self._cand, self._cand_status
-        self._detect(c.fv, mode, seed, cand, cand_status)
+        self._detect(c.fv, mode, seed, cand, cand_status, frame)
         if self.palm and not given:
-            self._detect_palm(c.fv, nb, cand, cand_status)
+            self._detect_palm(c.fv, nb, cand, cand_status, frame)
         if tracked and K > 1:
-            self._detect(c.fv, D.SEED_GIVEN, self._track, self._tcenters, self._tstatus)
+            # (on the RAW frames, also with isolate: which component a tracked centre belongs to is not decided here)
+            self._detect(c.fv, D.SEED_GIVEN, self._track, self._tcenters, self._tstatus, self._idx)
         # combine them: per slot the tracked centre where it holds, else the detector's; with identities the assignment
         if tracked and K == 1:
             self._centers_select(nv, self._tcenters, self._tstatus, cand, cand_status, self._centers, c.status)
         elif self.identity is not None:
             self._hands_assign(c)
+            if isolated:
+                # a slot crops from the isolated frame of the candidate it took; one that follows its tracked centre, or has none, from the raw frame
+                source = c.assigned[2].to(torch.int64)
+                c.frame = torch.where(source >= 0, self._idx + B + source * B, self._idx)
         self._crop_and_predict(c)
         if self.recenter or self.track:
             for k in range(self.recenter):
@@ -626,6 +667,8 @@ class Predictor:
             self._joints_filter(c, dt)
         if self.confidence:
             self._confidence_fields(c)
+        if self.isolate:
+            self.isolated = self._rows(((c.frame >= B) & (c.status == D.OK)).to(torch.int32), nb)
         return self._result(c, given)
 
     def _result(self, c, given):

@@ -983,6 +983,27 @@ int awr_detect_hands(const void* frames, int frame_type, int64_t n_frames, int f
                      int* labels_out /* B*fh*fw, may be NULL */, double* centers /* K,B,3 */, int* status /* K,B */,
                      int* info /* K,B,4 */, int* count /* B */, void* stream);
 
+/* A frame per hand (csrc/awr_isolate.hip; the numpy statement is awr_amd/detect.py isolate, results are bit-identical
+ * to it).  awr_detect_hands keeps a seed per hand, and awr_detect, awr_detect_palm, awr_detect_samples and the renderer read the whole raw
+ * frame again: two hands closer than half a crop cube stand in each other's window and crop.  This entry gives each hand a frame that
+ * holds only its own component.  Rule, per frame b and slot k, with labels (B, fh, fw) as awr_detect_hands' labels_out and
+ * root_k = info[1] * fw + info[0] of the slot's info row (info (K, B, 4), hand-major, as awr_detect_hands writes it):
+ *   output k equals the frame with every pixel set to 0 where labels >= 0 and labels != root_k;
+ *   when root_k < 0 (an EMPTY slot: info = (-1, -1, 0, 0)), output k is the unchanged frame;
+ *   unlabelled pixels stay: background, depth 0, and foreground beyond dmin + reach;
+ *   debris components below min_pixels are labelled, so they are removed from EVERY hand's frame.
+ * out: an output store in the FrameStore layout, (K * B, fh, fw) uint16, row k * B + b -- hand-major, so awr_detect and what follows take
+ * the rows as frame indices.  It may be rows of the allocation that holds `frames`, past the n_frames rows that are read.  status (B):
+ * AWR_DET_OK, or AWR_DET_BAD_FRAME where frame[b] is outside [0, n_frames): that frame's K outputs are zero frames and nothing is read.
+ *   K in [1, AWR_DET_MAX_HANDS], B in [1, AWR_DET_MAX_BATCH], fh, fw in [1, 16384]: anything else returns AWR_ERR_ARG with a message,
+ *   before any launch.  Only uint16 frames.
+ * ONE launch on `stream`: a thread per 8 pixels reads one 16-byte word of the frame and its 8 labels and writes K 16-byte words, so the
+ * frame and its labels are read once however large K is ((6 + 2 K) bytes per pixel); where fh * fw is no multiple of 8 or a base is not
+ * 16-byte aligned a thread per pixel does the same.  No atomics, no LDS, nothing synchronises. */
+int awr_hands_isolate(const void* frames, int frame_type, int64_t n_frames, int fh, int fw, const int64_t* frame, int B, int K,
+                      const int* labels /* B,fh,fw */, const int* info /* K,B,4 */, void* out /* K*B,fh,fw uint16 */, int* status /* B */,
+                      void* stream);
+
 /* Joints -> the next crop centre, per frame, with a gate (the numpy statement is awr_amd/detect.py joints_center,
  * results are bit-identical to it):
  *   xyz (B, J, 3) camera mm, as awr_joints_unproject writes xyz_out; center_uvd (B, 3) doubles, the centres this pass was cropped at;

@@ -31,6 +31,9 @@ pixel u, v, its pixels, its nearest depth) are written too.  Not combined with -
 assignment of each frame's detected hands to the previous frame's; defaults 150,60,5, UNMEASURED on real frames): the file
 is ONE sequence (batch size 1), --track and --smooth then work per hand, and pred_hand_id.txt (K columns, 0: a free slot) and
 pred_hand_code.txt (K columns, awr_amd.track.ASSIGN_NAMES) are written too; pred_hand_info.txt stays in detection order.
+--isolate (with --hands K) gives every hand a frame that holds only its own connected component before the refinement, the palm pass and
+the crop (awr_hands_isolate): two hands nearer than half a crop cube no longer stand in each other's crop.  Touching hands
+remain one component and one hand; UNMEASURED on real frames.
 --ema predicts with the checkpoint's averaged weights ("model_ema", written by a run with config.ema_decay) instead of "model".
 `--set` overrides config entries as train.py does (img_size, kernel_size, cube, batch_size, jt_num, downsample, winograd ...)."""
 import argparse
@@ -61,6 +64,7 @@ def parse_args(argv=None):
     ap.add_argument("--hands", type=int, default=1, metavar="K", help="look for up to K hands per frame (1 ... 4); the outputs gain a hand axis")
     ap.add_argument("--reach", type=float, default=None, metavar="MM", help="with --hands: depth of the foreground behind the nearest pixel (default 300)")
     ap.add_argument("--min-pixels", type=int, default=None, metavar="N", help="with --hands: the smallest component that counts as a hand (default 400)")
+    ap.add_argument("--isolate", action="store_true", help="with --hands: refine and crop every hand on a frame that holds only its own component")
     ap.add_argument("--identity", nargs="?", const="", default=None, metavar="GATE_MM,MERGE_MM,MAX_MISS",
                     help="with --hands: keep each hand in its slot across frames (the file is one sequence); optionally the gate, the merge distance and the misses allowed")
     ap.add_argument("--ema", action="store_true", help="load the checkpoint's \"model_ema\" (the EMA of the weights) instead of \"model\"")
@@ -138,7 +142,9 @@ def main(argv=None):
     views = None if args.views is None else detect.parse_views(args.views)
     if args.hands == 1 and (args.reach is not None or args.min_pixels is not None):
         raise SystemExit("--reach and --min-pixels belong to --hands K with K >= 2")
-    hands_kw = {} if args.hands == 1 else dict(hands=args.hands, reach=detect.REACH if args.reach is None else args.reach,
+    if args.isolate and (args.hands == 1 or args.views is not None):
+        raise SystemExit("--isolate belongs to --hands K with K >= 2, without --views")
+    hands_kw = {} if args.hands == 1 else dict(isolate=args.isolate, hands=args.hands, reach=detect.REACH if args.reach is None else args.reach,
                                                min_pixels=detect.MIN_PIXELS if args.min_pixels is None else args.min_pixels)
     K = args.hands
     pred = awr_amd.Predictor(net.cuda(), cfg.img_size, cfg.kernel_size, cube=cfg.cube, max_batch=bs, frame_shape=frames.shape[1:],
