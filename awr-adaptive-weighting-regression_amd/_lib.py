@@ -317,6 +317,15 @@ def stream():
     return torch.cuda.current_stream().cuda_stream
 
 
+def scratch(name, *args, dtype, device):
+    """An uninitialised tensor of the bytes the size function `name` (an awr_*_scratch export) asks for at `args`, as elements of `dtype`;
+    a size the library refuses (negative) raises AwrError with its message."""
+    nbytes = int(getattr(lib, name)(*args))
+    if nbytes < 0:
+        raise AwrError(last_error())
+    return torch.empty(nbytes // dtype.itemsize, dtype=dtype, device=device)
+
+
 def call(name, *args):
     if name in MISSING:
         raise AwrError("libawr_hip.so does not export %s -- rebuild it (__graft_entry__.build())" % name)

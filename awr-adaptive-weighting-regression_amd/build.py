@@ -66,6 +66,8 @@ def build_lib(force=False, verbose=True, study=None):
     study = (os.environ.get("AWR_BUILD_STUDY") == "1") if study is None else bool(study)
     os.makedirs(LIBDIR, exist_ok=True)
     hipcc = _hipcc()
+    # every csrc/*.h is a dependency of every object (awr_frame.h's double arithmetic is only ever included by sources that carry
+    # -ffp-contract=off above, awr_isolate.hip excepted, which uses its integers alone)
     headers = [os.path.join(CSRC, f) for f in os.listdir(CSRC) if f.endswith(".h")]
     headers.append(os.path.join(os.path.dirname(HERE), "include", "awr_hip.h"))
     objs, jobs = [], []

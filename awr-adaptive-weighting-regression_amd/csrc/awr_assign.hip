@@ -13,13 +13,12 @@
 #include <limits.h>
 #include <math.h>
 
-#include "awr_common.h"
+#include "awr_frame.h"
 
 namespace awr {
 
 constexpr int ASSIGN_THREADS = 256;
 constexpr int ASSIGN_FRAMES = ASSIGN_THREADS / WAVE;          // frames (waves) per workgroup
-constexpr int KMAX = AWR_ASSIGN_MAX_HANDS;
 
 struct assign_args {
     double* last_uvd;
@@ -55,10 +54,10 @@ __device__ __forceinline__ double dist2(const vec3& a, const vec3& b) {
 }
 
 // the p-th permutation of 0 .. K - 1 in lexicographic order: digit i of p in the factorial number system picks among the elements left
-__device__ __forceinline__ void decode_permutation(int p, int K, int perm[KMAX]) {
+__device__ __forceinline__ void decode_permutation(int p, int K, int perm[MAX_HANDS]) {
     int left = (1 << K) - 1;
 #pragma unroll
-    for (int i = 0; i < KMAX; ++i) {
+    for (int i = 0; i < MAX_HANDS; ++i) {
         perm[i] = i;
         if (i < K) {
             const int n = K - 1 - i;
@@ -67,7 +66,7 @@ __device__ __forceinline__ void decode_permutation(int p, int K, int perm[KMAX])
             p -= d * f;
             int pick = 0;
 #pragma unroll
-            for (int e = 0; e < KMAX; ++e) {
+            for (int e = 0; e < MAX_HANDS; ++e) {
                 if ((left >> e) & 1) {
                     if (d == 0) pick = e;
                     --d;
@@ -95,11 +94,11 @@ __global__ __launch_bounds__(ASSIGN_THREADS) void hands_assign_kernel(const assi
         return;
     }
     // ---- every lane loads the frame's K slots and K candidates (the same addresses across the wave) ----
-    int ident[KMAX], ms[KMAX], cd[KMAX];
-    bool held[KMAX], usable[KMAX], released[KMAX];
-    vec3 trk[KMAX], cand[KMAX], r[KMAX], q[KMAX];
+    int ident[MAX_HANDS], ms[MAX_HANDS], cd[MAX_HANDS];
+    bool held[MAX_HANDS], usable[MAX_HANDS], released[MAX_HANDS];
+    vec3 trk[MAX_HANDS], cand[MAX_HANDS], r[MAX_HANDS], q[MAX_HANDS];
 #pragma unroll
-    for (int i = 0; i < KMAX; ++i) {
+    for (int i = 0; i < MAX_HANDS; ++i) {
         ident[i] = 0; ms[i] = 0; cd[i] = AWR_ASSIGN_FREE;
         held[i] = usable[i] = released[i] = false;
         trk[i] = cand[i] = r[i] = q[i] = vec3{nan, nan, nan};
@@ -114,17 +113,16 @@ __global__ __launch_bounds__(ASSIGN_THREADS) void hands_assign_kernel(const assi
                 trk[i] = vec3{a.trk_uvd[3 * e], a.trk_uvd[3 * e + 1], a.trk_uvd[3 * e + 2]};
                 held[i] = ident[i] > 0 && a.trk_status[e] == AWR_DET_OK && finite3(trk[i]);
             }
-            // evaluator.uvd2xyz in its operation order, in double
-            const vec3 from = held[i] ? trk[i] : last;
-            r[i] = vec3{(from.x - a.u0) * from.z / a.fx, (from.y - a.v0) * from.z / a.fy * a.flip, from.z};
-            q[i] = vec3{(cand[i].x - a.u0) * cand[i].z / a.fx, (cand[i].y - a.v0) * cand[i].z / a.fy * a.flip, cand[i].z};
+            const vec3 from = held[i] ? trk[i] : last;                   // uvd2xyz, in double
+            r[i] = vec3{uvd2x(from.x, a.u0, from.z, a.fx), uvd2y(from.y, a.v0, from.z, a.fy, a.flip), from.z};
+            q[i] = vec3{uvd2x(cand[i].x, a.u0, cand[i].z, a.fx), uvd2y(cand[i].y, a.v0, cand[i].z, a.fy, a.flip), cand[i].z};
         }
     }
     // ---- 1. two tracked centres on one hand: the younger identity is released ----
 #pragma unroll
-    for (int i = 0; i < KMAX; ++i) {
+    for (int i = 0; i < MAX_HANDS; ++i) {
 #pragma unroll
-        for (int j = i + 1; j < KMAX; ++j) {
+        for (int j = i + 1; j < MAX_HANDS; ++j) {
             if (held[i] && held[j] && dist2(r[i], r[j]) <= a.merge2) {
                 const bool second = ident[j] > ident[i];
                 if (second) { held[j] = false; ident[j] = 0; ms[j] = 0; cd[j] = AWR_ASSIGN_MERGED; released[j] = true; }
@@ -133,28 +131,28 @@ __global__ __launch_bounds__(ASSIGN_THREADS) void hands_assign_kernel(const assi
         }
     }
     // ---- 2. the cost matrix and the admissible pairs ----
-    double c[KMAX][KMAX];
-    bool adm[KMAX][KMAX];
+    double c[MAX_HANDS][MAX_HANDS];
+    bool adm[MAX_HANDS][MAX_HANDS];
 #pragma unroll
-    for (int i = 0; i < KMAX; ++i) {
+    for (int i = 0; i < MAX_HANDS; ++i) {
 #pragma unroll
-        for (int j = 0; j < KMAX; ++j) {
+        for (int j = 0; j < MAX_HANDS; ++j) {
             c[i][j] = dist2(r[i], q[j]);
             adm[i][j] = ident[i] > 0 && usable[j] && c[i][j] <= a.gate2;        // (a NaN compares false)
         }
     }
     // ---- 3. lane p evaluates permutation p; the best (m descending, s ascending, p ascending) reaches every lane ----
     const int nperm = K == 4 ? 24 : (K == 3 ? 6 : K);
-    int perm[KMAX];
+    int perm[MAX_HANDS];
     int m = -1, p = lane;
     double s = 0.0;
     if (lane < nperm) {
         decode_permutation(lane, K, perm);
         m = 0;
 #pragma unroll
-        for (int i = 0; i < KMAX; ++i) {
+        for (int i = 0; i < MAX_HANDS; ++i) {
 #pragma unroll
-            for (int j = 0; j < KMAX; ++j) {
+            for (int j = 0; j < MAX_HANDS; ++j) {
                 if (perm[i] == j && adm[i][j]) { m += 1; s = s + c[i][j]; }
             }
         }
@@ -169,15 +167,15 @@ __global__ __launch_bounds__(ASSIGN_THREADS) void hands_assign_kernel(const assi
     }
     decode_permutation(p, K, perm);
     // ---- 4. every live slot: tracked, matched, coasting or lost (from here on every lane repeats the same scalar steps) ----
-    bool consumed[KMAX] = {false, false, false, false};
-    int out[KMAX];                                                   // the candidate index, SOURCE_TRACKED or SOURCE_NONE
+    bool consumed[MAX_HANDS] = {false, false, false, false};
+    int out[MAX_HANDS];                                              // the candidate index, SOURCE_TRACKED or SOURCE_NONE
 #pragma unroll
-    for (int i = 0; i < KMAX; ++i) {
+    for (int i = 0; i < MAX_HANDS; ++i) {
         out[i] = AWR_ASSIGN_SOURCE_NONE;
         if (ident[i] > 0) {
             int j = -1;
 #pragma unroll
-            for (int e = 0; e < KMAX; ++e)
+            for (int e = 0; e < MAX_HANDS; ++e)
                 if (perm[i] == e && adm[i][e]) j = e;
             if (held[i]) {
                 out[i] = AWR_ASSIGN_SOURCE_TRACKED; ms[i] = 0; cd[i] = AWR_ASSIGN_TRACKED;
@@ -192,31 +190,31 @@ __global__ __launch_bounds__(ASSIGN_THREADS) void hands_assign_kernel(const assi
                 }
             }
 #pragma unroll
-            for (int e = 0; e < KMAX; ++e)
+            for (int e = 0; e < MAX_HANDS; ++e)
                 if (j == e) consumed[e] = true;                      // (a tracked slot's match is the same hand seen twice)
         }
     }
     // ---- 5. births, in candidate order: the lowest free slot, else the slot that has coasted longest ----
     int nid = a.next_id[b], ndropped = 0;
-    int born[KMAX] = {0, 0, 0, 0};
+    int born[MAX_HANDS] = {0, 0, 0, 0};
 #pragma unroll
-    for (int j = 0; j < KMAX; ++j) {
+    for (int j = 0; j < MAX_HANDS; ++j) {
         if (j < K && usable[j] && !consumed[j]) {
             int slot = -1;
 #pragma unroll
-            for (int i = KMAX - 1; i >= 0; --i)
+            for (int i = MAX_HANDS - 1; i >= 0; --i)
                 if (i < K && ident[i] == 0) slot = i;
             if (slot < 0) {
                 int longest = INT_MIN;
 #pragma unroll
-                for (int i = 0; i < KMAX; ++i)
+                for (int i = 0; i < MAX_HANDS; ++i)
                     if (i < K && cd[i] == AWR_ASSIGN_COASTING && ms[i] > longest) { slot = i; longest = ms[i]; }
             }
             if (slot < 0) {
                 ndropped += 1;
             } else {
 #pragma unroll
-                for (int i = 0; i < KMAX; ++i)
+                for (int i = 0; i < MAX_HANDS; ++i)
                     if (i == slot) { ident[i] = nid; ms[i] = 0; cd[i] = AWR_ASSIGN_BORN; out[i] = j; born[i] = 1; }
                 if (nid < INT_MAX) nid += 1;
             }
@@ -225,13 +223,13 @@ __global__ __launch_bounds__(ASSIGN_THREADS) void hands_assign_kernel(const assi
     // ---- 6. outputs and state: lane 0 stores ----
     if (lane == 0) {
 #pragma unroll
-        for (int i = 0; i < KMAX; ++i) {
+        for (int i = 0; i < MAX_HANDS; ++i) {
             if (i < K) {
                 const int64_t e = (int64_t)i * B + b;
                 vec3 centre = {nan, nan, nan};
                 if (out[i] == AWR_ASSIGN_SOURCE_TRACKED) centre = trk[i];
 #pragma unroll
-                for (int j = 0; j < KMAX; ++j)
+                for (int j = 0; j < MAX_HANDS; ++j)
                     if (out[i] == j) centre = cand[j];
                 const bool ok = out[i] != AWR_ASSIGN_SOURCE_NONE;
                 a.centers[3 * e] = centre.x; a.centers[3 * e + 1] = centre.y; a.centers[3 * e + 2] = centre.z;
@@ -249,7 +247,7 @@ __global__ __launch_bounds__(ASSIGN_THREADS) void hands_assign_kernel(const assi
     // ---- the temporal filter's rows of a slot that started or lost an identity: no track (the wave strides over them) ----
     if (a.filter_state) {
 #pragma unroll
-        for (int i = 0; i < KMAX; ++i) {
+        for (int i = 0; i < MAX_HANDS; ++i) {
             if (i < K && (born[i] || released[i])) {
                 const int64_t row = (int64_t)i * B + b;
                 double* S = a.filter_state + row * a.J * 6;

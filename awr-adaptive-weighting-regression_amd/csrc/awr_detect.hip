@@ -10,7 +10,8 @@
 // (3) per-workgroup partial sums meet in LDS and leave as ONE set of four atomics per workgroup; (4) each pass is its own launch and
 // keeps its own accumulator slot in the caller's scratch, so the passes are ordered by the stream alone: nothing synchronises, and
 // every workgroup of a pass derives the window from the previous pass's sums by the same three double divisions.
-// The window arithmetic is nyu_data.center2bounds in IEEE double without contraction (this file is compiled with -ffp-contract=off).
+// The window arithmetic is awr_frame.h's bounds_window: nyu_data.center2bounds in IEEE double without contraction (this file is compiled
+// with -ffp-contract=off).
 // Two one-thread-per-frame passes close the loop from the network's output back to a crop centre: joints_center_kernel
 // (predicted joints -> the gated next centre, detect.joints_center in IEEE double) and centers_select_kernel (a tracked centre where it is
 // usable, the detector's otherwise).  Both are launch-bound; neither is clever.
@@ -22,59 +23,21 @@
 #include <limits.h>
 #include <math.h>
 
-#include "awr_common.h"
+#include "awr_frame.h"
 
 namespace awr {
 
 constexpr int DET_THREADS = 256;
 constexpr int DET_SLOTS = AWR_DET_MAX_ITERS + 2;      // slot 0: smallest depth (NEAREST), slot 1: seed pass, slots 2...: refinement passes
 constexpr int DET_MAX_PARTS = 1024;
-constexpr int DET_MAX_SIDE = 16384;                   // fh, fw: sums stay below 2^44, pixel offsets inside int32
-
-typedef unsigned long long u64;
 
 enum { PASS_MIN = 0, PASS_SEED = 1, PASS_REFINE = 2 };
-
-struct Window {
-    int u0, u1, v0, v1;       // clipped to the frame; empty when u0 >= u1 or v0 >= v1
-    int dlo, dhi;             // raw depths d with dlo <= d <= dhi (dlo >= 1: zero is "no measurement")
-};
-
-// int() of a finite double whose value may lie outside int32: every use clips to [0, 16384] afterwards, so clamping first changes nothing
-__device__ __forceinline__ int trunc_clamped(double x) {
-    return (int)fmin(fmax(trunc(x), -1073741824.0), 1073741824.0);
-}
-
-// zstart <= d <= zend and d != 0 for an integer d in [0, 65535]  <=>  dlo <= d <= dhi
-__device__ __forceinline__ void depth_bounds(double zstart, double zend, int& dlo, int& dhi) {
-    if (!(zstart <= zend)) { dlo = 1; dhi = 0; return; }                   // NaN or an empty range
-    dlo = max(1, (int)fmin(fmax(ceil(zstart), 0.0), 65536.0));
-    dhi = (int)fmin(fmax(floor(zend), -1.0), 65535.0);
-}
-
-// nyu_data.center2bounds (loader.py:181-188) clipped to the frame; a non-finite centre or bound is an empty window
-__device__ __forceinline__ Window bounds_window(const double* c, const double* cube, double fx, double fy, int fh, int fw) {
-    Window w{0, 0, 0, 0, 1, 0};
-    const double hu = (cube[0] / 2.0) / c[2] * fx, hv = (cube[1] / 2.0) / c[2] * fy;
-    const double us = c[0] - hu + 0.5, ue = c[0] + hu + 0.5, vs = c[1] - hv + 0.5, ve = c[1] + hv + 0.5;
-    if (!(isfinite(us) && isfinite(ue) && isfinite(vs) && isfinite(ve) && isfinite(c[2]))) return w;
-    w.u0 = max(trunc_clamped(us), 0); w.u1 = min(trunc_clamped(ue), fw);
-    w.v0 = max(trunc_clamped(vs), 0); w.v1 = min(trunc_clamped(ve), fh);
-    depth_bounds(c[2] - cube[2] / 2.0, c[2] + cube[2] / 2.0, w.dlo, w.dhi);
-    return w;
-}
 
 // centre of mass of an accumulator slot: three double divisions; n == 0 -> NaN
 __device__ __forceinline__ void slot_centre(const u64* s, double* c) {
     if (s[0] == 0) { c[0] = c[1] = c[2] = __builtin_nan(""); return; }
     const double n = (double)s[0];
     c[0] = (double)s[1] / n; c[1] = (double)s[2] / n; c[2] = (double)s[3] / n;
-}
-
-__device__ __forceinline__ u64 wave_sum_u64(u64 v) {
-#pragma unroll
-    for (int o = 32; o > 0; o >>= 1) v += (u64)__shfl_xor((long long)v, o, 64);
-    return v;
 }
 
 __global__ __launch_bounds__(DET_THREADS) void detect_init_kernel(u64* __restrict__ slots, int64_t n) {
@@ -161,7 +124,7 @@ __global__ __launch_bounds__(DET_THREADS) void detect_pass_kernel(const uint16_t
         }
         return;
     }
-    n = wave_sum_u64(n); su = wave_sum_u64(su); sv = wave_sum_u64(sv); sd = wave_sum_u64(sd);
+    n = wave_sum(n); su = wave_sum(su); sv = wave_sum(sv); sd = wave_sum(sd);
     if ((tid & 63) == 0) { red[0][tid >> 6] = n; red[1][tid >> 6] = su; red[2][tid >> 6] = sv; red[3][tid >> 6] = sd; }
     __syncthreads();
     if (tid < 4) {
@@ -209,9 +172,8 @@ __global__ __launch_bounds__(DET_THREADS) void detect_samples_kernel(const doubl
     const double* c = center + 3 * b;
     const double* cb = cube + (int64_t)b * cube_stride;
     awr_nyu_sample s;
-    // center2bounds (loader.py:181-188)
-    const double hu = (cb[0] / 2.0) / c[2] * fx, hv = (cb[1] / 2.0) / c[2] * fy;
-    const double us = c[0] - hu + 0.5, ue = c[0] + hu + 0.5, vs = c[1] - hv + 0.5, ve = c[1] + hv + 0.5;
+    const Bounds bd = center_bounds(c, cb, fx, fy);
+    const double us = bd.us, ue = bd.ue, vs = bd.vs, ve = bd.ve;
     bool ok = isfinite(us) && isfinite(ue) && isfinite(vs) && isfinite(ve) && isfinite(c[2]) && isfinite(cb[2]);
     // (a bound outside int32 cannot pass set_crop's tests with a positive extent that resizes to something: refused here)
     ok = ok && fabs(us) < 1073741824.0 && fabs(ue) < 1073741824.0 && fabs(vs) < 1073741824.0 && fabs(ve) < 1073741824.0;
@@ -259,9 +221,9 @@ __global__ __launch_bounds__(DET_THREADS) void detect_samples_kernel(const doubl
         if (status[b] == AWR_DET_OK) status[b] = AWR_DET_BAD_WINDOW;
     }
     samples[b] = s;
-    // evaluator.uvd2xyz (util.py:13-20) of the float64 centre, stored as float32
-    center_xyz[3 * b] = (float)((c[0] - u0) * c[2] / fx);
-    center_xyz[3 * b + 1] = (float)((c[1] - v0) * c[2] / fy * flip);
+    // uvd2xyz of the float64 centre, stored as float32
+    center_xyz[3 * b] = (float)uvd2x(c[0], u0, c[2], fx);
+    center_xyz[3 * b + 1] = (float)uvd2y(c[1], v0, c[2], fy, flip);
     center_xyz[3 * b + 2] = (float)c[2];
     cube_out[3 * b] = (float)cb[0]; cube_out[3 * b + 1] = (float)cb[1]; cube_out[3 * b + 2] = (float)cb[2];
 }
@@ -297,9 +259,9 @@ __global__ __launch_bounds__(DET_THREADS) void joints_center_kernel(const float*
         else if (!(zmin <= m[2] && m[2] <= zmax)) cd = AWR_RECENTER_KEPT_DEPTH;
         else if (!near) cd = AWR_RECENTER_KEPT_SHIFT;
         else {
-            cd = AWR_RECENTER_MOVED;                                        // evaluator.xyz2uvd (util.py:3-10) in double
-            const double y = m[1] * flip;
-            nc[0] = m[0] * fx / m[2] + u0; nc[1] = y * fy / m[2] + v0; nc[2] = m[2];
+            cd = AWR_RECENTER_MOVED;
+            const double yf = m[1] * flip;
+            nc[0] = xyz2u(m[0], fx, m[2], u0); nc[1] = xyz2v(yf, fy, m[2], v0); nc[2] = m[2];
         }
     }
     const bool moved = cd == AWR_RECENTER_MOVED;
@@ -344,12 +306,12 @@ __global__ __launch_bounds__(DET_THREADS) void view_centers_kernel(const double*
     const double sx = T[VT_SHIFT], sy = T[VT_SHIFT + 1], sz = T[VT_SHIFT + 2], sc = T[VT_SCALE];
     double c[3] = {center[3 * b], center[3 * b + 1], center[3 * b + 2]};
     if (!(sx == 0.0 && sy == 0.0 && sz == 0.0)) {
-        // evaluator.uvd2xyz (util.py:13-20), the shift, evaluator.xyz2uvd (util.py:3-10): loader.py:112 in double
-        const double x = (c[0] - u0) * c[2] / fx + sx;
-        const double y = (c[1] - v0) * c[2] / fy * flip + sy;
+        // uvd2xyz, the shift, xyz2uvd: loader.py:112 in double
+        const double x = uvd2x(c[0], u0, c[2], fx) + sx;
+        const double y = uvd2y(c[1], v0, c[2], fy, flip) + sy;
         const double z = c[2] + sz;
         const double yf = y * flip;
-        c[0] = x * fx / z + u0; c[1] = yf * fy / z + v0; c[2] = z;
+        c[0] = xyz2u(x, fx, z, u0); c[1] = xyz2v(yf, fy, z, v0); c[2] = z;
     }
     centers_out[3 * r] = c[0]; centers_out[3 * r + 1] = c[1]; centers_out[3 * r + 2] = c[2];
     cubes_out[3 * r] = cb[0] * sc; cubes_out[3 * r + 1] = cb[1] * sc; cubes_out[3 * r + 2] = cb[2] * sc;
@@ -455,20 +417,13 @@ __global__ __launch_bounds__(DET_THREADS) void views_fuse_kernel(const float* __
             }
         spread = sqrt(q / sw);
     }
-    const double yf = m[1] * flip;                                          // evaluator.xyz2uvd (util.py:3-10) in double
+    const double yf = m[1] * flip;
     float* xo = xyz_out + i * 3;
     float* uo = uvd_out + i * 3;
     xo[0] = (float)m[0]; xo[1] = (float)m[1]; xo[2] = (float)m[2];
-    uo[0] = (float)(used ? m[0] * fx / m[2] + u0 : nan); uo[1] = (float)(used ? yf * fy / m[2] + v0 : nan); uo[2] = (float)m[2];
+    uo[0] = (float)(used ? xyz2u(m[0], fx, m[2], u0) : nan); uo[1] = (float)(used ? xyz2v(yf, fy, m[2], v0) : nan); uo[2] = (float)m[2];
     spread_out[i] = (float)spread;
     used_out[i] = used;
-}
-
-static int detect_parts(int B, int fh) {
-    // about four workgroups per CU over the batch, never more than one per row of the frame (a workgroup's share is whole rows)
-    int p = (1024 + B - 1) / B;
-    p = p < fh ? p : fh;
-    return p < 1 ? 1 : (p > DET_MAX_PARTS ? DET_MAX_PARTS : p);
 }
 
 }  // namespace awr
@@ -489,11 +444,7 @@ int awr_detect(const void* frames, int frame_type, int64_t n_frames, int fh, int
                const double* seed_uvd, double zmin, double zmax, double slab, const double* cube, int cube_stride, double fx, double fy,
                int iters, int parts, void* scratch, double* center_uvd, int* status, void* stream) {
     AWR_REQUIRE(frames && frame && cube && scratch && center_uvd && status, "awr_detect: NULL pointer");
-    AWR_REQUIRE(frame_type == AWR_NYU_U16, "awr_detect: the frame store must be uint16 millimetres (AWR_NYU_U16): integer sums are what makes the "
-                "centre of mass independent of the summation order (got frame_type %d)", frame_type);
-    AWR_REQUIRE(B > 0 && B <= AWR_DET_MAX_BATCH, "awr_detect: B = %d is outside [1, %d]", B, AWR_DET_MAX_BATCH);
-    AWR_REQUIRE(n_frames > 0, "awr_detect: n_frames = %lld must be positive", (long long)n_frames);
-    AWR_REQUIRE(fh > 0 && fw > 0 && fh <= DET_MAX_SIDE && fw <= DET_MAX_SIDE, "awr_detect: frame of %d x %d is outside [1, %d]^2", fh, fw, DET_MAX_SIDE);
+    if (check_frame_store("awr_detect", frame_type, B, n_frames, fh, fw) != AWR_OK) return AWR_ERR_ARG;
     AWR_REQUIRE(iters >= 0 && iters <= AWR_DET_MAX_ITERS, "awr_detect: iters = %d is outside [0, %d]", iters, AWR_DET_MAX_ITERS);
     AWR_REQUIRE(seed_mode == AWR_DET_SEED_GIVEN || seed_mode == AWR_DET_SEED_RANGE || seed_mode == AWR_DET_SEED_NEAREST,
                 "awr_detect: seed_mode %d is none of AWR_DET_SEED_GIVEN / _RANGE / _NEAREST", seed_mode);
@@ -507,7 +458,7 @@ int awr_detect(const void* frames, int frame_type, int64_t n_frames, int fh, int
     hipStream_t s = as_stream(stream);
     u64* slots = (u64*)scratch;
     const int64_t nw = (int64_t)B * DET_SLOTS * 4;
-    const int P = parts ? parts : detect_parts(B, fh);
+    const int P = parts ? parts : frame_parts(B, fh, DET_MAX_PARTS);
     const uint16_t* F = (const uint16_t*)frames;
     detect_init_kernel<<<(unsigned)((nw + DET_THREADS - 1) / DET_THREADS), DET_THREADS, 0, s>>>(slots, nw);
     const dim3 grid(P, B);
@@ -532,8 +483,7 @@ int awr_detect_samples(const double* center_uvd, const double* cube, int cube_st
     AWR_REQUIRE(B > 0 && B <= AWR_DET_MAX_BATCH, "awr_detect_samples: B = %d is outside [1, %d]", B, AWR_DET_MAX_BATCH);
     AWR_REQUIRE(n_frames > 0, "awr_detect_samples: n_frames = %lld must be positive", (long long)n_frames);
     AWR_REQUIRE(dsize > 0 && dsize <= 4096, "awr_detect_samples: dsize = %d is outside [1, 4096]", dsize);
-    AWR_REQUIRE(fh > 0 && fw > 0 && fh <= DET_MAX_SIDE && fw <= DET_MAX_SIDE, "awr_detect_samples: frame of %d x %d is outside [1, %d]^2", fh, fw,
-                DET_MAX_SIDE);
+    AWR_REQUIRE(frame_sides_ok(fh, fw), "awr_detect_samples: frame of %d x %d is outside [1, %d]^2", fh, fw, FRAME_MAX_SIDE);
     AWR_REQUIRE(cube_stride == 0 || cube_stride == 3, "awr_detect_samples: cube_stride is 0 (one cube) or 3 (one per frame), not %d", cube_stride);
     AWR_REQUIRE(fx != 0.0 && fy != 0.0 && isfinite(fx) && isfinite(fy) && (flip == 1 || flip == -1), "awr_detect_samples: bad intrinsics / flip");
     detect_samples_kernel<<<(B + DET_THREADS - 1) / DET_THREADS, DET_THREADS, 0, as_stream(stream)>>>(

@@ -25,12 +25,13 @@
 //   6. hands_sums_kernel: n, su, sv, sd of the chosen components' pixels with d <= min(zc + slab, zmax), a block sum and one 64-bit
 //      atomicAdd per workgroup, slot and word;
 //   7. hands_finalize_kernel: a thread per frame and slot writes centre, status, info and count, hand-major (row k * B + b).
-// The depth tests are the statement's float64 comparisons: for an integer d, d <= x  <=>  d <= floor(x) (compiled with
-// -ffp-contract=off; the sums base + span are single double additions).
+// The depth tests are the statement's float64 comparisons: for an integer d, d <= x  <=>  d <= floor(x) (awr_frame.h's depth_bounds and
+// depth_floor; compiled with -ffp-contract=off; the sums base + span are single double additions).  The block reductions and the split of
+// a frame over workgroups are awr_frame.h's too.
 #include <limits.h>
 #include <math.h>
 
-#include "awr_common.h"
+#include "awr_frame.h"
 
 namespace awr {
 namespace {
@@ -38,16 +39,11 @@ namespace {
 constexpr int HANDS_THREADS = 256;
 constexpr int HANDS_WAVES = HANDS_THREADS / 64;
 constexpr int HANDS_TILE_W = 64, HANDS_TILE_H = 16;   // a wave per tile row, four rows per thread
-constexpr int HANDS_MAX_K = 4;
 constexpr int HANDS_MAX_PARTS = 64;                   // workgroups per frame of the streaming stages
-constexpr int HANDS_MAX_SIDE = 16384;                 // pixel indices stay inside int32, sums of columns below 2^42
-
-typedef unsigned long long u64;
-typedef long long i64;
 
 // a frame's slots: 64-bit words
-enum { HS_DMIN = 0, HS_COUNT = 1, HS_KEY = 2, HS_SUM = HS_KEY + HANDS_MAX_K, HS_PART = HS_SUM + 4 * HANDS_MAX_K };
-constexpr int HANDS_SLOTS = HS_PART + HANDS_MAX_PARTS * HANDS_MAX_K;
+enum { HS_DMIN = 0, HS_COUNT = 1, HS_KEY = 2, HS_SUM = HS_KEY + MAX_HANDS, HS_PART = HS_SUM + 4 * MAX_HANDS };
+constexpr int HANDS_SLOTS = HS_PART + HANDS_MAX_PARTS * MAX_HANDS;
 constexpr u64 HANDS_NONE = ~0ull;
 
 struct HandsArgs {
@@ -76,8 +72,7 @@ __device__ __forceinline__ HandsFrame hands_frame(const HandsArgs& a, int b) {
 
 // the largest integer d in [-1, 65535] with (double)d <= min(base + span, zmax)
 __device__ __forceinline__ int hands_limit(int base, double span, double zmax) {
-    const double lim = fmin((double)base + span, zmax);
-    return (int)fmin(fmax(floor(lim), -1.0), 65535.0);
+    return depth_floor(fmin((double)base + span, zmax));
 }
 
 // pixels [p0, p1) of workgroup blockIdx.x of gridDim.x: whole rows
@@ -85,33 +80,6 @@ __device__ __forceinline__ void hands_share(const HandsArgs& a, int& p0, int& p1
     const int per = (a.fh + (int)gridDim.x - 1) / (int)gridDim.x;
     const int r0 = min((int)blockIdx.x * per, a.fh), r1 = min(r0 + per, a.fh);
     p0 = r0 * a.fw; p1 = r1 * a.fw;
-}
-
-__device__ __forceinline__ u64 block_min(u64 v, u64* red) {
-#pragma unroll
-    for (int o = 32; o > 0; o >>= 1) {
-        const u64 t = (u64)__shfl_xor((i64)v, o, 64);
-        v = t < v ? t : v;
-    }
-    if ((threadIdx.x & 63) == 0) red[threadIdx.x >> 6] = v;
-    __syncthreads();
-    u64 r = red[0];
-#pragma unroll
-    for (int i = 1; i < HANDS_WAVES; ++i) r = red[i] < r ? red[i] : r;
-    __syncthreads();
-    return r;
-}
-
-__device__ __forceinline__ u64 block_sum(u64 v, u64* red) {
-#pragma unroll
-    for (int o = 32; o > 0; o >>= 1) v += (u64)__shfl_xor((i64)v, o, 64);
-    if ((threadIdx.x & 63) == 0) red[threadIdx.x >> 6] = v;
-    __syncthreads();
-    u64 r = 0;
-#pragma unroll
-    for (int i = 0; i < HANDS_WAVES; ++i) r += red[i];
-    __syncthreads();
-    return r;
 }
 
 // ---- the forest -------------------------------------------------------------------------------------------------------------------
@@ -143,20 +111,20 @@ __device__ __forceinline__ void uf_union(int* L, int a, int b) {
 
 // the K smallest of the words offered to it, ascending; HANDS_NONE where there are fewer
 struct SmallestK {
-    u64 k[HANDS_MAX_K];
+    u64 k[MAX_HANDS];
     __device__ __forceinline__ void clear() {
 #pragma unroll
-        for (int i = 0; i < HANDS_MAX_K; ++i) k[i] = HANDS_NONE;
+        for (int i = 0; i < MAX_HANDS; ++i) k[i] = HANDS_NONE;
     }
     __device__ __forceinline__ void offer(u64 v) {
 #pragma unroll
-        for (int i = 0; i < HANDS_MAX_K; ++i)
+        for (int i = 0; i < MAX_HANDS; ++i)
             if (v < k[i]) { const u64 t = k[i]; k[i] = v; v = t; }
     }
     __device__ __forceinline__ void pop() {
 #pragma unroll
-        for (int i = 0; i + 1 < HANDS_MAX_K; ++i) k[i] = k[i + 1];
-        k[HANDS_MAX_K - 1] = HANDS_NONE;
+        for (int i = 0; i + 1 < MAX_HANDS; ++i) k[i] = k[i + 1];
+        k[MAX_HANDS - 1] = HANDS_NONE;
     }
 };
 
@@ -183,7 +151,7 @@ __global__ __launch_bounds__(HANDS_THREADS) void hands_dmin_kernel(HandsArgs a) 
         const unsigned d = hf.F[p];
         if (d >= dlo && (int)d <= dhi && (u64)d < best) best = d;
     }
-    best = block_min(best, red);
+    best = block_reduce<HANDS_WAVES>(best, red, MinU64());
     if (threadIdx.x == 0 && best != HANDS_NONE) atomicMin(hf.S + HS_DMIN, best);
 }
 
@@ -305,25 +273,25 @@ __global__ __launch_bounds__(HANDS_THREADS) void hands_roots_kernel(HandsArgs a)
             mine.offer(((u64)(unsigned)hf.ZC[p] << 32) | (u64)(unsigned)p);
         }
     }
-    n = block_sum(n, red);
+    n = block_reduce<HANDS_WAVES>(n, red, SumU64());
     if (n == 0) return;                                                  // (uniform; the workgroup's words stay "none")
     if (threadIdx.x == 0) atomicAdd(hf.S + HS_COUNT, n);
     for (int i = 0; i < a.K; ++i) {
-        const u64 best = block_min(mine.k[0], red);
+        const u64 best = block_reduce<HANDS_WAVES>(mine.k[0], red, MinU64());
         if (best == HANDS_NONE) break;
         if (mine.k[0] == best) mine.pop();                               // (the words are unique: one thread holds it)
-        if (threadIdx.x == 0) hf.S[HS_PART + (int)blockIdx.x * HANDS_MAX_K + i] = best;
+        if (threadIdx.x == 0) hf.S[HS_PART + (int)blockIdx.x * MAX_HANDS + i] = best;
     }
 }
 
 // 5b. per frame: the K smallest of the workgroups' words, ascending
 __global__ __launch_bounds__(HANDS_THREADS) void hands_pick_kernel(HandsArgs a) {
     __shared__ u64 red[HANDS_WAVES];
-    static_assert(HANDS_MAX_PARTS * HANDS_MAX_K == HANDS_THREADS, "a word per thread");
+    static_assert(HANDS_MAX_PARTS * MAX_HANDS == HANDS_THREADS, "a word per thread");
     u64* S = a.slots + (int64_t)blockIdx.x * HANDS_SLOTS;
     u64 mine = S[HS_PART + threadIdx.x];
     for (int i = 0; i < a.K; ++i) {
-        const u64 best = block_min(mine, red);
+        const u64 best = block_reduce<HANDS_WAVES>(mine, red, MinU64());
         if (best == HANDS_NONE) break;
         if (mine == best) mine = HANDS_NONE;
         if (threadIdx.x == 0) S[HS_KEY + i] = best;
@@ -337,10 +305,10 @@ __global__ __launch_bounds__(HANDS_THREADS) void hands_sums_kernel(HandsArgs a) 
     if (hf.S[HS_KEY] == HANDS_NONE) return;                             // no candidate at all
     int p0, p1;
     hands_share(a, p0, p1);
-    int root[HANDS_MAX_K], lim[HANDS_MAX_K];
-    u64 acc[HANDS_MAX_K][4];
+    int root[MAX_HANDS], lim[MAX_HANDS];
+    u64 acc[MAX_HANDS][4];
 #pragma unroll
-    for (int k = 0; k < HANDS_MAX_K; ++k) {
+    for (int k = 0; k < MAX_HANDS; ++k) {
         const u64 key = k < a.K ? hf.S[HS_KEY + k] : HANDS_NONE;
         root[k] = key == HANDS_NONE ? -2 : (int)(key & 0xFFFFFFFFull);
         lim[k] = key == HANDS_NONE ? -1 : min(a.dhi, hands_limit((int)(key >> 32), a.slab, a.zmax));
@@ -352,17 +320,17 @@ __global__ __launch_bounds__(HANDS_THREADS) void hands_sums_kernel(HandsArgs a) 
         if (l < 0) continue;
         const int d = hf.F[p];
 #pragma unroll
-        for (int k = 0; k < HANDS_MAX_K; ++k)
+        for (int k = 0; k < MAX_HANDS; ++k)
             if (l == root[k] && d <= lim[k]) {
                 acc[k][0] += 1; acc[k][1] += (u64)(p % fw); acc[k][2] += (u64)(p / fw); acc[k][3] += (u64)d;
             }
     }
 #pragma unroll
-    for (int k = 0; k < HANDS_MAX_K; ++k) {
+    for (int k = 0; k < MAX_HANDS; ++k) {
         if (root[k] < 0) continue;                                       // (uniform)
         u64 s[4];
 #pragma unroll
-        for (int j = 0; j < 4; ++j) s[j] = block_sum(acc[k][j], red);
+        for (int j = 0; j < 4; ++j) s[j] = block_reduce<HANDS_WAVES>(acc[k][j], red, SumU64());
         if (threadIdx.x == 0 && s[0]) {
 #pragma unroll
             for (int j = 0; j < 4; ++j) atomicAdd(hf.S + HS_SUM + 4 * k + j, s[j]);
@@ -395,13 +363,6 @@ __global__ void hands_finalize_kernel(HandsArgs a, double* __restrict__ centers,
     if (k == 0) count[b] = hf.bad ? 0 : (int)hf.S[HS_COUNT];
 }
 
-static int hands_parts(int B, int fh) {
-    // about four workgroups per CU over the batch, at most 64 per frame and never more than one per row of the frame
-    int p = (1024 + B - 1) / B;
-    p = p < fh ? p : fh;
-    return p < 1 ? 1 : (p > HANDS_MAX_PARTS ? HANDS_MAX_PARTS : p);
-}
-
 }  // namespace awr
 
 using namespace awr;
@@ -409,9 +370,9 @@ using namespace awr;
 extern "C" {
 
 int64_t awr_detect_hands_scratch(int B, int fh, int fw) {
-    if (B <= 0 || B > AWR_DET_MAX_BATCH || fh <= 0 || fw <= 0 || fh > HANDS_MAX_SIDE || fw > HANDS_MAX_SIDE) {
+    if (B <= 0 || B > AWR_DET_MAX_BATCH || !frame_sides_ok(fh, fw)) {
         set_error("awr_detect_hands_scratch: B = %d is outside [1, %d] or the frame of %d x %d is outside [1, %d]^2", B, AWR_DET_MAX_BATCH, fh,
-                  fw, HANDS_MAX_SIDE);
+                  fw, FRAME_MAX_SIDE);
         return -1;
     }
     const int64_t words = 3 * (int64_t)B * fh * fw;                       // (a whole number of 64-bit words: callers allocate those)
@@ -421,33 +382,26 @@ int64_t awr_detect_hands_scratch(int B, int fh, int fw) {
 int awr_detect_hands(const void* frames, int frame_type, int64_t n_frames, int fh, int fw, const int64_t* frame, int B, int K, double zmin,
                      double zmax, double reach, double slab, int min_pixels, void* scratch, int* labels_out, double* centers, int* status,
                      int* info, int* count, void* stream) {
-    AWR_REQUIRE(frame_type == AWR_NYU_U16, "awr_detect_hands: the frame store must be uint16 millimetres (AWR_NYU_U16), as for awr_detect "
-                "(got frame_type %d)", frame_type);
-    AWR_REQUIRE(K >= 1 && K <= AWR_DET_MAX_HANDS, "awr_detect_hands: K = %d hands is outside [1, %d]", K, AWR_DET_MAX_HANDS);
-    AWR_REQUIRE(B > 0 && B <= AWR_DET_MAX_BATCH, "awr_detect_hands: B = %d is outside [1, %d]", B, AWR_DET_MAX_BATCH);
-    AWR_REQUIRE(n_frames > 0, "awr_detect_hands: n_frames = %lld must be positive", (long long)n_frames);
-    AWR_REQUIRE(fh > 0 && fw > 0 && fh <= HANDS_MAX_SIDE && fw <= HANDS_MAX_SIDE, "awr_detect_hands: frame of %d x %d is outside [1, %d]^2", fh,
-                fw, HANDS_MAX_SIDE);
+    if (check_frame_store("awr_detect_hands", frame_type, B, n_frames, fh, fw) != AWR_OK) return AWR_ERR_ARG;
+    AWR_REQUIRE(K >= 1 && K <= MAX_HANDS, "awr_detect_hands: K = %d hands is outside [1, %d]", K, MAX_HANDS);
     AWR_REQUIRE(min_pixels >= 1, "awr_detect_hands: min_pixels = %d must be at least 1", min_pixels);
     AWR_REQUIRE(zmin <= zmax, "awr_detect_hands: depth range needs zmin <= zmax (got %g, %g)", zmin, zmax);
     AWR_REQUIRE(reach >= 0.0, "awr_detect_hands: reach = %g must be >= 0", reach);
     AWR_REQUIRE(slab >= 0.0, "awr_detect_hands: slab = %g must be >= 0", slab);
     AWR_REQUIRE(frames && frame && scratch && centers && status && info && count, "awr_detect_hands: NULL pointer");
     AWR_REQUIRE(((uintptr_t)frames & 1) == 0 && ((uintptr_t)scratch & 7) == 0, "awr_detect_hands: misaligned frame store / scratch");
-    static_assert(AWR_DET_MAX_HANDS == HANDS_MAX_K, "the slots hold AWR_DET_MAX_HANDS hands");
     hipStream_t s = as_stream(stream);
     const int64_t np = (int64_t)B * fh * fw;
     HandsArgs a;
     a.frames = (const uint16_t*)frames; a.n_frames = n_frames; a.fh = fh; a.fw = fw; a.frame = frame; a.B = B; a.K = K;
-    a.dlo = (int)fmin(fmax(ceil(zmin), 1.0), 65536.0);
-    a.dhi = (int)fmin(fmax(floor(zmax), -1.0), 65535.0);
+    depth_bounds(zmin, zmax, a.dlo, a.dhi);
     a.zmax = zmax; a.reach = reach; a.slab = slab; a.min_pixels = min_pixels;
     a.slots = (u64*)scratch;
     a.L = (int*)(a.slots + (int64_t)B * HANDS_SLOTS); a.CNT = a.L + np; a.ZC = a.CNT + np;
     a.labels_out = labels_out;
     const int64_t nw = (int64_t)B * HANDS_SLOTS;
     const int tiles = ((fw + HANDS_TILE_W - 1) / HANDS_TILE_W) * ((fh + HANDS_TILE_H - 1) / HANDS_TILE_H);
-    const dim3 share(hands_parts(B, fh), B), tile(tiles, B);
+    const dim3 share(frame_parts(B, fh, HANDS_MAX_PARTS), B), tile(tiles, B);
     hands_init_kernel<<<(unsigned)((nw + HANDS_THREADS - 1) / HANDS_THREADS), HANDS_THREADS, 0, s>>>(a.slots, nw);
     hands_dmin_kernel<<<share, HANDS_THREADS, 0, s>>>(a);
     hands_tile_kernel<<<tile, HANDS_THREADS, 0, s>>>(a);
@@ -456,7 +410,7 @@ int awr_detect_hands(const void* frames, int frame_type, int64_t n_frames, int f
     hands_roots_kernel<<<share, HANDS_THREADS, 0, s>>>(a);
     hands_pick_kernel<<<B, HANDS_THREADS, 0, s>>>(a);
     hands_sums_kernel<<<share, HANDS_THREADS, 0, s>>>(a);
-    hands_finalize_kernel<<<B, HANDS_MAX_K, 0, s>>>(a, centers, status, info, count);
+    hands_finalize_kernel<<<B, MAX_HANDS, 0, s>>>(a, centers, status, info, count);
     return check_launch("awr_detect_hands");
 }
 

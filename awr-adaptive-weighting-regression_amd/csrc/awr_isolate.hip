@@ -8,14 +8,13 @@
 // and its labels are read once however large K is: (2 + 4 + 2 K) bytes per pixel, all of it streamed.  The 8-pixel form needs fh * fw to
 // be a multiple of 8 and the three bases 16-byte aligned (every row of the stores is then aligned too); anything else takes the scalar
 // form, a thread per pixel.  No atomics, no LDS, no workgroup waits for another, nothing synchronises.
-#include "awr_common.h"
+// (This file is built WITHOUT -ffp-contract=off: of awr_frame.h it uses the constants and the frame-store checks, none of its doubles.)
+#include "awr_frame.h"
 
 namespace awr {
 namespace {
 
 constexpr int ISO_THREADS = 256;
-constexpr int ISO_MAX_K = 4;
-constexpr int ISO_MAX_SIDE = 16384;                   // awr_detect_hands' bound: labels are pixel indices inside int32
 
 struct IsoArgs {
     const uint16_t* frames; int64_t n_frames; int64_t np; int fw;
@@ -25,9 +24,9 @@ struct IsoArgs {
 };
 
 // the roots of frame b's slots; -1: the slot has no component
-__device__ __forceinline__ void iso_roots(const IsoArgs& a, int b, int (&root)[ISO_MAX_K]) {
+__device__ __forceinline__ void iso_roots(const IsoArgs& a, int b, int (&root)[MAX_HANDS]) {
 #pragma unroll
-    for (int k = 0; k < ISO_MAX_K; ++k) {
+    for (int k = 0; k < MAX_HANDS; ++k) {
         root[k] = -1;
         if (k < a.K) {
             const int* in = a.info + 4 * ((int64_t)k * a.B + b);
@@ -51,7 +50,7 @@ __global__ __launch_bounds__(ISO_THREADS) void hands_isolate_vec_kernel(IsoArgs 
     if (i >= a.np / 8) return;
     uint4 d = make_uint4(0u, 0u, 0u, 0u);
     int lab[8] = {-1, -1, -1, -1, -1, -1, -1, -1};
-    int root[ISO_MAX_K] = {-1, -1, -1, -1};
+    int root[MAX_HANDS] = {-1, -1, -1, -1};
     if (!bad) {
         iso_roots(a, b, root);
         d = reinterpret_cast<const uint4*>(a.frames + f * a.np)[i];
@@ -61,7 +60,7 @@ __global__ __launch_bounds__(ISO_THREADS) void hands_isolate_vec_kernel(IsoArgs 
     }
     const unsigned w[4] = {d.x, d.y, d.z, d.w};
 #pragma unroll
-    for (int k = 0; k < ISO_MAX_K; ++k) {
+    for (int k = 0; k < MAX_HANDS; ++k) {
         if (k >= a.K) break;
         unsigned o[4];
 #pragma unroll
@@ -81,14 +80,14 @@ __global__ __launch_bounds__(ISO_THREADS) void hands_isolate_scalar_kernel(IsoAr
     if (p >= a.np) return;
     uint16_t d = 0;
     int lab = -1;
-    int root[ISO_MAX_K] = {-1, -1, -1, -1};
+    int root[MAX_HANDS] = {-1, -1, -1, -1};
     if (!bad) {
         iso_roots(a, b, root);
         d = a.frames[f * a.np + p];
         lab = a.labels[(int64_t)b * a.np + p];
     }
 #pragma unroll
-    for (int k = 0; k < ISO_MAX_K; ++k) {
+    for (int k = 0; k < MAX_HANDS; ++k) {
         if (k >= a.K) break;
         a.out[((int64_t)k * a.B + b) * a.np + p] = iso_keeps(lab, root[k]) ? d : (uint16_t)0;
     }
@@ -102,17 +101,11 @@ extern "C" {
 
 int awr_hands_isolate(const void* frames, int frame_type, int64_t n_frames, int fh, int fw, const int64_t* frame, int B, int K,
                       const int* labels, const int* info, void* out, int* status, void* stream) {
-    AWR_REQUIRE(frame_type == AWR_NYU_U16, "awr_hands_isolate: the frame store must be uint16 millimetres (AWR_NYU_U16), as for "
-                "awr_detect_hands (got frame_type %d)", frame_type);
-    AWR_REQUIRE(K >= 1 && K <= AWR_DET_MAX_HANDS, "awr_hands_isolate: K = %d hands is outside [1, %d]", K, AWR_DET_MAX_HANDS);
-    AWR_REQUIRE(B > 0 && B <= AWR_DET_MAX_BATCH, "awr_hands_isolate: B = %d is outside [1, %d]", B, AWR_DET_MAX_BATCH);
-    AWR_REQUIRE(n_frames > 0, "awr_hands_isolate: n_frames = %lld must be positive", (long long)n_frames);
-    AWR_REQUIRE(fh > 0 && fw > 0 && fh <= ISO_MAX_SIDE && fw <= ISO_MAX_SIDE, "awr_hands_isolate: frame of %d x %d is outside [1, %d]^2", fh, fw,
-                ISO_MAX_SIDE);
+    if (check_frame_store("awr_hands_isolate", frame_type, B, n_frames, fh, fw) != AWR_OK) return AWR_ERR_ARG;
+    AWR_REQUIRE(K >= 1 && K <= MAX_HANDS, "awr_hands_isolate: K = %d hands is outside [1, %d]", K, MAX_HANDS);
     AWR_REQUIRE(frames && frame && labels && info && out && status, "awr_hands_isolate: NULL pointer");
     AWR_REQUIRE(((uintptr_t)frames & 1) == 0 && ((uintptr_t)out & 1) == 0 && ((uintptr_t)labels & 3) == 0,
                 "awr_hands_isolate: misaligned frame store / output store / labels");
-    static_assert(AWR_DET_MAX_HANDS == ISO_MAX_K, "a root per hand in registers");
     IsoArgs a;
     a.frames = (const uint16_t*)frames; a.n_frames = n_frames; a.np = (int64_t)fh * fw; a.fw = fw; a.frame = frame; a.B = B; a.K = K;
     a.labels = labels; a.info = info; a.out = (uint16_t*)out; a.status = status;

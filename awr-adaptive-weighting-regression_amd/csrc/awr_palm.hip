@@ -29,87 +29,22 @@
 // with device-clock stamps on one MI355X (a 348 x 364 window, B = 1): 0.43 ms -- scans 93 us, row pass 102 us, max + e1 + e2 95 us,
 // counts + p* 78 us, disc 46 us, about 45 us per pass over 0.5 MB -- and unmoved by 1, 8 or 32 loads in flight per lane, by dropping the
 // divisions, by running the two scans side by side: one CU moved some 12 GB/s whatever it was asked.  This form: 0.10 ms at B = 1.
-// The window arithmetic is awr_detect.hip's bounds_window with the cube scaled by `search` (compiled with -ffp-contract=off).
+// The window arithmetic is awr_frame.h's bounds_window with the cube scaled by `search` (compiled with -ffp-contract=off).
 #include <limits.h>
 #include <math.h>
 
-#include "awr_common.h"
+#include "awr_frame.h"
 
 namespace awr {
 namespace {
 
 constexpr int PALM_THREADS = 256;
 constexpr int PALM_WAVES = PALM_THREADS / 64;
-constexpr int PALM_TILE = 16384;                      // LDS entries of a row tile: at least one row of the widest frame
+constexpr int PALM_TILE = FRAME_MAX_SIDE;             // LDS entries of a row tile: at least one row of the widest frame
 constexpr int PALM_BATCH = 8;                         // independent loads a lane issues before it uses the first
 constexpr int PALM_SCAN = 16;                         // ... and rows a column scan loads ahead of its dependent chain
 constexpr int PALM_SLOTS = 16;                        // 64-bit words of a frame's slots
-constexpr int PALM_MAX_SIDE = 16384;                  // fh, fw: see the magnitudes above; pixel offsets stay inside int32
-
-typedef unsigned long long u64;
-typedef long long i64;
-
-struct PalmWindow {
-    int u0, u1, v0, v1;       // clipped to the frame; empty when u0 >= u1 or v0 >= v1
-    int dlo, dhi;             // raw depths d with dlo <= d <= dhi (dlo >= 1: zero is "no measurement")
-};
-
-// int() of a finite double whose value may lie outside int32: every use clips to [0, 16384] afterwards
-__device__ __forceinline__ int palm_trunc(double x) {
-    return (int)fmin(fmax(trunc(x), -1073741824.0), 1073741824.0);
-}
-
-// zstart <= d <= zend and d != 0 for an integer d in [0, 65535]  <=>  dlo <= d <= dhi
-__device__ __forceinline__ void palm_depth(double zstart, double zend, int& dlo, int& dhi) {
-    if (!(zstart <= zend)) { dlo = 1; dhi = 0; return; }                   // NaN or an empty range
-    dlo = max(1, (int)fmin(fmax(ceil(zstart), 0.0), 65536.0));
-    dhi = (int)fmin(fmax(floor(zend), -1.0), 65535.0);
-}
-
-// nyu_data.center2bounds(c, search * cube) clipped to the frame, its depth range intersected with [zmin, zmax]
-__device__ __forceinline__ PalmWindow palm_window(const double* c, const double* cube, double search, double fx, double fy, double zmin,
-                                                  double zmax, int fh, int fw) {
-    PalmWindow w{0, 0, 0, 0, 1, 0};
-    const double cs0 = search * cube[0], cs1 = search * cube[1], cs2 = search * cube[2];
-    const double hu = (cs0 / 2.0) / c[2] * fx, hv = (cs1 / 2.0) / c[2] * fy;
-    const double us = c[0] - hu + 0.5, ue = c[0] + hu + 0.5, vs = c[1] - hv + 0.5, ve = c[1] + hv + 0.5;
-    if (!(isfinite(us) && isfinite(ue) && isfinite(vs) && isfinite(ve) && isfinite(c[2]))) return w;
-    w.u0 = max(palm_trunc(us), 0); w.u1 = min(palm_trunc(ue), fw);
-    w.v0 = max(palm_trunc(vs), 0); w.v1 = min(palm_trunc(ve), fh);
-    int lo, hi;
-    palm_depth(c[2] - cs2 / 2.0, c[2] + cs2 / 2.0, w.dlo, w.dhi);
-    palm_depth(zmin, zmax, lo, hi);
-    w.dlo = max(w.dlo, lo); w.dhi = min(w.dhi, hi);
-    return w;
-}
-
-// max / sum over the workgroup through LDS; every thread gets the result, and `red` is free again on return
-__device__ __forceinline__ u64 block_max(u64 v, u64* red) {
-#pragma unroll
-    for (int o = 32; o > 0; o >>= 1) {
-        const u64 t = (u64)__shfl_xor((i64)v, o, 64);
-        v = t > v ? t : v;
-    }
-    if ((threadIdx.x & 63) == 0) red[threadIdx.x >> 6] = v;
-    __syncthreads();
-    u64 r = red[0];
-#pragma unroll
-    for (int i = 1; i < PALM_WAVES; ++i) r = red[i] > r ? red[i] : r;
-    __syncthreads();
-    return r;
-}
-
-__device__ __forceinline__ u64 block_sum(u64 v, u64* red) {
-#pragma unroll
-    for (int o = 32; o > 0; o >>= 1) v += (u64)__shfl_xor((i64)v, o, 64);
-    if ((threadIdx.x & 63) == 0) red[threadIdx.x >> 6] = v;
-    __syncthreads();
-    u64 r = 0;
-#pragma unroll
-    for (int i = 0; i < PALM_WAVES; ++i) r += red[i];
-    __syncthreads();
-    return r;
-}
+constexpr int PALM_MAX_PARTS = 64;                    // workgroups per frame
 
 // a value and a raster index as one word whose maximum is the first maximum in raster order
 __device__ __forceinline__ u64 pack_key(i64 value, int index) { return ((u64)value << 32) | (u64)(0xFFFFFFFFu - (unsigned)index); }
@@ -128,7 +63,7 @@ struct PalmArgs {
 enum { SL_MAX = 0, SL_E1, SL_E2, SL_B1, SL_B2, SL_PS, SL_N, SL_SU, SL_SV, SL_SD };
 
 struct PalmFrame {
-    PalmWindow w;
+    Window w;
     const uint16_t* F;      // the frame
     int* D;                 // its fh * fw words of the scratch
     u64* S;                 // its slots
@@ -141,7 +76,7 @@ __device__ __forceinline__ PalmFrame palm_frame(const PalmArgs& a) {
     PalmFrame pf;
     const int b = blockIdx.y;
     const int64_t f = a.frame[b];
-    pf.w = PalmWindow{0, 0, 0, 0, 1, 0};
+    pf.w = Window{0, 0, 0, 0, 1, 0};
     pf.F = a.frames; pf.D = a.D + (int64_t)b * a.fh * a.fw; pf.S = a.slots + (int64_t)b * PALM_SLOTS;
     pf.ww = pf.wh = pf.r0 = pf.r1 = 0;
     if (f < 0 || f >= a.n_frames) { pf.code = AWR_DET_BAD_FRAME; return pf; }          // nothing of it is read
@@ -272,7 +207,7 @@ __global__ __launch_bounds__(PALM_THREADS) void palm_rows_kernel(PalmArgs a) {
         }
         __syncthreads();
     }
-    best = block_max(best, red);
+    best = block_reduce<PALM_WAVES>(best, red, MaxU64());
     if (threadIdx.x == 0 && best != 0) atomicMax(pf.S + SL_MAX, best);
 }
 
@@ -294,7 +229,7 @@ __global__ __launch_bounds__(PALM_THREADS) void palm_far_kernel(PalmArgs a, int 
             best = key > best ? key : best;
         }
     });
-    best = block_max(best, red);
+    best = block_reduce<PALM_WAVES>(best, red, MaxU64());
     if (threadIdx.x == 0 && best != 0) atomicMax(pf.S + (which == 1 ? SL_E1 : SL_E2), best);
 }
 
@@ -324,8 +259,8 @@ __global__ __launch_bounds__(PALM_THREADS) void palm_end_kernel(PalmArgs a, int 
             b1 += t < 0 ? 1u : 0u;
             b2 += t > x.L ? 1u : 0u;
         });
-        b1 = block_sum(b1, red);
-        b2 = block_sum(b2, red);
+        b1 = block_reduce<PALM_WAVES>(b1, red, SumU64());
+        b2 = block_reduce<PALM_WAVES>(b2, red, SumU64());
         if (threadIdx.x == 0) {
             if (b1) atomicAdd(pf.S + SL_B1, b1);
             if (b2) atomicAdd(pf.S + SL_B2, b2);
@@ -346,7 +281,7 @@ __global__ __launch_bounds__(PALM_THREADS) void palm_end_kernel(PalmArgs a, int 
             }
         }
     });
-    bp = block_max(bp, red);
+    bp = block_reduce<PALM_WAVES>(bp, red, MaxU64());
     if (threadIdx.x == 0 && bp != 0) atomicMax(pf.S + SL_PS, bp);
 }
 
@@ -366,7 +301,7 @@ __global__ __launch_bounds__(PALM_THREADS) void palm_disc_kernel(PalmArgs a) {
     const int ww = pf.ww, fw = a.fw;
     const int ps = palm_point(pf.S, ww, ww * pf.wh);
     const i64 psv = ps / ww, psu = ps % ww, lim = a.rho0 * (i64)pf.D[ps], rho1 = a.rho1;
-    const PalmWindow w = pf.w;
+    const Window w = pf.w;
     const uint16_t* F = pf.F;
     u64 cn = 0, su = 0, sv = 0, sd = 0;
     for_foreground(pf.D, pf.r0, pf.r1, ww, [&](int i, int j, int) {
@@ -376,7 +311,8 @@ __global__ __launch_bounds__(PALM_THREADS) void palm_disc_kernel(PalmArgs a) {
             sd += F[(w.v0 + i) * fw + w.u0 + j];
         }
     });
-    cn = block_sum(cn, red); su = block_sum(su, red); sv = block_sum(sv, red); sd = block_sum(sd, red);
+    cn = block_reduce<PALM_WAVES>(cn, red, SumU64()); su = block_reduce<PALM_WAVES>(su, red, SumU64());
+    sv = block_reduce<PALM_WAVES>(sv, red, SumU64()); sd = block_reduce<PALM_WAVES>(sd, red, SumU64());
     if (threadIdx.x == 0 && cn) {
         atomicAdd(pf.S + SL_N, cn); atomicAdd(pf.S + SL_SU, su); atomicAdd(pf.S + SL_SV, sv); atomicAdd(pf.S + SL_SD, sd);
     }
@@ -403,13 +339,6 @@ __global__ void palm_finalize_kernel(PalmArgs a, double* center_out, int* status
     if (info) { info[4 * b] = pu; info[4 * b + 1] = pv; info[4 * b + 2] = r2; info[4 * b + 3] = nd; }
 }
 
-static int palm_parts(int B, int fh) {
-    // about four workgroups per CU over the batch, at most 64 per frame and never more than one per row of the frame
-    int p = (1024 + B - 1) / B;
-    p = p < fh ? p : fh;
-    return p < 1 ? 1 : (p > 64 ? 64 : p);
-}
-
 }  // namespace awr
 
 using namespace awr;
@@ -417,9 +346,9 @@ using namespace awr;
 extern "C" {
 
 int64_t awr_detect_palm_scratch(int B, int fh, int fw) {
-    if (B <= 0 || B > AWR_DET_MAX_BATCH || fh <= 0 || fw <= 0 || fh > PALM_MAX_SIDE || fw > PALM_MAX_SIDE) {
+    if (B <= 0 || B > AWR_DET_MAX_BATCH || !frame_sides_ok(fh, fw)) {
         set_error("awr_detect_palm_scratch: B = %d is outside [1, %d] or the frame of %d x %d is outside [1, %d]^2", B, AWR_DET_MAX_BATCH, fh,
-                  fw, PALM_MAX_SIDE);
+                  fw, FRAME_MAX_SIDE);
         return -1;
     }
     return (int64_t)B * PALM_SLOTS * (int64_t)sizeof(u64) + (int64_t)B * fh * fw * (int64_t)sizeof(int);
@@ -430,12 +359,7 @@ int awr_detect_palm(const void* frames, int frame_type, int64_t n_frames, int fh
                     double fy, double search, int tau_num, int tau_den, int rho2_num, int rho2_den, void* scratch, double* center_out,
                     int* status_out, int* info, void* stream) {
     AWR_REQUIRE(frames && frame && center_in && status_in && cube && scratch && center_out && status_out, "awr_detect_palm: NULL pointer");
-    AWR_REQUIRE(frame_type == AWR_NYU_U16, "awr_detect_palm: the frame store must be uint16 millimetres (AWR_NYU_U16), as for awr_detect "
-                "(got frame_type %d)", frame_type);
-    AWR_REQUIRE(B > 0 && B <= AWR_DET_MAX_BATCH, "awr_detect_palm: B = %d is outside [1, %d]", B, AWR_DET_MAX_BATCH);
-    AWR_REQUIRE(n_frames > 0, "awr_detect_palm: n_frames = %lld must be positive", (long long)n_frames);
-    AWR_REQUIRE(fh > 0 && fw > 0 && fh <= PALM_MAX_SIDE && fw <= PALM_MAX_SIDE, "awr_detect_palm: frame of %d x %d is outside [1, %d]^2", fh, fw,
-                PALM_MAX_SIDE);
+    if (check_frame_store("awr_detect_palm", frame_type, B, n_frames, fh, fw) != AWR_OK) return AWR_ERR_ARG;
     AWR_REQUIRE(zmin <= zmax, "awr_detect_palm: depth range needs zmin <= zmax (got %g, %g)", zmin, zmax);
     AWR_REQUIRE(cube_stride == 0 || cube_stride == 3, "awr_detect_palm: cube_stride is 0 (one cube) or 3 (one per frame), not %d", cube_stride);
     AWR_REQUIRE(fx != 0.0 && fy != 0.0 && isfinite(fx) && isfinite(fy), "awr_detect_palm: bad intrinsics");
@@ -451,7 +375,7 @@ int awr_detect_palm(const void* frames, int frame_type, int64_t n_frames, int fh
     a.tau0 = tau_num; a.tau1 = tau_den; a.rho0 = rho2_num; a.rho1 = rho2_den;
     a.slots = (u64*)scratch; a.D = (int*)((u64*)scratch + (int64_t)B * PALM_SLOTS);
     const int64_t nw = (int64_t)B * PALM_SLOTS;
-    const dim3 grid(palm_parts(B, fh), B);
+    const dim3 grid(frame_parts(B, fh, PALM_MAX_PARTS), B);
     palm_init_kernel<<<(unsigned)((nw + PALM_THREADS - 1) / PALM_THREADS), PALM_THREADS, 0, s>>>(a.slots, nw);
     palm_scan_kernel<<<grid, PALM_THREADS, 0, s>>>(a);
     palm_rows_kernel<<<grid, PALM_THREADS, 0, s>>>(a);

@@ -10,7 +10,7 @@
 #include <limits.h>
 #include <math.h>
 
-#include "awr_common.h"
+#include "awr_frame.h"
 
 namespace awr {
 
@@ -92,8 +92,8 @@ __global__ __launch_bounds__(TRACK_THREADS) void joints_filter_kernel(double* __
             X[a] = (float)x[a];
             A[a] = (float)(x[a] + d[a] * dt);
         }
-        U[0] = (float)(x[0] * fx / x[2] + u0);                       // evaluator.xyz2uvd as awr_joints_center spells it
-        U[1] = (float)((x[1] * flip) * fy / x[2] + v0);
+        U[0] = (float)xyz2u(x[0], fx, x[2], u0);
+        U[1] = (float)xyz2v(x[1] * flip, fy, x[2], v0);
         U[2] = (float)x[2];
     } else {
         const float nan = __builtin_nanf("");

@@ -640,6 +640,12 @@ def _f64(x, dev):
     return torch.from_numpy(np.ascontiguousarray(x, dtype=np.float64)).to(dev)
 
 
+def _frame_index(frame_idx, dev):
+    """The frame of every batch row as the entry points read it: a device int64 tensor (one handed in is used as it is)."""
+    import torch
+    return frame_idx if isinstance(frame_idx, torch.Tensor) else torch.as_tensor(np.asarray(frame_idx, np.int64)).to(dev)
+
+
 def detect_device(store, frame_idx, seed="nearest", centers=None, cube=(300, 300, 300), paras=ND.PARAS, depth_range=DEPTH_RANGE, slab=SLAB,
                   iters=REFINE_ITERS, parts=0):
     """awr_detect on a nyu_device.FrameStore-like object (.data (n, fh, fw) uint16 on the device, .ftype, .fh, .fw): -> (centres (B, 3) float64,
@@ -647,16 +653,13 @@ def detect_device(store, frame_idx, seed="nearest", centers=None, cube=(300, 300
     import torch
     from . import _lib as L
     dev = store.data.device
-    idx = torch.as_tensor(np.asarray(frame_idx, np.int64)).to(dev) if not isinstance(frame_idx, torch.Tensor) else frame_idx
+    idx = _frame_index(frame_idx, dev)
     B = int(idx.shape[0])
     cb = _f64(cube, dev)
     seed_t = None
     if seed == "given":
         seed_t = centers if isinstance(centers, torch.Tensor) else _f64(centers, dev)
-    nbytes = int(L.lib.awr_detect_scratch(B))
-    if nbytes < 0:
-        raise L.AwrError(L.last_error())
-    scratch = torch.empty(nbytes // 8, dtype=torch.int64, device=dev)
+    scratch = L.scratch("awr_detect_scratch", B, dtype=torch.int64, device=dev)
     out = torch.empty((B, 3), dtype=torch.float64, device=dev)
     status = torch.empty(B, dtype=torch.int32, device=dev)
     L.call("awr_detect", store.data.data_ptr(), store.ftype, int(store.data.shape[0]), store.fh, store.fw, idx.data_ptr(), B, SEEDS[seed],
@@ -675,14 +678,11 @@ def palm_device(store, frame_idx, centers, status, cube=(300, 300, 300), paras=N
     from . import _lib as L
     search, (tau0, tau1), (rho0, rho1) = check_palm(search, tau, rho2)
     dev = store.data.device
-    idx = torch.as_tensor(np.asarray(frame_idx, np.int64)).to(dev) if not isinstance(frame_idx, torch.Tensor) else frame_idx
+    idx = _frame_index(frame_idx, dev)
     B = int(idx.shape[0])
     cb = cube if isinstance(cube, torch.Tensor) else _f64(cube, dev)
     if scratch is None:
-        nbytes = int(L.lib.awr_detect_palm_scratch(B, store.fh, store.fw))
-        if nbytes < 0:
-            raise L.AwrError(L.last_error())
-        scratch = torch.empty(nbytes // 4, dtype=torch.int32, device=dev)
+        scratch = L.scratch("awr_detect_palm_scratch", B, store.fh, store.fw, dtype=torch.int32, device=dev)
     center_out = torch.empty((B, 3), dtype=torch.float64, device=dev) if center_out is None else center_out
     status_out = torch.empty(B, dtype=torch.int32, device=dev) if status_out is None else status_out
     if info is True:
@@ -702,13 +702,10 @@ def hands_device(store, frame_idx, hands, depth_range=DEPTH_RANGE, reach=REACH, 
     import torch
     from . import _lib as L
     dev = store.data.device
-    idx = torch.as_tensor(np.asarray(frame_idx, np.int64)).to(dev) if not isinstance(frame_idx, torch.Tensor) else frame_idx
+    idx = _frame_index(frame_idx, dev)
     B, K = int(idx.shape[0]), int(hands)
     if scratch is None:
-        nbytes = int(L.lib.awr_detect_hands_scratch(B, store.fh, store.fw))
-        if nbytes < 0:
-            raise L.AwrError(L.last_error())
-        scratch = torch.empty(nbytes // 8, dtype=torch.int64, device=dev)
+        scratch = L.scratch("awr_detect_hands_scratch", B, store.fh, store.fw, dtype=torch.int64, device=dev)
     rows = max(K, 1)                                         # (a K the entry point refuses still gets its message from there)
     centers = torch.empty((rows, B, 3), dtype=torch.float64, device=dev)
     status = torch.empty((rows, B), dtype=torch.int32, device=dev)
@@ -731,7 +728,7 @@ def isolate_device(store, frame_idx, labels, roots=None, info=None, out=None):
     import torch
     from . import _lib as L
     dev = store.data.device
-    idx = torch.as_tensor(np.asarray(frame_idx, np.int64)).to(dev) if not isinstance(frame_idx, torch.Tensor) else frame_idx
+    idx = _frame_index(frame_idx, dev)
     B = int(idx.shape[0])
     if (roots is None) == (info is None):
         raise ValueError("isolate_device takes either roots or info")
@@ -759,7 +756,7 @@ def samples_device(centers, cube, dsize, frame_idx, n_frames, frame_shape, paras
     from . import _lib as L
     dev = centers.device
     B = int(centers.shape[0])
-    idx = torch.as_tensor(np.asarray(frame_idx, np.int64)).to(dev) if not isinstance(frame_idx, torch.Tensor) else frame_idx
+    idx = _frame_index(frame_idx, dev)
     cb = _f64(cube, dev)
     blocks = torch.empty((B, C.sizeof(L.NyuSample)), dtype=torch.uint8, device=dev)
     M = torch.empty((B, 3, 3), dtype=torch.float32, device=dev)

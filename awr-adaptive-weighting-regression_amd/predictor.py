@@ -229,7 +229,7 @@ class Predictor:
         self._render = DV.Renderer(self._store, self.S, P)
         self._idx = torch.arange(B, dtype=torch.int64, device=dev).repeat(K)          # (K > 1: the frame of every hand-major row)
         self._cube = torch.tensor([float(c) for c in cube], dtype=torch.float64, device=dev)
-        self._scratch = torch.empty(int(L.lib.awr_detect_scratch(B * K)) // 8, dtype=torch.int64, device=dev)
+        self._scratch = L.scratch("awr_detect_scratch", B * K, dtype=torch.int64, device=dev)
         self._centers = torch.empty((B * K, 3), dtype=torch.float64, device=dev)
         self._seed = torch.empty((B * K, 3), dtype=torch.float64, device=dev)
         self._blocks = torch.empty((P, DV.BLOCK_BYTES), dtype=torch.uint8, device=dev)
@@ -245,16 +245,10 @@ class Predictor:
             self._joints = None if center_joints is None else torch.tensor(center_joints, dtype=torch.int32, device=dev)
             self._moved = torch.empty((B * K, 3), dtype=torch.float64, device=dev)      # center_out of the call that only asks for `next`
         if palm:
-            nbytes = int(L.lib.awr_detect_palm_scratch(B * K, self.fh, self.fw))
-            if nbytes < 0:
-                raise L.AwrError(L.last_error())
-            self._palm_scratch = torch.empty(nbytes // 4, dtype=torch.int32, device=dev)
+            self._palm_scratch = L.scratch("awr_detect_palm_scratch", B * K, self.fh, self.fw, dtype=torch.int32, device=dev)
             self._palm_info = torch.empty((B * K, 4), dtype=torch.int32, device=dev)
         if K > 1:
-            nbytes = int(L.lib.awr_detect_hands_scratch(B, self.fh, self.fw))
-            if nbytes < 0:
-                raise L.AwrError(L.last_error())
-            self._hands_scratch = torch.empty(nbytes // 8, dtype=torch.int64, device=dev)
+            self._hands_scratch = L.scratch("awr_detect_hands_scratch", B, self.fh, self.fw, dtype=torch.int64, device=dev)
             self._hands_status = torch.empty((K, B), dtype=torch.int32, device=dev)
             self._hands_info = torch.empty((K, B, 4), dtype=torch.int32, device=dev)
             self._hands_count = torch.empty(B, dtype=torch.int32, device=dev)
