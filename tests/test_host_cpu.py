@@ -49,8 +49,27 @@ CASES = [("conv", 4, 6, 3, 1, 1, 6), ("conv", 4, 6, 3, 2, 1, 8), ("conv", 4, 6, 
          ("conv", 3, 5, 5, 1, 2, 7), ("deconv", 4, 6, 4, 2, 1, 4)]
 
 
+# the non-square row maps of tests/test_conv_rect_gpu.py (Hq x Wq / Hd x Wd: a stride-2 conv reads twice that): both sides powers of two with
+# different logarithms, exactly one side a power of two (both orientations), neither
+RECT_SHAPES = [(4, 16), (16, 4), (6, 8), (8, 6), (10, 14)]
+RECT_LAYERS = [("conv", 4, 6, 3, 1, 1), ("conv", 4, 6, 3, 2, 1), ("conv", 4, 6, 1, 2, 0), ("conv", 4, 6, 1, 1, 0), ("deconv", 4, 6, 4, 2, 1)]
+
+
 @pytest.mark.parametrize("kind,cin,cout,k,s,p,H", CASES)
 def test_geometry_forward_and_dgrad(amd, kind, cin, cout, k, s, p, H):
+    _geometry_forward_and_dgrad(kind, cin, cout, k, s, p, H, H)
+
+
+@pytest.mark.parametrize("shape", RECT_SHAPES, ids=lambda v: "%dx%d" % v)
+@pytest.mark.parametrize("kind,cin,cout,k,s,p", RECT_LAYERS)
+def test_geometry_forward_and_dgrad_on_rectangular_maps(amd, kind, cin, cout, k, s, p, shape):
+    """The same three contracts with Hin != Win, Hq != Wq, Hd != Wd (and Hg != Wg for the strided kinds): what the GPU tests of the rectangular
+    maps hold the kernels to is what ops.ConvSpec states, to 1e-10."""
+    H, W = (2 * shape[0], 2 * shape[1]) if kind == "conv" and s == 2 else shape
+    _geometry_forward_and_dgrad(kind, cin, cout, k, s, p, H, W)
+
+
+def _geometry_forward_and_dgrad(kind, cin, cout, k, s, p, H, W):
     from awr_amd import ops
     ops_K = ops.K_ALIGN
     ops.K_ALIGN = 1                      # the 32-channel granularity is a kernel constraint, not a geometry one
@@ -60,18 +79,18 @@ def test_geometry_forward_and_dgrad(amd, kind, cin, cout, k, s, p, H):
         ops.K_ALIGN = ops_K
     g = torch.Generator().manual_seed(0)
     w = torch.randn((cout, cin, k, k) if kind == "conv" else (cin, cout, k, k), generator=g, dtype=torch.float64)
-    x = torch.randn(2, cin, H, H, generator=g, dtype=torch.float64, requires_grad=True)
+    x = torch.randn(2, cin, H, W, generator=g, dtype=torch.float64, requires_grad=True)
     y_ref = (TF.conv2d if kind == "conv" else TF.conv_transpose2d)(x, w, None, s, p)
     gy = torch.randn(y_ref.shape, generator=g, dtype=torch.float64)
     (gx_ref,) = torch.autograd.grad(y_ref, x, gy)
     xn = x.detach().permute(0, 2, 3, 1)
-    y = emulate_gemm(spec.fwd_problem(H, H), xn, emulate_pack(w, spec.fwd_pack()))
+    y = emulate_gemm(spec.fwd_problem(H, W), xn, emulate_pack(w, spec.fwd_pack()))
     assert torch.allclose(y.permute(0, 3, 1, 2), y_ref.detach(), atol=1e-10)
-    dp = spec.dgrad_problem(H, H)
+    dp = spec.dgrad_problem(H, W)
     gx = emulate_gemm(dp, gy.permute(0, 2, 3, 1), emulate_pack(w, spec.dgrad_pack()))
     assert torch.allclose(gx.permute(0, 3, 1, 2), gx_ref, atol=1e-10)
     # wgrad contract: R[d0][t][d1] = sum_m D[m][d0] * G[gather(m,t)][d1]
-    wp = spec.wgrad_problem(H, H)
+    wp = spec.wgrad_problem(H, W)
     D, G = (gy, x.detach()) if wp["D"] == "dy" else (x.detach(), gy)
     Dn, Gn = D.permute(0, 2, 3, 1), G.permute(0, 2, 3, 1)
     R = torch.zeros(wp["Cd"], len(wp["taps"]), wp["Cg"], dtype=torch.float64)
@@ -84,6 +103,32 @@ def test_geometry_forward_and_dgrad(amd, kind, cin, cout, k, s, p, H):
     wd = w.clone().requires_grad_(True)
     (gw_ref,) = torch.autograd.grad((TF.conv2d if kind == "conv" else TF.conv_transpose2d)(x.detach(), wd, None, s, p), wd, gy)
     assert torch.allclose(R.permute(0, 2, 1).reshape(gw_ref.shape), gw_ref, atol=1e-9)
+
+
+@pytest.mark.parametrize("kind,cin,cout,k,s,p,hin,win", [("conv", 64, 96, 3, 1, 1, 4, 16), ("conv", 128, 160, 3, 2, 1, 12, 16), ("deconv", 128, 160, 4, 2, 1, 6, 8),
+                                                         ("conv", 64, 96, 1, 2, 0, 8, 32)])
+def test_a_swapped_row_stride_is_detectable_on_rectangular_maps(kind, cin, cout, k, s, p, hin, win):
+    """So that the GPU tests of the rectangular maps cannot pass by accident: a kernel that strides rows by H where it should use W reads the
+    input's NHWC bytes as a (W, H) map and writes its output the same way.  Evaluated in float64 on the inputs those tests draw, that result is
+    off by at least 10 % of the true one's scale (measured: 1.13 - 1.48), five orders of magnitude above their tolerances.  (On a square
+    map the two readings are the same tensor; a 1x1 stride-1 conv is pointwise and has no row stride to swap.)"""
+    from conv_cases import rel_err, rnd, torch_fwd, wshape_of
+    B = 3
+    w = rnd(*wshape_of(kind, cin, cout, k), seed=1, scale=(cin * k * k) ** -0.5).double()
+    x = rnd(B, cin, hin, win, seed=2).double()
+    ref = torch_fwd(kind, x, w, None, s, p)
+    x_nhwc = x.permute(0, 2, 3, 1).contiguous()
+    swapped_in = x_nhwc.view(B, win, hin, cin).permute(0, 3, 1, 2)                  # the same bytes, rows of hin pixels
+    y = torch_fwd(kind, swapped_in, w, None, s, p).permute(0, 2, 3, 1).contiguous()      # (B, wout, hout, cout)
+    assert y.shape[1:3] == (ref.shape[3], ref.shape[2])
+    swapped = y.view(B, ref.shape[2], ref.shape[3], cout).permute(0, 3, 1, 2)        # ... read back as rows of wout pixels
+    err = rel_err(swapped, ref)
+    print("swapped row stride, %s k%d s%d %dx%d: rel. error %.3f" % (kind, k, s, hin, win, err))
+    assert err >= 0.1
+    # the pointwise layer, for the record: invariant (to the summation order of the float64 reference)
+    w1 = rnd(cout, cin, 1, 1, seed=3).double()
+    a, b = TF.conv2d(x, w1), TF.conv2d(swapped_in, w1).permute(0, 2, 3, 1).contiguous().view(B, hin, win, cout).permute(0, 3, 1, 2)
+    assert torch.allclose(a, b, rtol=0, atol=1e-12)
 
 
 def test_scatter_phases_partition_the_taps(amd):
