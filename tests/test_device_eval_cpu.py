@@ -68,7 +68,7 @@ def test_trainer_sources_build_their_evaluators_through_the_config(lib):
     """Trainer needs a GPU to construct; its two loops take their evaluator from make_evaluator and nowhere else."""
     import inspect
     from awr_amd.trainer import Trainer
-    for fn in (Trainer.train, Trainer.test):
+    for fn in (Trainer.train, Trainer._score):      # (Trainer.test's scoring pass)
         src = inspect.getsource(fn)
         assert "make_evaluator(cfg, " in src and "self.EvalUtil(" not in src and "DeviceEvalUtil(" not in src
 
