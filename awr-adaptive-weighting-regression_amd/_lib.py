@@ -178,14 +178,16 @@ _SIGS = {
     "awr_upsample2_bwd": ([_P, _I, _I, _I, _I, _P, _I, _P], C.c_int),
     "awr_nhwc_to_nchw": ([_P, _I, _I, _I, _I, _P, _P], C.c_int),
     "awr_nchw_to_nhwc": ([_P, _I, _I, _I, _I, _P, _P], C.c_int),
-    # network-level API (csrc/awr_net.hip)
+    # network-level API: the model (csrc/awr_net.hip)
     "awr_net_create": ([_I, _I, _I, _I, _PP], C.c_int),
     "awr_net_destroy": ([_P], C.c_int),
     "awr_net_sizes": ([_P, C.POINTER(_L), C.POINTER(_L), C.POINTER(_L), C.POINTER(_L), C.POINTER(_I), C.POINTER(_I)], C.c_int),
     "awr_net_tensor_info": ([_P, _L, C.POINTER(C.c_char_p), C.POINTER(_I), C.POINTER(_I), C.POINTER(_L), C.POINTER(_L), C.POINTER(_I)], C.c_int),
     "awr_net_bind": ([_P, _P, _P, _P], C.c_int),
+    # ... building a plan (csrc/awr_plan_build.hip)
     "awr_plan_create": ([_P, _I, _I, _I, C.c_uint, _I, _I, _P, _PP, _PP, _PP], C.c_int),
     "awr_plan_create_modes": ([_P, _I, _I, _I, C.c_uint, _I, _I, _P, _PP, _PP, C.POINTER(PlanModes), _PP], C.c_int),
+    # ... using a plan: introspection, streams, replay, tuner (csrc/awr_plan_run.hip; the awr_head_* entries among them are csrc/awr_head.hip)
     "awr_plan_destroy": ([_P], C.c_int),
     "awr_plan_info": ([_P, C.POINTER(_L), C.POINTER(_I), C.POINTER(_I), C.POINTER(_I), C.POINTER(_I), C.POINTER(_I), C.POINTER(_I)], C.c_int),
     "awr_plan_bucket": ([_P, _I, C.POINTER(_L), C.POINTER(_L), C.POINTER(_I)], C.c_int),

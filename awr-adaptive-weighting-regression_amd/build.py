@@ -28,7 +28,9 @@ SOURCES = {
     "awr_wgrad.hip": [],      # weight gradients
     "awr_wino.hip": [],       # Winograd F(2x2, 3x3) forward of the stride-1 3x3 convolutions
     "awr_stem.hip": [],
-    "awr_net.hip": [],        # host-only: network-level plan builder / runner
+    "awr_net.hip": [],        # host-only: the backbones' layers bound to the caller's arenas (awr_net_*)
+    "awr_plan_build.hip": [],  # host-only: network-level plan builder (awr_plan_create[_modes])
+    "awr_plan_run.hip": [],   # host code + the stream pool's spin kernel: plan replay, tuner, streams, the other awr_plan_* entry points
     "awr_dp.hip": [],         # host-only: RCCL communicators through dlopen (no link-time dependency)
     "awr_nyu.hip": ["-ffp-contract=off"],     # NYU data path: numpy's / OpenCV's arithmetic, no fused multiply-adds
     "awr_eval.hip": ["-ffp-contract=off"],    # joint scoring: the host evaluator's numpy arithmetic

@@ -1,4 +1,4 @@
-"""Binding of the network-level engine of libawr_hip.so (csrc/awr_net.hip; include/awr_hip.h "Network-level API").
+"""Binding of the network-level engine of libawr_hip.so (csrc/awr_net.hip, csrc/awr_plan_build.hip, csrc/awr_plan_run.hip; include/awr_hip.h "Network-level API").
 
 The static execution plans of the AWR backbones -- buffer allocation, the forward launch list, the backward list derived by
 a static autograd, gradient buckets, weight repacking, side-stream scheduling, GEMM tile autotuning -- are built and replayed

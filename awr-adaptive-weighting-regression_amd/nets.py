@@ -5,7 +5,7 @@ arena in HBM; every entry of the reference's `state_dict()` (same keys, order, s
 SURVEY.md 8b) is a view into them, so `load_state_dict(torch.load(...)['model'])`, `parameters()`,
 `torch.optim.Adam(net.parameters())`, `.cuda()`, `.train()/.eval()` behave like the reference's
 modules while a gradient all-reduce / fused Adam can treat the whole network as one buffer.
-The checkpoint layout, the execution plans and their replay live in the library (csrc/awr_net.hip,
+The checkpoint layout, the execution plans and their replay live in the library (csrc/awr_net.hip, csrc/awr_plan_build.hip, csrc/awr_plan_run.hip,
 include/awr_hip.h "Network-level API"); this module is the nn.Module shell around those handles:
 there is no PyTorch implementation of the network anywhere in this package.
 """

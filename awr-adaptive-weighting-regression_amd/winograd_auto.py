@@ -1,7 +1,7 @@
 """winograd="auto": the Winograd mode of one engine's plan chosen by timing the candidates (TrainEngine / InferEngine).
 
 The reference turns on `cudnn.benchmark` (train.py:30): the framework times its convolution algorithms per shape and keeps the fastest.  Here the
-choice is per PLAN, not per launch (a weight gradient timed alone on its side stream misleads: csrc/awr_net.hip, autotune): every candidate mode
+choice is per PLAN, not per launch (a weight gradient timed alone on its side stream misleads: csrc/awr_plan_run.hip, autotune): every candidate mode
 is built as a whole plan, warmed up, tile-tuned and timed over a few steps, one plan alive at a time.  This module holds the host-side rules --
 candidates, collapsing of duplicate plans, the choice, the data-parallel agreement and the decision cache -- as plain functions; the engines
 supply the callbacks that build and time a plan.

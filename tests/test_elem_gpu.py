@@ -1,4 +1,4 @@
-"""GPU: the streaming kernels of csrc/awr_elem.hip as operators, in the forms plans run them (csrc/awr_net.hip): slot copies other than the
+"""GPU: the streaming kernels of csrc/awr_elem.hip as operators, in the forms plans run them (csrc/awr_plan_build.hip): slot copies other than the
 default, in-place dy_add / add, the half-batch BatchNorm backward on offset pointers, accumulate forms, non-square maps, overlapping pool
 windows, and every launch class of the channel reductions (tests/elem_cases.py; what each shape reaches is asserted without a GPU in
 tests/test_elem_cpu.py).

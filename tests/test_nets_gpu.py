@@ -1255,7 +1255,7 @@ def test_tuning_cache_round_trip(amd, dev, tmp_path, monkeypatch):
 def test_half_batch_batchnorm_backward_wavefront(amd, dev, net, streams, monkeypatch):
     """Round 5: where half a batch still fills the chip the BatchNorm-backward apply is written half by half -- half A on the
     issuing chain, half B on the stream the layer's weight gradient takes -- and the data gradient runs as two half-batch parts, the first beside
-    half B's pass (csrc/awr_net.hip: bn_bwd / conv_bwd, OP_HALFWAIT; awr_conv_gemm_part).  Forced on for every eligible layer of the batch-4 plans
+    half B's pass (csrc/awr_plan_build.hip: bn_bwd / conv_bwd; csrc/awr_plan_run.hip: OP_HALFWAIT; awr_conv_gemm_part).  Forced on for every eligible layer of the batch-4 plans
     here and compared, in deterministic mode, with the plan that applies and differentiates the whole batch at once: same losses, same gradients
     (the fp64 statistics slots are summed in another order: not bit for bit), with and without side streams."""
     from awr_amd.trainer import TrainEngine

@@ -1,4 +1,4 @@
-"""The plan engine's schedule, pinned to the commit before its scheduling moved from op names to op fields (csrc/awr_net.hip: run_list).
+"""The plan engine's schedule, pinned to the commit before its scheduling moved from op names to op fields (csrc/awr_plan_run.hip: run_list).
 
 tests/golden/plan_snapshot.json was written by tools/plan_snapshot.py on that commit: the op lists, buckets and counts of fourteen plans at
 B = 2, H = 128 (the smallest shape at which both networks fork in the forward and the Hourglass forks in the backward), and the bit patterns
