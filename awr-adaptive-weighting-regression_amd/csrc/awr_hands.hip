@@ -17,6 +17,9 @@
 //   2. hands_tile_kernel: a 64 x 16 tile per workgroup: the mask (foreground with d <= min(dmin + reach, zmax)), a union-find over the
 //      tile in LDS (left and upper neighbour), L = the global raster index of the local root, CNT = 0, ZC = INT_MAX;
 //   3. hands_border_kernel: joins across the tiles' upper and left borders in global memory;
+//      (stages 2 and 3 are the only ones that decide joins.  Each has a compile-time EDGE form for awr_detect_hands_edge, DESIGN.md
+//      4.29: a join also needs |d_a - d_b| <= elim, an integer test equal to the statement's float64 comparison against `edge`, since
+//      elim = depth_floor(edge).  The forms without it are what awr_detect_hands runs, and hold nothing of the test.)
 //   4. hands_flatten_kernel: L = find(L) (and labels_out); CNT and ZC of the root by atomicAdd / atomicMin, the lanes of a wave that
 //      share a root summed first;
 //   5. hands_roots_kernel: every workgroup's K smallest keys among its roots with CNT >= min_pixels (a sorted list per thread, then K
@@ -51,6 +54,7 @@ struct HandsArgs {
     const int64_t* frame; int B, K;
     int dlo, dhi;                 // zmin <= d <= zmax and d != 0  <=>  dlo <= d <= dhi
     double zmax, reach, slab; int min_pixels;
+    int elim;                     // EDGE kernels only: two neighbouring mask pixels join when |d_a - d_b| <= elim (depth_floor of the edge)
     u64* slots; int* L; int* CNT; int* ZC;
     int* labels_out;
 };
@@ -156,9 +160,12 @@ __global__ __launch_bounds__(HANDS_THREADS) void hands_dmin_kernel(HandsArgs a) 
 }
 
 // 2. a tile: the mask, the tile's own forest in LDS, L = the global raster index of the local root (-1 on background); CNT and ZC of
-// every pixel start at "none"
+// every pixel start at "none".  EDGE: the tile's raw depths are staged once next to `lab` (2 KB), and a pixel joins its left or upper
+// neighbour only when their depths differ by at most elim; without it nothing of this is compiled in
+template <bool EDGE>
 __global__ __launch_bounds__(HANDS_THREADS) void hands_tile_kernel(HandsArgs a) {
     __shared__ int lab[HANDS_TILE_W * HANDS_TILE_H];
+    __shared__ uint16_t dep[EDGE ? HANDS_TILE_W * HANDS_TILE_H : 1];
     const HandsFrame hf = hands_frame(a, blockIdx.y);
     const int fw = a.fw, fh = a.fh;
     const int tiles_x = (fw + HANDS_TILE_W - 1) / HANDS_TILE_W;
@@ -169,16 +176,20 @@ __global__ __launch_bounds__(HANDS_THREADS) void hands_tile_kernel(HandsArgs a) 
     const int dlo = a.dlo;
     const int dhi = (hf.bad || dmin == HANDS_NONE) ? -1 : min(a.dhi, hands_limit((int)dmin, a.reach, a.zmax));
     bool m[4];
+    int dq[4];
 #pragma unroll
     for (int q = 0; q < 4; ++q) {
         const int row = row0 + HANDS_WAVES * q, v = tv + row, i = row * HANDS_TILE_W + col;
         const bool inside = u < fw && v < fh;
         m[q] = false;
+        dq[q] = 0;
         if (inside && dhi >= dlo) {
             const int d = hf.F[v * fw + u];
             m[q] = d >= dlo && d <= dhi;
+            dq[q] = d;
         }
         lab[i] = m[q] ? i : -1;
+        if constexpr (EDGE) dep[i] = (uint16_t)dq[q];
         if (inside) { hf.CNT[v * fw + u] = 0; hf.ZC[v * fw + u] = INT_MAX; }
     }
     __syncthreads();
@@ -186,8 +197,12 @@ __global__ __launch_bounds__(HANDS_THREADS) void hands_tile_kernel(HandsArgs a) 
     for (int q = 0; q < 4; ++q) {
         const int row = row0 + HANDS_WAVES * q, i = row * HANDS_TILE_W + col;
         if (!m[q]) continue;
-        if (col > 0 && uf_load(lab + i - 1) >= 0) uf_union(lab, i, i - 1);
-        if (row > 0 && uf_load(lab + i - HANDS_TILE_W) >= 0) uf_union(lab, i, i - HANDS_TILE_W);
+        const auto near = [&](int n) {                                  // the depth test between this pixel and its mask neighbour n
+            if constexpr (EDGE) return abs(dq[q] - (int)dep[n]) <= a.elim;
+            return true;
+        };
+        if (col > 0 && uf_load(lab + i - 1) >= 0 && near(i - 1)) uf_union(lab, i, i - 1);
+        if (row > 0 && uf_load(lab + i - HANDS_TILE_W) >= 0 && near(i - HANDS_TILE_W)) uf_union(lab, i, i - HANDS_TILE_W);
     }
     __syncthreads();
 #pragma unroll
@@ -205,7 +220,8 @@ __global__ __launch_bounds__(HANDS_THREADS) void hands_tile_kernel(HandsArgs a) 
 }
 
 // 3. joins across the tiles' borders: threads 0 ... 63 the tile's first row with the row above it, 64 ... 79 its first column with the
-// column left of it
+// column left of it.  EDGE: the two raw depths are read from the frame and pass the tile kernel's test
+template <bool EDGE>
 __global__ __launch_bounds__(128) void hands_border_kernel(HandsArgs a) {
     const HandsFrame hf = hands_frame(a, blockIdx.y);
     const int fw = a.fw, fh = a.fh;
@@ -219,7 +235,12 @@ __global__ __launch_bounds__(128) void hands_border_kernel(HandsArgs a) {
         const int v = tv + t - HANDS_TILE_W;
         if (tu > 0 && v < fh) { p = v * fw + tu; q = p - 1; }
     }
-    if (p >= 0 && uf_load(hf.L + p) >= 0 && uf_load(hf.L + q) >= 0) uf_union(hf.L, p, q);
+    if (p >= 0 && uf_load(hf.L + p) >= 0 && uf_load(hf.L + q) >= 0) {
+        if constexpr (EDGE) {
+            if (abs((int)hf.F[p] - (int)hf.F[q]) > a.elim) return;      // (labelled pixels: the frame is inside the store)
+        }
+        uf_union(hf.L, p, q);
+    }
 }
 
 // 4. L = find(L); pixels and smallest depth of every component at its root's words
@@ -367,6 +388,49 @@ __global__ void hands_finalize_kernel(HandsArgs a, double* __restrict__ centers,
 
 using namespace awr;
 
+// both entry points: `edge` NULL is awr_detect_hands -- the kernels without a depth test, the launches it always issued
+static int detect_hands(const char* who, const void* frames, int frame_type, int64_t n_frames, int fh, int fw, const int64_t* frame, int B,
+                        int K, double zmin, double zmax, double reach, const double* edge, double slab, int min_pixels, void* scratch,
+                        int* labels_out, double* centers, int* status, int* info, int* count, void* stream) {
+    if (check_frame_store(who, frame_type, B, n_frames, fh, fw) != AWR_OK) return AWR_ERR_ARG;
+    AWR_REQUIRE(K >= 1 && K <= MAX_HANDS, "%s: K = %d hands is outside [1, %d]", who, K, MAX_HANDS);
+    AWR_REQUIRE(min_pixels >= 1, "%s: min_pixels = %d must be at least 1", who, min_pixels);
+    AWR_REQUIRE(zmin <= zmax, "%s: depth range needs zmin <= zmax (got %g, %g)", who, zmin, zmax);
+    AWR_REQUIRE(reach >= 0.0, "%s: reach = %g must be >= 0", who, reach);
+    AWR_REQUIRE(!edge || *edge >= 0.0, "%s: edge = %g must be >= 0 (infinity: no depth test)", who, edge ? *edge : 0.0);
+    AWR_REQUIRE(slab >= 0.0, "%s: slab = %g must be >= 0", who, slab);
+    AWR_REQUIRE(frames && frame && scratch && centers && status && info && count, "%s: NULL pointer", who);
+    AWR_REQUIRE(((uintptr_t)frames & 1) == 0 && ((uintptr_t)scratch & 7) == 0, "%s: misaligned frame store / scratch", who);
+    hipStream_t s = as_stream(stream);
+    const int64_t np = (int64_t)B * fh * fw;
+    HandsArgs a;
+    a.frames = (const uint16_t*)frames; a.n_frames = n_frames; a.fh = fh; a.fw = fw; a.frame = frame; a.B = B; a.K = K;
+    depth_bounds(zmin, zmax, a.dlo, a.dhi);
+    a.zmax = zmax; a.reach = reach; a.slab = slab; a.min_pixels = min_pixels;
+    a.elim = edge ? depth_floor(*edge) : 65535;      // (for integer depths |d_a - d_b| <= edge  <=>  |d_a - d_b| <= floor(edge))
+    a.slots = (u64*)scratch;
+    a.L = (int*)(a.slots + (int64_t)B * HANDS_SLOTS); a.CNT = a.L + np; a.ZC = a.CNT + np;
+    a.labels_out = labels_out;
+    const int64_t nw = (int64_t)B * HANDS_SLOTS;
+    const int tiles = ((fw + HANDS_TILE_W - 1) / HANDS_TILE_W) * ((fh + HANDS_TILE_H - 1) / HANDS_TILE_H);
+    const dim3 share(frame_parts(B, fh, HANDS_MAX_PARTS), B), tile(tiles, B);
+    hands_init_kernel<<<(unsigned)((nw + HANDS_THREADS - 1) / HANDS_THREADS), HANDS_THREADS, 0, s>>>(a.slots, nw);
+    hands_dmin_kernel<<<share, HANDS_THREADS, 0, s>>>(a);
+    if (edge) {
+        hands_tile_kernel<true><<<tile, HANDS_THREADS, 0, s>>>(a);
+        hands_border_kernel<true><<<tile, 128, 0, s>>>(a);
+    } else {
+        hands_tile_kernel<false><<<tile, HANDS_THREADS, 0, s>>>(a);
+        hands_border_kernel<false><<<tile, 128, 0, s>>>(a);
+    }
+    hands_flatten_kernel<<<share, HANDS_THREADS, 0, s>>>(a);
+    hands_roots_kernel<<<share, HANDS_THREADS, 0, s>>>(a);
+    hands_pick_kernel<<<B, HANDS_THREADS, 0, s>>>(a);
+    hands_sums_kernel<<<share, HANDS_THREADS, 0, s>>>(a);
+    hands_finalize_kernel<<<B, MAX_HANDS, 0, s>>>(a, centers, status, info, count);
+    return check_launch(who);
+}
+
 extern "C" {
 
 int64_t awr_detect_hands_scratch(int B, int fh, int fw) {
@@ -382,36 +446,15 @@ int64_t awr_detect_hands_scratch(int B, int fh, int fw) {
 int awr_detect_hands(const void* frames, int frame_type, int64_t n_frames, int fh, int fw, const int64_t* frame, int B, int K, double zmin,
                      double zmax, double reach, double slab, int min_pixels, void* scratch, int* labels_out, double* centers, int* status,
                      int* info, int* count, void* stream) {
-    if (check_frame_store("awr_detect_hands", frame_type, B, n_frames, fh, fw) != AWR_OK) return AWR_ERR_ARG;
-    AWR_REQUIRE(K >= 1 && K <= MAX_HANDS, "awr_detect_hands: K = %d hands is outside [1, %d]", K, MAX_HANDS);
-    AWR_REQUIRE(min_pixels >= 1, "awr_detect_hands: min_pixels = %d must be at least 1", min_pixels);
-    AWR_REQUIRE(zmin <= zmax, "awr_detect_hands: depth range needs zmin <= zmax (got %g, %g)", zmin, zmax);
-    AWR_REQUIRE(reach >= 0.0, "awr_detect_hands: reach = %g must be >= 0", reach);
-    AWR_REQUIRE(slab >= 0.0, "awr_detect_hands: slab = %g must be >= 0", slab);
-    AWR_REQUIRE(frames && frame && scratch && centers && status && info && count, "awr_detect_hands: NULL pointer");
-    AWR_REQUIRE(((uintptr_t)frames & 1) == 0 && ((uintptr_t)scratch & 7) == 0, "awr_detect_hands: misaligned frame store / scratch");
-    hipStream_t s = as_stream(stream);
-    const int64_t np = (int64_t)B * fh * fw;
-    HandsArgs a;
-    a.frames = (const uint16_t*)frames; a.n_frames = n_frames; a.fh = fh; a.fw = fw; a.frame = frame; a.B = B; a.K = K;
-    depth_bounds(zmin, zmax, a.dlo, a.dhi);
-    a.zmax = zmax; a.reach = reach; a.slab = slab; a.min_pixels = min_pixels;
-    a.slots = (u64*)scratch;
-    a.L = (int*)(a.slots + (int64_t)B * HANDS_SLOTS); a.CNT = a.L + np; a.ZC = a.CNT + np;
-    a.labels_out = labels_out;
-    const int64_t nw = (int64_t)B * HANDS_SLOTS;
-    const int tiles = ((fw + HANDS_TILE_W - 1) / HANDS_TILE_W) * ((fh + HANDS_TILE_H - 1) / HANDS_TILE_H);
-    const dim3 share(frame_parts(B, fh, HANDS_MAX_PARTS), B), tile(tiles, B);
-    hands_init_kernel<<<(unsigned)((nw + HANDS_THREADS - 1) / HANDS_THREADS), HANDS_THREADS, 0, s>>>(a.slots, nw);
-    hands_dmin_kernel<<<share, HANDS_THREADS, 0, s>>>(a);
-    hands_tile_kernel<<<tile, HANDS_THREADS, 0, s>>>(a);
-    hands_border_kernel<<<tile, 128, 0, s>>>(a);
-    hands_flatten_kernel<<<share, HANDS_THREADS, 0, s>>>(a);
-    hands_roots_kernel<<<share, HANDS_THREADS, 0, s>>>(a);
-    hands_pick_kernel<<<B, HANDS_THREADS, 0, s>>>(a);
-    hands_sums_kernel<<<share, HANDS_THREADS, 0, s>>>(a);
-    hands_finalize_kernel<<<B, MAX_HANDS, 0, s>>>(a, centers, status, info, count);
-    return check_launch("awr_detect_hands");
+    return detect_hands("awr_detect_hands", frames, frame_type, n_frames, fh, fw, frame, B, K, zmin, zmax, reach, nullptr, slab, min_pixels,
+                        scratch, labels_out, centers, status, info, count, stream);
+}
+
+int awr_detect_hands_edge(const void* frames, int frame_type, int64_t n_frames, int fh, int fw, const int64_t* frame, int B, int K,
+                          double zmin, double zmax, double reach, double edge, double slab, int min_pixels, void* scratch, int* labels_out,
+                          double* centers, int* status, int* info, int* count, void* stream) {
+    return detect_hands("awr_detect_hands_edge", frames, frame_type, n_frames, fh, fw, frame, B, K, zmin, zmax, reach, &edge, slab,
+                        min_pixels, scratch, labels_out, centers, status, info, count, stream);
 }
 
 }  // extern "C"

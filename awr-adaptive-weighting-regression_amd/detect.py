@@ -11,7 +11,8 @@ Two things live here:
   * `palm_center` and `distance_transform`: the statement of awr_detect_palm (csrc/awr_palm.hip) -- a detector centre ->
     the centre of the palm disc of an exact integer distance transform, which a forearm does not drag up the arm; `palm_device` wraps it.
   * `components` and `hand_seeds`: the statements of awr_detect_hands (csrc/awr_hands.hip) -- the near foreground split
-    into 4-connected components with canonical labels, the K nearest large ones seeded per component; `hands_device` wraps it.
+    into 4-connected components with canonical labels, the K nearest large ones seeded per component; `hands_device` wraps it.  With
+    `edge` they are the statements of awr_detect_hands_edge: neighbours join only within `edge` millimetres of depth.
   * `make_views`, `check_views`, `view_table`, `view_centers`, `view_rotate` and `fuse_views`: test-time views -- the host
     table of the views' rotations and the statements of awr_view_centers, awr_view_rotate and awr_views_fuse.
 
@@ -350,12 +351,29 @@ def _check_hands(hands, reach, slab, min_pixels):
     return int(hands), float(reach), float(slab), int(min_pixels)
 
 
-def components(frame, depth_range=DEPTH_RANGE, reach=REACH):
+def _check_edge(edge, value=True):
+    """edge: None (no depth test on the join) | a number of millimetres >= 0, infinity allowed, NaN not -> None | float.  value=False
+    checks the type alone (hands_device: a value the entry point refuses gets its message from there)."""
+    if edge is None:
+        return None
+    if isinstance(edge, (bool, str, bytes)) or not isinstance(edge, (int, float, np.integer, np.floating)):
+        raise TypeError("edge is None or a number of millimetres >= 0, not %r" % (edge,))
+    if value and not float(edge) >= 0.0:
+        raise ValueError("edge = %r must be >= 0 (infinity: no depth test)" % (edge,))
+    return float(edge)
+
+
+def components(frame, depth_range=DEPTH_RANGE, reach=REACH, edge=None):
     """-> labels (fh, fw) int32.  Foreground: zmin <= d <= zmax and d != 0; dmin its smallest depth; the mask is the foreground with
     d <= min(dmin + reach, zmax) (float64 comparisons, as in `detect`).  Two mask pixels are connected when they are 4-neighbours -- no
     depth test.  A pixel's label is the smallest raster index v * fw + u of its component, -1 on background: canonical, so any correct
-    algorithm gives these integers.  Here: the rows' runs, joined where the runs of two neighbouring rows share a column."""
+    algorithm gives these integers.  Here: the rows' runs, joined where the runs of two neighbouring rows share a column.
+    edge: a number of millimetres -- two mask pixels are JOINED when they are 4-neighbours and |d_a - d_b| <= edge, the
+    raw depths compared as float64, and the components are the transitive closure of that (a ramp of small steps is one component).
+    Then a run also starts where the left neighbour is in the mask but more than `edge` away in depth, and a vertical pair joins two
+    runs only if the two pixels pass the test.  An edge of 65535 or more gives the labels of edge=None."""
     frame = _u16(frame)
+    edge = _check_edge(edge)
     fh, fw = frame.shape
     zmin, zmax = float(depth_range[0]), float(depth_range[1])
     if not zmin <= zmax:
@@ -371,11 +389,16 @@ def components(frame, depth_range=DEPTH_RANGE, reach=REACH):
     # a run starts where a mask pixel has no mask pixel to its left; runs are numbered in raster order, so a smaller number is a smaller
     # first index, and the smallest run of a component starts at the component's smallest index
     start = mask.copy()
-    start[:, 1:] &= ~mask[:, :-1]
+    both = mask[:-1] & mask[1:]
+    if edge is None:
+        start[:, 1:] &= ~mask[:, :-1]
+    else:
+        d = frame.astype(np.float64)
+        start[:, 1:] &= ~(mask[:, :-1] & (np.abs(d[:, 1:] - d[:, :-1]) <= edge))
+        both &= np.abs(d[1:] - d[:-1]) <= edge
     run = np.cumsum(start.ravel()).reshape(fh, fw) - 1          # on a mask pixel: the number of its own run
     first = np.flatnonzero(start.ravel())
     parent = np.arange(first.size)
-    both = mask[:-1] & mask[1:]
     pairs = np.unique(run[:-1][both].astype(np.int64) * first.size + run[1:][both])
     p = parent.tolist()
     for a, b in zip((pairs // first.size).tolist(), (pairs % first.size).tolist()):
@@ -399,8 +422,9 @@ def components(frame, depth_range=DEPTH_RANGE, reach=REACH):
     return labels
 
 
-def hand_seeds(frame, hands, depth_range=DEPTH_RANGE, reach=REACH, slab=SLAB, min_pixels=MIN_PIXELS):
-    """The statement of awr_detect_hands for one frame: -> (centers (K, 3) float64, status (K,) int32, info (K, 4) int32, count).
+def hand_seeds(frame, hands, depth_range=DEPTH_RANGE, reach=REACH, slab=SLAB, min_pixels=MIN_PIXELS, edge=None):
+    """The statement of awr_detect_hands (edge=None) and awr_detect_hands_edge (edge: `components`' depth test on the join; everything
+    below reads its labels) for one frame: -> (centers (K, 3) float64, status (K,) int32, info (K, 4) int32, count).
     Candidates: the components of `components` with n >= min_pixels pixels; a candidate's key is (zc, root), zc its smallest raw depth
     and root its label; the K = hands smallest keys fill the slots in ascending order (slot 0: the nearest hand; a tie in depth goes to
     the smaller root).  A slot's seed is the centre of mass of its component's pixels with d <= min(zc + slab, zmax) -- the "nearest"
@@ -411,7 +435,7 @@ def hand_seeds(frame, hands, depth_range=DEPTH_RANGE, reach=REACH, slab=SLAB, mi
     frame = _u16(frame)
     fw = frame.shape[1]
     zmax = float(depth_range[1])
-    labels = components(frame, depth_range, reach)
+    labels = components(frame, depth_range, reach, edge)
     centers, status, info = np.full((K, 3), np.nan), np.full(K, EMPTY, np.int32), np.tile(np.array(_NO_INFO, np.int32), (K, 1))
     on = labels >= 0
     if not on.any():
@@ -695,12 +719,15 @@ def palm_device(store, frame_idx, centers, status, cube=(300, 300, 300), paras=N
     return center_out, status_out, info
 
 
-def hands_device(store, frame_idx, hands, depth_range=DEPTH_RANGE, reach=REACH, slab=SLAB, min_pixels=MIN_PIXELS, labels=False, scratch=None):
+def hands_device(store, frame_idx, hands, depth_range=DEPTH_RANGE, reach=REACH, slab=SLAB, min_pixels=MIN_PIXELS, labels=False, scratch=None,
+                 edge=None):
     """awr_detect_hands on a FrameStore-like object: -> (centres (K, B, 3) float64, status (K, B) int32, info (K, B, 4) int32, count (B,)
     int32, labels (B, fh, fw) int32 or None) on the device, hand-major, nothing synchronised.  labels: True (allocated), False (NULL) or
-    a tensor; scratch: an int64 tensor of at least awr_detect_hands_scratch(B, fh, fw) bytes."""
+    a tensor; scratch: an int64 tensor of at least awr_detect_hands_scratch(B, fh, fw) bytes.  edge: None issues awr_detect_hands,
+    anything else awr_detect_hands_edge (a type that is no number raises here; a value the entry point refuses gets its message there)."""
     import torch
     from . import _lib as L
+    edge = _check_edge(edge, value=False)
     dev = store.data.device
     idx = _frame_index(frame_idx, dev)
     B, K = int(idx.shape[0]), int(hands)
@@ -715,9 +742,14 @@ def hands_device(store, frame_idx, hands, depth_range=DEPTH_RANGE, reach=REACH, 
         labels = torch.empty((B, store.fh, store.fw), dtype=torch.int32, device=dev)
     elif labels is False:
         labels = None
-    L.call("awr_detect_hands", store.data.data_ptr(), store.ftype, int(store.data.shape[0]), store.fh, store.fw, idx.data_ptr(), B, K,
-           float(depth_range[0]), float(depth_range[1]), float(reach), float(slab), int(min_pixels), scratch.data_ptr(), L.ptr(labels),
-           centers.data_ptr(), status.data_ptr(), info.data_ptr(), count.data_ptr(), L.stream())
+    head = (store.data.data_ptr(), store.ftype, int(store.data.shape[0]), store.fh, store.fw, idx.data_ptr(), B, K, float(depth_range[0]),
+            float(depth_range[1]), float(reach))
+    tail = (float(slab), int(min_pixels), scratch.data_ptr(), L.ptr(labels), centers.data_ptr(), status.data_ptr(), info.data_ptr(),
+            count.data_ptr(), L.stream())
+    if edge is None:
+        L.call("awr_detect_hands", *head, *tail)
+    else:
+        L.call("awr_detect_hands_edge", *head, edge, *tail)
     return centers, status, info, count, labels
 
 

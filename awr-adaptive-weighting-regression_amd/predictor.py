@@ -18,9 +18,10 @@ detector for such a machine.  Every option is opt-in, and a predictor without it
     hands=K                                 up to K hands per frame from connected components; a hand axis             4.26
     hands=K, identity=True | dict           slot k is the same hand from call to call; track, smooth, lead per hand    4.27
     hands=K, isolate=True                   every hand refined and cropped on a frame that holds only its component    4.28
+    hands=K, edge_mm=E                      components join only within E mm of depth: a hand in front of another splits 4.29
 
 predict() is ONE pipeline over one stage method per entry point, and it reads top to bottom: upload the frames ->
-the seeds (given centres | awr_detect_hands | the configured seed mode) -> with isolate a frame per hand (awr_hands_isolate) -> the
+the seeds (given centres | awr_detect_hands, with edge_mm awr_detect_hands_edge | the configured seed mode) -> with isolate a frame per hand (awr_hands_isolate) -> the
 candidate centres (awr_detect, awr_detect_palm) -> the tracked detector (a second awr_detect) -> combine (awr_centers_select |
 awr_hands_assign | nothing) -> crop and predict
 (awr_detect_samples -> awr_nyu_batch -> the inference plan and the single-pass head -> awr_joints_unproject; with views awr_view_centers
@@ -65,7 +66,7 @@ class Predictor:
     def __init__(self, net, img_size, kernel_size, cube=(300, 300, 300), paras=ND.PARAS, flip=-1, max_batch=1, frame_shape=(480, 640),
                  seed="nearest", depth_range=D.DEPTH_RANGE, slab=D.SLAB, refine_iters=D.REFINE_ITERS, winograd=None, parity=False, confidence=False,
                  recenter=0, track=False, center_joints=None, max_shift=1.0, views=None, fuse="mean", palm=False, palm_search=D.PALM_SEARCH,
-                 smooth=None, hands=1, reach=D.REACH, min_pixels=D.MIN_PIXELS, identity=None, isolate=False):
+                 smooth=None, hands=1, reach=D.REACH, min_pixels=D.MIN_PIXELS, identity=None, isolate=False, edge_mm=None):
         """net: an awr_amd network on the GPU with its weights loaded.  cube: the crop cube in mm.  paras = (fx, fy, u0, v0), flip: the camera.
         max_batch: the static batch of the inference plan; smaller batches are padded, larger ones refused.  seed / depth_range / slab /
         refine_iters: the detector (awr_amd.detect); with `centers_uvd` handed to predict() the seed is the given centre and refine_iters
@@ -116,7 +117,7 @@ class Predictor:
         (nb, K, J, 3), center_xyz (nb, K, 3), M (nb, K, 3, 3), status (nb, K), conf / peak / spread_mm (nb, K, J) -- and n_hands (nb,)
         int32; slot 0 is the nearest hand, an absent hand has status EMPTY and NaN rows.  hand_info (nb, K, 4) int32 holds
         awr_detect_hands' info rows (the component's first pixel u, v, its pixels, its nearest depth) after a call.  Not combined with
-        views, track or smooth (track and smooth: unless identity is set, below); touching or overlapping hands are ONE component and count as one hand; reach and min_pixels are
+        views, track or smooth (track and smooth: unless identity is set, below); without edge_mm touching or overlapping hands are ONE component and count as one hand; reach and min_pixels are
         engineering defaults, UNMEASURED on real frames.
         identity: None | True (the defaults) | a dict of awr_amd.track.Identity's fields | an Identity -- with hands >= 2, keep every hand in
         ITS slot from call to call (statement: awr_amd.track.assign_step): one awr_hands_assign launch assigns this call's
@@ -138,8 +139,16 @@ class Predictor:
         other's window and crop.  With identity the candidates are refined on their isolated rows and a slot crops from the row of the
         candidate it took; a slot that follows its tracked centre, the tracker's own detector run and predict(centers_uvd=...) (which
         computes no labels) read the raw frames.  After a call `isolated` (nb, K) int32: 1 where the slot's row was an isolated frame, 0
-        for a raw one and for a slot without a hand.  Refused with hands=1 and with views.  Touching hands remain ONE component and ONE
-        hand; UNMEASURED on real frames."""
+        for a raw one and for a slot without a hand.  Refused with hands=1 and with views.  Without edge_mm touching or overlapping hands
+        remain ONE component and ONE hand; UNMEASURED on real frames.
+        edge_mm: None | a number of millimetres >= 0 -- with hands >= 2, the hands stage issues awr_detect_hands_edge (DESIGN.md 4.29;
+        statement: awr_amd.detect.components(edge=)): two neighbouring pixels of the near foreground are joined only when their raw depths
+        differ by at most edge_mm, so a hand held in front of another one is a component, a slot and (with isolate) a frame of its own.
+        Everything behind the hands stage is untouched and reads its labels, seeds and info rows.  What it does not split: hands that
+        touch in depth.  What it adds: an occluded hand cut into fragments by the front one gives several candidates (n_hands may be
+        larger), and with isolate the fragments that are not the slot's root are removed from that hand's own frame
+        (profiles/hands_overlap.txt).  No default is chosen: the right value depends on the sensor's noise, UNMEASURED on real frames.
+        Refused with hands=1."""
         if isinstance(hands, bool) or not isinstance(hands, int):
             raise TypeError("hands is an int in [1, %d], not %r" % (D.MAX_HANDS, hands))
         K, self.reach, _, self.min_pixels = D._check_hands(hands, reach, 0.0, min_pixels)
@@ -159,6 +168,9 @@ class Predictor:
         if isolate and (K == 1 or views is not None):
             raise ValueError("isolate gives each of SEVERAL hands a frame of its own component: it needs hands >= 2, and views are not combined with it")
         self.isolate, self.isolated = isolate, None
+        self.edge_mm = D._check_edge(edge_mm)
+        if self.edge_mm is not None and K == 1:
+            raise ValueError("edge_mm is the depth test on the joins of the connected components of SEVERAL hands: it needs hands >= 2")
         if not isinstance(palm, bool):
             raise TypeError("palm is True or False, not %r" % (palm,))
         self.palm, self.palm_search = palm, D.check_palm(palm_search)[0]
@@ -440,10 +452,15 @@ class Predictor:
 
     def _detect_hands(self, nb):
         """the K nearest components' seeds of every frame -> self._seed, hand-major"""
-        L.call("awr_detect_hands", self._frames.data_ptr(), 0, self.B, self.fh, self.fw, self._idx.data_ptr(), self.B, self.hands, self.depth_range[0],
-               self.depth_range[1], self.reach, self.slab, self.min_pixels, self._hands_scratch.data_ptr(),
-               self._labels.data_ptr() if self.isolate else None, self._seed.data_ptr(),
-               self._hands_status.data_ptr(), self._hands_info.data_ptr(), self._hands_count.data_ptr(), L.stream())
+        head = (self._frames.data_ptr(), 0, self.B, self.fh, self.fw, self._idx.data_ptr(), self.B, self.hands, self.depth_range[0],
+                self.depth_range[1], self.reach)
+        tail = (self.slab, self.min_pixels, self._hands_scratch.data_ptr(),
+                self._labels.data_ptr() if self.isolate else None, self._seed.data_ptr(),
+                self._hands_status.data_ptr(), self._hands_info.data_ptr(), self._hands_count.data_ptr(), L.stream())
+        if self.edge_mm is None:
+            L.call("awr_detect_hands", *head, *tail)
+        else:
+            L.call("awr_detect_hands_edge", *head, self.edge_mm, *tail)
         self.hand_info = self._hands_info[:, :nb].transpose(0, 1)
 
     def _hands_isolate(self):

@@ -983,6 +983,22 @@ int awr_detect_hands(const void* frames, int frame_type, int64_t n_frames, int f
                      int* labels_out /* B*fh*fw, may be NULL */, double* centers /* K,B,3 */, int* status /* K,B */,
                      int* info /* K,B,4 */, int* count /* B */, void* stream);
 
+/* awr_detect_hands with a depth test on the join (the statements are components / hand_seeds with edge=...): everything
+ * above holds, except step 3, which becomes
+ *   3'. Two mask pixels are JOINED when they are 4-neighbours and |d_a - d_b| <= edge, their raw depths compared in double; the
+ *       components are the transitive closure of that relation (a ramp whose neighbouring pixels differ by at most `edge` is ONE
+ *       component, however far apart its ends are).  Labels stay canonical: the smallest raster index of the component, -1 off the mask.
+ * so a hand held in front of another one, `edge` millimetres or more nearer along the whole contact line, is a component of its own.
+ * What it does not separate: hands that touch in depth, and an occluded hand that the front one cuts into fragments -- each fragment
+ * of min_pixels or more pixels is a candidate.  edge >= 0 (infinity allowed: awr_detect_hands' labels, as every edge >= 65535; NaN
+ * not): anything else returns AWR_ERR_ARG with a message that names it, before any launch.  For integer depths the test equals
+ * |d_a - d_b| <= floor(min(edge, 65535)), which is what the kernels compare.  The same nine launches, scratch and outputs: only the
+ * tile and the border stage differ (compile-time forms of the same two kernels; awr_detect_hands runs the forms without the test). */
+int awr_detect_hands_edge(const void* frames, int frame_type, int64_t n_frames, int fh, int fw, const int64_t* frame, int B, int K,
+                          double zmin, double zmax, double reach, double edge, double slab, int min_pixels, void* scratch,
+                          int* labels_out /* B*fh*fw, may be NULL */, double* centers /* K,B,3 */, int* status /* K,B */,
+                          int* info /* K,B,4 */, int* count /* B */, void* stream);
+
 /* A frame per hand (csrc/awr_isolate.hip; the numpy statement is awr_amd/detect.py isolate, results are bit-identical
  * to it).  awr_detect_hands keeps a seed per hand, and awr_detect, awr_detect_palm, awr_detect_samples and the renderer read the whole raw
  * frame again: two hands closer than half a crop cube stand in each other's window and crop.  This entry gives each hand a frame that

@@ -23,7 +23,7 @@ at the constant-velocity look-ahead of the joints.  pred_uvd.txt / pred_xyz.txt 
 pred_raw_xyz.txt (the network's own) and pred_filter_code.txt (J columns, awr_amd.track.FILTER_NAMES) are written too.
 --hands K (2 ... 4) looks for up to K hands per frame: awr_detect_hands splits the near foreground into connected components and seeds the K
 nearest large ones (--reach MM: how far behind the nearest pixel that foreground goes, default 300; --min-pixels N: the smallest component
-that counts, default 400; DESIGN.md 4.26 -- both UNMEASURED on real frames; touching hands are one hand).  The saved arrays gain the hand
+that counts, default 400; DESIGN.md 4.26 -- both UNMEASURED on real frames; without --edge-mm touching or overlapping hands are one hand).  The saved arrays gain the hand
 axis: pred_uvd.txt / pred_xyz.txt hold n * K rows (frame-major, the nearest hand first; an absent hand's row is nan), and pred_n_hands.txt
 (one count per frame), pred_hand_status.txt (K columns, awr_amd.detect's codes) and pred_hand_info.txt (n * K rows: the component's first
 pixel u, v, its pixels, its nearest depth) are written too.  Not combined with --views, --track or --smooth yet -- unless:
@@ -33,7 +33,11 @@ is ONE sequence (batch size 1), --track and --smooth then work per hand, and pre
 pred_hand_code.txt (K columns, awr_amd.track.ASSIGN_NAMES) are written too; pred_hand_info.txt stays in detection order.
 --isolate (with --hands K) gives every hand a frame that holds only its own connected component before the refinement, the palm pass and
 the crop (awr_hands_isolate): two hands nearer than half a crop cube no longer stand in each other's crop.  Touching hands
-remain one component and one hand; UNMEASURED on real frames.
+remain one component and one hand unless --edge-mm separates them; UNMEASURED on real frames.
+--edge-mm E (with --hands K) joins two neighbouring pixels of the near foreground only when their depths differ by at most E millimetres
+(awr_detect_hands_edge): a hand held in front of another one becomes a component of its own.  Hands that touch in depth
+stay one hand, and a rear hand that the front one cuts into pieces gives one candidate per piece of --min-pixels or more
+(profiles/hands_overlap.txt).  There is no default: the right E depends on the sensor's noise, UNMEASURED on real frames.
 --ema predicts with the checkpoint's averaged weights ("model_ema", written by a run with config.ema_decay) instead of "model".
 `--set` overrides config entries as train.py does (img_size, kernel_size, cube, batch_size, jt_num, downsample, winograd ...)."""
 import argparse
@@ -65,6 +69,7 @@ def parse_args(argv=None):
     ap.add_argument("--reach", type=float, default=None, metavar="MM", help="with --hands: depth of the foreground behind the nearest pixel (default 300)")
     ap.add_argument("--min-pixels", type=int, default=None, metavar="N", help="with --hands: the smallest component that counts as a hand (default 400)")
     ap.add_argument("--isolate", action="store_true", help="with --hands: refine and crop every hand on a frame that holds only its own component")
+    ap.add_argument("--edge-mm", type=float, default=None, metavar="E", help="with --hands: join neighbouring foreground pixels only within E mm of depth, so a hand in front of another one splits off")
     ap.add_argument("--identity", nargs="?", const="", default=None, metavar="GATE_MM,MERGE_MM,MAX_MISS",
                     help="with --hands: keep each hand in its slot across frames (the file is one sequence); optionally the gate, the merge distance and the misses allowed")
     ap.add_argument("--ema", action="store_true", help="load the checkpoint's \"model_ema\" (the EMA of the weights) instead of \"model\"")
@@ -144,7 +149,9 @@ def main(argv=None):
         raise SystemExit("--reach and --min-pixels belong to --hands K with K >= 2")
     if args.isolate and (args.hands == 1 or args.views is not None):
         raise SystemExit("--isolate belongs to --hands K with K >= 2, without --views")
-    hands_kw = {} if args.hands == 1 else dict(isolate=args.isolate, hands=args.hands, reach=detect.REACH if args.reach is None else args.reach,
+    if args.edge_mm is not None and args.hands == 1:
+        raise SystemExit("--edge-mm belongs to --hands K with K >= 2")
+    hands_kw = {} if args.hands == 1 else dict(isolate=args.isolate, edge_mm=args.edge_mm, hands=args.hands, reach=detect.REACH if args.reach is None else args.reach,
                                                min_pixels=detect.MIN_PIXELS if args.min_pixels is None else args.min_pixels)
     K = args.hands
     pred = awr_amd.Predictor(net.cuda(), cfg.img_size, cfg.kernel_size, cube=cfg.cube, max_batch=bs, frame_shape=frames.shape[1:],

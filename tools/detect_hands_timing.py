@@ -175,7 +175,7 @@ def main():
             "elsewhere %.1f %%; it never reports a second hand" % (100 * single[0], 100 * single[1], 100 * single[2]))
         say()
         del fa, fb, both, sa, sb, sc
-    say("touching or overlapping hands form ONE component and count as one hand; identity of a hand across calls is not tracked")
+    say("without the depth test on the join (edge, DESIGN.md 4.29) touching or overlapping hands form ONE component and count as one hand; identity of a hand across calls is not tracked")
     os.makedirs(os.path.dirname(a.out), exist_ok=True)
     with open(a.out, "w") as f:
         f.write("\n".join(lines) + "\n")
