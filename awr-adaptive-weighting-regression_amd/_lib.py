@@ -262,6 +262,8 @@ _SIGS = {
     "awr_detect_hands_edge": ([_P, _I, _L, _I, _I, _P, _I, _I, _D, _D, _D, _D, _D, _I, _P, _P, _P, _P, _P, _P, _P], C.c_int),
     # a frame per hand: the other labelled components removed (csrc/awr_isolate.hip)
     "awr_hands_isolate": ([_P, _I, _L, _I, _I, _P, _I, _I, _P, _P, _P, _P, _P], C.c_int),
+    # edge-preserving depth pre-filter in front of the detector (csrc/awr_denoise.hip)
+    "awr_frames_denoise": ([_P, _I, _L, _I, _I, _P, _I, _I, _D, _I, _I, _P, _P, _P], C.c_int),
     # test-time views (csrc/awr_detect.hip)
     "awr_view_centers": ([_P, _P, _P, _I, _P, _I, _I, _I, _D, _D, _D, _D, _I, _P, _P, _P, _P, _P], C.c_int),
     "awr_view_rotate": ([_P, _P, _P, _P, _I, _I, _I, _P], C.c_int),

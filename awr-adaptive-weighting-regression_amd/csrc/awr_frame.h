@@ -1,5 +1,5 @@
-// What the prediction path's translation units share (awr_detect.hip, awr_palm.hip, awr_hands.hip, awr_isolate.hip, awr_track.hip,
-// awr_assign.hip): the crop window and the camera model as scalar double arithmetic, and the 64-bit integer
+// What the prediction path's translation units share (awr_detect.hip, awr_palm.hip, awr_hands.hip, awr_isolate.hip, awr_denoise.hip,
+// awr_track.hip, awr_assign.hip): the crop window and the camera model as scalar double arithmetic, and the 64-bit integer
 // reductions, launch split and frame-store checks of the kernels that stream over a frame.  Each is written once, here.
 //
 // Part (a) is the single device statement of nyu_data.center2bounds, evaluator.uvd2xyz and evaluator.xyz2uvd: IEEE double in numpy's

@@ -13,6 +13,8 @@ Two things live here:
   * `components` and `hand_seeds`: the statements of awr_detect_hands (csrc/awr_hands.hip) -- the near foreground split
     into 4-connected components with canonical labels, the K nearest large ones seeded per component; `hands_device` wraps it.  With
     `edge` they are the statements of awr_detect_hands_edge: neighbours join only within `edge` millimetres of depth.
+  * `denoise`: the statement of awr_frames_denoise (csrc/awr_denoise.hip) -- an edge-preserving lower median with
+    speckle removal and hole filling in front of every stage; `denoise_device` wraps it.
   * `make_views`, `check_views`, `view_table`, `view_centers`, `view_rotate` and `fuse_views`: test-time views -- the host
     table of the views' rotations and the statements of awr_view_centers, awr_view_rotate and awr_views_fuse.
 
@@ -472,6 +474,86 @@ def isolate(frame, labels, roots):
     return out
 
 
+# ---- edge-preserving depth pre-filter in front of the detector (include/awr_hip.h awr_frames_denoise) -----------------
+# Engineering choices, not measured on real frames (none are available where this was written): a 3 x 3 window, the 40 mm edge DESIGN.md
+# 4.29 measured on procedural composites, no speckle removal and no hole filling -- a pure edge-preserving median.
+DENOISE_DEFAULTS = dict(radius=1, edge=40.0, support=0, fill=None)
+DENOISE_MAX_RADIUS = 2
+
+
+def _check_denoise(radius=1, edge=None, support=0, fill=None, value=True):
+    """Validate denoise's four knobs: -> (radius int, edge None | float, support int, fill None | int).  value=False checks the types
+    alone (denoise_device: a value the entry point refuses gets its message from there)."""
+    for x, what in ((radius, "radius"), (support, "support")) + (((fill, "fill"),) if fill is not None else ()):
+        if isinstance(x, bool) or not isinstance(x, (int, np.integer)):
+            raise TypeError("%s is an int%s, not %r" % (what, " or None" if what == "fill" else "", x))
+    most = (2 * int(radius) + 1) ** 2 - 1
+    if value and not 1 <= int(radius) <= DENOISE_MAX_RADIUS:
+        raise ValueError("radius = %d must be 1 or 2 (a 3 x 3 or a 5 x 5 window)" % radius)
+    if value and not 0 <= int(support) <= most:
+        raise ValueError("support = %d is outside [0, %d], the neighbours of a radius-%d window" % (support, most, radius))
+    if value and fill is not None and not 1 <= int(fill) <= most:
+        raise ValueError("fill = %d is outside [1, %d], the neighbours of a radius-%d window (None: no filling)" % (fill, most, radius))
+    return int(radius), _check_edge(edge, value), int(support), None if fill is None else int(fill)
+
+
+def check_denoise_option(denoise):
+    """Predictor(denoise=...) and FrameStore.denoised(**options): None | True (DENOISE_DEFAULTS) | a dict with any of the keys radius /
+    edge / support / fill over those defaults -> None | a dict of the four checked values."""
+    if denoise is None:
+        return None
+    if denoise is True:
+        denoise = {}
+    if not isinstance(denoise, dict):
+        raise TypeError("denoise is None, True or a dict with the keys radius / edge / support / fill, not %r" % (denoise,))
+    extra = set(denoise) - set(DENOISE_DEFAULTS)
+    if extra:
+        raise ValueError("denoise has unknown keys %s (radius, edge, support and fill exist)" % sorted(extra))
+    return dict(zip(("radius", "edge", "support", "fill"), _check_denoise(**dict(DENOISE_DEFAULTS, **denoise))))
+
+
+def denoise(frame, radius=1, edge=None, support=0, fill=None):
+    """The statement of awr_frames_denoise for one frame: -> (fh, fw) uint16.  The rule:
+
+    Every output pixel is a function of the INPUT frame alone. It is a single pass: not iterated, not in place.
+    Definitions for pixel p with depth d_p:
+      - W is the set of in-frame pixels of the (2 * radius + 1)^2 window around p, without p itself.
+      - elim = 65535 for edge=None, else floor(min(edge, 65535)). This is awr_frame.h's depth_floor, the integer form 4.29 already uses.
+      - A pixel is valid when its depth is not 0.
+      - The lower median of n values is element (n - 1) // 2 of the ascending sort. It is a value that occurs in the window, never an
+        average.
+    Output:
+      - If d_p != 0: let S = { q in W : d_q != 0 and |d_q - d_p| <= elim }.
+          - If |S| < support the output is 0. This removes a flying pixel or speckle.
+          - Otherwise the output is the lower median of S and p together, which is element |S| // 2 of its sort.
+      - If d_p == 0: let V = { q in W : d_q != 0 }.
+          - If fill is given and |V| >= fill, the output is the lower median of V.
+          - Otherwise the output is 0.
+    Out-of-frame positions and zero pixels are indistinguishable under this rule, because both thresholds are absolute counts. The frame
+    behaves as if surrounded by zeros, and the kernel may stage its halo that way.
+
+    Here: the window as zero-padded shifts of the frame, the pixels that do not count replaced by a sentinel above every depth, one sort
+    along the window axis and one take_along_axis."""
+    frame = _u16(frame)
+    r, edge, support, fill = _check_denoise(radius, edge, support, fill)
+    elim = 65535 if edge is None else int(np.floor(min(edge, 65535.0)))
+    fh, fw = frame.shape
+    padded = np.zeros((fh + 2 * r, fw + 2 * r), np.int32)
+    padded[r:r + fh, r:r + fw] = frame
+    shifts = [(dv, du) for dv in range(2 * r + 1) for du in range(2 * r + 1) if (dv, du) != (r, r)]
+    win = np.stack([padded[dv:dv + fh, du:du + fw] for dv, du in shifts])          # W, one plane per neighbour
+    d = frame.astype(np.int32)
+    seen = d != 0
+    counts = (win != 0) & (~seen | (np.abs(win - d) <= elim))                        # S where d_p != 0, V where it is 0
+    n = counts.sum(0)
+    keys = np.concatenate([np.where(counts, win, 65536), np.where(seen, d, 65536)[None]])
+    keys.sort(axis=0)
+    k = np.where(seen, n // 2, np.maximum(n - 1, 0) // 2)
+    median = np.take_along_axis(keys, k[None], 0)[0]
+    keep = np.where(seen, n >= support, (n >= fill) if fill is not None else False)
+    return np.where(keep, median, 0).astype(np.uint16)
+
+
 # ---- test-time views: the same hand under rotations, cube scales and centre shifts (DESIGN.md 4.22) ----------------------------------
 def _number(x, what):
     if isinstance(x, (bool, str, bytes)) or not isinstance(x, (int, float, np.integer, np.floating)):
@@ -778,6 +860,24 @@ def isolate_device(store, frame_idx, labels, roots=None, info=None, out=None):
     status = torch.empty(B, dtype=torch.int32, device=dev)
     L.call("awr_hands_isolate", store.data.data_ptr(), store.ftype, int(store.data.shape[0]), store.fh, store.fw, idx.data_ptr(), B, K,
            L.ptr(labels), L.ptr(info), L.ptr(out), status.data_ptr(), L.stream())
+    return out, status
+
+
+def denoise_device(store, frame_idx, radius=1, edge=None, support=0, fill=None, out=None):
+    """awr_frames_denoise on a FrameStore-like object: -> (out (B, fh, fw) uint16, row b the filtered frame frame_idx[b], status (B,)
+    int32) on the device, nothing synchronised.  out: a tensor to write into; it must not overlap the store.  The types are checked here
+    (edge as hands_device does); a value the entry point refuses gets its message from there."""
+    import torch
+    from . import _lib as L
+    radius, edge, support, fill = _check_denoise(radius, edge, support, fill, value=False)
+    dev = store.data.device
+    idx = _frame_index(frame_idx, dev)
+    B = int(idx.shape[0])
+    if out is None:
+        out = torch.empty((B, store.fh, store.fw), dtype=torch.uint16, device=dev)
+    status = torch.empty(B, dtype=torch.int32, device=dev)
+    L.call("awr_frames_denoise", store.data.data_ptr(), store.ftype, int(store.data.shape[0]), store.fh, store.fw, idx.data_ptr(), B, radius,
+           float("inf") if edge is None else edge, support, 0 if fill is None else fill, L.ptr(out), status.data_ptr(), L.stream())
     return out, status
 
 

@@ -152,6 +152,20 @@ class FrameStore:
     def nbytes(self):
         return self.data.numel() * self.data.element_size()
 
+    def denoised(self, chunk=256, **options):
+        """-> a new uint16 store whose frame i is awr_amd.detect.denoise(frame i, **options): a training set filtered
+        once, as Predictor(denoise=options) filters its frames.  options: radius / edge / support / fill over detect.DENOISE_DEFAULTS.
+        One awr_frames_denoise launch per `chunk` frames; nothing synchronised."""
+        from . import detect as D
+        options = D.check_denoise_option(options)
+        if self.ftype != 0:
+            raise ValueError("denoised filters uint16 millimetres: this store holds float32 frames")
+        out = torch.empty_like(self.data)
+        for lo in range(0, self.n, chunk):
+            hi = min(self.n, lo + chunk)
+            D.denoise_device(self, torch.arange(lo, hi, dtype=torch.int64, device=self.data.device), out=out[lo:hi], **options)
+        return FrameStore.from_device(out)
+
 
 def build_frame_cache(root, phase, out=None):
     """Decode every depth_1*.png of <root>/<phase> once (nyu_loader.py:71-74: depth = G*256 + B) into a uint16 .npy the FrameStore

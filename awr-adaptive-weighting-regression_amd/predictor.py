@@ -19,9 +19,10 @@ detector for such a machine.  Every option is opt-in, and a predictor without it
     hands=K, identity=True | dict           slot k is the same hand from call to call; track, smooth, lead per hand    4.27
     hands=K, isolate=True                   every hand refined and cropped on a frame that holds only its component    4.28
     hands=K, edge_mm=E                      components join only within E mm of depth: a hand in front of another splits 4.29
+    denoise=True | dict                     edge-preserving median, speckle removal, hole filling in front of every stage 4.30
 
-predict() is ONE pipeline over one stage method per entry point, and it reads top to bottom: upload the frames ->
-the seeds (given centres | awr_detect_hands, with edge_mm awr_detect_hands_edge | the configured seed mode) -> with isolate a frame per hand (awr_hands_isolate) -> the
+predict() is ONE pipeline over one stage method per entry point, and it reads top to bottom: upload the frames -> with denoise the filtered
+frames (awr_frames_denoise) -> the seeds (given centres | awr_detect_hands, with edge_mm awr_detect_hands_edge | the configured seed mode) -> with isolate a frame per hand (awr_hands_isolate) -> the
 candidate centres (awr_detect, awr_detect_palm) -> the tracked detector (a second awr_detect) -> combine (awr_centers_select |
 awr_hands_assign | nothing) -> crop and predict
 (awr_detect_samples -> awr_nyu_batch -> the inference plan and the single-pass head -> awr_joints_unproject; with views awr_view_centers
@@ -62,11 +63,12 @@ class Predictor:
     views, fuse, V = None, "mean", 1          # a predictor without views: one identity view, no view table, no per-view buffers
     smooth = None                             # a predictor without a temporal filter: no filter state, no launch, no extra attributes
     identity = None                           # a predictor without hand identities: no assignment state, no launch, no extra attributes
+    denoise = None                            # a predictor without the depth pre-filter: no raw buffer, no launch, no extra attributes
 
     def __init__(self, net, img_size, kernel_size, cube=(300, 300, 300), paras=ND.PARAS, flip=-1, max_batch=1, frame_shape=(480, 640),
                  seed="nearest", depth_range=D.DEPTH_RANGE, slab=D.SLAB, refine_iters=D.REFINE_ITERS, winograd=None, parity=False, confidence=False,
                  recenter=0, track=False, center_joints=None, max_shift=1.0, views=None, fuse="mean", palm=False, palm_search=D.PALM_SEARCH,
-                 smooth=None, hands=1, reach=D.REACH, min_pixels=D.MIN_PIXELS, identity=None, isolate=False, edge_mm=None):
+                 smooth=None, hands=1, reach=D.REACH, min_pixels=D.MIN_PIXELS, identity=None, isolate=False, edge_mm=None, denoise=None):
         """net: an awr_amd network on the GPU with its weights loaded.  cube: the crop cube in mm.  paras = (fx, fy, u0, v0), flip: the camera.
         max_batch: the static batch of the inference plan; smaller batches are padded, larger ones refused.  seed / depth_range / slab /
         refine_iters: the detector (awr_amd.detect); with `centers_uvd` handed to predict() the seed is the given centre and refine_iters
@@ -148,7 +150,19 @@ class Predictor:
         touch in depth.  What it adds: an occluded hand cut into fragments by the front one gives several candidates (n_hands may be
         larger), and with isolate the fragments that are not the slot's root are removed from that hand's own frame
         (profiles/hands_overlap.txt).  No default is chosen: the right value depends on the sensor's noise, UNMEASURED on real frames.
-        Refused with hands=1."""
+        Refused with hands=1.
+        denoise: None | True (awr_amd.detect.DENOISE_DEFAULTS: radius=1, edge=40.0, support=0, fill=None -- a pure edge-preserving 3 x 3
+        median) | a dict with any of the keys radius (1 | 2), edge (None | millimetres >= 0), support (a pixel with fewer neighbours
+        within `edge` becomes 0) and fill (None | a zero pixel with at least that many valid neighbours takes their lower median) over
+        those defaults (statement: awr_amd.detect.denoise).  The frames are uploaded into a raw buffer of max_batch rows
+        next to the frame store and ONE awr_frames_denoise launch writes the filtered frames into the store's rows [0, nb) before
+        anything else runs: the seeds, given centres, the tracker, hands, isolate, palm, views and the crop all read the filtered
+        frames, so the option combines with every other one and a prediction equals the plain predictor's on
+        awr_amd.detect.denoise of each frame, bit for bit.  After a call raw_frames (nb, fh, fw) uint16 is a view of the raw buffer
+        and denoise_status (nb,) int32 the launch's codes -- device tensors, nothing synchronised.  The defaults are engineering
+        choices (40 mm is the edge 4.29 measured on procedural composites), UNMEASURED on real frames."""
+        if denoise is not None:
+            self.denoise = D.check_denoise_option(denoise)
         if isinstance(hands, bool) or not isinstance(hands, int):
             raise TypeError("hands is an int in [1, %d], not %r" % (D.MAX_HANDS, hands))
         K, self.reach, _, self.min_pixels = D._check_hands(hands, reach, 0.0, min_pixels)
@@ -235,6 +249,11 @@ class Predictor:
         self._all_frames = torch.empty((self._nframes, self.fh, self.fw), dtype=torch.uint16, device=dev)
         self._all_frames.view(torch.int16).zero_()
         self._frames = self._all_frames[:B]
+        if self.denoise is not None:
+            # the frames as they arrive; the store's rows [0, B) then hold the filtered ones
+            self._raw = torch.empty((B, self.fh, self.fw), dtype=torch.uint16, device=dev)
+            self._denoise_status = torch.empty(B, dtype=torch.int32, device=dev)
+            self.raw_frames = self.denoise_status = None
         self._stage = torch.empty((B, self.fh, self.fw), dtype=torch.uint16).pin_memory()
         self._stage_free = None                  # event: the last upload from the staging buffer has been issued and has finished
         self._store = types.SimpleNamespace(data=self._all_frames, ftype=0, fh=self.fh, fw=self.fw, n=self._nframes)
@@ -437,6 +456,14 @@ class Predictor:
             c.fields = torch.empty((3, F, J), dtype=torch.float32, device=dev)
         return c
 
+    def _frames_denoise(self, nb):
+        """rows [0, nb) of the raw buffer -> rows [0, nb) of the frame store, filtered"""
+        o = self.denoise
+        L.call("awr_frames_denoise", self._raw.data_ptr(), 0, self.B, self.fh, self.fw, self._idx.data_ptr(), nb, o["radius"],
+               float("inf") if o["edge"] is None else o["edge"], o["support"], 0 if o["fill"] is None else o["fill"], self._frames.data_ptr(),
+               self._denoise_status.data_ptr(), L.stream())
+        self.raw_frames, self.denoise_status = self._raw[:nb], self._denoise_status[:nb]
+
     def _detect(self, n, mode, seed, centers, status, frame):
         L.call("awr_detect", self._frames.data_ptr(), 0, self._nframes, self.fh, self.fw, frame.data_ptr(), n, mode, L.ptr(seed), self.depth_range[0],
                self.depth_range[1], self.slab, self._cube.data_ptr(), 0, self.paras[0], self.paras[1], self.iters, 0, self._scratch.data_ptr(),
@@ -556,7 +583,7 @@ class Predictor:
             self._views_fuse(c)
 
     def _upload(self, frames):
-        """(nb, fh, fw) uint16 -> rows [0, nb) of the frame store, without blocking"""
+        """(nb, fh, fw) uint16 -> rows [0, nb) of the frame store (with denoise: of the raw buffer), without blocking"""
         if isinstance(frames, np.ndarray):
             if frames.dtype != np.uint16:
                 raise L.AwrError("frames must be uint16 millimetres (the sensor format; it makes the detector's sums exact), not %s" % frames.dtype)
@@ -576,7 +603,7 @@ class Predictor:
                 self._stage_free.synchronize()
             self._stage[:nb].copy_(frames)
             frames = self._stage[:nb]
-        self._frames[:nb].copy_(frames, non_blocking=True)
+        (self._frames if self.denoise is None else self._raw)[:nb].copy_(frames, non_blocking=True)
         if staged:
             self._stage_free = torch.cuda.Event()
             self._stage_free.record()
@@ -611,6 +638,8 @@ class Predictor:
         nv = nb if n_valid is None else int(n_valid)
         if not 0 < nv <= nb:
             raise L.AwrError("n_valid = %d is outside [1, %d]" % (nv, nb))
+        if self.denoise is not None:
+            self._frames_denoise(nb)          # (in front of the seeds, given centres and the tracker alike: every stage reads the filtered frames)
         # the seeds: given centres, the K nearest components, or the configured seed mode
         given = centers_uvd is not None
         mode, seed = (D.SEED_GIVEN, self._seed) if given or K > 1 else (D.SEEDS[self.seed], None)

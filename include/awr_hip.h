@@ -1020,6 +1020,39 @@ int awr_hands_isolate(const void* frames, int frame_type, int64_t n_frames, int 
                       const int* labels /* B,fh,fw */, const int* info /* K,B,4 */, void* out /* K*B,fh,fw uint16 */, int* status /* B */,
                       void* stream);
 
+/* Edge-preserving depth pre-filter (csrc/awr_denoise.hip; the numpy statement is awr_amd/detect.py denoise, results are
+ * bit-identical to it).  Output row b of `out` (B rows in the FrameStore layout) is the filtered frame frame[b].  The rule:
+ *
+ * Every output pixel is a function of the INPUT frame alone. It is a single pass: not iterated, not in place.
+ * Definitions for pixel p with depth d_p:
+ *   - W is the set of in-frame pixels of the (2 * radius + 1)^2 window around p, without p itself.
+ *   - elim = 65535 for edge=None, else floor(min(edge, 65535)). This is awr_frame.h's depth_floor, the integer form 4.29 already uses.
+ *   - A pixel is valid when its depth is not 0.
+ *   - The lower median of n values is element (n - 1) // 2 of the ascending sort. It is a value that occurs in the window, never an
+ *     average.
+ * Output:
+ *   - If d_p != 0: let S = { q in W : d_q != 0 and |d_q - d_p| <= elim }.
+ *       - If |S| < support the output is 0. This removes a flying pixel or speckle.
+ *       - Otherwise the output is the lower median of S and p together, which is element |S| // 2 of its sort.
+ *   - If d_p == 0: let V = { q in W : d_q != 0 }.
+ *       - If fill is given and |V| >= fill, the output is the lower median of V.
+ *       - Otherwise the output is 0.
+ * Out-of-frame positions and zero pixels are indistinguishable under this rule, because both thresholds are absolute counts. The frame
+ * behaves as if surrounded by zeros, and the kernel may stage its halo that way.
+ *
+ * Here edge = +infinity is edge=None (no depth test) and fill = 0 is fill=None (no filling).  status (B): AWR_DET_OK, or
+ * AWR_DET_BAD_FRAME where frame[b] is outside [0, n_frames): that row is a zero frame and nothing is read.
+ *   radius 1 or 2; edge >= 0 (NaN and negative values are refused); support in [0, (2 radius + 1)^2 - 1]; fill in [0, the same];
+ *   B in [1, AWR_DET_MAX_BATCH], fh, fw in [1, 16384]; only uint16 frames; `out` must not overlap the n_frames rows of the frame store
+ *   (the pass is not in place): anything else returns AWR_ERR_ARG with a message that names the entry point and the value, before any
+ *   launch.
+ * ONE launch on `stream`: a workgroup of 256 threads per 64 x 16 tile and batch row stages the tile and its halo in LDS as uint16, a
+ * thread filters four pixels of a row and writes them as one 8-byte store (fw a multiple of 4 and both bases 8-byte aligned; otherwise
+ * 2-byte loads and stores do the same).  The median is selected bit by bit from counts of the window's keys, integers only.  No atomics,
+ * no floating-point arithmetic on a depth, nothing synchronises. */
+int awr_frames_denoise(const void* frames, int frame_type, int64_t n_frames, int fh, int fw, const int64_t* frame, int B, int radius,
+                       double edge, int support, int fill, void* out /* B,fh,fw uint16 */, int* status /* B */, void* stream);
+
 /* Joints -> the next crop centre, per frame, with a gate (the numpy statement is awr_amd/detect.py joints_center,
  * results are bit-identical to it):
  *   xyz (B, J, 3) camera mm, as awr_joints_unproject writes xyz_out; center_uvd (B, 3) doubles, the centres this pass was cropped at;

@@ -38,6 +38,10 @@ remain one component and one hand unless --edge-mm separates them; UNMEASURED on
 (awr_detect_hands_edge): a hand held in front of another one becomes a component of its own.  Hands that touch in depth
 stay one hand, and a rear hand that the front one cuts into pieces gives one candidate per piece of --min-pixels or more
 (profiles/hands_overlap.txt).  There is no default: the right E depends on the sensor's noise, UNMEASURED on real frames.
+--denoise [RADIUS,EDGE,SUPPORT,FILL] filters every frame on the device before anything else reads it (awr_frames_denoise):
+per pixel the lower median of the window's valid depths within EDGE millimetres of its own; a pixel with fewer than SUPPORT such
+neighbours becomes 0; a zero pixel with at least FILL valid neighbours takes their lower median.  Without a value: 1,40,0,none (a 3 x 3
+edge-preserving median); EDGE and FILL may be "none".  Combines with every other option; the defaults are UNMEASURED on real frames.
 --ema predicts with the checkpoint's averaged weights ("model_ema", written by a run with config.ema_decay) instead of "model".
 `--set` overrides config entries as train.py does (img_size, kernel_size, cube, batch_size, jt_num, downsample, winograd ...)."""
 import argparse
@@ -72,8 +76,26 @@ def parse_args(argv=None):
     ap.add_argument("--edge-mm", type=float, default=None, metavar="E", help="with --hands: join neighbouring foreground pixels only within E mm of depth, so a hand in front of another one splits off")
     ap.add_argument("--identity", nargs="?", const="", default=None, metavar="GATE_MM,MERGE_MM,MAX_MISS",
                     help="with --hands: keep each hand in its slot across frames (the file is one sequence); optionally the gate, the merge distance and the misses allowed")
+    ap.add_argument("--denoise", nargs="?", const="", default=None, metavar="RADIUS,EDGE,SUPPORT,FILL",
+                    help="filter every frame on the device first: edge-preserving median, speckle removal, hole filling (default 1,40,0,none)")
     ap.add_argument("--ema", action="store_true", help="load the checkpoint's \"model_ema\" (the EMA of the weights) instead of \"model\"")
     return ap.parse_args(argv)
+
+
+def denoise_config(args):
+    """--denoise -> what Predictor(denoise=...) takes, or None"""
+    if args.denoise is None:
+        return None
+    if not args.denoise:
+        return True
+    vals = [v.strip().lower() for v in args.denoise.split(",")]
+    try:
+        if len(vals) != 4:
+            raise ValueError
+        return dict(radius=int(vals[0]), edge=None if vals[1] == "none" else float(vals[1]), support=int(vals[2]),
+                    fill=None if vals[3] == "none" else int(vals[3]))
+    except ValueError:
+        raise SystemExit("--denoise takes RADIUS,EDGE,SUPPORT,FILL (an int, a number or none, an int, an int or none), not %r" % args.denoise)
 
 
 def smooth_config(args):
@@ -119,6 +141,7 @@ def main(argv=None):
     args = parse_args(argv)
     smooth = smooth_config(args)
     identity = identity_config(args)
+    denoise = denoise_config(args)
     if args.identity and identity is None:
         raise SystemExit("--identity takes GATE_MM,MERGE_MM,MAX_MISS (two numbers and an int), not %r" % args.identity)
 
@@ -157,7 +180,7 @@ def main(argv=None):
     pred = awr_amd.Predictor(net.cuda(), cfg.img_size, cfg.kernel_size, cube=cfg.cube, max_batch=bs, frame_shape=frames.shape[1:],
                              winograd=cfg.winograd, parity=cfg.parity_infer, confidence=args.confidence,
                              recenter=args.recenter, track=args.track, views=views, fuse=args.fuse, palm=args.palm,
-                             smooth=smooth, identity=identity, **hands_kw)
+                             smooth=smooth, identity=identity, denoise=denoise, **hands_kw)
     hands = {"n_hands": [], "hand_status": [], "hand_info": []}
     if identity is not None:
         hands.update(hand_id=[], hand_code=[])
