@@ -1,11 +1,14 @@
 """Hand detection from a raw depth frame (csrc/awr_detect.hip; include/awr_hip.h "Hand detection on the device").
 
-Two things live here:
+What lives here: the numpy statements the kernels are tested against bit for bit, one group per entry point, and behind them thin
+operator-level wrappers over the entry points for tests and tools.
 
-  * the numpy restatement -- `center_of_mass`, `detect`, `sample_blocks` -- written to the definition in the header.  It is the
-    yardstick the kernels are tested against bit for bit, and a usable host fallback for a machine without a GPU;
-  * thin operator-level wrappers over the entry points (`detect_device`, `samples_device`, `unproject_device`, `joints_center_device`,
-    `select_device`) for tests and tools.  `awr_amd.predictor.Predictor` is the product path.
+  * the numpy restatement of the detector -- `center_of_mass`, `detect`, `sample_blocks` -- written to the definition in the header.  It is
+    the yardstick of awr_detect and awr_detect_samples, and a usable host fallback for a machine without a GPU;
+  * the wrappers (`detect_device`, `palm_device`, `hands_device`, `isolate_device`, `denoise_device`, `samples_device`, `unproject_device`,
+    `joints_center_device`, `select_device`, `view_centers_device`, `view_rotate_device`, `fuse_views_device`): they validate, allocate and
+    launch through `awr_amd.detect_calls`, where each entry point's argument list is stated once -- the list `awr_amd.predictor.Predictor`,
+    the product path, launches through as well;
   * `joints_center` and `select`: the statements of awr_joints_center (predicted joints -> the next crop centre, with a gate) and
     awr_centers_select (a tracked centre where it is usable, the detector's otherwise); DESIGN.md 4.19.
   * `palm_center` and `distance_transform`: the statement of awr_detect_palm (csrc/awr_palm.hip) -- a detector centre ->
@@ -746,6 +749,11 @@ def _f64(x, dev):
     return torch.from_numpy(np.ascontiguousarray(x, dtype=np.float64)).to(dev)
 
 
+def _source(store):
+    """A FrameStore-like object's five parts, as the entry points take a frame source."""
+    return store.data.data_ptr(), store.ftype, store.data.shape[0], store.fh, store.fw
+
+
 def _frame_index(frame_idx, dev):
     """The frame of every batch row as the entry points read it: a device int64 tensor (one handed in is used as it is)."""
     import torch
@@ -757,7 +765,7 @@ def detect_device(store, frame_idx, seed="nearest", centers=None, cube=(300, 300
     """awr_detect on a nyu_device.FrameStore-like object (.data (n, fh, fw) uint16 on the device, .ftype, .fh, .fw): -> (centres (B, 3) float64,
     status (B,) int32) on the device, nothing synchronised."""
     import torch
-    from . import _lib as L
+    from . import _lib as L, detect_calls as DC
     dev = store.data.device
     idx = _frame_index(frame_idx, dev)
     B = int(idx.shape[0])
@@ -768,9 +776,8 @@ def detect_device(store, frame_idx, seed="nearest", centers=None, cube=(300, 300
     scratch = L.scratch("awr_detect_scratch", B, dtype=torch.int64, device=dev)
     out = torch.empty((B, 3), dtype=torch.float64, device=dev)
     status = torch.empty(B, dtype=torch.int32, device=dev)
-    L.call("awr_detect", store.data.data_ptr(), store.ftype, int(store.data.shape[0]), store.fh, store.fw, idx.data_ptr(), B, SEEDS[seed],
-           L.ptr(seed_t), float(depth_range[0]), float(depth_range[1]), float(slab), cb.data_ptr(), 3 if cb.dim() == 2 else 0,
-           float(paras[0]), float(paras[1]), int(iters), int(parts), scratch.data_ptr(), out.data_ptr(), status.data_ptr(), L.stream())
+    DC.awr_detect(*_source(store), idx.data_ptr(), B, seed, L.ptr(seed_t), depth_range, slab, cb.data_ptr(), cb.dim() == 2, paras, iters, parts,
+                  scratch.data_ptr(), out.data_ptr(), status.data_ptr())
     return out, status
 
 
@@ -781,8 +788,8 @@ def palm_device(store, frame_idx, centers, status, cube=(300, 300, 300), paras=N
     tensors to write into (they may be the inputs); info: True (allocated), False (NULL) or a tensor; scratch: an int32 tensor of at least
     awr_detect_palm_scratch(B, fh, fw) bytes."""
     import torch
-    from . import _lib as L
-    search, (tau0, tau1), (rho0, rho1) = check_palm(search, tau, rho2)
+    from . import _lib as L, detect_calls as DC
+    search, tau, rho2 = check_palm(search, tau, rho2)
     dev = store.data.device
     idx = _frame_index(frame_idx, dev)
     B = int(idx.shape[0])
@@ -795,9 +802,8 @@ def palm_device(store, frame_idx, centers, status, cube=(300, 300, 300), paras=N
         info = torch.empty((B, 4), dtype=torch.int32, device=dev)
     elif info is False:
         info = None
-    L.call("awr_detect_palm", store.data.data_ptr(), store.ftype, int(store.data.shape[0]), store.fh, store.fw, idx.data_ptr(), B, L.ptr(centers),
-           L.ptr(status), float(depth_range[0]), float(depth_range[1]), cb.data_ptr(), 3 if cb.dim() == 2 else 0, float(paras[0]),
-           float(paras[1]), search, tau0, tau1, rho0, rho1, scratch.data_ptr(), L.ptr(center_out), L.ptr(status_out), L.ptr(info), L.stream())
+    DC.awr_detect_palm(*_source(store), idx.data_ptr(), B, L.ptr(centers), L.ptr(status), depth_range, cb.data_ptr(), cb.dim() == 2, paras, search,
+                       tau, rho2, scratch.data_ptr(), L.ptr(center_out), L.ptr(status_out), L.ptr(info))
     return center_out, status_out, info
 
 
@@ -808,7 +814,7 @@ def hands_device(store, frame_idx, hands, depth_range=DEPTH_RANGE, reach=REACH, 
     a tensor; scratch: an int64 tensor of at least awr_detect_hands_scratch(B, fh, fw) bytes.  edge: None issues awr_detect_hands,
     anything else awr_detect_hands_edge (a type that is no number raises here; a value the entry point refuses gets its message there)."""
     import torch
-    from . import _lib as L
+    from . import _lib as L, detect_calls as DC
     edge = _check_edge(edge, value=False)
     dev = store.data.device
     idx = _frame_index(frame_idx, dev)
@@ -824,14 +830,8 @@ def hands_device(store, frame_idx, hands, depth_range=DEPTH_RANGE, reach=REACH, 
         labels = torch.empty((B, store.fh, store.fw), dtype=torch.int32, device=dev)
     elif labels is False:
         labels = None
-    head = (store.data.data_ptr(), store.ftype, int(store.data.shape[0]), store.fh, store.fw, idx.data_ptr(), B, K, float(depth_range[0]),
-            float(depth_range[1]), float(reach))
-    tail = (float(slab), int(min_pixels), scratch.data_ptr(), L.ptr(labels), centers.data_ptr(), status.data_ptr(), info.data_ptr(),
-            count.data_ptr(), L.stream())
-    if edge is None:
-        L.call("awr_detect_hands", *head, *tail)
-    else:
-        L.call("awr_detect_hands_edge", *head, edge, *tail)
+    DC.awr_detect_hands(*_source(store), idx.data_ptr(), B, K, depth_range, reach, edge, slab, min_pixels, scratch.data_ptr(), L.ptr(labels),
+                        centers.data_ptr(), status.data_ptr(), info.data_ptr(), count.data_ptr())
     return centers, status, info, count, labels
 
 
@@ -840,7 +840,7 @@ def isolate_device(store, frame_idx, labels, roots=None, info=None, out=None):
     (K, B) ints (negative: an EMPTY slot), on the device or numpy -> (out (K * B, fh, fw) uint16, row k * B + b, status (B,) int32) on the
     device, nothing synchronised.  out: a tensor to write into."""
     import torch
-    from . import _lib as L
+    from . import _lib as L, detect_calls as DC
     dev = store.data.device
     idx = _frame_index(frame_idx, dev)
     B = int(idx.shape[0])
@@ -858,8 +858,7 @@ def isolate_device(store, frame_idx, labels, roots=None, info=None, out=None):
     if out is None:
         out = torch.empty((max(K, 1) * B, store.fh, store.fw), dtype=torch.uint16, device=dev)
     status = torch.empty(B, dtype=torch.int32, device=dev)
-    L.call("awr_hands_isolate", store.data.data_ptr(), store.ftype, int(store.data.shape[0]), store.fh, store.fw, idx.data_ptr(), B, K,
-           L.ptr(labels), L.ptr(info), L.ptr(out), status.data_ptr(), L.stream())
+    DC.awr_hands_isolate(*_source(store), idx.data_ptr(), B, K, L.ptr(labels), L.ptr(info), L.ptr(out), status.data_ptr())
     return out, status
 
 
@@ -868,7 +867,7 @@ def denoise_device(store, frame_idx, radius=1, edge=None, support=0, fill=None, 
     int32) on the device, nothing synchronised.  out: a tensor to write into; it must not overlap the store.  The types are checked here
     (edge as hands_device does); a value the entry point refuses gets its message from there."""
     import torch
-    from . import _lib as L
+    from . import _lib as L, detect_calls as DC
     radius, edge, support, fill = _check_denoise(radius, edge, support, fill, value=False)
     dev = store.data.device
     idx = _frame_index(frame_idx, dev)
@@ -876,8 +875,7 @@ def denoise_device(store, frame_idx, radius=1, edge=None, support=0, fill=None, 
     if out is None:
         out = torch.empty((B, store.fh, store.fw), dtype=torch.uint16, device=dev)
     status = torch.empty(B, dtype=torch.int32, device=dev)
-    L.call("awr_frames_denoise", store.data.data_ptr(), store.ftype, int(store.data.shape[0]), store.fh, store.fw, idx.data_ptr(), B, radius,
-           float("inf") if edge is None else edge, support, 0 if fill is None else fill, L.ptr(out), status.data_ptr(), L.stream())
+    DC.awr_frames_denoise(*_source(store), idx.data_ptr(), B, radius, edge, support, fill, L.ptr(out), status.data_ptr())
     return out, status
 
 
@@ -885,7 +883,7 @@ def samples_device(centers, cube, dsize, frame_idx, n_frames, frame_shape, paras
     """awr_detect_samples: centres (B, 3) float64 on the device -> (blocks (B, BLOCK_BYTES) uint8, M (B, 3, 3), center_xyz (B, 3), cube (B, 3)
     float32, status (B,) int32) on the device."""
     import torch
-    from . import _lib as L
+    from . import _lib as L, detect_calls as DC
     dev = centers.device
     B = int(centers.shape[0])
     idx = _frame_index(frame_idx, dev)
@@ -895,23 +893,22 @@ def samples_device(centers, cube, dsize, frame_idx, n_frames, frame_shape, paras
     cxyz = torch.empty((B, 3), dtype=torch.float32, device=dev)
     cube32 = torch.empty((B, 3), dtype=torch.float32, device=dev)
     status = torch.zeros(B, dtype=torch.int32, device=dev) if status is None else status
-    L.call("awr_detect_samples", L.ptr(centers), cb.data_ptr(), 3 if cb.dim() == 2 else 0, int(n_frames), idx.data_ptr(), B, int(dsize),
-           int(frame_shape[0]), int(frame_shape[1]), float(paras[0]), float(paras[1]), float(paras[2]), float(paras[3]), int(flip),
-           blocks.data_ptr(), L.ptr(M), L.ptr(cxyz), L.ptr(cube32), status.data_ptr(), L.stream())
+    DC.awr_detect_samples(L.ptr(centers), cb.data_ptr(), cb.dim() == 2, n_frames, idx.data_ptr(), B, dsize, frame_shape[0], frame_shape[1], paras, flip,
+                          blocks.data_ptr(), L.ptr(M), L.ptr(cxyz), L.ptr(cube32), status.data_ptr())
     return blocks, M, cxyz, cube32, status
 
 
 def unproject_device(jt_pred, center_xyz, M, cube, img_size, paras=ND.PARAS, flip=-1, n_valid=None, uvd_out=None, xyz_out=None, status=None):
     """awr_joints_unproject: -> (uvd (B, J, 3), xyz (B, J, 3), status (B,)); rows >= n_valid of the outputs are left as they are."""
     import torch
-    from . import _lib as L
+    from . import _lib as L, detect_calls as DC
     B, J = int(jt_pred.shape[0]), int(jt_pred.shape[1])
     n = B if n_valid is None else int(n_valid)
     uvd = torch.empty_like(jt_pred) if uvd_out is None else uvd_out
     xyz = torch.empty_like(jt_pred) if xyz_out is None else xyz_out
     status = torch.zeros(B, dtype=torch.int32, device=jt_pred.device) if status is None else status
-    L.call("awr_joints_unproject", L.ptr(jt_pred), L.ptr(center_xyz), L.ptr(M), L.ptr(cube), B, J, n, float(img_size), float(paras[0]),
-           float(paras[1]), float(paras[2]), float(paras[3]), int(flip), L.ptr(uvd), L.ptr(xyz), status.data_ptr(), L.stream())
+    DC.awr_joints_unproject(L.ptr(jt_pred), L.ptr(center_xyz), L.ptr(M), L.ptr(cube), B, J, n, img_size, paras, flip, L.ptr(uvd), L.ptr(xyz),
+                            status.data_ptr())
     return uvd, xyz, status
 
 
@@ -920,7 +917,7 @@ def joints_center_device(xyz, center_uvd, center_xyz, cube, status, ustatus, par
     """awr_joints_center on device tensors: -> (center_out (B, 3) float64, next (B, 3) float64, code (B,) int32); rows >= n_valid of the
     outputs are left as they are.  joints: a device int32 tensor, a list of indices or None (all joints); center_out may be center_uvd."""
     import torch
-    from . import _lib as L
+    from . import _lib as L, detect_calls as DC
     B, J = int(xyz.shape[0]), int(xyz.shape[1])
     dev = xyz.device
     n = B if n_valid is None else int(n_valid)
@@ -929,22 +926,21 @@ def joints_center_device(xyz, center_uvd, center_xyz, cube, status, ustatus, par
     center_out = torch.empty((B, 3), dtype=torch.float64, device=dev) if center_out is None else center_out
     next_out = torch.empty((B, 3), dtype=torch.float64, device=dev) if next_out is None else next_out
     code = torch.empty(B, dtype=torch.int32, device=dev) if code is None else code
-    L.call("awr_joints_center", L.ptr(xyz), L.ptr(center_uvd), L.ptr(center_xyz), L.ptr(cube), L.ptr(status), L.ptr(ustatus), B, J, n,
-           L.ptr(joints), 0 if joints is None else int(joints.numel()), float(paras[0]), float(paras[1]), float(paras[2]), float(paras[3]),
-           int(flip), float(depth_range[0]), float(depth_range[1]), float(max_shift), L.ptr(center_out), L.ptr(next_out), L.ptr(code), L.stream())
+    DC.awr_joints_center(L.ptr(xyz), L.ptr(center_uvd), L.ptr(center_xyz), L.ptr(cube), L.ptr(status), L.ptr(ustatus), B, J, n,
+                         None if joints is None else (L.ptr(joints), joints.numel()), paras, flip, depth_range, max_shift, L.ptr(center_out),
+                         L.ptr(next_out), L.ptr(code))
     return center_out, next_out, code
 
 
 def select_device(a_center, a_status, b_center, b_status):
     """awr_centers_select on device tensors: -> (center (B, 3) float64, status (B,) int32, which (B,) int32)."""
     import torch
-    from . import _lib as L
+    from . import _lib as L, detect_calls as DC
     B, dev = int(a_center.shape[0]), a_center.device
     out = torch.empty((B, 3), dtype=torch.float64, device=dev)
     status = torch.empty(B, dtype=torch.int32, device=dev)
     which = torch.empty(B, dtype=torch.int32, device=dev)
-    L.call("awr_centers_select", L.ptr(a_center), L.ptr(a_status), L.ptr(b_center), L.ptr(b_status), B, L.ptr(out), L.ptr(status),
-           L.ptr(which), L.stream())
+    DC.awr_centers_select(L.ptr(a_center), L.ptr(a_status), L.ptr(b_center), L.ptr(b_status), B, L.ptr(out), L.ptr(status), L.ptr(which))
     return out, status, which
 
 
@@ -953,7 +949,7 @@ def view_centers_device(centers, status, cube, table, B=None, n_valid=None, para
     float64 -> (centres (V * B, 3) float64, cubes (V * B, 3) float64, frame (V * B,) int64, status (V * B,) int32); out: these four, to write
     into (rows with b >= n_valid are left as they are)."""
     import torch
-    from . import _lib as L
+    from . import _lib as L, detect_calls as DC
     dev = centers.device
     B = int(centers.shape[0]) if B is None else int(B)
     n = B if n_valid is None else int(n_valid)
@@ -963,8 +959,8 @@ def view_centers_device(centers, status, cube, table, B=None, n_valid=None, para
     if out is None:
         out = (torch.empty((V * B, 3), dtype=torch.float64, device=dev), torch.empty((V * B, 3), dtype=torch.float64, device=dev),
                torch.empty(V * B, dtype=torch.int64, device=dev), torch.empty(V * B, dtype=torch.int32, device=dev))
-    L.call("awr_view_centers", L.ptr(centers), L.ptr(status), L.ptr(cb), 3 if cb.dim() == 2 else 0, L.ptr(table), V, B, n, float(paras[0]),
-           float(paras[1]), float(paras[2]), float(paras[3]), int(flip), L.ptr(out[0]), L.ptr(out[1]), L.ptr(out[2]), L.ptr(out[3]), L.stream())
+    DC.awr_view_centers(L.ptr(centers), L.ptr(status), L.ptr(cb), cb.dim() == 2, L.ptr(table), V, B, n, paras, flip, L.ptr(out[0]), L.ptr(out[1]),
+                        L.ptr(out[2]), L.ptr(out[3]))
     return out
 
 
@@ -972,11 +968,11 @@ def view_rotate_device(blocks, M, status, table, n_valid=None):
     """awr_view_rotate: blocks (V * B, BLOCK_BYTES) uint8 and M (V * B, 3, 3) float32 are patched in place; status (V * B,) int32 the rows' codes
     after awr_detect_samples."""
     import torch
-    from . import _lib as L
+    from . import _lib as L, detect_calls as DC
     table = table if isinstance(table, torch.Tensor) else _f64(table, M.device)
     V = int(table.shape[0])
     B = int(M.shape[0]) // V
-    L.call("awr_view_rotate", L.ptr(blocks), L.ptr(M), L.ptr(status), L.ptr(table), V, B, B if n_valid is None else int(n_valid), L.stream())
+    DC.awr_view_rotate(L.ptr(blocks), L.ptr(M), L.ptr(status), L.ptr(table), V, B, B if n_valid is None else n_valid)
     return blocks, M
 
 
@@ -984,13 +980,12 @@ def fuse_views_device(xyz, status, ustatus, weights, mode, paras=ND.PARAS, flip=
     """awr_views_fuse: xyz (V, B, J, 3) float32, status / ustatus (V, B) or (V * B,) int32, weights (V, B, J) float32 or None ->
     (xyz (B, J, 3), uvd (B, J, 3), view_spread_mm (B, J) float32, views_used (B, J) int32); rows >= n_valid are left as they are."""
     import torch
-    from . import _lib as L
+    from . import _lib as L, detect_calls as DC
     V, B, J = (int(x) for x in xyz.shape[:3])
     dev = xyz.device
     if out is None:
         out = (torch.empty((B, J, 3), dtype=torch.float32, device=dev), torch.empty((B, J, 3), dtype=torch.float32, device=dev),
                torch.empty((B, J), dtype=torch.float32, device=dev), torch.empty((B, J), dtype=torch.int32, device=dev))
-    L.call("awr_views_fuse", L.ptr(xyz), L.ptr(status), L.ptr(ustatus), L.ptr(weights), FUSE_MODES[mode] if mode in FUSE_MODES else int(mode), V, B, J,
-           B if n_valid is None else int(n_valid), float(paras[0]), float(paras[1]), float(paras[2]), float(paras[3]), int(flip),
-           L.ptr(out[0]), L.ptr(out[1]), L.ptr(out[2]), L.ptr(out[3]), L.stream())
+    DC.awr_views_fuse(L.ptr(xyz), L.ptr(status), L.ptr(ustatus), L.ptr(weights), mode, V, B, J, B if n_valid is None else n_valid, paras, flip,
+                      L.ptr(out[0]), L.ptr(out[1]), L.ptr(out[2]), L.ptr(out[3]))
     return out

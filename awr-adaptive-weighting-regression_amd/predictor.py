@@ -42,6 +42,7 @@ import torch
 
 from . import _lib as L
 from . import detect as D
+from . import detect_calls as DC
 from . import nyu_data as ND
 from . import track as T
 
@@ -459,85 +460,74 @@ class Predictor:
     def _frames_denoise(self, nb):
         """rows [0, nb) of the raw buffer -> rows [0, nb) of the frame store, filtered"""
         o = self.denoise
-        L.call("awr_frames_denoise", self._raw.data_ptr(), 0, self.B, self.fh, self.fw, self._idx.data_ptr(), nb, o["radius"],
-               float("inf") if o["edge"] is None else o["edge"], o["support"], 0 if o["fill"] is None else o["fill"], self._frames.data_ptr(),
-               self._denoise_status.data_ptr(), L.stream())
+        DC.awr_frames_denoise(self._raw.data_ptr(), 0, self.B, self.fh, self.fw, self._idx.data_ptr(), nb, o["radius"], o["edge"], o["support"],
+                              o["fill"], self._frames.data_ptr(), self._denoise_status.data_ptr())
         self.raw_frames, self.denoise_status = self._raw[:nb], self._denoise_status[:nb]
 
-    def _detect(self, n, mode, seed, centers, status, frame):
-        L.call("awr_detect", self._frames.data_ptr(), 0, self._nframes, self.fh, self.fw, frame.data_ptr(), n, mode, L.ptr(seed), self.depth_range[0],
-               self.depth_range[1], self.slab, self._cube.data_ptr(), 0, self.paras[0], self.paras[1], self.iters, 0, self._scratch.data_ptr(),
-               centers.data_ptr(), status.data_ptr(), L.stream())
+    def _detect(self, n, seed, seed_centers, centers, status, frame):
+        DC.awr_detect(self._frames.data_ptr(), 0, self._nframes, self.fh, self.fw, frame.data_ptr(), n, seed, L.ptr(seed_centers), self.depth_range,
+                      self.slab, self._cube.data_ptr(), False, self.paras, self.iters, 0, self._scratch.data_ptr(), centers.data_ptr(), status.data_ptr())
 
     def _detect_palm(self, n, nb, centers, status, frame):
         """in place: a frame that is not OK keeps its centre and status"""
-        L.call("awr_detect_palm", self._frames.data_ptr(), 0, self._nframes, self.fh, self.fw, frame.data_ptr(), n, centers.data_ptr(),
-               status.data_ptr(), self.depth_range[0], self.depth_range[1], self._cube.data_ptr(), 0, self.paras[0], self.paras[1], self.palm_search,
-               D.PALM_TAU[0], D.PALM_TAU[1], D.PALM_RHO2[0], D.PALM_RHO2[1], self._palm_scratch.data_ptr(), centers.data_ptr(),
-               status.data_ptr(), self._palm_info.data_ptr(), L.stream())
+        DC.awr_detect_palm(self._frames.data_ptr(), 0, self._nframes, self.fh, self.fw, frame.data_ptr(), n, centers.data_ptr(), status.data_ptr(),
+                           self.depth_range, self._cube.data_ptr(), False, self.paras, self.palm_search, D.PALM_TAU, D.PALM_RHO2,
+                           self._palm_scratch.data_ptr(), centers.data_ptr(), status.data_ptr(), self._palm_info.data_ptr())
         self.palm_info = self._rows(self._palm_info, nb)
 
     def _detect_hands(self, nb):
         """the K nearest components' seeds of every frame -> self._seed, hand-major"""
-        head = (self._frames.data_ptr(), 0, self.B, self.fh, self.fw, self._idx.data_ptr(), self.B, self.hands, self.depth_range[0],
-                self.depth_range[1], self.reach)
-        tail = (self.slab, self.min_pixels, self._hands_scratch.data_ptr(),
-                self._labels.data_ptr() if self.isolate else None, self._seed.data_ptr(),
-                self._hands_status.data_ptr(), self._hands_info.data_ptr(), self._hands_count.data_ptr(), L.stream())
-        if self.edge_mm is None:
-            L.call("awr_detect_hands", *head, *tail)
-        else:
-            L.call("awr_detect_hands_edge", *head, self.edge_mm, *tail)
+        DC.awr_detect_hands(self._frames.data_ptr(), 0, self.B, self.fh, self.fw, self._idx.data_ptr(), self.B, self.hands, self.depth_range, self.reach,
+                            self.edge_mm, self.slab, self.min_pixels, self._hands_scratch.data_ptr(), self._labels.data_ptr() if self.isolate else None,
+                            self._seed.data_ptr(), self._hands_status.data_ptr(), self._hands_info.data_ptr(), self._hands_count.data_ptr())
         self.hand_info = self._hands_info[:, :nb].transpose(0, 1)
 
     def _hands_isolate(self):
         """the raw frames, their labels and the slots' info rows -> rows [B, B + K * B) of the frame store: a frame per hand, hand-major"""
-        L.call("awr_hands_isolate", self._frames.data_ptr(), 0, self.B, self.fh, self.fw, self._idx.data_ptr(), self.B, self.hands,
-               self._labels.data_ptr(), self._hands_info.data_ptr(), self._all_frames[self.B:].data_ptr(), self._iso_status.data_ptr(), L.stream())
+        DC.awr_hands_isolate(self._frames.data_ptr(), 0, self.B, self.fh, self.fw, self._idx.data_ptr(), self.B, self.hands, self._labels.data_ptr(),
+                             self._hands_info.data_ptr(), self._all_frames[self.B:].data_ptr(), self._iso_status.data_ptr())
 
     def _centers_select(self, n, first, first_status, second, second_status, out, out_status):
         """per row `first` where its status is OK, else `second`"""
-        L.call("awr_centers_select", first.data_ptr(), first_status.data_ptr(), second.data_ptr(), second_status.data_ptr(), n, out.data_ptr(),
-               out_status.data_ptr(), None, L.stream())
+        DC.awr_centers_select(first.data_ptr(), first_status.data_ptr(), second.data_ptr(), second_status.data_ptr(), n, out.data_ptr(),
+                              out_status.data_ptr(), None)
 
     def _hands_assign(self, c):
         """the candidates (and the tracked centres) -> every slot's centre and status, in self._centers / c.status; the state moves on"""
-        cfg, smooth = self.identity, self.smooth is not None
-        L.call("awr_hands_assign", self._id_last.data_ptr(), self._id_ids.data_ptr(), self._id_miss.data_ptr(), self._id_next.data_ptr(),
-               self._cand.data_ptr(), self._cand_status.data_ptr(), self._tcenters.data_ptr() if self.track else None,
-               self._tstatus.data_ptr() if self.track else None, self.hands, self.B, c.nv, cfg.gate_mm, cfg.merge_mm, cfg.max_miss, *self.paras,
-               self.flip, self._filter_state.data_ptr() if smooth else None, self._filter_count.data_ptr() if smooth else None,
-               self.J if smooth else 0, self._centers.data_ptr(), c.status.data_ptr(), L.ptr(c.assigned[0]), L.ptr(c.assigned[1]),
-               L.ptr(c.assigned[2]), c.dropped.data_ptr(), L.stream())
+        smooth = self.smooth is not None
+        DC.awr_hands_assign(self._id_last.data_ptr(), self._id_ids.data_ptr(), self._id_miss.data_ptr(), self._id_next.data_ptr(), self._cand.data_ptr(),
+                            self._cand_status.data_ptr(), self._tcenters.data_ptr() if self.track else None,
+                            self._tstatus.data_ptr() if self.track else None, self.hands, self.B, c.nv, self.identity, self.paras, self.flip,
+                            self._filter_state.data_ptr() if smooth else None, self._filter_count.data_ptr() if smooth else None,
+                            self.J if smooth else 0, self._centers.data_ptr(), c.status.data_ptr(), L.ptr(c.assigned[0]), L.ptr(c.assigned[1]),
+                            L.ptr(c.assigned[2]), c.dropped.data_ptr())
 
-    def _detect_samples(self, n, c, centers, cubes, cube_stride, frame, status):
+    def _detect_samples(self, n, c, centers, cubes, cube_rows, frame, status):
         """centres -> crop blocks, crop matrices, centres in camera space, float cubes"""
-        L.call("awr_detect_samples", centers.data_ptr(), cubes.data_ptr(), cube_stride, self._nframes, frame.data_ptr(), n, self.S, self.fh, self.fw,
-               *self.paras, self.flip, self._blocks.data_ptr(), L.ptr(c.M), L.ptr(c.cxyz), L.ptr(self._cube32), status.data_ptr(), L.stream())
+        DC.awr_detect_samples(centers.data_ptr(), cubes.data_ptr(), cube_rows, self._nframes, frame.data_ptr(), n, self.S, self.fh, self.fw, self.paras,
+                              self.flip, self._blocks.data_ptr(), L.ptr(c.M), L.ptr(c.cxyz), L.ptr(self._cube32), status.data_ptr())
 
     def _joints_unproject(self, n, nv, jt, c):
-        L.call("awr_joints_unproject", L.ptr(jt), L.ptr(c.cxyz), L.ptr(c.M), L.ptr(self._cube32), n, self.J, nv, float(self.S), *self.paras, self.flip,
-               L.ptr(c.uvd), L.ptr(c.xyz), c.ustatus.data_ptr(), L.stream())
+        DC.awr_joints_unproject(L.ptr(jt), L.ptr(c.cxyz), L.ptr(c.M), L.ptr(self._cube32), n, self.J, nv, self.S, self.paras, self.flip, L.ptr(c.uvd),
+                                L.ptr(c.xyz), c.ustatus.data_ptr())
 
     def _view_centers(self, c):
         """the centres -> one centre, cube and frame row per view, and the rows' status"""
-        L.call("awr_view_centers", self._centers.data_ptr(), c.status.data_ptr(), self._cube.data_ptr(), 0, self._vtable.data_ptr(), self.V, self.B,
-               c.nv, *self.paras, self.flip, self._vcenters.data_ptr(), self._vcubes.data_ptr(), self._vframe.data_ptr(), c.vstatus.data_ptr(),
-               L.stream())
+        DC.awr_view_centers(self._centers.data_ptr(), c.status.data_ptr(), self._cube.data_ptr(), False, self._vtable.data_ptr(), self.V, self.B, c.nv,
+                            self.paras, self.flip, self._vcenters.data_ptr(), self._vcubes.data_ptr(), self._vframe.data_ptr(), c.vstatus.data_ptr())
 
     def _view_rotate(self, c):
-        L.call("awr_view_rotate", self._blocks.data_ptr(), L.ptr(c.M), c.vstatus.data_ptr(), self._vtable.data_ptr(), self.V, self.B, c.nv, L.stream())
+        DC.awr_view_rotate(self._blocks.data_ptr(), L.ptr(c.M), c.vstatus.data_ptr(), self._vtable.data_ptr(), self.V, self.B, c.nv)
 
     def _views_fuse(self, c):
-        L.call("awr_views_fuse", L.ptr(c.xyz), c.vstatus.data_ptr(), c.ustatus.data_ptr(), L.ptr(c.weights), D.FUSE_MODES[self.fuse], self.V, self.B,
-               self.J, c.nv, *self.paras, self.flip, L.ptr(c.fxyz), L.ptr(c.fuvd), L.ptr(c.vspread), L.ptr(c.vused), L.stream())
+        DC.awr_views_fuse(L.ptr(c.xyz), c.vstatus.data_ptr(), c.ustatus.data_ptr(), L.ptr(c.weights), self.fuse, self.V, self.B, self.J, c.nv, self.paras,
+                          self.flip, L.ptr(c.fxyz), L.ptr(c.fuvd), L.ptr(c.vspread), L.ptr(c.vused))
 
     def _joints_center(self, c, joints, center_out, next_out, code):
         """the joints' centre per frame row, gated (see __init__): moved rows into center_out, every row's into next_out (NaN: not moved)"""
-        L.call("awr_joints_center", L.ptr(joints), self._centers.data_ptr(), L.ptr(c.cxyz), L.ptr(self._cube32), c.status_j.data_ptr(),
-               c.ustatus.data_ptr(), c.F, self.J, c.fv, L.ptr(self._joints), 0 if self._joints is None else int(self._joints.numel()), *self.paras,
-               self.flip, self.depth_range[0], self.depth_range[1], self.max_shift, center_out.data_ptr(), L.ptr(next_out), code.data_ptr(),
-               L.stream())
+        DC.awr_joints_center(L.ptr(joints), self._centers.data_ptr(), L.ptr(c.cxyz), L.ptr(self._cube32), c.status_j.data_ptr(), c.ustatus.data_ptr(),
+                             c.F, self.J, c.fv, None if self._joints is None else (self._joints.data_ptr(), self._joints.numel()), self.paras, self.flip,
+                             self.depth_range, self.max_shift, center_out.data_ptr(), L.ptr(next_out), code.data_ptr())
 
     def _joints_filter(self, c, dt):
         """awr_joints_filter over the call's joints, one launch per group of max_batch rows (the rows past n_valid of EVERY group keep their
@@ -548,16 +538,15 @@ class Predictor:
             conf = c.weights if c.weights is not None else self.engine.conf[:c.F, :, 0].contiguous()
         out = [torch.empty((c.F, J, 3), dtype=torch.float32, device=dev) for _ in range(3)] + [torch.empty((c.F, J), dtype=torch.int32, device=dev)]
         for o in range(0, c.F, B):
-            L.call("awr_joints_filter", self._filter_state[o:].data_ptr(), self._filter_count[o:].data_ptr(), c.xyz_j[o:].data_ptr(),
-                   c.status_j[o:].data_ptr(), c.ustatus[o:].data_ptr(), None if conf is None else conf[o:].data_ptr(), B, J, c.nv, dt, cfg.min_cutoff,
-                   cfg.beta, cfg.d_cutoff, -1.0 if cfg.gate_mm is None else cfg.gate_mm, cfg.max_coast, T.WEIGHTS[cfg.weight], cfg.conf_floor,
-                   *self.paras, self.flip, out[0][o:].data_ptr(), out[1][o:].data_ptr(), out[2][o:].data_ptr(), out[3][o:].data_ptr(), L.stream())
+            DC.awr_joints_filter(self._filter_state[o:].data_ptr(), self._filter_count[o:].data_ptr(), c.xyz_j[o:].data_ptr(), c.status_j[o:].data_ptr(),
+                                 c.ustatus[o:].data_ptr(), None if conf is None else conf[o:].data_ptr(), B, J, c.nv, dt, cfg, self.paras, self.flip,
+                                 out[0][o:].data_ptr(), out[1][o:].data_ptr(), out[2][o:].data_ptr(), out[3][o:].data_ptr())
         c.filtered = out
 
     def _confidence_fields(self, c):
         """conf, peak, spread_mm of every frame row (with views: view 0's rows are the first of every per-row buffer) -> c.fields"""
-        L.call("awr_confidence_fields", L.ptr(self.engine.conf), L.ptr(self.engine.stat), L.ptr(self._cube32), c.status_j.data_ptr(),
-               c.ustatus.data_ptr(), c.F, self.J, c.fv, L.ptr(c.fields[0]), L.ptr(c.fields[1]), L.ptr(c.fields[2]), L.stream())
+        DC.awr_confidence_fields(L.ptr(self.engine.conf), L.ptr(self.engine.stat), L.ptr(self._cube32), c.status_j.data_ptr(), c.ustatus.data_ptr(),
+                                 c.F, self.J, c.fv, L.ptr(c.fields[0]), L.ptr(c.fields[1]), L.ptr(c.fields[2]))
 
     def _crop_and_predict(self, c):
         """self._centers -> c.xyz / c.uvd (with views: and the fused c.fxyz / c.fuvd): crop, render, the network, un-projection"""
@@ -566,10 +555,10 @@ class Predictor:
             if c.nv < self.B:
                 self._vcenters.fill_(float("nan"))
             self._view_centers(c)
-            self._detect_samples(c.R, c, self._vcenters, self._vcubes, 3, self._vframe, c.vstatus)
+            self._detect_samples(c.R, c, self._vcenters, self._vcubes, True, self._vframe, c.vstatus)
             self._view_rotate(c)
         else:
-            self._detect_samples(c.fv, c, self._centers, self._cube, 0, c.frame, c.status)
+            self._detect_samples(c.fv, c, self._centers, self._cube, False, c.frame, c.status)
         if c.R == self.B:
             self._render(self._blocks[:c.nv], out=self._img[:c.nv])
             if c.nv < self.B:
@@ -642,7 +631,7 @@ class Predictor:
             self._frames_denoise(nb)          # (in front of the seeds, given centres and the tracker alike: every stage reads the filtered frames)
         # the seeds: given centres, the K nearest components, or the configured seed mode
         given = centers_uvd is not None
-        mode, seed = (D.SEED_GIVEN, self._seed) if given or K > 1 else (D.SEEDS[self.seed], None)
+        mode, seed = ("given", self._seed) if given or K > 1 else (self.seed, None)
         if given:
             self._given_centers(centers_uvd, nb)
             self.hand_info = None
@@ -664,7 +653,7 @@ class Predictor:
         cand, cand_status = self._centers, c.status
         if tracked and K == 1:
             cand, cand_status = self._dcenters, self._dstatus
-            self._detect(c.fv, D.SEED_GIVEN, self._track, self._tcenters, self._tstatus, self._idx)          # (one slot: the tracker goes first)
+            self._detect(c.fv, "given", self._track, self._tcenters, self._tstatus, self._idx)          # (one slot: the tracker goes first)
         elif self.identity is not None:
             cand, cand_status = self._cand, self._cand_status
         self._detect(c.fv, mode, seed, cand, cand_status, frame)
@@ -672,7 +661,7 @@ class Predictor:
             self._detect_palm(c.fv, nb, cand, cand_status, frame)
         if tracked and K > 1:
             # (on the RAW frames, also with isolate: which component a tracked centre belongs to is not decided here)
-            self._detect(c.fv, D.SEED_GIVEN, self._track, self._tcenters, self._tstatus, self._idx)
+            self._detect(c.fv, "given", self._track, self._tcenters, self._tstatus, self._idx)
         # combine them: per slot the tracked centre where it holds, else the detector's; with identities the assignment
         if tracked and K == 1:
             self._centers_select(nv, self._tcenters, self._tstatus, cand, cand_status, self._centers, c.status)

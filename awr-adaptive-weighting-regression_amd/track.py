@@ -224,7 +224,7 @@ def filter_step_device(state, count, xyz, status, ustatus, conf, cfg, dt=None, n
     -> (xyz_f, uvd_f, ahead (B, J, 3) float32, code (B, J) int32) device tensors (`out`: these four, to write into); rows >= n_valid are
     left as they are.  Nothing synchronises.  There is no host fall-back: filter_step is the statement for a machine without a GPU."""
     import torch
-    from . import _lib as L
+    from . import _lib as L, detect_calls as DC
     cfg = check_filter(cfg)
     dt = check_dt(1.0 / cfg.fps if dt is None else dt)
     if state.dtype != torch.float64 or state.dim() != 3 or state.shape[2] != 6:
@@ -245,10 +245,8 @@ def filter_step_device(state, count, xyz, status, ustatus, conf, cfg, dt=None, n
     for t, shape, dtype in zip(out, ((B, J, 3),) * 3 + ((B, J),), (torch.float32,) * 3 + (torch.int32,)):
         if tuple(t.shape) != shape or t.dtype != dtype:
             raise L.AwrError("out is (xyz_f, uvd_f, ahead (B, J, 3) float32, code (B, J) int32)")
-    L.call("awr_joints_filter", L.ptr(state), L.ptr(count), L.ptr(xyz), L.ptr(status), L.ptr(ustatus), L.ptr(conf) if weighted else None, B, J,
-           B if n_valid is None else int(n_valid), dt, cfg.min_cutoff, cfg.beta, cfg.d_cutoff, -1.0 if cfg.gate_mm is None else cfg.gate_mm,
-           cfg.max_coast, WEIGHTS[cfg.weight], cfg.conf_floor, float(paras[0]), float(paras[1]), float(paras[2]), float(paras[3]), int(flip),
-           L.ptr(out[0]), L.ptr(out[1]), L.ptr(out[2]), L.ptr(out[3]), L.stream())
+    DC.awr_joints_filter(L.ptr(state), L.ptr(count), L.ptr(xyz), L.ptr(status), L.ptr(ustatus), L.ptr(conf) if weighted else None, B, J,
+                         B if n_valid is None else n_valid, dt, cfg, paras, flip, L.ptr(out[0]), L.ptr(out[1]), L.ptr(out[2]), L.ptr(out[3]))
     return out
 
 
@@ -479,7 +477,7 @@ def assign_step_device(last_uvd, ids, miss, next_id, cand_uvd, cand_status, trk_
     dropped (B,) int32) device tensors (`out`: these six, to write into).  Nothing synchronises.  There is no host fall-back: assign_step is
     the statement for a machine without a GPU."""
     import torch
-    from . import _lib as L
+    from . import _lib as L, detect_calls as DC
     cfg = check_identity(cfg)
     if last_uvd.dtype != torch.float64 or last_uvd.dim() != 3 or last_uvd.shape[2] != 3:
         raise L.AwrError("last_uvd is a (K, B, 3) float64 device tensor")
@@ -509,8 +507,7 @@ def assign_step_device(last_uvd, ids, miss, next_id, cand_uvd, cand_status, trk_
     for t, shape, dtype in zip(out, ((K, B, 3),) + ((K, B),) * 4 + ((B,),), (torch.float64,) + (torch.int32,) * 5):
         if tuple(t.shape) != shape or t.dtype != dtype:
             raise L.AwrError("out is (centers (K, B, 3) float64, status, code, reset, source (K, B) int32, dropped (B,) int32)")
-    L.call("awr_hands_assign", L.ptr(last_uvd), L.ptr(ids), L.ptr(miss), L.ptr(next_id), L.ptr(cand_uvd), L.ptr(cand_status), L.ptr(trk_uvd),
-           L.ptr(trk_status), K, B, B if n_valid is None else int(n_valid), cfg.gate_mm, cfg.merge_mm, cfg.max_miss, float(paras[0]), float(paras[1]),
-           float(paras[2]), float(paras[3]), int(flip), L.ptr(filter_state), L.ptr(filter_count), J, L.ptr(out[0]), L.ptr(out[1]), L.ptr(out[2]),
-           L.ptr(out[3]), L.ptr(out[4]), L.ptr(out[5]), L.stream())
+    DC.awr_hands_assign(L.ptr(last_uvd), L.ptr(ids), L.ptr(miss), L.ptr(next_id), L.ptr(cand_uvd), L.ptr(cand_status), L.ptr(trk_uvd),
+                        L.ptr(trk_status), K, B, B if n_valid is None else n_valid, cfg, paras, flip, L.ptr(filter_state), L.ptr(filter_count), J,
+                        L.ptr(out[0]), L.ptr(out[1]), L.ptr(out[2]), L.ptr(out[3]), L.ptr(out[4]), L.ptr(out[5]))
     return out

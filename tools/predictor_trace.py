@@ -1,10 +1,15 @@
 """What Predictor.predict launches, configuration by configuration -> tests/golden/predictor_trace.json (and, with --bits, what it returns)
 
-    python tools/predictor_trace.py [--out tests/golden/predictor_trace.json] [--bits FILE] [--config NAME ...]
+    python tools/predictor_trace.py [--table options | newer | both] [--out FILE] [--bits FILE] [--config NAME ...]
 
 The golden file is recorded ONCE, at the commit before predict() became one pipeline of stages, and never regenerated from a later
 predictor: tests/test_predictor_trace_gpu.py asserts that every configuration still issues the same launches, in the same order, with the
 same sizes.  The tool uses the public API only, so it runs unchanged in a checkout of any commit that has the options it names.
+
+Two tables, two golden files (TABLES).  CONFIGS -> predictor_trace.json is the one above and stays as it was recorded.  NEWER ->
+predictor_trace_newer.json holds the options that came after it (isolate=, edge_mm=, denoise=), recorded ONCE at the commit before the
+detector's launches moved into detect_calls.py, and never regenerated either.  STAGES names the three entry points of those options too;
+no configuration of the first table issues them, so its trace is what it was.
 
 Recording (the trick of test_hands_1_is_todays_path): awr_amd._lib.call is replaced by a recorder.  For the predictor's own entry points
 (STAGES) it keeps the name and those positional arguments that are int or float, not bool, with abs(x) < 2**20 -- row counts, strides,
@@ -35,7 +40,7 @@ sys.path[:0] = [p for p in (REPO, os.path.join(REPO, "oracle")) if p not in sys.
 
 STAGES = ("awr_detect", "awr_detect_palm", "awr_detect_hands", "awr_detect_samples", "awr_joints_unproject", "awr_joints_center",
           "awr_joints_filter", "awr_confidence_fields", "awr_centers_select", "awr_hands_assign", "awr_view_centers", "awr_view_rotate",
-          "awr_views_fuse")
+          "awr_views_fuse", "awr_hands_isolate", "awr_detect_hands_edge", "awr_frames_denoise")
 S, J, B = 64, 14, 2
 EH, EW = 120, 160
 SMALL = dict(cube=(300.0, 300.0, 300.0), paras=(147.0, 146.8, 80.0, 60.0), flip=-1, frame_shape=(EH, EW), depth_range=(200.0, 1200.0), slab=100.0,
@@ -59,9 +64,21 @@ CONFIGS = {
     "hands2_identity_full": dict(hands=2, identity=True, track=True, smooth=dict(lead=True), recenter=1, palm=True, confidence=True),
     "hands3_identity_smooth_conf": dict(hands=3, identity=True, smooth=dict(weight="conf")),
 }
+# the options behind the first golden file, over the same fixture
+NEWER = {
+    "isolate": dict(hands=2, isolate=True),
+    "isolate_identity_track": dict(hands=2, isolate=True, identity=True, track=True),
+    "edge": dict(hands=2, edge_mm=40.0),
+    "edge_isolate_palm_recenter1": dict(hands=2, edge_mm=40.0, isolate=True, palm=True, recenter=1),
+    "denoise": dict(denoise=True),
+    "denoise_fill_views": dict(denoise=dict(radius=2, edge=None, support=2, fill=3), views=VIEWS),
+    "denoise_identity_full": dict(denoise=True, hands=2, identity=True, track=True, smooth=dict(lead=True), recenter=1, palm=True, confidence=True),
+    "denoise_edge_isolate": dict(denoise=dict(edge=25.0), hands=2, edge_mm=40.0, isolate=True),
+}
+TABLES = {"options": (CONFIGS, "predictor_trace.json"), "newer": (NEWER, "predictor_trace_newer.json")}
 # the documented after-call attributes and the axis of each that is the batch
 ATTRS = dict(centers_uvd=0, next_centers_uvd=0, recenter_codes=1, raw_xyz=0, raw_uvd=0, ahead_xyz=0, filter_codes=0, hand_info=0, hand_codes=0,
-             hand_source=0, hands_dropped=0, palm_info=0)
+             hand_source=0, hands_dropped=0, palm_info=0, isolated=0, raw_frames=0, denoise_status=0)
 
 
 def blobs(*hands):
@@ -113,7 +130,7 @@ def trace(name, net, bits=False):
     """-> (the three recorded calls' launches, their bits or None) of configuration `name`"""
     import awr_amd
     from awr_amd import _lib as L
-    kw = CONFIGS[name]
+    kw = CONFIGS[name] if name in CONFIGS else NEWER[name]
     K = kw.get("hands", 1)
     pred = awr_amd.Predictor(net, S, 1.0, max_batch=B, **SMALL, **kw)
     centers = CENTERS[:, :K] if K > 1 else CENTERS[:, 0]
@@ -142,10 +159,17 @@ def trace(name, net, bits=False):
 
 def main():
     ap = argparse.ArgumentParser()
-    ap.add_argument("--out", default=os.path.join(REPO, "tests", "golden", "predictor_trace.json"))
+    ap.add_argument("--table", default="options", choices=list(TABLES) + ["both"], help="both: one file over both tables, for --bits (pass --out)")
+    ap.add_argument("--out", default=None, help="default: the table's golden file under tests/golden/")
     ap.add_argument("--bits", default=None, help="also write the SHA-256 of every returned field and after-call attribute to this file")
-    ap.add_argument("--config", nargs="*", default=list(CONFIGS))
+    ap.add_argument("--config", nargs="*", default=None, help="default: every configuration of the table")
     a = ap.parse_args()
+    if a.table == "both" and a.out is None:
+        raise SystemExit("--table both writes no golden file: pass --out")
+    if a.out is None:
+        a.out = os.path.join(REPO, "tests", "golden", TABLES[a.table][1])
+    if a.config is None:
+        a.config = [name for t in (TABLES if a.table == "both" else [a.table]) for name in TABLES[t][0]]
     if not torch.cuda.is_available():
         raise SystemExit("tools/predictor_trace.py needs a GPU: nothing is launched without one")
     if a.bits is not None:
