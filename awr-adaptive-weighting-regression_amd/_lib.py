@@ -274,6 +274,8 @@ _SIGS = {
     "awr_joints_filter": ([_P, _P, _P, _P, _P, _P, _I, _I, _I, _D, _D, _D, _D, _D, _I, _I, _D, _D, _D, _D, _D, _I, _P, _P, _P, _P, _P], C.c_int),
     # hand identities across calls (csrc/awr_assign.hip)
     "awr_hands_assign": ([_P, _P, _P, _P, _P, _P, _P, _P, _I, _I, _I, _D, _D, _I, _D, _D, _D, _D, _I, _P, _P, _I, _P, _P, _P, _P, _P, _P, _P], C.c_int),
+    # label-free check of joints against the depth frame (csrc/awr_surface.hip)
+    "awr_joints_surface": ([_P, _I, _L, _I, _I, _P, _P, _P, _P, _I, _I, _I, _P, _I, _I, _I, _D, _D, _I, _P, _P, _P, _P, _P], C.c_int),
 }
 
 # entry points of study builds only (hipcc -DAWR_STUDY, AWR_BUILD_STUDY=1 for awr_amd.build): measured-and-rejected forms that the default

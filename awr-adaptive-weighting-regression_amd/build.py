@@ -42,6 +42,7 @@ SOURCES = {
     "awr_synth.hip": ["-ffp-contract=off"],   # synthetic hand frames: the ray / capsule arithmetic of synth.render, operation by operation
     "awr_track.hip": ["-ffp-contract=off"],   # temporal joint filter: track.filter_step's double arithmetic, operation by operation
     "awr_assign.hip": ["-ffp-contract=off"],  # hand identities: track.assign_step's double arithmetic and its total order over permutations
+    "awr_surface.hip": ["-ffp-contract=off"],  # joints against the depth frame: surface.joints_surface's comparisons and its one interpolation
 }
 
 

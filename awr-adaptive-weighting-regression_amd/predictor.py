@@ -20,6 +20,7 @@ detector for such a machine.  Every option is opt-in, and a predictor without it
     hands=K, isolate=True                   every hand refined and cropped on a frame that holds only its component    4.28
     hands=K, edge_mm=E                      components join only within E mm of depth: a hand in front of another splits 4.29
     denoise=True | dict                     edge-preserving median, speckle removal, hole filling in front of every stage 4.30
+    surface=True | dict                     per joint: on the surface the sensor saw, occluded, or off the silhouette; label-free 4.31
 
 predict() is ONE pipeline over one stage method per entry point, and it reads top to bottom: upload the frames -> with denoise the filtered
 frames (awr_frames_denoise) -> the seeds (given centres | awr_detect_hands, with edge_mm awr_detect_hands_edge | the configured seed mode) -> with isolate a frame per hand (awr_hands_isolate) -> the
@@ -27,7 +28,8 @@ candidate centres (awr_detect, awr_detect_palm) -> the tracked detector (a secon
 awr_hands_assign | nothing) -> crop and predict
 (awr_detect_samples -> awr_nyu_batch -> the inference plan and the single-pass head -> awr_joints_unproject; with views awr_view_centers
 and awr_view_rotate around the crop and awr_views_fuse behind it) -> the recenter passes (awr_joints_center, crop and predict) -> the next
-centre, from the look-ahead joints with lead -> the tracker's state -> awr_joints_filter -> awr_confidence_fields -> the named tuple.
+centre, from the look-ahead joints with lead -> the tracker's state -> awr_joints_filter -> awr_confidence_fields -> with surface
+awr_joints_surface -> the named tuple.
 The plan's rows are group-major: G = V views or K hands, each a group of max_batch rows, group 0 first (_rows).
 
 What is measured and what is not stands with each option in DESIGN.md: accuracy on real frames is UNMEASURED throughout (no NYU frames
@@ -44,6 +46,7 @@ from . import _lib as L
 from . import detect as D
 from . import detect_calls as DC
 from . import nyu_data as ND
+from . import surface as SF
 from . import track as T
 
 Prediction = collections.namedtuple("Prediction", "xyz uvd center_xyz M status")
@@ -65,11 +68,13 @@ class Predictor:
     smooth = None                             # a predictor without a temporal filter: no filter state, no launch, no extra attributes
     identity = None                           # a predictor without hand identities: no assignment state, no launch, no extra attributes
     denoise = None                            # a predictor without the depth pre-filter: no raw buffer, no launch, no extra attributes
+    surface = None                            # a predictor without the surface check: no bone table, no launch, no extra attributes
 
     def __init__(self, net, img_size, kernel_size, cube=(300, 300, 300), paras=ND.PARAS, flip=-1, max_batch=1, frame_shape=(480, 640),
                  seed="nearest", depth_range=D.DEPTH_RANGE, slab=D.SLAB, refine_iters=D.REFINE_ITERS, winograd=None, parity=False, confidence=False,
                  recenter=0, track=False, center_joints=None, max_shift=1.0, views=None, fuse="mean", palm=False, palm_search=D.PALM_SEARCH,
-                 smooth=None, hands=1, reach=D.REACH, min_pixels=D.MIN_PIXELS, identity=None, isolate=False, edge_mm=None, denoise=None):
+                 smooth=None, hands=1, reach=D.REACH, min_pixels=D.MIN_PIXELS, identity=None, isolate=False, edge_mm=None, denoise=None,
+                 surface=None):
         """net: an awr_amd network on the GPU with its weights loaded.  cube: the crop cube in mm.  paras = (fx, fy, u0, v0), flip: the camera.
         max_batch: the static batch of the inference plan; smaller batches are padded, larger ones refused.  seed / depth_range / slab /
         refine_iters: the detector (awr_amd.detect); with `centers_uvd` handed to predict() the seed is the given centre and refine_iters
@@ -161,9 +166,32 @@ class Predictor:
         frames, so the option combines with every other one and a prediction equals the plain predictor's on
         awr_amd.detect.denoise of each frame, bit for bit.  After a call raw_frames (nb, fh, fw) uint16 is a view of the raw buffer
         and denoise_status (nb,) int32 the launch's codes -- device tensors, nothing synchronised.  The defaults are engineering
-        choices (40 mm is the edge 4.29 measured on procedural composites), UNMEASURED on real frames."""
+        choices (40 mm is the edge 4.29 measured on procedural composites), UNMEASURED on real frames.
+        surface: None | True (awr_amd.surface.SURFACE_DEFAULTS: radius=1, in_mm=40.0, out_mm=15.0, min_on=1, bones=None, samples=3) | a dict
+        with any of the keys radius (0 ... 3), in_mm, out_mm (finite millimetres >= 0), min_on (1 ... (2 radius + 1)^2), bones (None: the
+        pairs of vis_tool's skeleton for J = 14 and J = 21, none for another J | up to 64 (from, to) joint index pairs) and samples (1 ... 7)
+        over those defaults (statement: awr_amd.surface.joints_surface) -- a label-free check of every joint against the
+        depth frame, next to `confidence`, which is the network's opinion of itself.  A joint lies inside the hand, a few millimetres
+        behind the surface the sensor sees at its pixel: it is ON (0) where at least min_on valid pixels of the (2 radius + 1)^2 window
+        around its pixel lie at most in_mm in front of it and at most out_mm behind it, else OCCLUDED (1) where a pixel is more than in_mm
+        in front of it -- the joint may be right, but it is unseen -- else OFF (2): only background or nothing is there, the joint floats
+        off the silhouette; OUTSIDE (3) off the frame or not finite, SKIPPED (4) in a row without a prediction.  ONE awr_joints_surface
+        launch behind the final pass over the joints predict() measured -- the fused ones with views, the MEASUREMENT and not the filtered
+        joints with smooth -- and over the stored frames: the denoised ones with denoise, and never a hand's isolated frame, on which the
+        other hand is zeroed and a joint behind it would read OFF where OCCLUDED is the truth.  After a call: surface_codes (nb, J) int32,
+        surface_gap_mm (nb, J) float32 (the joint's depth minus the nearest-in-depth valid pixel of its window; NaN without one),
+        surface_counts (nb, 8) int32 (joints ON / OCCLUDED / OFF / OUTSIDE, then `samples` points along every bone, linear in uvd, the
+        same four) and surface_status (nb,) int32 (0, 1: the row was skipped, 2: its frame is outside the store), with the hand axis
+        behind the batch axis where hands >= 2 -- device tensors, nothing synchronised.  The returned named tuples do not change and every
+        other bit of a call is what it is without the option, which combines with every other one.  The defaults are engineering choices:
+        on procedural hands true joints are ON or OCCLUDED and joints moved 40 mm sideways are OFF in two of three cases, but a skeleton
+        laid over the wrong piece of a surface -- a crop that slid onto the forearm -- reads ON everywhere, so the counts do not rank a
+        trained network's gross failures (profiles/surface_check.txt); UNMEASURED on real frames."""
         if denoise is not None:
             self.denoise = D.check_denoise_option(denoise)
+        if surface is not None:
+            self.surface = SF.check_surface_option(surface)
+            surface_bones = SF.bone_table(self.surface["bones"], int(net.J))          # (refused here, before anything is allocated)
         if isinstance(hands, bool) or not isinstance(hands, int):
             raise TypeError("hands is an int in [1, %d], not %r" % (D.MAX_HANDS, hands))
         K, self.reach, _, self.min_pixels = D._check_hands(hands, reach, 0.0, min_pixels)
@@ -292,6 +320,10 @@ class Predictor:
             self._filter_state = torch.zeros((B * K, self.J, 6), dtype=torch.float64, device=dev)      # x0 x1 x2 d0 d1 d2 per slot (and hand) and joint
             self._filter_count = torch.zeros((B * K, self.J, 2), dtype=torch.int32, device=dev)        # age, coast
             self.raw_xyz = self.raw_uvd = self.ahead_xyz = self.filter_codes = None
+        if self.surface is not None:
+            self._surface_bones = torch.from_numpy(surface_bones).to(dev) if len(surface_bones) else None          # uploaded once
+            self._surface_n_bones = len(surface_bones)
+            self.surface_codes = self.surface_gap_mm = self.surface_counts = self.surface_status = None
         if self.identity is not None:
             # the assignment's state, hand-major (track.identity_state), and the candidates it chooses among
             self._id_last = torch.full((K, B, 3), float("nan"), dtype=torch.float64, device=dev)
@@ -455,6 +487,9 @@ class Predictor:
             c.nxt = torch.full((F, 3), float("nan"), dtype=torch.float64, device=dev)
         if self.confidence:
             c.fields = torch.empty((3, F, J), dtype=torch.float32, device=dev)
+        if self.surface is not None:
+            c.surface = (torch.empty((F, J), dtype=torch.int32, device=dev), torch.empty((F, J), dtype=torch.float32, device=dev),
+                         torch.empty((F, 8), dtype=torch.int32, device=dev), torch.empty(F, dtype=torch.int32, device=dev))
         return c
 
     def _frames_denoise(self, nb):
@@ -547,6 +582,15 @@ class Predictor:
         """conf, peak, spread_mm of every frame row (with views: view 0's rows are the first of every per-row buffer) -> c.fields"""
         DC.awr_confidence_fields(L.ptr(self.engine.conf), L.ptr(self.engine.stat), L.ptr(self._cube32), c.status_j.data_ptr(), c.ustatus.data_ptr(),
                                  c.F, self.J, c.fv, L.ptr(c.fields[0]), L.ptr(c.fields[1]), L.ptr(c.fields[2]))
+
+    def _joints_surface(self, c):
+        """the call's joints (the measurement; with views the fused ones and view 0's codes) against the STORED frame of every frame row ->
+        c.surface = (codes, gap_mm (F, J), counts (F, 8), row_status (F,)) and the after-call attributes"""
+        o = self.surface
+        SF.awr_joints_surface(self._frames.data_ptr(), 0, self.B, self.fh, self.fw, self._idx.data_ptr(), L.ptr(c.uvd_j), c.status_j.data_ptr(),
+                              c.ustatus.data_ptr(), c.F, self.J, c.fv, L.ptr(self._surface_bones), self._surface_n_bones, o["samples"], o["radius"],
+                              o["in_mm"], o["out_mm"], o["min_on"], *(L.ptr(t) for t in c.surface))
+        self.surface_codes, self.surface_gap_mm, self.surface_counts, self.surface_status = (self._rows(t, c.nb) for t in c.surface)
 
     def _crop_and_predict(self, c):
         """self._centers -> c.xyz / c.uvd (with views: and the fused c.fxyz / c.fuvd): crop, render, the network, un-projection"""
@@ -696,6 +740,8 @@ class Predictor:
             self._joints_filter(c, dt)
         if self.confidence:
             self._confidence_fields(c)
+        if self.surface is not None:
+            self._joints_surface(c)
         if self.isolate:
             self.isolated = self._rows(((c.frame >= B) & (c.status == D.OK)).to(torch.int32), nb)
         return self._result(c, given)

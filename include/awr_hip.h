@@ -1275,6 +1275,62 @@ int awr_hands_assign(double* last_uvd, int* ids, int* miss, int* next_id, const 
                      double u0, double v0, int flip, double* filter_state, int* filter_count, int J, double* centers, int* status, int* code,
                      int* reset, int* source, int* dropped, void* stream);
 
+/* ------------------------------------------------------------------------------------------
+ * Label-free check of joints against the depth frame (csrc/awr_surface.hip; statement: awr_amd/surface.py joints_surface, results are
+ * bit-identical to it)
+ *
+ * awr_joints_surface asks, per joint and per sample along a bone, what the sensor saw at the point's pixel.  Inputs per row r < n:
+ *   uvd (n, J, 3) float32: original-image pixel u, v and depth in millimetres, as awr_joints_unproject / awr_views_fuse write it;
+ *   the row's frame frame[r] of the frame store: uint16 millimetres, 0 means no measurement;  status, ustatus (n): the row's codes.
+ *   bones: n_bones pairs of int32 joint indices on the device (NULL with n_bones = 0);  samples points along each bone.
+ * The rule:
+ *
+ * A point is a triple (u, v, d) in float64. A joint's point is its float32 values converted exactly. Sample s = 1 ... samples of bone
+ * (a, b) is p = A + (B - A) * (s / (samples + 1)), per component in float64, in exactly this order. It is linear in uvd, not in camera
+ * space.
+ * For one point:
+ *   1. If u, v or d is not finite, the code is OUTSIDE.
+ *   2. Otherwise pu = floor(u + 0.5) and pv = floor(v + 0.5), clamped before the integer conversion as awr_frame.h's trunc_clamped does.
+ *      If pu is not in [0, fw) or pv is not in [0, fh), the code is OUTSIDE.
+ *   3. W is the set of in-frame pixels of the (2 * radius + 1)^2 window around (pu, pv). The centre is included and the window is
+ *      clipped at the frame's edges.
+ *   4. For q in W with d_q != 0: g_q = d - (double)d_q.
+ *   5. n_on = #{-out_mm <= g_q <= in_mm}, n_front = #{g_q > in_mm}.
+ *   6. The code is ON (0) if n_on >= min_on; else OCCLUDED (1) if n_front >= 1; else OFF (2). A window of zeros only is OFF too.
+ *   7. The gap is the g_q of smallest |g_q|, the positive one on a tie of +g and -g, rounded to float32. It is NaN if no pixel of W is
+ *      valid, and NaN for OUTSIDE. It is a value, not a position, so the scan order cannot matter.
+ * A row whose status is not AWR_DET_OK or whose ustatus is not 0 is SKIPPED: every code of the row is 4, its gaps are NaN, its counts are
+ * 0 and its row_status is 1; its frame index is not looked at. Otherwise a row whose frame index lies outside [0, n_frames) gets
+ * row_status 2 and the same outputs. Rows at or past n_valid are not written at all.
+ * A bone with an index outside [0, J) yields OUTSIDE samples, never a fault.
+ *
+ * Outputs per row:  codes (n, J) int32;  gap_mm (n, J) float32 (every NaN is the quiet NaN 0x7FC00000);  counts (n, 8) int32: joints
+ * ON / OCCLUDED / OFF / OUTSIDE, then bone samples ON / OCCLUDED / OFF / OUTSIDE;  row_status (n) int32.
+ *   radius in [0, AWR_SURFACE_MAX_RADIUS]; in_mm, out_mm finite and >= 0; min_on in [1, (2 radius + 1)^2]; n_bones in
+ *   [0, AWR_SURFACE_MAX_BONES]; samples in [1, AWR_SURFACE_MAX_SAMPLES]; J in [1, AWR_SURFACE_MAX_JOINTS]; n in [1, AWR_DET_MAX_BATCH],
+ *   n_valid in [0, n], fh, fw in [1, 16384]; only uint16 frames: anything else returns AWR_ERR_ARG with a message that names the entry
+ *   point and the value, before any launch; n_valid = 0 returns AWR_OK without one.
+ * ONE launch on `stream`: one wave per row, its lanes stride over the row's J + n_bones * samples points, each lane gathers its window
+ * with 2-byte loads and the eight counts are two packed wave sums.  Comparisons and exact differences in double, the one interpolation
+ * without contraction.  No atomics, no LDS, no scratch, nothing synchronises. */
+#define AWR_SURFACE_ON 0
+#define AWR_SURFACE_OCCLUDED 1
+#define AWR_SURFACE_OFF 2
+#define AWR_SURFACE_OUTSIDE 3
+#define AWR_SURFACE_SKIPPED 4
+#define AWR_SURFACE_ROW_OK 0
+#define AWR_SURFACE_ROW_SKIPPED 1
+#define AWR_SURFACE_ROW_BAD_FRAME 2
+#define AWR_SURFACE_MAX_RADIUS 3
+#define AWR_SURFACE_MAX_JOINTS 256
+#define AWR_SURFACE_MAX_BONES 64
+#define AWR_SURFACE_MAX_SAMPLES 7
+int awr_joints_surface(const void* frames, int frame_type, int64_t n_frames, int fh, int fw, const int64_t* frame /* n */,
+                       const float* uvd /* n,J,3 */, const int* status /* n */, const int* ustatus /* n */, int n, int J, int n_valid,
+                       const int* bones /* n_bones,2 or NULL */, int n_bones, int samples, int radius, double in_mm, double out_mm,
+                       int min_on, int* codes /* n,J */, float* gap_mm /* n,J */, int* counts /* n,8 */, int* row_status /* n */,
+                       void* stream);
+
 #ifdef __cplusplus
 }
 #endif

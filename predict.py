@@ -42,6 +42,13 @@ stay one hand, and a rear hand that the front one cuts into pieces gives one can
 per pixel the lower median of the window's valid depths within EDGE millimetres of its own; a pixel with fewer than SUPPORT such
 neighbours becomes 0; a zero pixel with at least FILL valid neighbours takes their lower median.  Without a value: 1,40,0,none (a 3 x 3
 edge-preserving median); EDGE and FILL may be "none".  Combines with every other option; the defaults are UNMEASURED on real frames.
+--surface [RADIUS,IN_MM,OUT_MM] checks every predicted joint against the depth frame it was predicted from (awr_joints_surface, DESIGN.md
+4.31): ON (0) where a valid pixel of the (2 RADIUS + 1)^2 window around the joint's pixel lies at most IN_MM in front of the joint and at
+most OUT_MM behind it, OCCLUDED (1) where something much nearer covers the pixel, OFF (2) where only background or nothing is there,
+OUTSIDE (3) off the frame, SKIPPED (4) for a frame or hand without a prediction.  Without a value: 1,40,15.  Writes pred_surface_code.txt
+and pred_surface_gap_mm.txt (a row per frame and hand, a column per joint) and pred_surface_counts.txt (joints ON / OCCLUDED / OFF /
+OUTSIDE, then the same for three samples along each bone of the skeleton).  It needs no labels; it changes no prediction.  Combines with
+every other option; the defaults are engineering choices, UNMEASURED on real frames.
 --ema predicts with the checkpoint's averaged weights ("model_ema", written by a run with config.ema_decay) instead of "model".
 `--set` overrides config entries as train.py does (img_size, kernel_size, cube, batch_size, jt_num, downsample, winograd ...)."""
 import argparse
@@ -78,6 +85,8 @@ def parse_args(argv=None):
                     help="with --hands: keep each hand in its slot across frames (the file is one sequence); optionally the gate, the merge distance and the misses allowed")
     ap.add_argument("--denoise", nargs="?", const="", default=None, metavar="RADIUS,EDGE,SUPPORT,FILL",
                     help="filter every frame on the device first: edge-preserving median, speckle removal, hole filling (default 1,40,0,none)")
+    ap.add_argument("--surface", nargs="?", const="", default=None, metavar="RADIUS,IN_MM,OUT_MM",
+                    help="check every predicted joint against the depth frame: on the seen surface, occluded or off it (default 1,40,15)")
     ap.add_argument("--ema", action="store_true", help="load the checkpoint's \"model_ema\" (the EMA of the weights) instead of \"model\"")
     return ap.parse_args(argv)
 
@@ -96,6 +105,21 @@ def denoise_config(args):
                     fill=None if vals[3] == "none" else int(vals[3]))
     except ValueError:
         raise SystemExit("--denoise takes RADIUS,EDGE,SUPPORT,FILL (an int, a number or none, an int, an int or none), not %r" % args.denoise)
+
+
+def surface_config(args):
+    """--surface -> what Predictor(surface=...) takes, or None"""
+    if args.surface is None:
+        return None
+    if not args.surface:
+        return True
+    vals = [v.strip() for v in args.surface.split(",")]
+    try:
+        if len(vals) != 3:
+            raise ValueError
+        return dict(radius=int(vals[0]), in_mm=float(vals[1]), out_mm=float(vals[2]))
+    except ValueError:
+        raise SystemExit("--surface takes RADIUS,IN_MM,OUT_MM (an int and two numbers), not %r" % args.surface)
 
 
 def smooth_config(args):
@@ -142,6 +166,7 @@ def main(argv=None):
     smooth = smooth_config(args)
     identity = identity_config(args)
     denoise = denoise_config(args)
+    surface = surface_config(args)
     if args.identity and identity is None:
         raise SystemExit("--identity takes GATE_MM,MERGE_MM,MAX_MISS (two numbers and an int), not %r" % args.identity)
 
@@ -180,7 +205,7 @@ def main(argv=None):
     pred = awr_amd.Predictor(net.cuda(), cfg.img_size, cfg.kernel_size, cube=cfg.cube, max_batch=bs, frame_shape=frames.shape[1:],
                              winograd=cfg.winograd, parity=cfg.parity_infer, confidence=args.confidence,
                              recenter=args.recenter, track=args.track, views=views, fuse=args.fuse, palm=args.palm,
-                             smooth=smooth, identity=identity, denoise=denoise, **hands_kw)
+                             smooth=smooth, identity=identity, denoise=denoise, surface=surface, **hands_kw)
     hands = {"n_hands": [], "hand_status": [], "hand_info": []}
     if identity is not None:
         hands.update(hand_id=[], hand_code=[])
@@ -189,6 +214,7 @@ def main(argv=None):
     uvd, xyz, extra = [], [], {"conf": [], "peak": [], "spread_mm": []}
     fused = {"view_spread_mm": [], "views_used": []}
     raw = {"raw_uvd": [], "raw_xyz": [], "filter_code": []}
+    seen = {"surface_code": [], "surface_gap_mm": [], "surface_counts": []}
     for lo in range(0, len(frames), bs):
         out = pred.predict(np.array(frames[lo:lo + bs]))
         uvd.append(out.uvd.cpu().numpy())
@@ -202,6 +228,9 @@ def main(argv=None):
         if smooth is not None:
             for k, t in (("raw_uvd", pred.raw_uvd), ("raw_xyz", pred.raw_xyz), ("filter_code", pred.filter_codes)):
                 raw[k].append(t.cpu().numpy())
+        if surface is not None:
+            for k, t in (("surface_code", pred.surface_codes), ("surface_gap_mm", pred.surface_gap_mm), ("surface_counts", pred.surface_counts)):
+                seen[k].append(t.cpu().numpy().reshape(-1, t.shape[-1]))
         if K > 1:
             hands["n_hands"].append(out.n_hands.cpu().numpy())
             hands["hand_status"].append(out.status.cpu().numpy())
@@ -232,6 +261,9 @@ def main(argv=None):
         for k in ("raw_uvd", "raw_xyz"):
             np.savetxt(os.path.join(args.out, "pred_%s.txt" % k), np.concatenate(raw[k], 0).reshape(len(frames) * K, cfg.jt_num * 3), fmt="%.3f")
         np.savetxt(os.path.join(args.out, "pred_filter_code.txt"), np.concatenate(raw["filter_code"], 0).reshape(len(frames) * K, cfg.jt_num), fmt="%d")
+    if surface is not None:
+        for k, rows in seen.items():
+            np.savetxt(os.path.join(args.out, "pred_%s.txt" % k), np.concatenate(rows, 0), fmt="%.6g" if k == "surface_gap_mm" else "%d")
     if stateful:
         np.savetxt(os.path.join(args.out, "pred_center_uvd.txt"), np.concatenate(centers, 0), fmt="%.6f")
         np.savetxt(os.path.join(args.out, "pred_recenter_code.txt"), np.concatenate(codes, 0), fmt="%d")
