@@ -276,6 +276,9 @@ _SIGS = {
     "awr_hands_assign": ([_P, _P, _P, _P, _P, _P, _P, _P, _I, _I, _I, _D, _D, _I, _D, _D, _D, _D, _I, _P, _P, _I, _P, _P, _P, _P, _P, _P, _P], C.c_int),
     # label-free check of joints against the depth frame (csrc/awr_surface.hip)
     "awr_joints_surface": ([_P, _I, _L, _I, _I, _P, _P, _P, _P, _I, _I, _I, _P, _I, _I, _I, _D, _D, _I, _P, _P, _P, _P, _P], C.c_int),
+    # static-scene background model in front of every stage (csrc/awr_background.hip)
+    "awr_background_learn": ([_P, _I, _L, _I, _I, _P, _I, _I, _I, _P, _P, _P], C.c_int),
+    "awr_frames_foreground": ([_P, _I, _L, _I, _I, _P, _I, _I, _P, _I, _I, _D, _I, _I, _P, _P, _P], C.c_int),
 }
 
 # entry points of study builds only (hipcc -DAWR_STUDY, AWR_BUILD_STUDY=1 for awr_amd.build): measured-and-rejected forms that the default

@@ -39,6 +39,7 @@ SOURCES = {
     "awr_hands.hip": ["-ffp-contract=off"],   # several hands: integer connected components; the depth limits are single double additions
     "awr_isolate.hip": [],                    # a frame per hand: integer selects on labels, 16-byte loads and stores
     "awr_denoise.hip": ["-ffp-contract=off"],  # depth pre-filter: integer median selection; depth_floor's double arithmetic on the host
+    "awr_background.hip": ["-ffp-contract=off"],  # background model: integer compares and rank selection; depth_floor's double arithmetic on the host
     "awr_synth.hip": ["-ffp-contract=off"],   # synthetic hand frames: the ray / capsule arithmetic of synth.render, operation by operation
     "awr_track.hip": ["-ffp-contract=off"],   # temporal joint filter: track.filter_step's double arithmetic, operation by operation
     "awr_assign.hip": ["-ffp-contract=off"],  # hand identities: track.assign_step's double arithmetic and its total order over permutations

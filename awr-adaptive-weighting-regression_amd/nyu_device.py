@@ -166,6 +166,33 @@ class FrameStore:
             D.denoise_device(self, torch.arange(lo, hi, dtype=torch.int64, device=self.data.device), out=out[lo:hi], **options)
         return FrameStore.from_device(out)
 
+    def foreground(self, model, chunk=256, **options):
+        """-> a new uint16 store whose frame i is awr_amd.background.foreground(frame i, model, **options)[0]: a recorded
+        set without its static background, as Predictor(background=options) with that model sees its frames.  model: (fh, fw) uint16,
+        numpy or device tensor (awr_amd.background.learn / learn_device make one).  options: margin / unknown over
+        background.BACKGROUND_DEFAULTS; adapt is refused: the frames of a store have no order in time that a model could follow.  One
+        awr_frames_foreground launch per `chunk` frames; nothing synchronised."""
+        from . import background as BG
+        extra = set(options) - {"margin", "unknown", "adapt"}
+        if extra:
+            raise ValueError("foreground has unknown options %s (margin and unknown exist)" % sorted(extra))
+        if options.get("adapt") is not None:
+            raise ValueError("foreground of a store does not adapt the model (adapt = %r): Predictor(background=dict(adapt=...)) does" % (options["adapt"],))
+        o = BG.check_background_option({k: v for k, v in options.items() if k != "adapt"})
+        if self.ftype != 0:
+            raise ValueError("foreground filters uint16 millimetres: this store holds float32 frames")
+        if not isinstance(model, torch.Tensor):
+            model = torch.from_numpy(np.array(model))          # (a copy: the caller's array may be read-only)
+        if model.dtype != torch.uint16 or tuple(model.shape) != (self.fh, self.fw):
+            raise ValueError("model must be (%d, %d) uint16, got %s %s" % (self.fh, self.fw, model.dtype, tuple(model.shape)))
+        model = model.to(self.data.device).contiguous()
+        out = torch.empty_like(self.data)
+        for lo in range(0, self.n, chunk):
+            hi = min(self.n, lo + chunk)
+            BG.foreground_device(self, torch.arange(lo, hi, dtype=torch.int64, device=self.data.device), model, margin=o["margin"],
+                                 unknown=o["unknown"], out=out[lo:hi])
+        return FrameStore.from_device(out)
+
 
 def build_frame_cache(root, phase, out=None):
     """Decode every depth_1*.png of <root>/<phase> once (nyu_loader.py:71-74: depth = G*256 + B) into a uint16 .npy the FrameStore

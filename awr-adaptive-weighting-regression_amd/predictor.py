@@ -21,8 +21,10 @@ detector for such a machine.  Every option is opt-in, and a predictor without it
     hands=K, edge_mm=E                      components join only within E mm of depth: a hand in front of another splits 4.29
     denoise=True | dict                     edge-preserving median, speckle removal, hole filling in front of every stage 4.30
     surface=True | dict                     per joint: on the surface the sensor saw, occluded, or off the silhouette; label-free 4.31
+    background=True | dict                  a learnt static-scene model; only what is nearer than it reaches any other stage      4.32
 
-predict() is ONE pipeline over one stage method per entry point, and it reads top to bottom: upload the frames -> with denoise the filtered
+predict() is ONE pipeline over one stage method per entry point, and it reads top to bottom: upload the frames -> with background the
+frames without their learnt background (awr_frames_foreground) -> with denoise the filtered
 frames (awr_frames_denoise) -> the seeds (given centres | awr_detect_hands, with edge_mm awr_detect_hands_edge | the configured seed mode) -> with isolate a frame per hand (awr_hands_isolate) -> the
 candidate centres (awr_detect, awr_detect_palm) -> the tracked detector (a second awr_detect) -> combine (awr_centers_select |
 awr_hands_assign | nothing) -> crop and predict
@@ -43,6 +45,7 @@ import numpy as np
 import torch
 
 from . import _lib as L
+from . import background as BG
 from . import detect as D
 from . import detect_calls as DC
 from . import nyu_data as ND
@@ -69,12 +72,13 @@ class Predictor:
     identity = None                           # a predictor without hand identities: no assignment state, no launch, no extra attributes
     denoise = None                            # a predictor without the depth pre-filter: no raw buffer, no launch, no extra attributes
     surface = None                            # a predictor without the surface check: no bone table, no launch, no extra attributes
+    background = None                         # a predictor without a background model: no model, no upload buffer, no launch, no extra attributes
 
     def __init__(self, net, img_size, kernel_size, cube=(300, 300, 300), paras=ND.PARAS, flip=-1, max_batch=1, frame_shape=(480, 640),
                  seed="nearest", depth_range=D.DEPTH_RANGE, slab=D.SLAB, refine_iters=D.REFINE_ITERS, winograd=None, parity=False, confidence=False,
                  recenter=0, track=False, center_joints=None, max_shift=1.0, views=None, fuse="mean", palm=False, palm_search=D.PALM_SEARCH,
                  smooth=None, hands=1, reach=D.REACH, min_pixels=D.MIN_PIXELS, identity=None, isolate=False, edge_mm=None, denoise=None,
-                 surface=None):
+                 background=None, surface=None):
         """net: an awr_amd network on the GPU with its weights loaded.  cube: the crop cube in mm.  paras = (fx, fy, u0, v0), flip: the camera.
         max_batch: the static batch of the inference plan; smaller batches are padded, larger ones refused.  seed / depth_range / slab /
         refine_iters: the detector (awr_amd.detect); with `centers_uvd` handed to predict() the seed is the given centre and refine_iters
@@ -186,7 +190,33 @@ class Predictor:
         other bit of a call is what it is without the option, which combines with every other one.  The defaults are engineering choices:
         on procedural hands true joints are ON or OCCLUDED and joints moved 40 mm sideways are OFF in two of three cases, but a skeleton
         laid over the wrong piece of a surface -- a crop that slid onto the forearm -- reads ON everywhere, so the counts do not rank a
-        trained network's gross failures (profiles/surface_check.txt); UNMEASURED on real frames."""
+        trained network's gross failures (profiles/surface_check.txt); UNMEASURED on real frames.
+        background: None | True (awr_amd.background.BACKGROUND_DEFAULTS: margin=30.0, unknown="keep", adapt=None, shared=True,
+        rank="median", min_valid=1) | a dict with any of those keys over the defaults (statements:
+        awr_amd.background.learn and foreground) -- for a FIXED sensor with static things nearer than the hand (a table edge, a monitor,
+        a knee, a torso), which every other stage would take for the hand.  The predictor keeps a model, one uint16 depth per pixel (0: no
+        background known here), zeros at first; learn_background(frames) learns it from 1 ... 64 frames of the scene without a hand
+        (rank: "median" the lower median of a pixel's valid depths | "min" | "max"; a pixel valid in fewer than min_valid frames stays
+        0), set_background(model) takes one from outside, reset_background() zeroes it.  The frames are uploaded into a buffer of
+        max_batch rows of their own and ONE awr_frames_foreground launch, in front of everything else, writes them without their
+        background where every other stage reads (with denoise: its raw buffer, so the order is sensor -> foreground -> denoise): a pixel
+        stays where it is at least margin millimetres nearer than the model (d + floor(margin) < m) or, with unknown="keep", where the
+        model is 0, and becomes 0 otherwise.  The option combines with every other one, and a prediction equals the plain predictor's
+        on awr_amd.background.foreground of each frame, bit for bit; with an all-zero model and unknown="keep" it equals the plain
+        predictor's.  adapt: None | step 1 ... 65535 -- every call moves the model at most step millimetres towards the frame where the
+        pixel is valid BACKGROUND (not kept, model known), in rows below n_valid: slow drift is followed, a hand is foreground and is
+        never absorbed; furniture moved NEARER after learning stays foreground until the model is learnt again.  shared: True -- one
+        model for every batch slot | False -- one per batch slot, where slot b is the same camera from call to call, as the tracker's
+        and the filter's slots are; adapt with shared=True and max_batch > 1 is refused (several rows would step one model).  After a
+        call sensor_frames (nb, fh, fw) uint16 is a view of the upload buffer and background_status (nb,) int32 the launch's codes --
+        device tensors, nothing synchronised; raw_frames keeps its meaning (the frames denoise read).  The named tuples do not change.
+        The defaults are engineering choices; what the option loses -- hand pixels within margin of the desk -- and what it leaves
+        stand in profiles/background_accuracy.txt, procedural frames only; UNMEASURED on real frames."""
+        if background is not None:
+            self.background = BG.check_background_option(background)
+            if self.background["adapt"] is not None and self.background["shared"] and int(max_batch) > 1:
+                raise ValueError("background adapt = %d with shared=True and max_batch = %d: several rows of a batch would step ONE model "
+                                 "(shared=False keeps a model per batch slot)" % (self.background["adapt"], int(max_batch)))
         if denoise is not None:
             self.denoise = D.check_denoise_option(denoise)
         if surface is not None:
@@ -283,6 +313,13 @@ class Predictor:
             self._raw = torch.empty((B, self.fh, self.fw), dtype=torch.uint16, device=dev)
             self._denoise_status = torch.empty(B, dtype=torch.int32, device=dev)
             self.raw_frames = self.denoise_status = None
+        if self.background is not None:
+            # the frames as the sensor gave them; the store's rows [0, B) (with denoise: the raw buffer) then hold them without their background
+            self._sensor = torch.empty((B, self.fh, self.fw), dtype=torch.uint16, device=dev)
+            self._bg_model = torch.empty((1 if self.background["shared"] else B, self.fh, self.fw), dtype=torch.uint16, device=dev)
+            self._bg_model.view(torch.int16).zero_()
+            self._bg_status = torch.empty(B, dtype=torch.int32, device=dev)
+            self.sensor_frames = self.background_status = self.background_learn_status = None
         self._stage = torch.empty((B, self.fh, self.fw), dtype=torch.uint16).pin_memory()
         self._stage_free = None                  # event: the last upload from the staging buffer has been issued and has finished
         self._store = types.SimpleNamespace(data=self._all_frames, ftype=0, fh=self.fh, fw=self.fw, n=self._nframes)
@@ -417,6 +454,72 @@ class Predictor:
         if self.smooth is not None:
             self.reset_smooth(slots)
 
+    def _background_rows(self, slots):
+        """the model rows a call names: every row for slots=None; with a shared model there is one row and slots must be None"""
+        if self.background is None:
+            raise L.AwrError("the background model needs a Predictor built with background=...")
+        if slots is not None and self.background["shared"]:
+            raise L.AwrError("slots name the models of batch slots: this predictor keeps ONE shared model (background shared=False keeps one per slot)")
+        return self._slots(slots)
+
+    def _put_background(self, model, idx):
+        """a (fh, fw) device model -> the model rows idx (None: all of them)"""
+        if idx is None:
+            self._bg_model.copy_(model.expand_as(self._bg_model))
+        else:                                    # (index operations take the bits as int16)
+            self._bg_model.view(torch.int16).index_copy_(0, idx, model.view(torch.int16).expand(idx.shape[0], self.fh, self.fw))
+
+    def learn_background(self, frames, slots=None):
+        """Learn the background model from frames (n, fh, fw) uint16 of the scene WITHOUT a hand, 1 <= n <= 64, numpy or tensor, host or
+        device: one awr_background_learn launch with the predictor's rank and min_valid (awr_amd.background.learn is its statement), and
+        the model replaces what the predictor had.  With shared=False, slots names the batch slots that take the model (default: all of
+        them).  background_learn_status (1,) int32 is the launch's status word, a device tensor.  Does not block."""
+        idx = self._background_rows(slots)
+        if isinstance(frames, np.ndarray):
+            if frames.dtype != np.uint16:
+                raise L.AwrError("frames must be uint16 millimetres, not %s" % frames.dtype)
+            frames = torch.from_numpy(np.ascontiguousarray(frames))
+        if not isinstance(frames, torch.Tensor) or frames.dtype != torch.uint16:
+            raise L.AwrError("frames must be a uint16 numpy array or tensor")
+        if frames.dim() != 3 or tuple(frames.shape[1:]) != (self.fh, self.fw) or not 1 <= frames.shape[0] <= BG.MAX_FRAMES:
+            raise L.AwrError("frames must be (n, %d, %d) with n in [1, %d], got %s" % (self.fh, self.fw, BG.MAX_FRAMES, tuple(frames.shape)))
+        o, n = self.background, int(frames.shape[0])
+        if o["min_valid"] > n:
+            raise L.AwrError("min_valid = %d needs at least that many frames to learn from, got %d" % (o["min_valid"], n))
+        frames = frames.to(self.device, non_blocking=True).contiguous()
+        model = torch.empty((self.fh, self.fw), dtype=torch.uint16, device=self.device)
+        status = torch.empty(1, dtype=torch.int32, device=self.device)
+        listed = torch.arange(n, dtype=torch.int64, device=self.device)
+        BG.awr_background_learn(frames.data_ptr(), 0, n, self.fh, self.fw, listed.data_ptr(), n, o["rank"], o["min_valid"], model.data_ptr(),
+                                status.data_ptr())
+        self._put_background(model, idx)
+        self.background_learn_status = status
+
+    def set_background(self, model, slots=None):
+        """Set the background model from outside: model (fh, fw) uint16, numpy or tensor, host or device (0: no background known at that
+        pixel).  With shared=False, slots names the batch slots that take it (default: all of them).  Does not block."""
+        idx = self._background_rows(slots)
+        m = model if isinstance(model, torch.Tensor) else torch.from_numpy(np.array(model))          # (a copy: the caller's array may be read-only)
+        if m.dtype != torch.uint16 or tuple(m.shape) != (self.fh, self.fw):
+            raise L.AwrError("model must be (%d, %d) uint16, got %s %s" % (self.fh, self.fw, m.dtype, tuple(m.shape)))
+        self._put_background(m.to(self.device, non_blocking=True), idx)
+
+    def reset_background(self, slots=None):
+        """Zero the background model (with shared=False: of batch slots `slots`, default all of them): everything is foreground again
+        (with unknown="drop": nothing is).  Does not block."""
+        idx = self._background_rows(slots)
+        if idx is None:
+            self._bg_model.view(torch.int16).zero_()
+        else:
+            self._bg_model.view(torch.int16).index_fill_(0, idx, 0)
+
+    @property
+    def background_model(self):
+        """the model store, a device tensor: (1, fh, fw) uint16 with shared=True, else (max_batch, fh, fw), row b the model of batch slot b"""
+        if self.background is None:
+            raise L.AwrError("background_model needs a Predictor built with background=...")
+        return self._bg_model
+
     def _set_track_hands(self, centers_uvd, slots):
         """set_track with identities: centers_uvd (n, K, 3); a finite row puts slot k of its batch slot there -- it keeps the identity it has, a
         free slot gets the next one -- and a NaN row ends the slot's identity.  Device arithmetic only; does not block."""
@@ -491,6 +594,15 @@ class Predictor:
             c.surface = (torch.empty((F, J), dtype=torch.int32, device=dev), torch.empty((F, J), dtype=torch.float32, device=dev),
                          torch.empty((F, 8), dtype=torch.int32, device=dev), torch.empty(F, dtype=torch.int32, device=dev))
         return c
+
+    def _frames_foreground(self, nb, nv):
+        """rows [0, nb) of the upload buffer -> rows [0, nb) of what the next stage reads, without their background; rows below nv adapt"""
+        o = self.background
+        out = self._frames if self.denoise is None else self._raw
+        BG.awr_frames_foreground(self._sensor.data_ptr(), 0, self.B, self.fh, self.fw, self._idx.data_ptr(), nb, nv, self._bg_model.data_ptr(),
+                                 self._bg_model.shape[0], not o["shared"], o["margin"], o["unknown"], o["adapt"], out.data_ptr(),
+                                 self._bg_status.data_ptr())
+        self.sensor_frames, self.background_status = self._sensor[:nb], self._bg_status[:nb]
 
     def _frames_denoise(self, nb):
         """rows [0, nb) of the raw buffer -> rows [0, nb) of the frame store, filtered"""
@@ -616,7 +728,8 @@ class Predictor:
             self._views_fuse(c)
 
     def _upload(self, frames):
-        """(nb, fh, fw) uint16 -> rows [0, nb) of the frame store (with denoise: of the raw buffer), without blocking"""
+        """(nb, fh, fw) uint16 -> rows [0, nb) of the frame store (with denoise: of the raw buffer; with background: of its upload buffer),
+        without blocking"""
         if isinstance(frames, np.ndarray):
             if frames.dtype != np.uint16:
                 raise L.AwrError("frames must be uint16 millimetres (the sensor format; it makes the detector's sums exact), not %s" % frames.dtype)
@@ -636,7 +749,10 @@ class Predictor:
                 self._stage_free.synchronize()
             self._stage[:nb].copy_(frames)
             frames = self._stage[:nb]
-        (self._frames if self.denoise is None else self._raw)[:nb].copy_(frames, non_blocking=True)
+        if self.background is not None:
+            self._sensor[:nb].copy_(frames, non_blocking=True)
+        else:
+            (self._frames if self.denoise is None else self._raw)[:nb].copy_(frames, non_blocking=True)
         if staged:
             self._stage_free = torch.cuda.Event()
             self._stage_free.record()
@@ -671,6 +787,8 @@ class Predictor:
         nv = nb if n_valid is None else int(n_valid)
         if not 0 < nv <= nb:
             raise L.AwrError("n_valid = %d is outside [1, %d]" % (nv, nb))
+        if self.background is not None:
+            self._frames_foreground(nb, nv)          # (in front of the filter: the sensor's frames -> foreground -> denoise -> every other stage)
         if self.denoise is not None:
             self._frames_denoise(nb)          # (in front of the seeds, given centres and the tracker alike: every stage reads the filtered frames)
         # the seeds: given centres, the K nearest components, or the configured seed mode

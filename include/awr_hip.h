@@ -1331,6 +1331,63 @@ int awr_joints_surface(const void* frames, int frame_type, int64_t n_frames, int
                        int min_on, int* codes /* n,J */, float* gap_mm /* n,J */, int* counts /* n,8 */, int* row_status /* n */,
                        void* stream);
 
+/* Static-scene background model (csrc/awr_background.hip; the numpy statements are awr_amd/background.py learn and
+ * foreground, results are bit-identical to them).  Every other stage assumes that the hand is the nearest thing in the frame; with a
+ * fixed sensor there may be static things nearer than it.  A model is learnt once from frames of the scene without a hand, and a pass in
+ * front of every other stage keeps only what is nearer than the model.
+ *
+ * Learning a model.  The model is one uint16 depth per pixel, and 0 means "no background known here".
+ *
+ *   Input: n listed frames of the store, 1 <= n <= AWR_BG_MAX_FRAMES = 64, a rank in {MIN, MEDIAN, MAX}, min_valid in [1, n].
+ *   For pixel p: V = the multiset { frame_i[p] : frame_i[p] != 0 }, over the listed frames whose index lies inside the store.
+ *     - If |V| < min_valid the model is 0.
+ *     - Otherwise the model is element k of the ascending sort of V: k = 0 (MIN), (|V| - 1) // 2 (MEDIAN, the lower median), |V| - 1 (MAX).
+ *       It is a value that occurs, never an average.
+ *   A listed frame index outside the store contributes no value to any pixel; the call's one status word is then AWR_DET_BAD_FRAME, else
+ *   AWR_DET_OK.
+ *
+ * MEDIAN survives sensor noise and a hand that crosses a pixel in fewer than half the frames; MIN is the conservative choice for an
+ * empty-scene capture; MAX suits a capture in which a person walks through.
+ *   n, rank, min_valid outside those ranges, model_out overlapping the n_frames rows of the store, a frame store check_frame_store
+ *   refuses (only uint16 frames; fh, fw in [1, 16384]): AWR_ERR_ARG with a message that names the entry point and the value, before any
+ *   launch.
+ * ONE launch on `stream`: a workgroup of 256 threads stages n x 256 depths in at most 32 KB of LDS, frame-major, and each thread selects
+ * element k of its pixel's column by building the answer from bit 15 down out of counts.  No atomics, integers only. */
+#define AWR_BG_MAX_FRAMES 64
+#define AWR_BG_MIN 0
+#define AWR_BG_MEDIAN 1
+#define AWR_BG_MAX 2
+int awr_background_learn(const void* frames, int frame_type, int64_t n_frames, int fh, int fw, const int64_t* frame /* n */, int n, int rank,
+                         int min_valid, void* model_out /* fh,fw uint16 */, int* status /* 1 */, void* stream);
+
+/* Applying it.  The pass is pointwise.  Every output pixel depends on that pixel of the input frame and of the model alone.
+ *
+ *   d = input depth, m = model depth, both as int. margin = floor(min(margin_mm, 65535)) (awr_frame.h's depth_floor, the integer form 4.29
+ *   and 4.30 use; negative or NaN is refused before any launch). unknown_keep in {0, 1}.
+ *     keep = d != 0 and ( m == 0 ? unknown_keep == 1 : d + margin < m )        -- int arithmetic: d + margin may reach 131070 and must not wrap
+ *     out  = keep ? d : 0
+ *   With adapt = step >= 1, for rows b < n_valid only, and only at pixels with d != 0, m != 0 and not keep (a valid background pixel):
+ *     m' = m + min(max(d - m, -step), step)                                    -- between m and d, so it stays in [1, 65535]
+ *   Every other model pixel keeps its value. adapt = 0: the model is only read.
+ *   Row b reads frame index frame[b] (outside the store: a zero output row, status AWR_DET_BAD_FRAME, no adaptation) and model row
+ *   (per_row ? b : 0).
+ *
+ * So an all-zero model with unknown_keep = 1 passes every frame through unchanged; a hand is foreground and is never absorbed by adapt;
+ * furniture moved NEARER after learning stays foreground until the model is learnt again (a stated limitation).
+ * out: B rows in the FrameStore layout.  model: model_rows rows of fh x fw uint16.  status (B).
+ *   Refused with AWR_ERR_ARG and a message, before any launch: `out` overlapping the n_frames rows of the frame store, or the model_rows
+ *   rows of the model overlapping either; adapt > 0 with per_row == 0 and B > 1 (several rows would race on one model); model_rows <
+ *   (per_row ? B : 1); n_valid outside [0, B]; margin negative or NaN; unknown_keep or per_row outside {0, 1}; adapt outside [0, 65535];
+ *   B outside [1, AWR_DET_MAX_BATCH], fh, fw outside [1, 16384], frames that are not uint16.
+ * ONE launch on `stream`, about 6 bytes per pixel, 8 with adapt: a thread owns 8 pixels of a row -- one 16-byte load of the frame, one of
+ * the model, one 16-byte store of the output and, with adapt, one of the model (fw a multiple of 8 and the three bases 16-byte aligned;
+ * otherwise a thread per pixel with 2-byte accesses).  adapt is a compile-time form of the same kernel: the form without it never writes
+ * the model.  A model pixel is read and written by one thread only.  No atomics, no LDS, no floating point on the device, nothing
+ * synchronises. */
+int awr_frames_foreground(const void* frames, int frame_type, int64_t n_frames, int fh, int fw, const int64_t* frame /* B */, int B,
+                          int n_valid, void* model /* model_rows,fh,fw uint16 */, int model_rows, int per_row, double margin,
+                          int unknown_keep, int adapt, void* out /* B,fh,fw uint16 */, int* status /* B */, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

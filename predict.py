@@ -49,6 +49,12 @@ OUTSIDE (3) off the frame, SKIPPED (4) for a frame or hand without a prediction.
 and pred_surface_gap_mm.txt (a row per frame and hand, a column per joint) and pred_surface_counts.txt (joints ON / OCCLUDED / OFF /
 OUTSIDE, then the same for three samples along each bone of the skeleton).  It needs no labels; it changes no prediction.  Combines with
 every other option; the defaults are engineering choices, UNMEASURED on real frames.
+--background EMPTY.npy learns a static-scene background model from the (n, h, w) uint16 frames of EMPTY.npy (1 ... 64 frames of the scene
+WITHOUT a hand, as many as 64 are used) before the first prediction, and every frame then reaches the detector without it
+(awr_background_learn, awr_frames_foreground): a pixel stays where it is at least --background-margin MM (default 30)
+nearer than the learnt depth, or where no background was ever seen.  For a FIXED sensor with a table edge, a monitor or a body nearer
+than the hand.  --background-adapt STEP treats the file as one sequence and lets the model follow the background STEP millimetres per
+frame.  Combines with every other option; the defaults are engineering choices, UNMEASURED on real frames.
 --ema predicts with the checkpoint's averaged weights ("model_ema", written by a run with config.ema_decay) instead of "model".
 `--set` overrides config entries as train.py does (img_size, kernel_size, cube, batch_size, jt_num, downsample, winograd ...)."""
 import argparse
@@ -87,6 +93,10 @@ def parse_args(argv=None):
                     help="filter every frame on the device first: edge-preserving median, speckle removal, hole filling (default 1,40,0,none)")
     ap.add_argument("--surface", nargs="?", const="", default=None, metavar="RADIUS,IN_MM,OUT_MM",
                     help="check every predicted joint against the depth frame: on the seen surface, occluded or off it (default 1,40,15)")
+    ap.add_argument("--background", default=None, metavar="EMPTY.npy",
+                    help="learn a background model from these frames of the empty scene first; only what is nearer than it is looked at")
+    ap.add_argument("--background-margin", type=float, default=None, metavar="MM", help="with --background: how much nearer than the model a pixel must be (default 30)")
+    ap.add_argument("--background-adapt", type=int, default=None, metavar="STEP", help="with --background: the file is one sequence; the model follows the background STEP mm per frame")
     ap.add_argument("--ema", action="store_true", help="load the checkpoint's \"model_ema\" (the EMA of the weights) instead of \"model\"")
     return ap.parse_args(argv)
 
@@ -105,6 +115,20 @@ def denoise_config(args):
                     fill=None if vals[3] == "none" else int(vals[3]))
     except ValueError:
         raise SystemExit("--denoise takes RADIUS,EDGE,SUPPORT,FILL (an int, a number or none, an int, an int or none), not %r" % args.denoise)
+
+
+def background_config(args):
+    """--background / --background-margin / --background-adapt -> what Predictor(background=...) takes, or None"""
+    if args.background is None:
+        if args.background_margin is not None or args.background_adapt is not None:
+            raise SystemExit("--background-margin and --background-adapt belong to --background EMPTY.npy")
+        return None
+    cfg = {}
+    if args.background_margin is not None:
+        cfg["margin"] = args.background_margin
+    if args.background_adapt is not None:
+        cfg["adapt"] = args.background_adapt
+    return cfg or True
 
 
 def surface_config(args):
@@ -167,6 +191,7 @@ def main(argv=None):
     identity = identity_config(args)
     denoise = denoise_config(args)
     surface = surface_config(args)
+    background = background_config(args)
     if args.identity and identity is None:
         raise SystemExit("--identity takes GATE_MM,MERGE_MM,MAX_MISS (two numbers and an int), not %r" % args.identity)
 
@@ -191,7 +216,7 @@ def main(argv=None):
     if key not in pth:
         raise awr_amd._lib.AwrError("{} holds no \"{}\" entry{}".format(cfg.load_model, key, " (--ema needs a checkpoint written with ema_decay)" if args.ema else ""))
     net.load_state_dict(pth[key])
-    bs = 1 if args.track or smooth is not None or identity is not None else min(cfg.batch_size, len(frames))
+    bs = 1 if args.track or smooth is not None or identity is not None or args.background_adapt is not None else min(cfg.batch_size, len(frames))
     views = None if args.views is None else detect.parse_views(args.views)
     if args.hands == 1 and (args.reach is not None or args.min_pixels is not None):
         raise SystemExit("--reach and --min-pixels belong to --hands K with K >= 2")
@@ -205,7 +230,13 @@ def main(argv=None):
     pred = awr_amd.Predictor(net.cuda(), cfg.img_size, cfg.kernel_size, cube=cfg.cube, max_batch=bs, frame_shape=frames.shape[1:],
                              winograd=cfg.winograd, parity=cfg.parity_infer, confidence=args.confidence,
                              recenter=args.recenter, track=args.track, views=views, fuse=args.fuse, palm=args.palm,
-                             smooth=smooth, identity=identity, denoise=denoise, surface=surface, **hands_kw)
+                             smooth=smooth, identity=identity, denoise=denoise, surface=surface, background=background, **hands_kw)
+    if background is not None:
+        from awr_amd import background as BG
+        empty = np.load(args.background, mmap_mode="r")
+        if empty.ndim != 3 or empty.dtype != np.uint16 or empty.shape[1:] != frames.shape[1:]:
+            raise SystemExit("--background: %s holds %s %s, not uint16 frames of %s" % (args.background, empty.dtype, empty.shape, tuple(frames.shape[1:])))
+        pred.learn_background(np.array(empty[:BG.MAX_FRAMES]))
     hands = {"n_hands": [], "hand_status": [], "hand_info": []}
     if identity is not None:
         hands.update(hand_id=[], hand_code=[])
