@@ -260,6 +260,7 @@ _SIGS = {
     "awr_detect_hands_scratch": ([_I, _I, _I], C.c_int64),
     "awr_detect_hands": ([_P, _I, _L, _I, _I, _P, _I, _I, _D, _D, _D, _D, _I, _P, _P, _P, _P, _P, _P, _P], C.c_int),
     "awr_detect_hands_edge": ([_P, _I, _L, _I, _I, _P, _I, _I, _D, _D, _D, _D, _D, _I, _P, _P, _P, _P, _P, _P, _P], C.c_int),
+    "awr_detect_hands_link": ([_P, _I, _L, _I, _I, _P, _I, _I, _D, _D, _D, _D, _D, _I, _D, _I, _P, _P, _P, _P, _P, _P, _P], C.c_int),
     # a frame per hand: the other labelled components removed (csrc/awr_isolate.hip)
     "awr_hands_isolate": ([_P, _I, _L, _I, _I, _P, _I, _I, _P, _P, _P, _P, _P], C.c_int),
     # edge-preserving depth pre-filter in front of the detector (csrc/awr_denoise.hip)

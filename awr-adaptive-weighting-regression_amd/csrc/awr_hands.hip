@@ -19,7 +19,9 @@
 //   3. hands_border_kernel: joins across the tiles' upper and left borders in global memory;
 //      (stages 2 and 3 are the only ones that decide joins.  Each has a compile-time EDGE form for awr_detect_hands_edge, DESIGN.md
 //      4.29: a join also needs |d_a - d_b| <= elim, an integer test equal to the statement's float64 comparison against `edge`, since
-//      elim = depth_floor(edge).  The forms without it are what awr_detect_hands runs, and hold nothing of the test.)
+//      elim = depth_floor(edge).  The forms without it are what awr_detect_hands runs, and hold nothing of the test.
+//      awr_detect_hands_link, DESIGN.md 4.33, adds ONE launch here, hands_link_kernel: joins of a rear pixel with the first pixel behind
+//      at most `gap` occluders in a row or column, so the fragments a front hand cuts a rear hand into are one component again.)
 //   4. hands_flatten_kernel: L = find(L) (and labels_out); CNT and ZC of the root by atomicAdd / atomicMin, the lanes of a wave that
 //      share a root summed first;
 //   5. hands_roots_kernel: every workgroup's K smallest keys among its roots with CNT >= min_pixels (a sorted list per thread, then K
@@ -57,6 +59,7 @@ struct HandsArgs {
     int elim;                     // EDGE kernels only: two neighbouring mask pixels join when |d_a - d_b| <= elim (depth_floor of the edge)
     u64* slots; int* L; int* CNT; int* ZC;
     int* labels_out;
+    int llim, gap;                // hands_link_kernel only: a walk of at most `gap` occluders links p and q when |d_p - d_q| <= llim
 };
 
 struct HandsFrame {
@@ -243,6 +246,39 @@ __global__ __launch_bounds__(128) void hands_border_kernel(HandsArgs a) {
     }
 }
 
+// 3b. links across an occluder (awr_detect_hands_link), a thread per pixel: a labelled pixel p looks at its four
+// neighbours, and where one is an OCCLUDER of p (d != 0 and d_p - d > elim: raw depths, in the mask or not) it walks on in that direction
+// over at most `gap` occluders to the first pixel q that is none.  q in the mask with |d_q - d_p| <= llim: p and q are joined in the
+// forest, as any other pair.  The walk links nothing where it leaves the frame or where q_1 ... q_{gap + 1} are all occluders; a zero
+// pixel is no occluder and ends it.  Only a pixel at the rear side of an occlusion edge walks, gap + 1 two-byte loads of the frame at
+// the most.  Integer compares only; every index is inside the row (u) or the column (v) of the frame before it is read
+__global__ __launch_bounds__(HANDS_THREADS) void hands_link_kernel(HandsArgs a) {
+    const HandsFrame hf = hands_frame(a, blockIdx.y);
+    if (hf.bad) return;
+    int p0, p1;
+    hands_share(a, p0, p1);
+    const int fw = a.fw, fh = a.fh, elim = a.elim, llim = a.llim, gap = a.gap;
+    for (int p = p0 + (int)threadIdx.x; p < p1; p += HANDS_THREADS) {
+        if (uf_load(hf.L + p) < 0) continue;
+        const int dp = hf.F[p], u = p % fw, v = p / fw;
+#pragma unroll
+        for (int dir = 0; dir < 4; ++dir) {                              // right, left, down, up
+            const int step = dir == 0 ? 1 : dir == 1 ? -1 : dir == 2 ? fw : -fw;
+            const int room = dir == 0 ? fw - 1 - u : dir == 1 ? u : dir == 2 ? fh - 1 - v : v;      // pixels ahead of p inside the frame
+            if (room < 2) continue;                                      // (an occluder and a pixel behind it)
+            int d = hf.F[p + step];
+            if (d == 0 || dp - d <= elim) continue;                      // q_1 is no occluder: p does not walk
+            const int last = min(gap + 1, room);
+            int t = 2, q = -1;
+            for (; t <= last; ++t) {
+                d = hf.F[p + t * step];
+                if (d == 0 || dp - d <= elim) { q = p + t * step; break; }
+            }
+            if (q >= 0 && uf_load(hf.L + q) >= 0 && abs(d - dp) <= llim) uf_union(hf.L, p, q);
+        }
+    }
+}
+
 // 4. L = find(L); pixels and smallest depth of every component at its root's words
 __global__ __launch_bounds__(HANDS_THREADS) void hands_flatten_kernel(HandsArgs a) {
     const HandsFrame hf = hands_frame(a, blockIdx.y);
@@ -388,16 +424,19 @@ __global__ void hands_finalize_kernel(HandsArgs a, double* __restrict__ centers,
 
 using namespace awr;
 
-// both entry points: `edge` NULL is awr_detect_hands -- the kernels without a depth test, the launches it always issued
+// the three entry points: `edge` NULL is awr_detect_hands -- the kernels without a depth test, the launches it always issued; `link` NULL
+// is awr_detect_hands_edge -- its launches; with a link the link stage runs between the borders and the flattening
 static int detect_hands(const char* who, const void* frames, int frame_type, int64_t n_frames, int fh, int fw, const int64_t* frame, int B,
-                        int K, double zmin, double zmax, double reach, const double* edge, double slab, int min_pixels, void* scratch,
-                        int* labels_out, double* centers, int* status, int* info, int* count, void* stream) {
+                        int K, double zmin, double zmax, double reach, const double* edge, const double* link, int gap, double slab,
+                        int min_pixels, void* scratch, int* labels_out, double* centers, int* status, int* info, int* count, void* stream) {
     if (check_frame_store(who, frame_type, B, n_frames, fh, fw) != AWR_OK) return AWR_ERR_ARG;
     AWR_REQUIRE(K >= 1 && K <= MAX_HANDS, "%s: K = %d hands is outside [1, %d]", who, K, MAX_HANDS);
     AWR_REQUIRE(min_pixels >= 1, "%s: min_pixels = %d must be at least 1", who, min_pixels);
     AWR_REQUIRE(zmin <= zmax, "%s: depth range needs zmin <= zmax (got %g, %g)", who, zmin, zmax);
     AWR_REQUIRE(reach >= 0.0, "%s: reach = %g must be >= 0", who, reach);
     AWR_REQUIRE(!edge || *edge >= 0.0, "%s: edge = %g must be >= 0 (infinity: no depth test)", who, edge ? *edge : 0.0);
+    AWR_REQUIRE(!link || *link >= 0.0, "%s: link = %g must be >= 0 (infinity: any two depths agree)", who, link ? *link : 0.0);
+    AWR_REQUIRE(!link || (gap >= 1 && gap <= AWR_HANDS_MAX_GAP), "%s: gap = %d is outside [1, %d]", who, gap, AWR_HANDS_MAX_GAP);
     AWR_REQUIRE(slab >= 0.0, "%s: slab = %g must be >= 0", who, slab);
     AWR_REQUIRE(frames && frame && scratch && centers && status && info && count, "%s: NULL pointer", who);
     AWR_REQUIRE(((uintptr_t)frames & 1) == 0 && ((uintptr_t)scratch & 7) == 0, "%s: misaligned frame store / scratch", who);
@@ -411,6 +450,7 @@ static int detect_hands(const char* who, const void* frames, int frame_type, int
     a.slots = (u64*)scratch;
     a.L = (int*)(a.slots + (int64_t)B * HANDS_SLOTS); a.CNT = a.L + np; a.ZC = a.CNT + np;
     a.labels_out = labels_out;
+    a.llim = link ? depth_floor(*link) : 0; a.gap = link ? gap : 0;
     const int64_t nw = (int64_t)B * HANDS_SLOTS;
     const int tiles = ((fw + HANDS_TILE_W - 1) / HANDS_TILE_W) * ((fh + HANDS_TILE_H - 1) / HANDS_TILE_H);
     const dim3 share(frame_parts(B, fh, HANDS_MAX_PARTS), B), tile(tiles, B);
@@ -419,6 +459,7 @@ static int detect_hands(const char* who, const void* frames, int frame_type, int
     if (edge) {
         hands_tile_kernel<true><<<tile, HANDS_THREADS, 0, s>>>(a);
         hands_border_kernel<true><<<tile, 128, 0, s>>>(a);
+        if (link) hands_link_kernel<<<share, HANDS_THREADS, 0, s>>>(a);
     } else {
         hands_tile_kernel<false><<<tile, HANDS_THREADS, 0, s>>>(a);
         hands_border_kernel<false><<<tile, 128, 0, s>>>(a);
@@ -446,15 +487,22 @@ int64_t awr_detect_hands_scratch(int B, int fh, int fw) {
 int awr_detect_hands(const void* frames, int frame_type, int64_t n_frames, int fh, int fw, const int64_t* frame, int B, int K, double zmin,
                      double zmax, double reach, double slab, int min_pixels, void* scratch, int* labels_out, double* centers, int* status,
                      int* info, int* count, void* stream) {
-    return detect_hands("awr_detect_hands", frames, frame_type, n_frames, fh, fw, frame, B, K, zmin, zmax, reach, nullptr, slab, min_pixels,
-                        scratch, labels_out, centers, status, info, count, stream);
+    return detect_hands("awr_detect_hands", frames, frame_type, n_frames, fh, fw, frame, B, K, zmin, zmax, reach, nullptr, nullptr, 0, slab,
+                        min_pixels, scratch, labels_out, centers, status, info, count, stream);
 }
 
 int awr_detect_hands_edge(const void* frames, int frame_type, int64_t n_frames, int fh, int fw, const int64_t* frame, int B, int K,
                           double zmin, double zmax, double reach, double edge, double slab, int min_pixels, void* scratch, int* labels_out,
                           double* centers, int* status, int* info, int* count, void* stream) {
-    return detect_hands("awr_detect_hands_edge", frames, frame_type, n_frames, fh, fw, frame, B, K, zmin, zmax, reach, &edge, slab,
-                        min_pixels, scratch, labels_out, centers, status, info, count, stream);
+    return detect_hands("awr_detect_hands_edge", frames, frame_type, n_frames, fh, fw, frame, B, K, zmin, zmax, reach, &edge, nullptr, 0,
+                        slab, min_pixels, scratch, labels_out, centers, status, info, count, stream);
+}
+
+int awr_detect_hands_link(const void* frames, int frame_type, int64_t n_frames, int fh, int fw, const int64_t* frame, int B, int K,
+                          double zmin, double zmax, double reach, double edge, double link, int gap, double slab, int min_pixels,
+                          void* scratch, int* labels_out, double* centers, int* status, int* info, int* count, void* stream) {
+    return detect_hands("awr_detect_hands_link", frames, frame_type, n_frames, fh, fw, frame, B, K, zmin, zmax, reach, &edge, &link, gap,
+                        slab, min_pixels, scratch, labels_out, centers, status, info, count, stream);
 }
 
 }  // extern "C"

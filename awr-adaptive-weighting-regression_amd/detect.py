@@ -16,6 +16,8 @@ operator-level wrappers over the entry points for tests and tools.
   * `components` and `hand_seeds`: the statements of awr_detect_hands (csrc/awr_hands.hip) -- the near foreground split
     into 4-connected components with canonical labels, the K nearest large ones seeded per component; `hands_device` wraps it.  With
     `edge` they are the statements of awr_detect_hands_edge: neighbours join only within `edge` millimetres of depth.
+    With `link` and `gap` besides they are the statements of awr_detect_hands_link: a rear pixel is joined with the
+    first pixel behind at most `gap` occluders, so the fragments a front hand cuts a rear hand into are one component again.
   * `denoise`: the statement of awr_frames_denoise (csrc/awr_denoise.hip) -- an edge-preserving lower median with
     speckle removal and hole filling in front of every stage; `denoise_device` wraps it.
   * `make_views`, `check_views`, `view_table`, `view_centers`, `view_rotate` and `fuse_views`: test-time views -- the host
@@ -337,6 +339,9 @@ def palm_center(frame, center, status=OK, cube=(300, 300, 300), paras=ND.PARAS, 
 # arm's reach behind the nearest pixel, and a component of fewer than 400 pixels (a 20 x 20 patch; a hand at 1.5 m covers some 2000) is
 # debris, not a hand.
 MAX_HANDS, REACH, MIN_PIXELS = 4, 300.0, 400
+# links across an occluder: a walk crosses at most LINK_GAP occluders unless told otherwise -- an engineering choice,
+# UNMEASURED on real frames -- and never more than MAX_GAP (AWR_HANDS_MAX_GAP)
+LINK_GAP, MAX_GAP = 32, 64
 
 
 def _check_hands(hands, reach, slab, min_pixels):
@@ -368,7 +373,55 @@ def _check_edge(edge, value=True):
     return float(edge)
 
 
-def components(frame, depth_range=DEPTH_RANGE, reach=REACH, edge=None):
+def _check_link(link, gap=LINK_GAP, edge=None, value=True):
+    """link: None (no links: `gap` is not looked at) | a number of millimetres >= 0, infinity allowed, NaN not; gap: an int in
+    [1, MAX_GAP] -> (None | float, int).  A link needs an edge: without one no pixel is an occluder.  value=False checks the types alone
+    (hands_device: a value the entry point refuses gets its message from there)."""
+    if link is None:
+        return None, LINK_GAP
+    if isinstance(link, (bool, str, bytes)) or not isinstance(link, (int, float, np.integer, np.floating)):
+        raise TypeError("link is None or a number of millimetres >= 0, not %r" % (link,))
+    if isinstance(gap, bool) or not isinstance(gap, (int, np.integer)):
+        raise TypeError("gap is an int in [1, %d], not %r" % (MAX_GAP, gap))
+    if edge is None:
+        raise ValueError("link = %r needs an edge: an occluder is a pixel more than `edge` millimetres nearer" % (link,))
+    if value and not float(link) >= 0.0:
+        raise ValueError("link = %r must be >= 0 (infinity: any two depths agree)" % (link,))
+    if value and not 1 <= int(gap) <= MAX_GAP:
+        raise ValueError("gap = %d is outside [1, %d]" % (gap, MAX_GAP))
+    return float(link), int(gap)
+
+
+def _links(frame, mask, edge, link, gap):
+    """The links of `components`: -> (p, q) int64 raster indices, a pair per link.  One pass per direction and step t over shifted views:
+    `walking` holds the mask pixels whose q_1 ... q_{t-1} were all occluders; those whose q_t lies outside the frame stop (nothing), those
+    whose q_t is an occluder go on (past t = gap + 1: nothing), and the others end at q = q_t -- a link when t >= 2, q is in the mask and
+    |d_q - d_p| <= link."""
+    fh, fw = frame.shape
+    d = frame.astype(np.float64)
+    index = np.arange(fh * fw, dtype=np.int64).reshape(fh, fw)
+    ps, qs = [], []
+    for axis, forward in ((1, True), (1, False), (0, True), (0, False)):          # right, left, down, up
+        n = frame.shape[axis]
+        walking = mask
+        for t in range(1, min(gap + 1, n - 1) + 1):
+            near, far = slice(0, n - t), slice(t, n)
+            sp, sq = (near, far) if forward else (far, near)
+            sp, sq = ((slice(None), sp), (slice(None), sq)) if axis == 1 else ((sp, slice(None)), (sq, slice(None)))
+            occluder = (d[sq] != 0) & (d[sp] - d[sq] > edge)
+            if t >= 2:
+                hit = walking[sp] & ~occluder & mask[sq] & (np.abs(d[sq] - d[sp]) <= link)
+                ps.append(index[sp][hit])
+                qs.append(index[sq][hit])
+            on = np.zeros((fh, fw), bool)
+            on[sp] = walking[sp] & occluder
+            walking = on
+            if not walking.any():
+                break
+    return np.concatenate(ps) if ps else np.zeros(0, np.int64), np.concatenate(qs) if qs else np.zeros(0, np.int64)
+
+
+def components(frame, depth_range=DEPTH_RANGE, reach=REACH, edge=None, link=None, gap=LINK_GAP):
     """-> labels (fh, fw) int32.  Foreground: zmin <= d <= zmax and d != 0; dmin its smallest depth; the mask is the foreground with
     d <= min(dmin + reach, zmax) (float64 comparisons, as in `detect`).  Two mask pixels are connected when they are 4-neighbours -- no
     depth test.  A pixel's label is the smallest raster index v * fw + u of its component, -1 on background: canonical, so any correct
@@ -376,9 +429,22 @@ def components(frame, depth_range=DEPTH_RANGE, reach=REACH, edge=None):
     edge: a number of millimetres -- two mask pixels are JOINED when they are 4-neighbours and |d_a - d_b| <= edge, the
     raw depths compared as float64, and the components are the transitive closure of that (a ramp of small steps is one component).
     Then a run also starts where the left neighbour is in the mask but more than `edge` away in depth, and a vertical pair joins two
-    runs only if the two pixels pass the test.  An edge of 65535 or more gives the labels of edge=None."""
+    runs only if the two pixels pass the test.  An edge of 65535 or more gives the labels of edge=None.
+    link, gap (only with edge): the components are the transitive closure of the joins above AND of these links.  For
+    every mask pixel p (raw depth d_p) and each of the four directions (right, left, down, up), q_t being the pixel t steps from p:
+      1. a pixel o is an OCCLUDER of p when d_o != 0 and d_p - d_o > edge.  Raw depths only: o need not lie in the mask and may be nearer
+         than zmin;
+      2. n is the number of consecutive occluders q_1 ... q_n, counted up to gap.  Nothing happens when n == 0, when q_1 ... q_gap and
+         q_{gap+1} are all occluders, or when the walk leaves the frame before it ends;
+      3. otherwise q = q_{n+1} is the first pixel that is no occluder, 1 <= n <= gap; when q is a mask pixel and |d_q - d_p| <= link
+         (float64), p and q are joined.
+    The test is p's alone: one direction of a pair may hold and the other not; either one joins.  A zero pixel inside the gap is no
+    occluder and ends the walk, so sensor shadows break links.  An edge of 65535 or more makes no pixel an occluder: the labels of
+    edge=None.  Two DIFFERENT hands at similar depth with a nearer object between them, gap pixels or fewer wide, are linked.
+    link=None: no links.  A link without an edge raises ValueError."""
     frame = _u16(frame)
     edge = _check_edge(edge)
+    link, gap = _check_link(link, gap, edge)
     fh, fw = frame.shape
     zmin, zmax = float(depth_range[0]), float(depth_range[1])
     if not zmin <= zmax:
@@ -404,7 +470,11 @@ def components(frame, depth_range=DEPTH_RANGE, reach=REACH, edge=None):
     run = np.cumsum(start.ravel()).reshape(fh, fw) - 1          # on a mask pixel: the number of its own run
     first = np.flatnonzero(start.ravel())
     parent = np.arange(first.size)
-    pairs = np.unique(run[:-1][both].astype(np.int64) * first.size + run[1:][both])
+    pairs = run[:-1][both].astype(np.int64) * first.size + run[1:][both]
+    if link is not None:                                          # a link joins the runs of its two pixels, as a vertical pair does
+        lp, lq = _links(frame, mask, edge, link, gap)
+        pairs = np.concatenate([pairs, run.ravel()[lp].astype(np.int64) * first.size + run.ravel()[lq]])
+    pairs = np.unique(pairs)
     p = parent.tolist()
     for a, b in zip((pairs // first.size).tolist(), (pairs % first.size).tolist()):
         while p[a] != a:
@@ -427,9 +497,9 @@ def components(frame, depth_range=DEPTH_RANGE, reach=REACH, edge=None):
     return labels
 
 
-def hand_seeds(frame, hands, depth_range=DEPTH_RANGE, reach=REACH, slab=SLAB, min_pixels=MIN_PIXELS, edge=None):
-    """The statement of awr_detect_hands (edge=None) and awr_detect_hands_edge (edge: `components`' depth test on the join; everything
-    below reads its labels) for one frame: -> (centers (K, 3) float64, status (K,) int32, info (K, 4) int32, count).
+def hand_seeds(frame, hands, depth_range=DEPTH_RANGE, reach=REACH, slab=SLAB, min_pixels=MIN_PIXELS, edge=None, link=None, gap=LINK_GAP):
+    """The statement of awr_detect_hands (edge=None), awr_detect_hands_edge (edge: `components`' depth test on the join) and
+    awr_detect_hands_link (link, gap: `components`' links across an occluder; everything below reads its labels) for one frame: -> (centers (K, 3) float64, status (K,) int32, info (K, 4) int32, count).
     Candidates: the components of `components` with n >= min_pixels pixels; a candidate's key is (zc, root), zc its smallest raw depth
     and root its label; the K = hands smallest keys fill the slots in ascending order (slot 0: the nearest hand; a tie in depth goes to
     the smaller root).  A slot's seed is the centre of mass of its component's pixels with d <= min(zc + slab, zmax) -- the "nearest"
@@ -440,7 +510,7 @@ def hand_seeds(frame, hands, depth_range=DEPTH_RANGE, reach=REACH, slab=SLAB, mi
     frame = _u16(frame)
     fw = frame.shape[1]
     zmax = float(depth_range[1])
-    labels = components(frame, depth_range, reach, edge)
+    labels = components(frame, depth_range, reach, edge, link, gap)
     centers, status, info = np.full((K, 3), np.nan), np.full(K, EMPTY, np.int32), np.tile(np.array(_NO_INFO, np.int32), (K, 1))
     on = labels >= 0
     if not on.any():
@@ -808,14 +878,16 @@ def palm_device(store, frame_idx, centers, status, cube=(300, 300, 300), paras=N
 
 
 def hands_device(store, frame_idx, hands, depth_range=DEPTH_RANGE, reach=REACH, slab=SLAB, min_pixels=MIN_PIXELS, labels=False, scratch=None,
-                 edge=None):
+                 edge=None, link=None, gap=LINK_GAP):
     """awr_detect_hands on a FrameStore-like object: -> (centres (K, B, 3) float64, status (K, B) int32, info (K, B, 4) int32, count (B,)
     int32, labels (B, fh, fw) int32 or None) on the device, hand-major, nothing synchronised.  labels: True (allocated), False (NULL) or
     a tensor; scratch: an int64 tensor of at least awr_detect_hands_scratch(B, fh, fw) bytes.  edge: None issues awr_detect_hands,
-    anything else awr_detect_hands_edge (a type that is no number raises here; a value the entry point refuses gets its message there)."""
+    anything else awr_detect_hands_edge (a type that is no number raises here; a value the entry point refuses gets its message there).
+    link, gap: with a link (which needs an edge) awr_detect_hands_link is issued instead; link=None is the call without them."""
     import torch
     from . import _lib as L, detect_calls as DC
     edge = _check_edge(edge, value=False)
+    link, gap = _check_link(link, gap, edge, value=False)
     dev = store.data.device
     idx = _frame_index(frame_idx, dev)
     B, K = int(idx.shape[0]), int(hands)
@@ -831,7 +903,7 @@ def hands_device(store, frame_idx, hands, depth_range=DEPTH_RANGE, reach=REACH, 
     elif labels is False:
         labels = None
     DC.awr_detect_hands(*_source(store), idx.data_ptr(), B, K, depth_range, reach, edge, slab, min_pixels, scratch.data_ptr(), L.ptr(labels),
-                        centers.data_ptr(), status.data_ptr(), info.data_ptr(), count.data_ptr())
+                        centers.data_ptr(), status.data_ptr(), info.data_ptr(), count.data_ptr(), link=link, gap=gap)
     return centers, status, info, count, labels
 
 

@@ -6,11 +6,12 @@ Buffers are device addresses (int; None: NULL) -- L.ptr(t) of a tensor a user ha
 one the Predictor allocated itself; both launch through here, so the list the operator tests prove is the list the product path runs.
 Nothing is allocated, validated or computed.  A frame source is its five parts: frames (address), ftype, n_frames, fh, fw.  The conventions:
     edge=None -> +inf (no depth test), and awr_detect_hands instead of awr_detect_hands_edge        fill=None -> 0 (no filling)
+    link=None -> the call above; a link -> awr_detect_hands_link, gap=None -> detect.LINK_GAP
     cfg.gate_mm=None (the filter's) -> -1.0 (no gate)                                                joints=None -> (NULL, 0): all joints
     cube_rows: False -> stride 0, one cube for every row | True -> stride 3, an (n, 3) table         the camera: fx, fy, u0, v0, then flip
     seed, fuse and cfg.weight are the names of detect.SEEDS, detect.FUSE_MODES and track.WEIGHTS"""
 from . import _lib as L
-from .detect import FUSE_MODES, SEEDS
+from .detect import FUSE_MODES, LINK_GAP, SEEDS
 from .track import WEIGHTS
 
 
@@ -41,11 +42,14 @@ def awr_detect_palm(frames, ftype, n_frames, fh, fw, frame_idx, n, centers, stat
 
 
 def awr_detect_hands(frames, ftype, n_frames, fh, fw, frame_idx, n, hands, depth_range, reach, edge, slab, min_pixels, scratch, labels, centers, status,
-                     info, count):
-    """the K nearest components' seeds, hand-major; labels (n, fh, fw) int32 or NULL.  edge: None | the join's depth test in millimetres"""
+                     info, count, *, link=None, gap=None):
+    """the K nearest components' seeds, hand-major; labels (n, fh, fw) int32 or NULL.  edge: None | the join's depth test in millimetres;
+    link: None | the depth agreement of a link across an occluder in millimetres, gap: the occluders a link crosses at the most"""
     head = (frames, int(ftype), int(n_frames), int(fh), int(fw), frame_idx, int(n), int(hands), float(depth_range[0]), float(depth_range[1]), float(reach))
     tail = (float(slab), int(min_pixels), scratch, labels, centers, status, info, count, L.stream())
-    if edge is None:
+    if link is not None:
+        L.call("awr_detect_hands_link", *head, float("inf") if edge is None else float(edge), float(link), LINK_GAP if gap is None else int(gap), *tail)
+    elif edge is None:
         L.call("awr_detect_hands", *head, *tail)
     else:
         L.call("awr_detect_hands_edge", *head, float(edge), *tail)

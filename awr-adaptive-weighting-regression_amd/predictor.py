@@ -22,10 +22,11 @@ detector for such a machine.  Every option is opt-in, and a predictor without it
     denoise=True | dict                     edge-preserving median, speckle removal, hole filling in front of every stage 4.30
     surface=True | dict                     per joint: on the surface the sensor saw, occluded, or off the silhouette; label-free 4.31
     background=True | dict                  a learnt static-scene model; only what is nearer than it reaches any other stage      4.32
+    hands=K, edge_mm=E, link_mm=L           a rear hand's fragments rejoined across the hand in front of it            4.33
 
 predict() is ONE pipeline over one stage method per entry point, and it reads top to bottom: upload the frames -> with background the
 frames without their learnt background (awr_frames_foreground) -> with denoise the filtered
-frames (awr_frames_denoise) -> the seeds (given centres | awr_detect_hands, with edge_mm awr_detect_hands_edge | the configured seed mode) -> with isolate a frame per hand (awr_hands_isolate) -> the
+frames (awr_frames_denoise) -> the seeds (given centres | awr_detect_hands, with edge_mm awr_detect_hands_edge, with link_mm awr_detect_hands_link | the configured seed mode) -> with isolate a frame per hand (awr_hands_isolate) -> the
 candidate centres (awr_detect, awr_detect_palm) -> the tracked detector (a second awr_detect) -> combine (awr_centers_select |
 awr_hands_assign | nothing) -> crop and predict
 (awr_detect_samples -> awr_nyu_batch -> the inference plan and the single-pass head -> awr_joints_unproject; with views awr_view_centers
@@ -78,7 +79,7 @@ class Predictor:
                  seed="nearest", depth_range=D.DEPTH_RANGE, slab=D.SLAB, refine_iters=D.REFINE_ITERS, winograd=None, parity=False, confidence=False,
                  recenter=0, track=False, center_joints=None, max_shift=1.0, views=None, fuse="mean", palm=False, palm_search=D.PALM_SEARCH,
                  smooth=None, hands=1, reach=D.REACH, min_pixels=D.MIN_PIXELS, identity=None, isolate=False, edge_mm=None, denoise=None,
-                 background=None, surface=None):
+                 background=None, link_mm=None, link_gap=D.LINK_GAP, surface=None):
         """net: an awr_amd network on the GPU with its weights loaded.  cube: the crop cube in mm.  paras = (fx, fy, u0, v0), flip: the camera.
         max_batch: the static batch of the inference plan; smaller batches are padded, larger ones refused.  seed / depth_range / slab /
         refine_iters: the detector (awr_amd.detect); with `centers_uvd` handed to predict() the seed is the given centre and refine_iters
@@ -161,6 +162,15 @@ class Predictor:
         larger), and with isolate the fragments that are not the slot's root are removed from that hand's own frame
         (profiles/hands_overlap.txt).  No default is chosen: the right value depends on the sensor's noise, UNMEASURED on real frames.
         Refused with hands=1.
+        link_mm, link_gap: None | a number of millimetres >= 0, and an int in [1, 64] (default 32) -- with hands >= 2 and edge_mm, the hands
+        stage issues awr_detect_hands_link (statement: awr_amd.detect.components(edge=, link=, gap=)): a pixel with a
+        run of 1 ... link_gap OCCLUDERS beside it in its row or column (non-zero pixels more than edge_mm nearer than itself) is joined
+        with the first pixel behind them when that one is in the near foreground and within link_mm of its own depth, so the fragments
+        the front hand cuts a rear hand into are ONE component, slot and (with isolate) frame again.  Both are handed to the hands stage
+        only; everything behind it reads its labels.  Limits: a zero pixel (a sensor shadow) inside the gap breaks the link; hands that
+        touch in depth stay merged; two DIFFERENT hands at similar depth with a nearer object of link_gap pixels or fewer between them
+        are linked (profiles/hands_link.txt).  No default for link_mm; link_gap = 32 is an engineering choice; both UNMEASURED on real
+        frames.  Refused with hands=1 and without edge_mm; link_mm=None is the predictor without it.
         denoise: None | True (awr_amd.detect.DENOISE_DEFAULTS: radius=1, edge=40.0, support=0, fill=None -- a pure edge-preserving 3 x 3
         median) | a dict with any of the keys radius (1 | 2), edge (None | millimetres >= 0), support (a pixel with fewer neighbours
         within `edge` becomes 0) and fill (None | a zero pixel with at least that many valid neighbours takes their lower median) over
@@ -244,6 +254,10 @@ class Predictor:
         self.edge_mm = D._check_edge(edge_mm)
         if self.edge_mm is not None and K == 1:
             raise ValueError("edge_mm is the depth test on the joins of the connected components of SEVERAL hands: it needs hands >= 2")
+        if link_mm is not None and (K == 1 or self.edge_mm is None):
+            D._check_link(link_mm, link_gap, 0.0)          # (a wrong type or value is named first)
+            raise ValueError("link_mm rejoins a rear hand's fragments across an occluder, a pixel more than edge_mm nearer: it needs hands >= 2 and edge_mm")
+        self.link_mm, self.link_gap = D._check_link(link_mm, link_gap, self.edge_mm)
         if not isinstance(palm, bool):
             raise TypeError("palm is True or False, not %r" % (palm,))
         self.palm, self.palm_search = palm, D.check_palm(palm_search)[0]
@@ -626,7 +640,8 @@ class Predictor:
         """the K nearest components' seeds of every frame -> self._seed, hand-major"""
         DC.awr_detect_hands(self._frames.data_ptr(), 0, self.B, self.fh, self.fw, self._idx.data_ptr(), self.B, self.hands, self.depth_range, self.reach,
                             self.edge_mm, self.slab, self.min_pixels, self._hands_scratch.data_ptr(), self._labels.data_ptr() if self.isolate else None,
-                            self._seed.data_ptr(), self._hands_status.data_ptr(), self._hands_info.data_ptr(), self._hands_count.data_ptr())
+                            self._seed.data_ptr(), self._hands_status.data_ptr(), self._hands_info.data_ptr(), self._hands_count.data_ptr(),
+                            link=self.link_mm, gap=self.link_gap)
         self.hand_info = self._hands_info[:, :nb].transpose(0, 1)
 
     def _hands_isolate(self):

@@ -999,6 +999,29 @@ int awr_detect_hands_edge(const void* frames, int frame_type, int64_t n_frames, 
                           int* labels_out /* B*fh*fw, may be NULL */, double* centers /* K,B,3 */, int* status /* K,B */,
                           int* info /* K,B,4 */, int* count /* B */, void* stream);
 
+/* awr_detect_hands_edge with links across an occluder (the statements are components / hand_seeds with edge=, link=,
+ * gap=): the fragments a front hand cuts a rear hand into are joined again.  Everything above holds; the components are the transitive
+ * closure of the joins of 3' and of these links.  For every mask pixel p (raw depth d_p) and each of the four directions (right, left,
+ * down, up), with q_t the pixel t steps from p in that direction:
+ *   a. a pixel o is an OCCLUDER of p when d_o != 0 and d_p - d_o > edge -- raw depths only: it need not lie in the mask and may be nearer
+ *      than zmin;
+ *   b. n = the number of consecutive occluders q_1 ... q_n, counted up to gap.  Nothing happens when n == 0, when q_1 ... q_gap and
+ *      q_{gap+1} are all occluders, or when the walk leaves the frame before it ends;
+ *   c. otherwise q = q_{n+1} is the first pixel that is no occluder; when q is a mask pixel and |d_q - d_p| <= link, p and q are joined.
+ * The test is p's alone: one direction of a pair may hold and the other not, and either one joins.  A zero pixel inside the gap is no
+ * occluder and ends the walk (sensor shadows break links).  An edge >= 65535 makes no pixel an occluder: awr_detect_hands' labels.  Two
+ * DIFFERENT hands at similar depth with a nearer object of gap pixels or fewer between them are linked.  Labels stay canonical.
+ * link >= 0 (infinity allowed, NaN not), gap in [1, AWR_HANDS_MAX_GAP], edge >= 0: anything else returns AWR_ERR_ARG with a message that
+ * names the entry point and the argument, before any launch.  For integer depths the tests equal d_p - d_o > floor(min(edge, 65535)) and
+ * |d_q - d_p| <= floor(min(link, 65535)), which is what the kernel compares.  Ten launches: awr_detect_hands_edge's nine and, between
+ * the tile borders and the flattening, the link stage -- a thread per pixel, at most gap + 1 loads of the frame per direction for a
+ * pixel at the rear side of an occlusion edge, joins by the forest's atomicMin.  The same scratch and outputs. */
+#define AWR_HANDS_MAX_GAP 64
+int awr_detect_hands_link(const void* frames, int frame_type, int64_t n_frames, int fh, int fw, const int64_t* frame, int B, int K,
+                          double zmin, double zmax, double reach, double edge, double link, int gap, double slab, int min_pixels,
+                          void* scratch, int* labels_out /* B*fh*fw, may be NULL */, double* centers /* K,B,3 */, int* status /* K,B */,
+                          int* info /* K,B,4 */, int* count /* B */, void* stream);
+
 /* A frame per hand (csrc/awr_isolate.hip; the numpy statement is awr_amd/detect.py isolate, results are bit-identical
  * to it).  awr_detect_hands keeps a seed per hand, and awr_detect, awr_detect_palm, awr_detect_samples and the renderer read the whole raw
  * frame again: two hands closer than half a crop cube stand in each other's window and crop.  This entry gives each hand a frame that

@@ -38,6 +38,10 @@ remain one component and one hand unless --edge-mm separates them; UNMEASURED on
 (awr_detect_hands_edge): a hand held in front of another one becomes a component of its own.  Hands that touch in depth
 stay one hand, and a rear hand that the front one cuts into pieces gives one candidate per piece of --min-pixels or more
 (profiles/hands_overlap.txt).  There is no default: the right E depends on the sensor's noise, UNMEASURED on real frames.
+--link-mm L [--link-gap G] (with --hands K --edge-mm E) joins those pieces again (awr_detect_hands_link): a pixel beside
+1 ... G pixels that are more than E millimetres nearer is joined with the first pixel behind them when the two depths differ by at most L
+millimetres.  G is 32 unless given, 64 at the most.  A zero pixel in the gap breaks the link, and two different hands at similar depth
+behind one narrow nearer object are linked (profiles/hands_link.txt).  No default for L; UNMEASURED on real frames.
 --denoise [RADIUS,EDGE,SUPPORT,FILL] filters every frame on the device before anything else reads it (awr_frames_denoise):
 per pixel the lower median of the window's valid depths within EDGE millimetres of its own; a pixel with fewer than SUPPORT such
 neighbours becomes 0; a zero pixel with at least FILL valid neighbours takes their lower median.  Without a value: 1,40,0,none (a 3 x 3
@@ -87,6 +91,8 @@ def parse_args(argv=None):
     ap.add_argument("--min-pixels", type=int, default=None, metavar="N", help="with --hands: the smallest component that counts as a hand (default 400)")
     ap.add_argument("--isolate", action="store_true", help="with --hands: refine and crop every hand on a frame that holds only its own component")
     ap.add_argument("--edge-mm", type=float, default=None, metavar="E", help="with --hands: join neighbouring foreground pixels only within E mm of depth, so a hand in front of another one splits off")
+    ap.add_argument("--link-mm", type=float, default=None, metavar="L", help="with --hands and --edge-mm: rejoin the pieces a nearer hand cuts a rear hand into, where their depths agree within L mm")
+    ap.add_argument("--link-gap", type=int, default=None, metavar="G", help="with --link-mm: the widest occluder, in pixels, a link crosses (default 32, at most 64)")
     ap.add_argument("--identity", nargs="?", const="", default=None, metavar="GATE_MM,MERGE_MM,MAX_MISS",
                     help="with --hands: keep each hand in its slot across frames (the file is one sequence); optionally the gate, the merge distance and the misses allowed")
     ap.add_argument("--denoise", nargs="?", const="", default=None, metavar="RADIUS,EDGE,SUPPORT,FILL",
@@ -224,13 +230,18 @@ def main(argv=None):
         raise SystemExit("--isolate belongs to --hands K with K >= 2, without --views")
     if args.edge_mm is not None and args.hands == 1:
         raise SystemExit("--edge-mm belongs to --hands K with K >= 2")
+    if args.link_mm is not None and (args.hands == 1 or args.edge_mm is None):
+        raise SystemExit("--link-mm belongs to --hands K with K >= 2 and --edge-mm E")
+    if args.link_gap is not None and args.link_mm is None:
+        raise SystemExit("--link-gap belongs to --link-mm L")
+    link_kw = {} if args.link_mm is None else dict(link_mm=args.link_mm, link_gap=detect.LINK_GAP if args.link_gap is None else args.link_gap)
     hands_kw = {} if args.hands == 1 else dict(isolate=args.isolate, edge_mm=args.edge_mm, hands=args.hands, reach=detect.REACH if args.reach is None else args.reach,
                                                min_pixels=detect.MIN_PIXELS if args.min_pixels is None else args.min_pixels)
     K = args.hands
     pred = awr_amd.Predictor(net.cuda(), cfg.img_size, cfg.kernel_size, cube=cfg.cube, max_batch=bs, frame_shape=frames.shape[1:],
                              winograd=cfg.winograd, parity=cfg.parity_infer, confidence=args.confidence,
                              recenter=args.recenter, track=args.track, views=views, fuse=args.fuse, palm=args.palm,
-                             smooth=smooth, identity=identity, denoise=denoise, surface=surface, background=background, **hands_kw)
+                             smooth=smooth, identity=identity, denoise=denoise, surface=surface, background=background, **hands_kw, **link_kw)
     if background is not None:
         from awr_amd import background as BG
         empty = np.load(args.background, mmap_mode="r")
